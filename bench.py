@@ -21,7 +21,17 @@ static CFG inputs, of the cross-attention K/V and of the decoder's reference K/V
 `--batched-decode B` measures BASELINE.json configs[3] (perframe_ae=False): B clips per GPU whose B*T frames
 go through ONE decoder call (the only B>1-correct geometry of the dual-reference fusion).
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
+A plain run sets up, warms up, times `--steps` steps and prints ONE JSON line (rank 0): metric, value, unit,
+higher_is_better, dtype, ms_per_step (one timed step, wall clock) and the per-stage split of the timed steps.
+`--dump-outputs DIR` then writes what the last timed step returned to its caller, as float32 .npy files:
+  video.npy     : rank 0's decoded clip (clips_per_step, 3, 16, 320, 512), the fp32 tensor `step()` returns;
+  frames_u8.npy : the writer-side uint8 clip (clips_per_step, 16, 320, 512, 3) that is gathered, as float32.
+Each array keeps at most DUMP_BYTES_PER_ARRAY; a larger one (--batched-decode B > 1) is replaced by a fixed,
+seeded sample of its flattened elements.  The DDIM noise source is seeded before the warm-up, so the same
+arguments give the same inputs and noise on every run.
+
+`--full` adds, after the timed region, everything the headline does not need: a lease calibration around
+the timed region (`value_normalised`), per-rank evidence and a timed gather, the first-stage encoder, and
   roofline     : bf16 MFMA GEMM/implicit-conv kernel -- sum(algorithmic FLOP)/sum(duration) over
                  every launch of one B=2 UNet forward, HIP events on the launch stream;
   roofline_hbm : the GroupNorm(+SiLU) operator (HBM-bound): algorithmic bytes (2 B read + 2 B written per
@@ -503,7 +513,7 @@ def other_binding_clip(args):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.abspath(__file__), "--steps", "2", "--warmup", "1", "--ddim-steps", str(args.ddim_steps),
-           "--no-cpu-baseline", "--no-roofline", "--no-extras"] + (["--fp8"] if args.fp8 else [])
+           "--full", "--no-cpu-baseline", "--no-roofline", "--no-extras"] + (["--fp8"] if args.fp8 else [])
     try:
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
         line = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -735,6 +745,23 @@ def launcher_selftest(args):
         dist.destroy_process_group()
 
 
+DUMP_BYTES_PER_ARRAY = 30 << 20    # two arrays stay under 64 MB in all; one (1, 3, 16, 320, 512) fp32 clip is exactly this
+NOISE_SEED = 20240607
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each tensor as out_dir/<name>.npy in float32; one larger than DUMP_BYTES_PER_ARRAY becomes a fixed
+    sample of its flattened elements (indices from a seeded generator, ascending), the same on every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float()
+        if a.numel() * 4 > DUMP_BYTES_PER_ARRAY:
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_BYTES_PER_ARRAY // 4]
+            a = a.flatten()[idx.sort().values.to(a.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), a.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -746,16 +773,23 @@ def main():
     ap.add_argument("--fp8", action="store_true",
                     help="configs[4]: MXFP8 (e4m3 + E8M0 block scales) operands on the qkv / GEGLU projections (TC_FP8=1; "
                          "export TC_FP8=all to add the convolutions)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the lease calibration, per-rank evidence, encoder, roofline, "
+                         "boundary, host handover, ROCm-eager baseline, other binding and CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline / boundary / handover probes")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the after-the-fact extras (ROCm-eager baseline, two clips through the other binding)")
+                    help="with --full: skip the after-the-fact extras (ROCm-eager baseline, two clips through the other binding)")
     ap.add_argument("--launcher-selftest", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--retry", action="store_true",
                     help="supervise the run in a child process and repeat it ONLY if the lease itself is unhealthy "
                          "(scripts/gpu_health.py fails); off by default")
     ap.add_argument("--no-retry", action="store_true", help=argparse.SUPPRESS)      # accepted for old command lines
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.fp8:
         os.environ["TC_FP8"] = os.environ.get("TC_FP8", "1")      # read when the operator backend is created
@@ -821,7 +855,8 @@ def main():
             return lease_calibration(device)
         except Exception as e:                                           # noqa: BLE001  (calibration only: never fatal)
             return {"matmul_8192_bf16_tflops": None, "copy_1gib_gbs": None, "error": f"{type(e).__name__}: {e}"[:200]}
-    calib_pre = calibrate() if rank == 0 else None
+    calib_pre = calibrate() if rank == 0 and args.full else None
+    torch.manual_seed(NOISE_SEED + rank)                                 # the DDIM noise (eta = 1) of every step
     for _ in range(args.warmup):
         step()
         _log("warmup step done")
@@ -838,8 +873,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
     finite = bool(torch.isfinite(video).all())
-    calib_post = calibrate() if rank == 0 else None
-    evidence = rank_evidence(device, rank, local, world, last_u8[0], gather_buf)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"video": video, "frames_u8": last_u8[0]})
+    calib_post = calibrate() if rank == 0 and args.full else None
+    evidence = rank_evidence(device, rank, local, world, last_u8[0], gather_buf) if args.full else {}
 
     result = None
     if rank == 0:
@@ -868,12 +905,13 @@ def main():
             "binding_fallback": ops.binding_fallback(),        # None, or why the default custom-op layer was not taken
             **evidence,
         }
-        mms = [c["matmul_8192_bf16_tflops"] for c in (calib_pre, calib_post) if c.get("matmul_8192_bf16_tflops")]
-        mm = sum(mms) / len(mms) if mms else None
-        result["lease_calibration"] = {"before_timed_region": calib_pre, "after_timed_region": calib_post, "reference": CALIB_REFERENCE,
-                                       "what": "hipBLASLt 8192^3 bf16 (torch.matmul) and a 1 GiB d2d copy, measured in this process on "
-                                               "rank 0; calibration only, not on the product path"}
-        result["value_normalised"] = round(result["value"] * CALIB_REFERENCE["matmul_8192_bf16_tflops"] / mm, 4) if mm else None
+        if args.full:
+            mms = [c["matmul_8192_bf16_tflops"] for c in (calib_pre, calib_post) if c.get("matmul_8192_bf16_tflops")]
+            mm = sum(mms) / len(mms) if mms else None
+            result["lease_calibration"] = {"before_timed_region": calib_pre, "after_timed_region": calib_post, "reference": CALIB_REFERENCE,
+                                           "what": "hipBLASLt 8192^3 bf16 (torch.matmul) and a 1 GiB d2d copy, measured in this process on "
+                                                   "rank 0; calibration only, not on the product path"}
+            result["value_normalised"] = round(result["value"] * CALIB_REFERENCE["matmul_8192_bf16_tflops"] / mm, 4) if mm else None
         if args.fp8:
             result["fp8_gemm_calls"] = dict(ops.backend().fp8_calls)
         if STAGE_EVENTS:
@@ -886,7 +924,7 @@ def main():
         # rank 0 alone and must not sit inside anybody's collective timeout
         dist.barrier()
         dist.destroy_process_group()
-    if rank == 0:
+    if rank == 0 and args.full:
         # row f1 (not part of `value`): the first-stage encoder that produces z and the reference
         # hidden states, 16 frames at 320x512, reported so that "with encoder" can be derived
         frames = torch.rand((16, 3, 320, 512), device=device) * 2 - 1
@@ -900,7 +938,7 @@ def main():
         result["encoder_16f_ms"] = round(enc_ms, 2)
         _log("encoder done")
         result["frames_per_s_with_encoder"] = round(16.0 / (dt / args.steps / clips_per_step + enc_ms * 1e-3), 4)
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         result["roofline"] = _measured(measure_roofline, model, inps[0])
         if args.fp8 and "error" not in result["roofline"]:
             result["roofline"]["note"] = ("--fp8: the timed launches include the routed tc_gemm_mxfp8 ones; FLOPs are priced "
@@ -911,7 +949,7 @@ def main():
         result["boundary_host_overhead"] = _measured(measure_boundary, model, inps[0])
         _log("boundary done")
         result["host_handover"] = _measured(host_handover, device, dt / args.steps / clips_per_step * 1e3)
-    if rank == 0 and world == 1 and not args.no_extras and bdec == 0:
+    if rank == 0 and world == 1 and args.full and not args.no_extras and bdec == 0:
         try:                                                         # an extra must never cost the headline
             result["rocm_eager_baseline"] = rocm_eager_baseline(model, inps[0])
         except Exception as e:                                       # noqa: BLE001
@@ -919,7 +957,7 @@ def main():
         _log("rocm eager baseline done")
         result["binding_ab"] = other_binding_clip(args)
         _log("other binding clip done")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = _measured(cpu_baseline, model, inps[0])
     if rank == 0:
         print(json.dumps(result))

@@ -3,7 +3,7 @@
 VAR=$1; A=$2; B=$3; R=${4:-2}
 bash scripts/which_gpu.sh
 for r in $(seq $R); do for v in $A $B; do
-  env $VAR=$v timeout 600 python bench.py --steps 2 --warmup 1 --no-cpu-baseline > /tmp/ab.log 2>&1
+  env $VAR=$v timeout 600 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > /tmp/ab.log 2>&1
   python - "$VAR=$v" <<'PY'
 import json, sys
 line = [l for l in open("/tmp/ab.log") if l.startswith("{")]

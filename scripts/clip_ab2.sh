@@ -3,7 +3,7 @@
 # each arm is a string of VAR=value assignments (may be empty = the defaults)
 A=$1; B=$2; R=${3:-2}
 for r in $(seq $R); do for v in "$A" "$B"; do
-  env $v timeout 600 python bench.py --steps 2 --warmup 1 --no-cpu-baseline > /tmp/ab.log 2>&1
+  env $v timeout 600 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > /tmp/ab.log 2>&1
   python - "[$v]" <<'PY'
 import json, sys
 line = [l for l in open("/tmp/ab.log") if l.startswith("{")]

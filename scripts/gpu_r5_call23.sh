@@ -11,5 +11,5 @@ t0=$(date +%s)
 timeout 120 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke rc=$? $(( $(date +%s) - t0 )) s" | tee -a $OUT/log.txt
 tail -2 $OUT/smoke.log
 t0=$(date +%s)
-timeout 420 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$? $(( $(date +%s) - t0 )) s" | tee -a $OUT/log.txt
+timeout 420 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$? $(( $(date +%s) - t0 )) s" | tee -a $OUT/log.txt
 cat $OUT/bench.json | cut -c1-600; tail -3 $OUT/bench.err

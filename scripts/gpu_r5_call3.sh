@@ -8,6 +8,6 @@ tail -4 $OUT/pytest_all.log
 timeout 300 python scripts/forward_breakdown.py --top 70 > $OUT/forward_breakdown_unet.txt 2>&1; echo "breakdown unet rc=$?" | tee -a $OUT/log.txt
 timeout 300 python scripts/forward_breakdown.py --decoder --top 40 > $OUT/forward_breakdown_decoder.txt 2>&1; echo "breakdown dec rc=$?" | tee -a $OUT/log.txt
 timeout 400 python scripts/ws_bench.py > $OUT/ws_bench.txt 2>&1; echo "ws_bench rc=$?" | tee -a $OUT/log.txt
-timeout 600 python bench.py --steps 6 --warmup 2 --no-cpu-baseline > $OUT/bench_quick.json 2> $OUT/bench_quick.err; echo "bench rc=$?" | tee -a $OUT/log.txt
+timeout 600 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline > $OUT/bench_quick.json 2> $OUT/bench_quick.err; echo "bench rc=$?" | tee -a $OUT/log.txt
 head -c 600 $OUT/bench_quick.json; echo
 head -12 $OUT/forward_breakdown_unet.txt

@@ -6,5 +6,5 @@ timeout 900 python -m pytest tests -m gpu -x -q -p no:cacheprovider > $OUT/pytes
 tail -3 $OUT/pytest_all.log
 timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke rc=$?" | tee -a $OUT/log.txt
 tail -2 $OUT/smoke.log
-timeout 1200 python bench.py --steps 6 --warmup 2 --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?" | tee -a $OUT/log.txt
+timeout 1200 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?" | tee -a $OUT/log.txt
 head -c 300 $OUT/bench.json; echo; tail -3 $OUT/bench.err

@@ -6,5 +6,5 @@ t0=$(date +%s); timeout 1200 python -m pytest tests -m gpu -x -q -p no:cacheprov
 tail -3 $OUT/pytest_all.log
 t0=$(date +%s); timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke rc=$? $(( $(date +%s) - t0 )) s" | tee -a $OUT/log.txt
 tail -2 $OUT/smoke.log
-t0=$(date +%s); timeout 1200 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$? $(( $(date +%s) - t0 )) s" | tee -a $OUT/log.txt
+t0=$(date +%s); timeout 1200 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$? $(( $(date +%s) - t0 )) s" | tee -a $OUT/log.txt
 head -c 300 $OUT/bench.json; echo

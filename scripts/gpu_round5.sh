@@ -19,15 +19,15 @@ for s in "$@"; do
   case $s in
     unver)   timeout 300 python -m pytest tests/test_gpu_conv_halo.py -m gpu -x -q -p no:cacheprovider > $OUT/pytest_unverified.log 2>&1 ;;
     halo)    timeout 300 python scripts/conv_halo_bench.py > $OUT/conv_halo_bench.txt 2>&1 ;;
-    haloclip) (for v in 0 1 0 1; do echo "== TC_CONV_HALO=$v"; TC_CONV_HALO=$v timeout 300 python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-roofline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['stage_ms_per_clip'])"; done) > $OUT/conv_halo_clip_ab.txt 2>&1 ;;
+    haloclip) (for v in 0 1 0 1; do echo "== TC_CONV_HALO=$v"; TC_CONV_HALO=$v timeout 300 python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-roofline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['stage_ms_per_clip'])"; done) > $OUT/conv_halo_clip_ab.txt 2>&1 ;;
     gn)      timeout 300 python scripts/norm_bench.py > $OUT/norm_bench.txt 2>&1 ;;
     fuseunet) TC_GN_FUSE=1 TC_CONV_HALO=1 timeout 600 python -m pytest tests/test_gpu_fullsize.py tests/test_gpu_models.py -m gpu -x -q -p no:cacheprovider > $OUT/pytest_fused_unet.log 2>&1 ;;
-    fuseclip) (for v in "0 0" "1 1" "0 0" "1 1" "1 0"; do set -- $v; echo "== TC_CONV_HALO=$1 TC_GN_FUSE=$2"; TC_CONV_HALO=$1 TC_GN_FUSE=$2 timeout 300 python bench.py --steps 4 --warmup 1 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['stage_ms_per_clip'], 'gemm frac', d['roofline']['frac'], 'gn ms', d['roofline_hbm']['ms_per_unet_fwd_b2'])"; done) > $OUT/fuse_clip_ab.txt 2>&1 ;;
+    fuseclip) (for v in "0 0" "1 1" "0 0" "1 1" "1 0"; do set -- $v; echo "== TC_CONV_HALO=$1 TC_GN_FUSE=$2"; TC_CONV_HALO=$1 TC_GN_FUSE=$2 timeout 300 python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['stage_ms_per_clip'], 'gemm frac', d['roofline']['frac'], 'gn ms', d['roofline_hbm']['ms_per_unet_fwd_b2'])"; done) > $OUT/fuse_clip_ab.txt 2>&1 ;;
     all)     timeout 900 python -m pytest tests -m gpu -x -q -p no:cacheprovider > $OUT/pytest_all.log 2>&1 ;;
     smoke)   timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 ;;
-    bench)   timeout 900 python bench.py --steps 10 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err ;;
-    benchq)  timeout 600 python bench.py --steps 6 --warmup 2 --no-cpu-baseline > $OUT/bench_quick.json 2> $OUT/bench_quick.err ;;
-    prof)    (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/profclip -o prof -- python $REPO/bench.py --steps 1 --warmup 0 --ddim-steps 10 --no-cpu-baseline --no-roofline > $REPO/$OUT/prof.log 2>&1; python $REPO/scripts/prof_summary.py "$(find /tmp/profclip -name '*.db' | head -1)" 50 > $REPO/$OUT/prof_stats.txt 2>> $REPO/$OUT/prof.log) ;;
+    bench)   timeout 900 python bench.py --full --steps 10 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err ;;
+    benchq)  timeout 600 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline > $OUT/bench_quick.json 2> $OUT/bench_quick.err ;;
+    prof)    (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/profclip -o prof -- python $REPO/bench.py --full --steps 1 --warmup 0 --ddim-steps 10 --no-cpu-baseline --no-roofline > $REPO/$OUT/prof.log 2>&1; python $REPO/scripts/prof_summary.py "$(find /tmp/profclip -name '*.db' | head -1)" 50 > $REPO/$OUT/prof_stats.txt 2>> $REPO/$OUT/prof.log) ;;
     pmchalo) bash scripts/pmc_halo.sh > $OUT/pmc_halo.log 2>&1 ;;
     halodbg) (for a in "3x3" "t3" "3x3 2 20 32 128 160 tall" "3x3 2 10 16 256 160 ksplit" "3x3 2 20 32 128 160 gn"; do timeout 120 python scripts/conv_halo_debug.py $a; done) > $OUT/conv_halo_debug.txt 2>&1 ;;
     py:*)    timeout 600 python ${s#py:} > $OUT/$(basename ${s#py:} .py).txt 2>&1 ;;

@@ -3,7 +3,7 @@
 cp tooncrafter_amd/libtooncrafter_hip.so /tmp/new.so
 for r in 1 2; do for v in new old; do
   if [ $v = old ]; then cp scripts/bin/prev/libtooncrafter_hip.so tooncrafter_amd/libtooncrafter_hip.so; else cp /tmp/new.so tooncrafter_amd/libtooncrafter_hip.so; fi
-  timeout 600 python bench.py --steps 2 --warmup 1 --no-cpu-baseline > /tmp/ab.log 2>&1
+  timeout 600 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > /tmp/ab.log 2>&1
   python - "[$v]" <<'PY'
 import json, sys
 line = [l for l in open("/tmp/ab.log") if l.startswith("{")]

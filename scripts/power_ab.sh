@@ -3,11 +3,11 @@
 VAR=$1; A=$2; B=$3
 bash scripts/which_gpu.sh
 timeout 300 python scripts/gpu_health.py 2>&1 | tail -2
-env $VAR=$A timeout 600 python bench.py --steps 1 --warmup 1 --ddim-steps 10 --no-cpu-baseline --no-roofline > /tmp/ab0.log 2>&1; echo "no-sampler run rc=$?"; grep -v "^{" /tmp/ab0.log | tail -3
+env $VAR=$A timeout 600 python bench.py --full --steps 1 --warmup 1 --ddim-steps 10 --no-cpu-baseline --no-roofline > /tmp/ab0.log 2>&1; echo "no-sampler run rc=$?"; grep -v "^{" /tmp/ab0.log | tail -3
 for v in $A $B; do
   ( while true; do rocm-smi --showclocks --showpower --json 2>/dev/null | tr -d '\n'; echo; sleep 0.1; done ) > /tmp/smi_$v.log &
   SMI=$!
-  env $VAR=$v timeout 600 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-roofline > /tmp/ab.log 2>&1
+  env $VAR=$v timeout 600 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-roofline > /tmp/ab.log 2>&1
   kill $SMI 2>/dev/null; wait $SMI 2>/dev/null
   python - "$VAR=$v" /tmp/smi_$v.log <<'PY'
 import json, re, sys

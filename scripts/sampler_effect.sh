@@ -2,7 +2,7 @@
 # Does a concurrent rocm-smi poller change the clip time?  Same box, alternating: no poller / poller at 100 ms / poller at 1 s
 bash scripts/which_gpu.sh
 run() {  # $1 = label
-  timeout 600 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-roofline > /tmp/ab.log 2>&1
+  timeout 600 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-roofline > /tmp/ab.log 2>&1
   python - "$1" <<'PY'
 import json, sys
 line = [l for l in open("/tmp/ab.log") if l.startswith("{")]
