@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define TC_ABI_VERSION 13
+#define TC_ABI_VERSION 14
 
 enum {
   TC_OK = 0,
@@ -222,6 +222,28 @@ typedef struct TcAttnParams {
  * Replaces xformers.ops.memory_efficient_attention at lvdm/modules/attention.py:175,187 and
  * lvdm/models/autoencoder_dualref.py:316,326 (and the einsum fallback attention.py:103-134). */
 int tc_attn_d64(const TcAttnParams* p, void* stream);
+
+/* ABI 14 -- 8-bit spatial self-attention (BASELINE.json configs[4], the fp8 attention path; csrc/attention_q8.hip):
+ * softmax(q k^T * scale) v with q k^T on int8 operands (one fp32 scale per row and head) and P v on MXFP8 operands (V^T and
+ * the in-kernel P in e4m3 with one E8M0 scale per 32 keys).  Replaces the xformers self-attention of
+ * lvdm/modules/attention.py:175 (CrossAttention.efficient_forward with context = None, called from the spatial
+ * BasicTransformerBlock.attn1) where ops.HipOps.spatial_attn_q8_eligible routes it; formats in the source's header.
+ * Two launches: tc_attn_q8_quant_kv quantises K and V into `workspace` (tc_attn_q8_workspace bytes, 16-byte aligned), then
+ * tc_attn_d64_q8 reads q and that workspace and writes o.  Element (b, h, i, d) lives at ptr + b*sb + i*ss + h*64 + d, as in
+ * TcAttnParams; the quantiser reads k / v, the attention q / o, both the workspace.  No key/value batch sharing, no second
+ * key/value set, no accumulate: TcAttnParams covers those. */
+typedef struct TcAttnQ8Params {
+  const tc_bf16* q; const tc_bf16* k; const tc_bf16* v; tc_bf16* o;
+  int32_t batch, heads, lq, lk;
+  int64_t q_sb, k_sb, v_sb, o_sb;
+  int32_t q_ss, k_ss, v_ss, o_ss;
+  float scale;         /* d^-0.5; must be > 0 */
+  void* workspace;
+  int64_t workspace_bytes;
+} TcAttnQ8Params;
+int64_t tc_attn_q8_workspace(const TcAttnQ8Params* p);
+int tc_attn_q8_quant_kv(const TcAttnQ8Params* p, void* stream);
+int tc_attn_d64_q8(const TcAttnQ8Params* p, void* stream);
 
 /* Temporal self-attention over <=16 frames at every pixel (attention.py:81-144 via
  * TemporalTransformer, attention.py:365-412).  qkv: fused [rows, 3*C] projection with

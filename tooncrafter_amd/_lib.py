@@ -11,7 +11,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libtooncrafter_hip.so")
 
-TC_ABI_VERSION = 13
+TC_ABI_VERSION = 14
 ACT_NONE, ACT_SILU, ACT_GELU, ACT_GEGLU = 0, 1, 2, 3
 GATHER_LINEAR, GATHER_CONV3x3, GATHER_CONVT3 = 0, 1, 2
 
@@ -53,6 +53,17 @@ class TcAttnParams(C.Structure):
         ("kv_bdiv", C.c_int32), ("accumulate", C.c_int32), ("scale", C.c_float),
         ("k2", C.c_void_p), ("v2", C.c_void_p), ("lk2", C.c_int32), ("kv2_bdiv", C.c_int32),
         ("k2_sb", C.c_int64), ("v2_sb", C.c_int64), ("k2_ss", C.c_int32), ("v2_ss", C.c_int32),
+    ]
+
+
+class TcAttnQ8Params(C.Structure):
+    _fields_ = [
+        ("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("o", C.c_void_p),
+        ("batch", C.c_int32), ("heads", C.c_int32), ("lq", C.c_int32), ("lk", C.c_int32),
+        ("q_sb", C.c_int64), ("k_sb", C.c_int64), ("v_sb", C.c_int64), ("o_sb", C.c_int64),
+        ("q_ss", C.c_int32), ("k_ss", C.c_int32), ("v_ss", C.c_int32), ("o_ss", C.c_int32),
+        ("scale", C.c_float),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
     ]
 
 
@@ -114,6 +125,9 @@ SYMBOLS = {
     "tc_layernorm_mxfp8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                      C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
     "tc_attn_d64": (C.c_int, [C.POINTER(TcAttnParams), C.c_void_p]),
+    "tc_attn_q8_workspace": (C.c_int64, [C.POINTER(TcAttnQ8Params)]),
+    "tc_attn_q8_quant_kv": (C.c_int, [C.POINTER(TcAttnQ8Params), C.c_void_p]),
+    "tc_attn_d64_q8": (C.c_int, [C.POINTER(TcAttnQ8Params), C.c_void_p]),
     "tc_attn_temporal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                    C.c_float, C.c_void_p]),
     "tc_groupnorm_workspace": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),

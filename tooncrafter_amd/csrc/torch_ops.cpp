@@ -3,7 +3,7 @@
 // The reference binds ATen / xformers operators from Python (utils/utils.py:27-42 instantiates lvdm classes whose
 // forward methods call torch ops); this registers the MI355X kernels as first-class torch operators instead:
 //   torch.ops.tooncrafter.gemm / quant_mxfp8 / gemm_mx / attention / attention_temporal / groupnorm(_pf) / layernorm(_pf) / ddim_step /
-//   ff_geglu_fused / temporal_attn_fused / temporal_qkv_attn
+//   ff_geglu_fused / temporal_attn_fused / temporal_qkv_attn / attention_q8
 // with (i) a CUDA(HIP)-key implementation that validates the tensors, allocates the result from the caching allocator,
 // picks up the CURRENT stream and calls the same extern "C" entry point the ctypes binding calls, and (ii) a Meta-key
 // implementation (shape / dtype inference only) so the ops can be traced, exported and shape-checked without a GPU.
@@ -191,6 +191,33 @@ Tensor attention_cuda(const Tensor& q, const Tensor& k, const Tensor& v, int64_t
 
 Tensor attention_meta(const Tensor& q, const Tensor&, const Tensor&, int64_t batch, int64_t heads, int64_t lq, int64_t, int64_t,
                       double, const optional<Tensor>&, const optional<Tensor>&, int64_t, int64_t) {
+  return at::empty({batch * lq, heads * 64}, q.options());
+}
+
+// ABI 14: the 8-bit self-attention -- K / V quantised into a workspace from the caching allocator, then the attention
+Tensor attention_q8_cuda(const Tensor& q, const Tensor& k, const Tensor& v, int64_t batch, int64_t heads, int64_t lq, int64_t lk,
+                         double scale) {
+  check_rows(q, "attention_q8: q"); check_rows(k, "attention_q8: k"); check_rows(v, "attention_q8: v");
+  const int64_t hd = heads * 64;
+  TORCH_CHECK(q.size(0) == batch * lq && q.size(1) == hd && k.size(0) == batch * lk && k.size(1) == hd &&
+              v.size(0) == batch * lk && v.size(1) == hd,
+              "attention_q8: q must be [batch*lq, heads*64], k and v [batch*lk, heads*64]");
+  Tensor out = at::empty({batch * lq, hd}, q.options());
+  TcAttnQ8Params p = {};
+  p.q = bf(q); p.k = bf(k); p.v = bf(v); p.o = reinterpret_cast<tc_bf16*>(out.data_ptr());
+  p.batch = (int32_t)batch; p.heads = (int32_t)heads; p.lq = (int32_t)lq; p.lk = (int32_t)lk;
+  p.q_ss = (int32_t)q.stride(0); p.k_ss = (int32_t)k.stride(0); p.v_ss = (int32_t)v.stride(0); p.o_ss = (int32_t)out.stride(0);
+  p.q_sb = lq * q.stride(0); p.k_sb = lk * k.stride(0); p.v_sb = lk * v.stride(0); p.o_sb = lq * out.stride(0);
+  p.scale = (float)scale;
+  const int64_t nbytes = tc_attn_q8_workspace(&p);
+  Tensor ws = at::empty({nbytes > 16 ? nbytes : 16}, q.options().dtype(at::kByte));
+  p.workspace = ws.data_ptr(); p.workspace_bytes = ws.numel();
+  check_rc(tc_attn_q8_quant_kv(&p, cur_stream()), "tc_attn_q8_quant_kv");
+  check_rc(tc_attn_d64_q8(&p, cur_stream()), "tc_attn_d64_q8");
+  return out;
+}
+
+Tensor attention_q8_meta(const Tensor& q, const Tensor&, const Tensor&, int64_t batch, int64_t heads, int64_t lq, int64_t, double) {
   return at::empty({batch * lq, heads * 64}, q.options());
 }
 
@@ -402,6 +429,7 @@ TORCH_LIBRARY(tooncrafter, m) {
   m.def("attention(Tensor q, Tensor k, Tensor v, int batch, int heads, int lq, int lk, int kv_bdiv, float scale, "
         "Tensor? k2, Tensor? v2, int lk2, int kv2_bdiv) -> Tensor");
   m.def("attention_temporal(Tensor qkv, int b, int t, int hw, int heads, float scale) -> Tensor");
+  m.def("attention_q8(Tensor q, Tensor k, Tensor v, int batch, int heads, int lq, int lk, float scale) -> Tensor");
   m.def("groupnorm(Tensor x, Tensor gamma, Tensor beta, int samples, int rows, float eps, bool silu) -> Tensor");
   m.def("ff_geglu_fused(Tensor x, Tensor w1, Tensor b1, Tensor w2, Tensor b2, float ln_eps) -> Tensor");
   m.def("temporal_attn_fused(Tensor x, Tensor wqkv, Tensor bqkv, Tensor wo, Tensor bo, int b, int t, int hw, int heads, float ln_eps, float scale) -> Tensor");
@@ -421,6 +449,7 @@ TORCH_LIBRARY_IMPL(tooncrafter, CUDA, m) {
   m.impl("gemm_mx", gemm_mx_cuda);
   m.impl("attention", attention_cuda);
   m.impl("attention_temporal", attention_temporal_cuda);
+  m.impl("attention_q8", attention_q8_cuda);
   m.impl("groupnorm", groupnorm_cuda);
   m.impl("layernorm", layernorm_cuda);
   m.impl("groupnorm_pf", groupnorm_pf_cuda);
@@ -437,6 +466,7 @@ TORCH_LIBRARY_IMPL(tooncrafter, Meta, m) {
   m.impl("gemm_mx", gemm_mx_meta);
   m.impl("attention", attention_meta);
   m.impl("attention_temporal", attention_temporal_meta);
+  m.impl("attention_q8", attention_q8_meta);
   m.impl("groupnorm", like_meta3);
   m.impl("layernorm", like_meta_ln);
   m.impl("groupnorm_pf", groupnorm_pf_meta);

@@ -185,8 +185,14 @@ class CrossAttention(PackedModule):
         pk = self.pk
         c = self.heads * 64
         qkv = ops.gemm(x_norm, pk["wqkv"]) if ln is None else ops.gemm(x_norm, ln[0], ln[1], a_norm_eps=ln[2])
-        a = ops.attention(qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:], batch=act.frames, heads=self.heads,
-                          lq=act.hw, lk=act.hw, scale=self.scale)
+        # the 8-bit route (ABI 14, TC_FP8_ATTN=1): the backend's own rule decides; backends without it keep bf16
+        q8 = getattr(ops.backend(), "spatial_attn_q8_eligible", None)
+        if q8 is not None and q8(lk=act.hw):
+            a = ops.attention_q8(qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:], batch=act.frames, heads=self.heads,
+                                 lq=act.hw, lk=act.hw, scale=self.scale)
+        else:
+            a = ops.attention(qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:], batch=act.frames, heads=self.heads,
+                              lq=act.hw, lk=act.hw, scale=self.scale)
         return ops.gemm(a, pk["wo"], pk["bo"], residual=residual)
 
     # -- self attention over the T frames at each pixel

@@ -270,8 +270,8 @@ class LatentDiffusion(DDPM):
 
         if self.use_hipgraph and x_noisy.is_cuda:
             # a captured graph replays the kernels and the packed-weight pointers it recorded: new weights
-            # (load_state_dict / invalidate) or another MXFP8 routing since capture make it stale
-            sig = (PackedModule.graph_epoch(), getattr(ops.backend(), "fp8", None), branches)
+            # (load_state_dict / invalidate) or another MXFP8 / 8-bit attention routing since capture make it stale
+            sig = (PackedModule.graph_epoch(), getattr(ops.backend(), "fp8", None), getattr(ops.backend(), "fp8_attn", None), branches)
             if st["graph"] is not None and st.get("graph_sig") != sig:
                 st["graph"], st["calls"] = None, 0
             if st["graph"] is None and st["calls"] >= 1:             # first call ran eagerly (warm caches)

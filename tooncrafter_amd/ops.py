@@ -23,7 +23,7 @@ import torch
 
 from . import _lib
 from ._lib import (ACT_GEGLU, ACT_GELU, ACT_NONE, ACT_SILU, GATHER_CONV3x3, GATHER_CONVT3,
-                   GATHER_LINEAR, TcAttnParams, TcDdimParams, TcFfParams, TcGemmMxParams, TcGemmParams, TcTbParams, TcTqaParams)
+                   GATHER_LINEAR, TcAttnParams, TcAttnQ8Params, TcDdimParams, TcFfParams, TcGemmMxParams, TcGemmParams, TcTbParams, TcTqaParams)
 
 BF16 = torch.bfloat16
 
@@ -103,7 +103,11 @@ class HipOps:
         self.fp8_min_m = 1024
         self.fp8_decoder = os.environ.get("TC_FP8_DECODER", "0") == "1"
         self.fp8_fuse_ln = os.environ.get("TC_FP8_FUSE_LN", "1") != "0"     # LayerNorm emits MXFP8 for its fp8 consumer
-        self.fp8_calls = {"mx": 0, "bf16": 0}
+        # ABI 14: TC_FP8_ATTN=1 runs the spatial self-attentions with lk >= fp8_attn_min_lk (640: UNet levels 0 and 1) on
+        # int8 q k^T + MXFP8 P v (csrc/attention_q8.hip, spatial_attn_q8_eligible); independent of TC_FP8, off by default
+        self.fp8_attn = os.environ.get("TC_FP8_ATTN", "0") == "1"
+        self.fp8_attn_min_lk = int(os.environ.get("TC_FP8_ATTN_MIN_LK", "640"))
+        self.fp8_calls = {"mx": 0, "bf16": 0, "attn_q8": 0}
         self._wq = {}
         # LayerNorm -> consumer GEMM fusion (ABI 8, gemm_ln_eligible); TC_FUSE_LN=0 keeps the separate launch (A/B runs)
         self.fuse_ln = os.environ.get("TC_FUSE_LN", "1") != "0"
@@ -473,6 +477,37 @@ class HipOps:
             p.k2_ss, p.v2_ss = k2.stride(0), v2.stride(0)
             p.k2_sb, p.v2_sb = lk2 * k2.stride(0), lk2 * v2.stride(0)
         _lib.check(self.lib.tc_attn_d64(C.byref(p), _stream()), "tc_attn_d64")
+        return out
+
+    def spatial_attn_q8_eligible(self, *, lk, kv_bdiv=1, k2=None, accumulate=False) -> bool:
+        """Routing rule of the 8-bit spatial self-attention (ABI 14): the switch is on, it is a plain self-attention (one
+        key/value set, no K/V batch sharing, no accumulate) and long enough (lk >= fp8_attn_min_lk)."""
+        return self.fp8_attn and k2 is None and not accumulate and kv_bdiv == 1 and lk >= self.fp8_attn_min_lk
+
+    def _q8_params(self, q, k, v, out, batch, heads, lq, lk, scale):
+        hd = heads * 64
+        if q.shape != (batch * lq, hd) or k.shape != (batch * lk, hd) or v.shape != (batch * lk, hd):
+            raise ValueError("attention_q8: q must be [batch*lq, heads*64], k and v [batch*lk, heads*64]")
+        p = TcAttnQ8Params()
+        p.q, p.k, p.v, p.o = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
+        p.batch, p.heads, p.lq, p.lk = batch, heads, lq, lk
+        p.q_ss, p.k_ss, p.v_ss, p.o_ss = q.stride(0), k.stride(0), v.stride(0), out.stride(0)
+        p.q_sb, p.k_sb, p.v_sb, p.o_sb = lq * q.stride(0), lk * k.stride(0), lk * v.stride(0), lq * out.stride(0)
+        p.scale = float(scale if scale is not None else 64 ** -0.5)
+        return p
+
+    def attention_q8(self, q, k, v, *, batch, heads, lq, lk, scale=None):
+        """8-bit self-attention (ABI 14): out[batch*lq, heads*64] = softmax(q k^T * scale) v per (batch, head), q k^T on
+        int8 operands and P v on MXFP8 -- tc_attn_q8_quant_kv into a workspace from the caching allocator, then
+        tc_attn_d64_q8.  Rows views as for attention()."""
+        q, k, v = _rows_view(q), _rows_view(k), _rows_view(v)
+        out = torch.empty((batch * lq, heads * 64), dtype=BF16, device=q.device)
+        p = self._q8_params(q, k, v, out, batch, heads, lq, lk, scale)
+        ws = self._workspace(self.lib.tc_attn_q8_workspace(C.byref(p)), q.device)
+        p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
+        _lib.check(self.lib.tc_attn_q8_quant_kv(C.byref(p), _stream()), "tc_attn_q8_quant_kv")
+        _lib.check(self.lib.tc_attn_d64_q8(C.byref(p), _stream()), "tc_attn_d64_q8")
+        self.fp8_calls["attn_q8"] += 1
         return out
 
     def attention_temporal(self, qkv, *, b, t, hw, heads, scale=None):

@@ -81,6 +81,11 @@ class TorchLibOps(HipOps):
         return self.t.attention(q, k, v, batch, heads, lq, lk, kv_bdiv, float(64 ** -0.5 if scale is None else scale),
                                 k2, v2, int(lk2), int(kv2_bdiv))
 
+    def attention_q8(self, q, k, v, *, batch, heads, lq, lk, scale=None):
+        out = self.t.attention_q8(q, k, v, int(batch), int(heads), int(lq), int(lk), float(64 ** -0.5 if scale is None else scale))
+        self.fp8_calls["attn_q8"] += 1
+        return out
+
     def attention_temporal(self, qkv, *, b, t, hw, heads, scale=None):
         return self.t.attention_temporal(qkv, b, t, hw, heads, float(64 ** -0.5 if scale is None else scale))
 
