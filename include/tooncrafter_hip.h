@@ -245,10 +245,14 @@ int64_t tc_attn_q8_workspace(const TcAttnQ8Params* p);
 int tc_attn_q8_quant_kv(const TcAttnQ8Params* p, void* stream);
 int tc_attn_d64_q8(const TcAttnQ8Params* p, void* stream);
 
-/* Temporal self-attention over <=16 frames at every pixel (attention.py:81-144 via
+/* Temporal self-attention over 1 .. TC_TEMPORAL_MAX_FRAMES frames at every pixel (attention.py:81-144 via
  * TemporalTransformer, attention.py:365-412).  qkv: fused [rows, 3*C] projection with
  * row = (b*T + t)*HW + p; columns [0,C)=q, [C,2C)=k, [2C,3C)=v, head h at h*64.
- * out: [rows, C] bf16. */
+ * out: [rows, C] bf16.  t <= 16: one wave per (pixel, head) on the VALU, fp32 softmax weights;
+ * 16 < t <= 64 (long clips, --video_length above 16): csrc/attention_temporal_long.hip, MFMA with the frames padded
+ * to 32 | 64, bf16 softmax weights as csrc/qkv_attn.hip; t > TC_TEMPORAL_MAX_FRAMES: TC_ESHAPE, nothing launched.
+ * (The signature is unchanged from ABI 14 -- a caller built against it keeps working; the accepted t range grew.) */
+#define TC_TEMPORAL_MAX_FRAMES 64
 int tc_attn_temporal(const tc_bf16* qkv, tc_bf16* out, int32_t b, int32_t t, int32_t hw,
                      int32_t heads, float scale, void* stream);
 

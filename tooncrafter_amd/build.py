@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libtooncrafter_hip.so")
-SOURCES = ["gemm.hip", "gemm_wide.hip", "gemm16.hip", "conv_halo.hip", "gemm8.hip", "ff_fused.hip", "tb_fused.hip", "qkv_attn.hip", "gemm_ws.hip", "gemm_mx.hip", "attention.hip", "attention_q8.hip", "norm.hip", "elementwise.hip"]
+SOURCES = ["gemm.hip", "gemm_wide.hip", "gemm16.hip", "conv_halo.hip", "gemm8.hip", "ff_fused.hip", "tb_fused.hip", "qkv_attn.hip", "gemm_ws.hip", "gemm_mx.hip", "attention.hip", "attention_temporal_long.hip", "attention_q8.hip", "norm.hip", "elementwise.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "gemm_epilogue.h"), os.path.join(CSRC, "gemm_persist.h"), os.path.join(CSRC, "conv_halo_index.h"),
            os.path.join(ROOT, "include", "tooncrafter_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on",
@@ -26,7 +26,8 @@ if os.environ.get("TC_TIMING_BUILDS") == "1":       # the timing-ablation / inte
 # per-source flags.  attention.hip: MFMA results straight into VGPRs (gfx950's register file is unified) -- by default
 # hipcc parks the score / output accumulators in AGPRs and the in-register softmax then pays 224 v_accvgpr_read/write
 # moves per 64-key tile
-EXTRA_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "attention_q8.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
+EXTRA_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "attention_q8.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+               "attention_temporal_long.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 
 
 def _hipcc() -> str:

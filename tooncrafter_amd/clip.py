@@ -21,6 +21,7 @@ from typing import List, Optional
 
 import torch
 
+from .lvdm.attention import check_frames
 from .lvdm.ddim import DDIMSampler
 from .lvdm.ddim_multiplecond import DDIMSampler as ThreeWaySampler
 
@@ -101,6 +102,7 @@ class SamplingPlan:
 
 def sample(model, cond: Conditions, plan: SamplingPlan, latent_shape, x_T=None):
     """Latents (b, 4, t, h, w) of one clip batch."""
+    check_frames(latent_shape[2])
     sampler = (ThreeWaySampler if cond.three_way else DDIMSampler)(model)
     extra = dict(plan.extra)
     x_T = extra.pop("x_T", x_T)                    # the reference's callers hand the start noise over among their **kwargs

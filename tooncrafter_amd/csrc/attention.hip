@@ -10,7 +10,8 @@
 // V^T fragments with the same permutation, so P never touches LDS.
 //
 // attn_temporal_kernel: 16-frame (or shorter) self-attention at every pixel; the whole
-// problem is 16x16x64 per (pixel, head), done on the VALU by one wave.
+// problem is 16x16x64 per (pixel, head), done on the VALU by one wave.  Longer clips (17 .. 64
+// frames) go to csrc/attention_temporal_long.hip.
 #include "gemm_common.h"
 
 #include <stdlib.h>
@@ -553,11 +554,18 @@ extern "C" int tc_attn_d64(const TcAttnParams* pp, void* stream) {
   return TC_OK;
 }
 
+// 17 .. TC_TEMPORAL_MAX_FRAMES frames: csrc/attention_temporal_long.hip (MFMA, frames padded to 32 | 64)
+int attn_temporal_long_launch(const bf16_t* qkv, bf16_t* out, int32_t b, int32_t t, int32_t hw, int32_t heads, float scale,
+                              hipStream_t stream);
+
 extern "C" int tc_attn_temporal(const tc_bf16* qkv, tc_bf16* out, int32_t b, int32_t t, int32_t hw,
                                 int32_t heads, float scale, void* stream) {
   if (!qkv || !out || b <= 0 || t <= 0 || hw <= 0 || heads <= 0) return TC_EINVAL;
-  if (t > 16) return TC_ESHAPE;
+  if (t > TC_TEMPORAL_MAX_FRAMES) return TC_ESHAPE;
   if (!tc_aligned16(qkv) || !tc_aligned16(out)) return TC_EALIGN;
+  if (t > 16)
+    return attn_temporal_long_launch(reinterpret_cast<const bf16_t*>(qkv), reinterpret_cast<bf16_t*>(out), b, t, hw, heads,
+                                     scale, reinterpret_cast<hipStream_t>(stream));
   const int64_t total = (int64_t)b * hw * heads;
   const int64_t nblk = (total + 3) / 4;
   if (nblk > 0x7fffffffLL) return TC_ESHAPE;

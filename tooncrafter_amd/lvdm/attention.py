@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from .._lib import ACT_GEGLU
+from .._lib import ACT_GEGLU, TC_TEMPORAL_MAX_FRAMES
 from .common import Act, CfgShare, PackedModule, SourceKey, f32, fold_layernorm, pack_geglu, pack_linear
 
 
@@ -199,7 +199,8 @@ class CrossAttention(PackedModule):
     def forward_temporal_self(self, x_norm, residual, act: Act, ln=None):
         pk = self.pk
         # levels 1-3: the fused projection and the 16 x 16 attentions as ONE launch (csrc/qkv_attn.hip, ABI 13) -- the
-        # [rows, 3C] tensor between them never reaches HBM; the library's own rule decides (16 frames, hw % 8 == 0)
+        # [rows, 3C] tensor between them never reaches HBM; the library's own rule decides (16 frames, hw % 8 == 0).
+        # Any other frame count takes the projection + tc_attn_temporal (17 .. 64 frames: csrc/attention_temporal_long.hip)
         fused = getattr(ops.backend(), "temporal_qkv_attn_eligible", None) if ln is None and torch.is_tensor(x_norm) else None
         if fused is not None and fused(b=act.b, t=act.t, hw=act.hw, c=x_norm.shape[1], heads=self.heads, ldx=x_norm.stride(0)):
             a = ops.temporal_qkv_attn(x_norm, pk["wqkv"], None, b=act.b, t=act.t, hw=act.hw, heads=self.heads, scale=self.scale)
@@ -395,6 +396,14 @@ class SpatialTransformer(PackedModule):
         return act.like(ops.gemm(h, pk["wo"], pk["bo"], residual=act.rows))
 
 
+def check_frames(t: int) -> None:
+    """The temporal self-attention (tc_attn_temporal) takes clips of 1 .. TC_TEMPORAL_MAX_FRAMES frames: a longer latent is
+    refused here, at the model / sampler entry, before anything is launched."""
+    if t > TC_TEMPORAL_MAX_FRAMES:
+        raise ValueError(f"a clip of {t} latent frames: the temporal attention supports at most "
+                         f"TC_TEMPORAL_MAX_FRAMES = {TC_TEMPORAL_MAX_FRAMES}")
+
+
 class TemporalTransformer(PackedModule):
     def __init__(self, in_channels, n_heads, d_head, depth=1, dropout=0., context_dim=None,
                  use_checkpoint=True, use_linear=False, only_self_att=True, causal_attention=False,
@@ -402,8 +411,9 @@ class TemporalTransformer(PackedModule):
         super().__init__()
         if not only_self_att or causal_attention or relative_position:
             raise NotImplementedError("only the non-causal self-attention temporal transformer of the config")
-        if temporal_length is not None and temporal_length > 16:
-            raise NotImplementedError("temporal attention kernel handles up to 16 frames")
+        if temporal_length is not None and temporal_length > TC_TEMPORAL_MAX_FRAMES:
+            raise ValueError(f"temporal_length {temporal_length}: the temporal attention supports at most "
+                             f"TC_TEMPORAL_MAX_FRAMES = {TC_TEMPORAL_MAX_FRAMES} frames")
         self.in_channels = in_channels
         inner = n_heads * d_head
         self.norm = nn.GroupNorm(32, in_channels, eps=1e-6, affine=True)

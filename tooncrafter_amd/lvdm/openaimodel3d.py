@@ -20,7 +20,7 @@ import torch.nn as nn
 
 from .. import ops
 from .._lib import ACT_SILU
-from .attention import ContextCache, SpatialTransformer, TemporalTransformer
+from .attention import ContextCache, SpatialTransformer, TemporalTransformer, check_frames
 from .common import Act, CfgShare, PackedModule, ceil_to, f32, pack_conv3x3, pack_convt3, pack_linear
 
 
@@ -366,6 +366,7 @@ class UNetModel(PackedModule):
             raise NotImplementedError("features_adapter is unused by the inference path")
         parts = x_parts if x_parts is not None else [x]
         b, _, t, hh, ww = parts[0].shape
+        check_frames(t)
         if replicas > 1 and (context is None or context.shape[0] != replicas * b):
             raise ValueError(f"replicas={replicas}: context must carry {replicas * b} samples")
         cin_pad = ceil_to(self.in_channels, 64)
