@@ -31,7 +31,7 @@ class EmuOps:
         self.tqa = tqa                       # tests only: offer the qkv + attention launch (ABI 13; library: wherever c = heads * 64, t = 16, hw % 8 == 0)
         self.tqa_calls = 0
         self.ln_fusion_k = ln_fusion_k       # tests only: accept a_norm_eps for EVERY consumer with this K.  The HIP library's
-                                             # default rule (csrc/gemm_ws.hip: ws_shape_ok, mode 1) is narrower: K = 320, N = 320,
+                                             # default rule (csrc/gemm_route.cpp: tc_gemm_ws_takes, mode 1) is narrower: K = 320, N = 320,
                                              # no GEGLU, M >= 65536 -- only the level-0 projections; TC_GEMM_WS=2 widens it to the
                                              # qkv / GEGLU consumers (tests/test_gpu_gemm_ws.py runs those)
         self.ln_fused_calls = 0

@@ -153,7 +153,7 @@ def test_repeated_launches_are_bit_identical(hip):
 
 
 def test_default_heuristic_takes_the_level1_ff2(hip, emu):
-    """The routing rule of tc_gemm8_try (one round of tiles, long K): same bits with and without it."""
+    """The 8-wave rule of tc_gemm_route (csrc/gemm_route.cpp: one round of tiles, long K): same bits with and without it."""
     m, n, k = 20480, 640, 2560
     a, w, bias = rnd(m, k, seed=61), rnd(n, k, seed=62, scale=k ** -0.5), rnd(n, seed=63, dtype=torch.float32)
     res = rnd(m, n, seed=64)

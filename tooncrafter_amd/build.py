@@ -16,8 +16,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libtooncrafter_hip.so")
-SOURCES = ["gemm.hip", "gemm_wide.hip", "gemm16.hip", "conv_halo.hip", "gemm8.hip", "ff_fused.hip", "tb_fused.hip", "qkv_attn.hip", "gemm_ws.hip", "gemm_mx.hip", "attention.hip", "attention_temporal_long.hip", "attention_q8.hip", "norm.hip", "elementwise.hip"]
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "gemm_epilogue.h"), os.path.join(CSRC, "gemm_persist.h"), os.path.join(CSRC, "conv_halo_index.h"),
+SOURCES = ["gemm_route.cpp", "gemm.hip", "gemm_wide.hip", "gemm16.hip", "conv_halo.hip", "gemm8.hip", "ff_fused.hip", "tb_fused.hip", "qkv_attn.hip", "gemm_ws.hip", "gemm_mx.hip", "attention.hip", "attention_temporal_long.hip", "attention_q8.hip", "norm.hip", "elementwise.hip"]
+HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "gemm_route.h"), os.path.join(CSRC, "gemm_epilogue.h"), os.path.join(CSRC, "gemm_persist.h"), os.path.join(CSRC, "conv_halo_index.h"),
            os.path.join(ROOT, "include", "tooncrafter_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on",
          "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
@@ -104,9 +104,11 @@ def build(force: bool = False, verbose: bool = True) -> str:
     procs = []
     objs = []
     for s in SOURCES:
-        o = os.path.join(objdir, s.replace(".hip", ".o"))
+        o = os.path.join(objdir, os.path.splitext(s)[0] + ".o")
         objs.append(o)
-        cmd = [hipcc, *FLAGS, *EXTRA_FLAGS.get(s, []), f'-DTC_SRC_DIGEST="{dig}"', "-c", os.path.join(CSRC, s), "-o", o]
+        # .cpp = host-only code (gemm_route.cpp): plain C++, nothing for the device
+        flags = FLAGS if s.endswith(".hip") else ["-x", "c++", *[f for f in FLAGS if not f.startswith("--offload-arch")]]
+        cmd = [hipcc, *flags, *EXTRA_FLAGS.get(s, []), f'-DTC_SRC_DIGEST="{dig}"', "-c", os.path.join(CSRC, s), "-o", o]
         if verbose:
             print("[build]", " ".join(cmd), flush=True)
         procs.append((s, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))

@@ -43,10 +43,6 @@
 
 #include "conv_halo_index.h"
 
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
 namespace {
 
 // every address formula of the kernel lives in conv_halo_index.h (namespace chx), shared with the host-side check
@@ -54,7 +50,7 @@ constexpr int CH_BN = chx::BN, CH_WT = chx::WT, CH_NT = chx::NT;
 constexpr int CH_HX = chx::HX;                             // halo patch width (16 + 2) for both geometries
 constexpr int CH_W_STAGE = chx::W_STAGE;                   // 20 KiB
 constexpr int CH_NV = chx::NV;                             // halo vectors per thread and chunk: ceil(216 * 8 / 256) = ceil(396 * 8 / 512)
-static_assert(chx::GATHER_3x3 == TC_GATHER_CONV3x3 && chx::GATHER_T3 == TC_GATHER_CONVT3 && chx::BK == TC_BK && chx::OOB == TC_OOB, "conv_halo_index.h");
+static_assert(chx::GATHER_3x3 == TC_GATHER_CONV3x3 && chx::GATHER_T3 == TC_GATHER_CONVT3 && chx::BK == TC_BK && chx::OOB == TC_OOB && chx::BN == TC_T16, "conv_halo_index.h");
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
 // WM = waves along M: 2 = the 160-row patch (PY = 10 patch rows, 4 waves, two blocks per CU); 4 = a TALL 320-row patch
@@ -305,105 +301,16 @@ __global__ __launch_bounds__(128 * WM * KS, (WM == 2 && KS == 1) ? 2 : 1) void c
   epi_pass(ic<4>{});
 }
 
-int conv_halo_mode() {        // TC_CONV_HALO = 0 never | 1 / unset: the measured routing | 2 strict (tests): whenever the shape allows, else FAIL; read per call
-  const char* e = getenv("TC_CONV_HALO");
-  return e ? atoi(e) : 1;
-}
-int conv_halo_ksplit() {      // TC_CONV_HALO_KSPLIT = 0: never | 1 / unset: launches of at most 256 patches-blocks (one per CU) | 2: whenever cin / 64 is even
-  const char* e = getenv("TC_CONV_HALO_KSPLIT");
-  return e ? atoi(e) : 1;
-}
-int conv_halo_tall() {        // TC_CONV_HALO_TALL = 0 / unset: 160-row patches | 1: 320-row patches where they fill the 256 CUs | 2: wherever they tile
-  const char* e = getenv("TC_CONV_HALO_TALL");
-  return e ? atoi(e) : 0;
-}
-
 }  // namespace
 
-// shape rules + launch.  1 = launched (or would be: dry), 0 = not this kernel's problem
-static int conv_halo_launch(const TcGemmParams& p, int batch, hipStream_t s, bool dry) {
-  if (p.gather != TC_GATHER_CONV3x3 && p.gather != TC_GATHER_CONVT3) return 0;
-  if (p.act == TC_ACT_GEGLU || p.gn_part || p.a_norm || (p.n % CH_BN) != 0 || (p.cin % TC_BK) != 0 ||
-      p.k != (p.gather == TC_GATHER_CONV3x3 ? 9 : 3) * p.cin) return 0;
-  const int hw = p.h_out * p.w_out;
-  int64_t tiles_m, tiles_tall = 0;                                       // 160-row patches; 320-row patches (0: do not tile)
-  if (p.gather == TC_GATHER_CONV3x3) {
-    if (p.stride != 1 || p.upsample || p.pad != 1 || p.h_in != p.h_out || p.w_in != p.w_out) return 0;
-    if ((p.h_out % 10) != 0 || (p.w_out % 16) != 0) return 0;
-    tiles_m = (int64_t)p.frames * (p.h_out / 10) * (p.w_out / 16);
-    if ((p.h_out % 20) == 0) tiles_tall = tiles_m / 2;
-  } else {
-    if (p.t_len != 16 || (p.frames % 16) != 0 || (hw % 10) != 0) return 0;
-    tiles_m = (int64_t)(p.frames / 16) * (hw / 10);
-    if ((hw % 20) == 0) tiles_tall = tiles_m / 2;
-    if ((int64_t)17 * hw * p.lda * 2 >= 0x7fffff00LL) return 0;          // a patch spans the clip's 16 frames: 31-bit offsets
-  }
-  if (tiles_m * 160 != p.m) return 0;
-  const int tiles_n = p.n / CH_BN;
-  const int tall = conv_halo_tall();
-  const bool use_tall = tiles_tall > 0 && (tall == 2 || (tall == 1 && tiles_tall * tiles_n * batch >= 256));
-  const int64_t tm = use_tall ? tiles_tall : tiles_m;
-  const int64_t nblk = (int64_t)tiles_n * 8 * ((tm + 7) / 8);
-  if (nblk > 0x7fffffffLL || batch > 65535) return 0;
-  if (dry) return 1;
-  dim3 grid((unsigned)nblk, 1, (unsigned)batch);
-  const int order = tc_gemm_tile_order(p, tiles_n);
-  const int ksm = conv_halo_ksplit();
-  const int nchunks = p.cin / TC_BK;
-  const bool ksplit = !use_tall && (nchunks % 2) == 0 && nchunks >= 4 &&
-                      (ksm == 2 || (ksm == 1 && tiles_m * tiles_n * batch <= 256));
-#define TC_LAUNCH_HALO(G, WM_, KS_, T_) hipLaunchKernelGGL((conv_halo_kernel<G, WM_, KS_>), grid, dim3(T_), 0, s, p, order)
-  if (use_tall) {
-    if (p.gather == TC_GATHER_CONV3x3) TC_LAUNCH_HALO(TC_GATHER_CONV3x3, 4, 1, 512);
-    else TC_LAUNCH_HALO(TC_GATHER_CONVT3, 4, 1, 512);
-  } else if (ksplit) {
-    if (p.gather == TC_GATHER_CONV3x3) TC_LAUNCH_HALO(TC_GATHER_CONV3x3, 2, 2, 512);
-    else TC_LAUNCH_HALO(TC_GATHER_CONVT3, 2, 2, 512);
-  } else {
-    if (p.gather == TC_GATHER_CONV3x3) TC_LAUNCH_HALO(TC_GATHER_CONV3x3, 2, 1, 256);
-    else TC_LAUNCH_HALO(TC_GATHER_CONVT3, 2, 1, 256);
-  }
-#undef TC_LAUNCH_HALO
-  return 1;
-}
-
-// Decide whether the tap-reuse kernel takes this (already validated) convolution, and launch it.  1 = launched, 0 = not
-// taken, -1 = TC_CONV_HALO=2 ("strict", the parity tests) and a convolution was NOT taken: the caller fails the call, so a
-// test that passes under mode 2 has provably run this kernel and not a fallback.
-// Mode 1 (the default) is the measured routing: the 3x3 convolutions (1.03-1.27x), not the temporal ones (0.5-0.99x) unless
-// TC_CONV_HALO_T3=1; TC_CONV_HALO_3X3=0 keeps the 3x3 ones on the implicit GEMM as well (A/B runs).
-int tc_conv_halo_try(const TcGemmParams& p, int batch, hipStream_t s, bool dry) {
-  const int mode = conv_halo_mode();
-  if (mode == 0) return 0;
-  if (p.gather != TC_GATHER_CONV3x3 && p.gather != TC_GATHER_CONVT3) return 0;
-  if (mode == 1) {
-    // a switch that selects among the IMPLICIT-GEMM kernels names the kernel under test / under measurement: keep out of its way
-    // -- but only when it actually FORCES something, i.e. carries a value other than its default (an A/B script that
-    // exports `TC_GEMM8=1` for one arm had every 3x3 convolution moved to another kernel in BOTH arms, silently -- round 6's
-    // switch sweep ran into exactly that), and say so, once, when it happens
-    struct Sw { const char* name; const char* dflt; };            // dflt == nullptr: any value forces
-    static const Sw sws[] = {{"TC_GEMM_TILE16", "1"}, {"TC_GEMM8", "1"}, {"TC_GEMM_PIPE", "1"}, {"TC_GEMM_SPLITK", nullptr}, {"TC_GEMM_WS", "1"},
-                             {"TC_G16_ILV", nullptr}, {"TC_G16_TALL", "0"}, {"TC_GEMM_WIDE", "1"}, {"TC_GEMM_ORDER", "8"}, {"TC_GEMM_NMAJOR", "1"}};
-    for (const Sw& sw : sws) {
-      const char* e = getenv(sw.name);
-      if (e && e[0] && !(sw.dflt && strcmp(e, sw.dflt) == 0)) {
-        static bool said = false;
-        if (!said && !dry) {
-          said = true;
-          fprintf(stderr, "[tooncrafter_hip] %s=%s is set: the 3x3 convolutions stay on the implicit-GEMM kernels "
-                          "(halo-patch route suppressed; TC_CONV_HALO=2 forces it)\n", sw.name, e);
-        }
-        return 0;
-      }
-    }
-    if (p.gather == TC_GATHER_CONV3x3) {
-      const char* e = getenv("TC_CONV_HALO_3X3");
-      if (e && e[0] == '0') return 0;
-    } else {
-      const char* e = getenv("TC_CONV_HALO_T3");
-      if (!(e && e[0] == '1')) return 0;
-    }
-  }
-  const int r = conv_halo_launch(p, batch, s, dry);
-  return r ? 1 : (mode == 2 ? -1 : 0);
+void tc_conv_halo_launch(const TcGemmParams& p, const TcGemmRoute& r, hipStream_t s) {
+  const dim3 grid(r.grid[0], r.grid[1], r.grid[2]), block(r.block);
+  const auto go = [&](auto g) {
+    constexpr int G = decltype(g)::value;
+    if (r.wm == 4) hipLaunchKernelGGL((conv_halo_kernel<G, 4, 1>), grid, block, 0, s, p, r.order);
+    else if (r.ks == 2) hipLaunchKernelGGL((conv_halo_kernel<G, 2, 2>), grid, block, 0, s, p, r.order);
+    else hipLaunchKernelGGL((conv_halo_kernel<G, 2, 1>), grid, block, 0, s, p, r.order);
+  };
+  if (p.gather == TC_GATHER_CONV3x3) go(std::integral_constant<int, TC_GATHER_CONV3x3>{});      // two gathers only: no linear form
+  else go(std::integral_constant<int, TC_GATHER_CONVT3>{});
 }

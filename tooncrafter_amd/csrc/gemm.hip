@@ -25,9 +25,7 @@
 #include "gemm_common.h"
 #include "gemm_epilogue.h"
 
-#include <stdlib.h>
-
-#include <type_traits>
+#include <stdio.h>
 
 namespace {
 
@@ -353,197 +351,41 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const TcGemmParams p
 
 }  // namespace
 
-// Split-K factor (1 = no split).  Candidates: one problem (no batching), vector epilogue, no GEGLU, so few
-// 128x128 tiles that most of the 512 block slots (2 per CU) would idle, and a K long enough to pay for
-// the partial tiles and the reduction pass (~12 us): measured on the M = 1280 layers
-// (profiles/r01_v6_gemm_splitk.txt) the 3x3 convolutions (K = 11520 / 23040) gain 1.28x / 1.51x over
-// their 64x64-tile launch, while K <= 5120 (linear, temporal conv) loses -- those keep the 64x64 tiles.
-// TC_GEMM_SPLITK=n forces n (tuning), 0 disables.
-static int tc_gemm_splits(const TcGemmParams& p) {
-  const int force = [] { const char* e = getenv("TC_GEMM_SPLITK"); return e ? atoi(e) : -1; }();     // per call (sweeps)
-  const int batch = p.batch > 0 ? p.batch : 1;
-  if (force == 0 || batch != 1 || p.act == TC_ACT_GEGLU || (p.n & 7) != 0) return 1;
-  const int nk = (p.k + BK - 1) / BK;
-  const int64_t tiles = (int64_t)((p.n + 127) / 128) * ((p.m + 127) / 128);
-  if (tiles >= 200 || (force < 0 && nk < 128)) return 1;
-  int s = force > 0 ? force : (int)(512 / tiles);
-  if (s > 8) s = 8;
-  if (s > nk / 8) s = nk / 8;
-  // a power of two: at 100 tiles (the level-3 convolutions) 4 slices measured 1.33-1.41x faster than 5
-  // (profiles/r03_gemm_autotune_unet.txt: 61.5 vs 82.3 us at K = 11520, 101.9 vs 143.9 us at K = 23040)
-  if (force <= 0) while (s & (s - 1)) s &= s - 1;
-  return s < 2 ? 1 : s;
+static void tc_gemm_tile_launch(const TcGemmParams& p, const TcGemmRoute& r, hipStream_t s) {
+  const dim3 grid(r.grid[0], r.grid[1], r.grid[2]), block(r.block);
+  const auto go = [&](auto g, auto pipe) {
+    constexpr int G = decltype(g)::value, P = decltype(pipe)::value;
+    if (r.tm == 2 && r.tn == 2) hipLaunchKernelGGL((gemm_kernel<G, 2, 2, P>), grid, block, 0, s, p, r.splits, r.order, r.late_epi);
+    else if (r.tm == 2) hipLaunchKernelGGL((gemm_kernel<G, 2, 1, P>), grid, block, 0, s, p, r.splits, r.order, r.late_epi);
+    else if (r.tn == 2) hipLaunchKernelGGL((gemm_kernel<G, 1, 2, P>), grid, block, 0, s, p, r.splits, r.order, r.late_epi);
+    else hipLaunchKernelGGL((gemm_kernel<G, 1, 1, P>), grid, block, 0, s, p, r.splits, r.order, r.late_epi);
+  };
+  tc_with_gather(p.gather, [&](auto g) { if (r.pipe) go(g, std::true_type{}); else go(g, std::false_type{}); });
 }
 
-extern "C" int64_t tc_gemm_workspace(const TcGemmParams* p) {
-  if (!p || p->m <= 0 || p->n <= 0 || p->k <= 0) return 0;
-  const int s = tc_gemm_splits(*p);
-  return s > 1 ? (int64_t)s * p->m * p->n * (int64_t)sizeof(float) : 0;
-}
-
-// Tile family for the 4-wave kernel: (64 tm) x (64 tn).  The sweep (profiles/r01_v6_gemm_tile_sweep.txt)
-// has 128x128 ahead on every UNet/decoder shape -- 128x64 and 64x128 lose 5-45 % to their higher LDS/L1
-// traffic per FLOP even where they would fill the CUs more evenly -- except the lowest-resolution layers
-// (M = 1280 rows), whose 100 128-tiles leave most of the 256 CUs idle: those take 64x64 (+32-37 %).
-static void tc_gemm_pick_tile(int m, int n, int batch, bool geglu, int* tm, int* tn) {
-  const int64_t big_tiles = (int64_t)((n + 127) / 128) * ((m + 127) / 128) * batch;
-  const bool small = !geglu && big_tiles < 384;
-  *tm = small ? 1 : 2;
-  *tn = small ? 1 : 2;
-  // the 3- / 4-channel output convolutions: a 64-column tile wastes half as many MFMAs on padding (measured,
-  // profiles/r03_gemm_autotune_*.txt: decoder conv_out 1362 -> 701 us with 128x64, UNet out 106 -> 67 us with 64x64)
-  if (!geglu && n <= 64) {
-    *tn = 1;
-    *tm = m >= 262144 ? 2 : 1;
-  }
-}
-
-// ABI 9: row-block height of gn_part under the routing tc_gemm_bf16 would take (same order of the same questions)
-extern "C" int tc_gemm_gn_rows(const TcGemmParams* pp) {
-  if (!pp) return 0;
-  const TcGemmParams& p = *pp;
-  const int batch = p.batch > 0 ? p.batch : 1;
-  if (batch != 1 || p.act == TC_ACT_GEGLU || p.out_f32 || (p.n & 7) != 0 || p.a_norm || p.m <= 0 || p.n <= 0 || p.k <= 0) return 0;
-  if (getenv("TC_GEMM_TILE") && getenv("TC_GEMM_TILE")[0]) return 0;          // forced tile families: tuning runs only
-  if (const char* e = getenv("TC_GN_PART")) { if (e[0] == '0') return 0; }    // A/B switch: never emit
-  if (tc_gemm_ws_try(p, batch, nullptr, true)) return 0;
-  // (no question to the halo-patch kernel: it emits no statistics, and tc_gemm_bf16 sets it aside for a call that carries
-  // gn_part -- so TC_GN_PART=1 measures what profiles/r04_gn_part_ab.txt measured, producer statistics from every
-  // 160 / 128-tile convolution, and not only from the few the halo route leaves over: ADVICE r5)
-  if (tc_gemm8_try(p, batch, nullptr, true)) return 0;
-  if (tc_gemm_tile16_try(p, batch, nullptr, true)) return 160;
-  if (tc_gemm_wide_try(p, batch, nullptr, false, true)) return 0;
-  if (p.workspace && tc_gemm_splits(p) > 1 &&
-      p.workspace_bytes >= (int64_t)tc_gemm_splits(p) * p.m * p.n * (int64_t)sizeof(float)) return 0;
-  int tm, tn;
-  tc_gemm_pick_tile(p.m, p.n, batch, false, &tm, &tn);
-  return (tm == 2 && tn == 2) ? 128 : 0;
-}
-
+// Where the call goes is decided in gemm_route.cpp; here: validate, route, launch.
 extern "C" int tc_gemm_bf16(const TcGemmParams* pp, void* stream) {
   if (!pp) return TC_EINVAL;
   const TcGemmParams& p = *pp;
-  if (!p.a || !p.w || !p.c || p.m <= 0 || p.n <= 0 || p.k <= 0) return TC_EINVAL;
-  if (!tc_aligned16(p.a) || !tc_aligned16(p.w) || !tc_aligned16(p.c)) return TC_EALIGN;
-  if (p.residual && !tc_aligned16(p.residual)) return TC_EALIGN;
-  if ((p.k & 7) || (p.lda & 7) || (p.ldw & 7)) return TC_EALIGN;
-  if (p.ldw < p.k) return TC_ESHAPE;
-  const bool geglu = p.act == TC_ACT_GEGLU;
-  const int n_out = geglu ? p.n / 2 : p.n;
-  if ((n_out & 7) == 0) {
-    if (p.out_f32 ? (p.ldc & 3) : (p.ldc & 7)) return TC_EALIGN;
-    if (p.residual && (p.ldr & 7)) return TC_EALIGN;
-    if (p.bias && (reinterpret_cast<uintptr_t>(p.bias) & 15u)) return TC_EALIGN;
-    if (p.row_bias && ((reinterpret_cast<uintptr_t>(p.row_bias) & 15u) || (p.ldrb & 3))) return TC_EALIGN;
+  if (const int rc = tc_gemm_validate(p)) return rc;
+  static const int cus = [] { int d = 0, n = 256; if (hipGetDevice(&d) == hipSuccess) hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n; }();
+  const TcGemmSwitches sw = tc_gemm_switches();
+  TcGemmRoute r;
+  const int rc = tc_gemm_route(p, sw, cus, &r);
+  static bool said = false;
+  if (r.halo_yielded && !said) {          // say so, once, when a tuning switch moves the convolutions to another kernel
+    said = true;
+    fprintf(stderr, "[tooncrafter_hip] %s=%s is set: the 3x3 convolutions stay on the implicit-GEMM kernels "
+                    "(halo-patch route suppressed; TC_CONV_HALO=2 forces it)\n", sw.forcing_name, sw.forcing_value);
   }
-  if (p.ldc < n_out || (p.residual && p.ldr < n_out)) return TC_ESHAPE;
-  if (geglu && ((p.n % 128) != 0 || p.row_bias || p.residual)) return TC_ESHAPE;
-  if (p.row_bias && (p.row_div <= 0 || p.ldrb < p.n)) return TC_EINVAL;
-  if (p.act < TC_ACT_NONE || p.act > TC_ACT_GEGLU) return TC_EINVAL;
-  const int batch = p.batch > 0 ? p.batch : 1;
-  if (p.gather == TC_GATHER_LINEAR) {
-    if (p.lda < p.k) return TC_ESHAPE;
-  } else if (p.gather == TC_GATHER_CONV3x3 || p.gather == TC_GATHER_CONVT3) {
-    const int taps = p.gather == TC_GATHER_CONV3x3 ? 9 : 3;
-    if (p.cin <= 0 || (p.cin % 64) != 0 || p.k != taps * p.cin || p.lda < p.cin) return TC_ESHAPE;
-    if (p.frames <= 0 || p.h_out <= 0 || p.w_out <= 0) return TC_ESHAPE;
-    if ((int64_t)p.frames * p.h_out * p.w_out != p.m) return TC_ESHAPE;
-    if (p.gather == TC_GATHER_CONV3x3) {
-      if (p.h_in <= 0 || p.w_in <= 0 || (p.stride != 1 && p.stride != 2)) return TC_ESHAPE;
-      if (p.upsample && p.stride != 1) return TC_ESHAPE;
-      const int hvv = p.upsample ? 2 * p.h_in : p.h_in, wvv = p.upsample ? 2 * p.w_in : p.w_in;
-      if (p.pad != 0 && p.pad != 1) return TC_ESHAPE;
-      // pad = 1: symmetric padding 1; pad = 0: one trailing row/column of zeros only (0,1,0,1)
-      const int extra = p.pad == 1 ? 2 : 1;
-      if ((hvv + extra - 3) / p.stride + 1 != p.h_out || (wvv + extra - 3) / p.stride + 1 != p.w_out) return TC_ESHAPE;
-    } else {
-      if (p.t_len <= 0 || (p.frames % p.t_len) != 0) return TC_ESHAPE;
-    }
-  } else {
-    return TC_EINVAL;
-  }
-  if (!tc_gemm_offsets_fit(p)) return TC_ESHAPE;          // buffer-load offsets are 31-bit
-  if (p.gn_part && tc_gemm_gn_rows(&p) == 0) return TC_ESHAPE;          // the kernel of this problem emits no statistics
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  // TC_GEMM_TILE = wide | 22 | 21 | 12 | 11 forces one tile family (tuning / A-B runs); default: heuristic
-  const int force = [] {                                   // per call (scripts/gemm_autotune.py sweeps it in one process)
-    const char* e = getenv("TC_GEMM_TILE");
-    if (!e) return 0;
-    if (e[0] == 'w') return 1;
-    if (e[0] == 'b') return 22;
-    if (e[0] == 's') return 11;
-    const int v = atoi(e);
-    return (v == 22 || v == 21 || v == 12 || v == 11) ? v : 0;
-  }();
-  if (force == 0 && tc_gemm_ws_try(p, batch, s)) {                     // K = 320 linear layers of level 0: W in registers
-    TC_LAUNCH_CHECK();
-    return TC_OK;
-  }
-  if (p.a_norm) return TC_ESHAPE;                                      // only the weight-stationary kernel normalises A rows
-  if (force == 0 && !p.gn_part) {                                      // tap-reuse patches: the default route of the 3x3 convolutions of levels 0-2 (TC_CONV_HALO=0: never); a call that asks for producer statistics keeps the implicit GEMM, whose epilogue emits them
-    const int r = tc_conv_halo_try(p, batch, s);
-    if (r < 0) return TC_ESHAPE;                                       // strict mode (tests): a convolution it could not take
-    if (r > 0) {
-      TC_LAUNCH_CHECK();
-      return TC_OK;
-    }
-  }
-  if (force == 0 && tc_gemm8_try(p, batch, s)) {                       // long-K / wide-N problems: 8-wave 256x256 ping-pong
-    TC_LAUNCH_CHECK();
-    return TC_OK;
-  }
-  if (force == 0 && tc_gemm_tile16_try(p, batch, s)) {                 // widths 320 k at levels 0 / 1: 160x160 tiles
-    TC_LAUNCH_CHECK();
-    return TC_OK;
-  }
-  if (force <= 1 && tc_gemm_wide_try(p, batch, s, force == 1)) {       // big-M layers: 256-row tiles
-    TC_LAUNCH_CHECK();
-    return TC_OK;
-  }
-  int tm = 2, tn = 2;
-  int splits = (p.workspace && force == 0) ? tc_gemm_splits(p) : 1;
-  if (splits > 1 && p.workspace_bytes < (int64_t)splits * p.m * p.n * (int64_t)sizeof(float)) splits = 1;
-  if (splits > 1 && !tc_aligned16(p.workspace)) return TC_EALIGN;
-  if (force > 1) {
-    tm = force / 10;
-    tn = geglu ? 2 : force % 10;
-  } else if (splits == 1) {
-    tc_gemm_pick_tile(p.m, p.n, batch, geglu, &tm, &tn);
-  }
-  const int bm = 64 * tm, bn = 64 * tn;
-  const int tiles_n = (p.n + bn - 1) / bn;
-  const int tiles_m = (p.m + bm - 1) / bm;
-  const bool nmajor = tc_gemm_nmajor(p);
-  const int64_t nblk = nmajor ? 8 * (((int64_t)tiles_m * tiles_n + 7) / 8) : (int64_t)tiles_n * 8 * ((tiles_m + 7) / 8);
-  if (nblk > 0x7fffffffLL || batch > 65535) return TC_ESHAPE;
-  dim3 grid((unsigned)nblk, (unsigned)splits, (unsigned)batch), block(256);
-  const int order = nmajor ? -1 : tc_gemm_tile_order(p, tiles_n);
-  // TC_GEMM_PIPE = 0: the one-K-step-in-flight loop; 1 (default): two in flight (read per call: A/B in one process)
-  const bool pipe = [] { const char* e = getenv("TC_GEMM_PIPE"); return !(e && e[0] == '0'); }();
-  const int late_epi = [] { const char* e = getenv("TC_GEMM_EPI_LATE"); return (e && e[0] == '1') ? 1 : 0; }();
-#define TC_LAUNCH_GEMM_P(G, P)                                                                      \
-  do {                                                                                              \
-    if (tm == 2 && tn == 2) hipLaunchKernelGGL((gemm_kernel<G, 2, 2, P>), grid, block, 0, s, p, splits, order, late_epi);   \
-    else if (tm == 2) hipLaunchKernelGGL((gemm_kernel<G, 2, 1, P>), grid, block, 0, s, p, splits, order, late_epi);         \
-    else if (tn == 2) hipLaunchKernelGGL((gemm_kernel<G, 1, 2, P>), grid, block, 0, s, p, splits, order, late_epi);         \
-    else hipLaunchKernelGGL((gemm_kernel<G, 1, 1, P>), grid, block, 0, s, p, splits, order, late_epi);                      \
-  } while (0)
-#define TC_LAUNCH_GEMM(G)                                                                           \
-  do {                                                                                              \
-    if (pipe) TC_LAUNCH_GEMM_P(G, true);                                                            \
-    else TC_LAUNCH_GEMM_P(G, false);                                                                \
-  } while (0)
-  switch (p.gather) {
-    case TC_GATHER_LINEAR: TC_LAUNCH_GEMM(TC_GATHER_LINEAR); break;
-    case TC_GATHER_CONV3x3: TC_LAUNCH_GEMM(TC_GATHER_CONV3x3); break;
-    default: TC_LAUNCH_GEMM(TC_GATHER_CONVT3); break;
-  }
-#undef TC_LAUNCH_GEMM
-#undef TC_LAUNCH_GEMM_P
+  if (rc != TC_OK) return rc;
+  static TcGemmLaunch* const launch[] = {tc_gemm_ws_launch, tc_conv_halo_launch, tc_gemm8_launch, tc_gemm_tile16_launch,
+                                         tc_gemm_wide_launch, tc_gemm_tile_launch};          // indexed by TcGemmFamily
+  launch[r.family](p, r, reinterpret_cast<hipStream_t>(stream));
   TC_LAUNCH_CHECK();
-  if (splits > 1) {
+  if (r.family == TC_FAM_TILE && r.splits > 1) {
     const int64_t vecs = (int64_t)p.m * (p.n >> 3);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((vecs + 255) / 256)), dim3(256), 0, s, p, splits);
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((vecs + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, r.splits);
     TC_LAUNCH_CHECK();
   }
   return TC_OK;

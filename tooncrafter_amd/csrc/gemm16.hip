@@ -20,11 +20,9 @@
 
 #include <stdlib.h>
 
-#include <type_traits>
-
 namespace {
 
-constexpr int T16_BM = 160, T16_BN = 160;
+constexpr int T16_BM = TC_T16, T16_BN = TC_T16;
 constexpr int T16_STAGE = (T16_BM + T16_BN) * TC_BK * 2;     // 40 KiB
 constexpr int T16_R = T16_BM / 32;                           // loader passes of 32 rows: 5 (A) + 5 (W)
 constexpr int T16_WT = 80;                                   // wave tile
@@ -444,115 +442,34 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void gemm16_kernel(const
   }
 }
 
-int tile16_mode() {        // TC_GEMM_TILE16 = 0 never | 1 heuristic (default) | 2 whenever the shape allows
-  const char* e = getenv("TC_GEMM_TILE16");     // read per call: the parity tests flip it inside one process
-  return e ? atoi(e) : 1;
-}
-
 }  // namespace
 
-// Decide whether the 160x160 kernel should take this (already validated) GEMM, and launch it.  1 = launched.
-int tc_gemm_tile16_try(const TcGemmParams& p, int batch, hipStream_t s, bool dry) {
-  const int mode = tile16_mode();
-  if (mode == 0 || p.act == TC_ACT_GEGLU || (p.n % T16_BN) != 0) return 0;
-  const int tiles_n = p.n / T16_BN;
-  const int tiles_m = (p.m + T16_BM - 1) / T16_BM;
-  const int64_t tiles = (int64_t)tiles_n * tiles_m * batch;
-  if (mode == 1) {
-    // worth it where the 160-grid quantises better than the 128-grid onto the 512 resident block slots:
-    // efficiency = useful work / (whole rounds of 512 blocks x padded tile area)
-    const int64_t t128 = (int64_t)((p.n + 127) / 128) * ((p.m + 127) / 128) * batch;
-    const double eff16 = (double)tiles / (double)((tiles + 511) / 512 * 512) * ((double)p.m / ((double)tiles_m * T16_BM));
-    const double eff128 = (double)t128 / (double)((t128 + 511) / 512 * 512) *
-                          ((double)p.n / (double)((p.n + 127) / 128 * 128)) *
-                          ((double)p.m / (double)((p.m + 127) / 128 * 128));
-    // measured (profiles/r02_tile16_ab.txt, r02_tile16_cold_sustained.txt): 3x3 / temporal convolutions gain
-    // 1.12-1.32x (cache-hot, cache-cold and sustained alike), K >= 1280 linear layers 1.0-1.18x, short-K projections
-    // (K <= 640: five-pass epilogue per 160x160 tile against 5-10 K-steps) LOSE 8-18 %.  The heuristic takes the
-    // convolutions only: the linear layers' gain is within the run-to-run spread of a whole clip.
-    if (tiles < 512 || eff16 < eff128 + 0.04 || p.k < 960 || p.gather == TC_GATHER_LINEAR) return 0;
-  }
-  const int64_t nblk = (int64_t)tiles_n * 8 * ((tiles_m + 7) / 8);
-  if (nblk > 0x7fffffffLL) return 0;
-  if (dry) return 1;
-  dim3 grid((unsigned)nblk, 1, (unsigned)batch), block(256);
-  const int order = tc_gemm_tile_order(p, tiles_n);
-  const bool stats = p.gn_part != nullptr;
-  // TC_GEMM_PIPE = 2 only: on this tile the deeper prefetch measured 0.97-1.02x (profiles/r03_pipe_bench.txt) -- two
-  // blocks of 80 KiB per CU already overlap each other's load latency -- so the default keeps the plain loop
-  const bool pipe = [] { const char* e = getenv("TC_GEMM_PIPE"); return e && e[0] == '2'; }();      // per call (A/B runs)
+void tc_gemm_tile16_launch(const TcGemmParams& p, const TcGemmRoute& r, hipStream_t s) {
+  const dim3 grid(r.grid[0], r.grid[1], r.grid[2]), block(r.block);
+  const int order = r.order;
 #ifdef TC_TIMING_BUILDS      /* timing ablations: WRONG results by construction, never in the product library */
   const int abl = [] { const char* e = getenv("TC_G16_ABLATE"); return e ? atoi(e) : 0; }();             // per call (timing runs)
-  if (abl >= 1 && abl <= 4 && p.gather == TC_GATHER_CONV3x3 && !stats) {
-    if (abl == 1) hipLaunchKernelGGL((gemm16_kernel<TC_GATHER_CONV3x3, false, false, 1>), grid, block, 0, s, p, order);
-    if (abl == 2) hipLaunchKernelGGL((gemm16_kernel<TC_GATHER_CONV3x3, false, false, 2>), grid, block, 0, s, p, order);
-    if (abl == 3) hipLaunchKernelGGL((gemm16_kernel<TC_GATHER_CONV3x3, false, false, 3>), grid, block, 0, s, p, order);
-    if (abl == 4) hipLaunchKernelGGL((gemm16_kernel<TC_GATHER_CONV3x3, false, false, 4>), grid, block, 0, s, p, order);
-    return 1;
+  if (abl >= 1 && abl <= 4 && p.gather == TC_GATHER_CONV3x3 && !p.gn_part) {
+    const int tiles_m = (p.m + T16_BM - 1) / T16_BM;
+    const dim3 g2((unsigned)((int64_t)(p.n / T16_BN) * 8 * ((tiles_m + 7) / 8)), 1, r.grid[2]), b2(256);      // the 160-row tile's grid
+    if (abl == 1) hipLaunchKernelGGL((gemm16_kernel<TC_GATHER_CONV3x3, false, false, 1>), g2, b2, 0, s, p, order);
+    if (abl == 2) hipLaunchKernelGGL((gemm16_kernel<TC_GATHER_CONV3x3, false, false, 2>), g2, b2, 0, s, p, order);
+    if (abl == 3) hipLaunchKernelGGL((gemm16_kernel<TC_GATHER_CONV3x3, false, false, 3>), g2, b2, 0, s, p, order);
+    if (abl == 4) hipLaunchKernelGGL((gemm16_kernel<TC_GATHER_CONV3x3, false, false, 4>), g2, b2, 0, s, p, order);
+    return;
   }
 #endif
-  // TC_G16_ILV: requests between the MFMAs (see the kernel header).  Unset = loop 2 for the convolutions, the plain loop
-  // for linear problems (measured, profiles/r04_g16_tall_ilv_bench.txt: 3x3 / temporal convolutions 1.01-1.03x on the
-  // 160-row tile, linear 0.98-1.02x; inside the UNet 8.29 / 8.30 against 8.27 / 8.28 frames/s, alternating on one lease:
-  // profiles/r04_clip_ab_g16.txt); 0 = never; 1 | 2 = that loop wherever it can run.  Read per call (A/B runs).
-  const bool ilv_ok = (p.gather == TC_GATHER_LINEAR || ((p.cin % TC_BK) == 0 && p.cin <= 4096)) && p.k < 1024 * TC_BK &&
-                      (p.gather != TC_GATHER_CONV3x3 || (p.stride == 1 && !p.upsample && p.pad == 1));
-  const int ilv = [&] { const char* e = getenv("TC_G16_ILV"); return e ? atoi(e) : (p.gather != TC_GATHER_LINEAR ? 2 : 0); }();
-  // TC_G16_TALL: the 320 x 160 tile on eight waves (WM = 4), one block per CU.  0 (default) = never; 1 = convolutions whose
-  // tall tiles fill whole rounds of the 256 CUs as well as the 160-row tiles fill their 512 slots (levels 0 / 1 of the
-  // UNet); 2 = whenever the shape allows.  OFF although it wins kernel by kernel (with loop 2: level 0 1.035-1.06x, level
-  // 1 1.09x; level 2 has 128 tall tiles: 0.8x; linear problems 0.94-1.05x): inside the UNet, alternating on one lease, it
-  // LOSES 0.8 % of a clip (8.22 vs 8.27-8.29 frames/s, and 7.32 vs 7.38 together with loop 2:
-  // profiles/r04_clip_ab_g16.txt) -- one 8-wave block per CU has nothing to fill its ramp and tail with.
-  const int tall = [] { const char* e = getenv("TC_G16_TALL"); return e ? atoi(e) : 0; }();
-  if (tall >= 1 && !stats && (ilv == 0 || ilv_ok) && (tall == 2 || p.gather != TC_GATHER_LINEAR)) {
-    const int tm4 = (p.m + 2 * T16_BM - 1) / (2 * T16_BM);
-    const int64_t t4 = (int64_t)tiles_n * tm4 * batch;
-    const double e4 = (double)t4 / (double)((t4 + 255) / 256 * 256) * ((double)p.m / ((double)tm4 * 2 * T16_BM));
-    const double e2 = (double)tiles / (double)((tiles + 511) / 512 * 512) * ((double)p.m / ((double)tiles_m * T16_BM));
-    if (tall == 2 || (t4 >= 256 && e4 >= e2 - 0.02)) {
-      const int64_t nb4 = (int64_t)tiles_n * 8 * ((tm4 + 7) / 8);
-      dim3 grid4((unsigned)nb4, 1, (unsigned)batch), block4(512);
-#define TC_LAUNCH16_TALL(G)                                                                                          \
-  do {                                                                                                               \
-    if (ilv == 1) hipLaunchKernelGGL((gemm16_kernel<G, false, false, 0, 1, 4>), grid4, block4, 0, s, p, order);      \
-    else if (ilv == 2) hipLaunchKernelGGL((gemm16_kernel<G, false, false, 0, 2, 4>), grid4, block4, 0, s, p, order); \
-    else hipLaunchKernelGGL((gemm16_kernel<G, false, false, 0, 0, 4>), grid4, block4, 0, s, p, order);               \
-  } while (0)
-      switch (p.gather) {
-        case TC_GATHER_LINEAR: TC_LAUNCH16_TALL(TC_GATHER_LINEAR); break;
-        case TC_GATHER_CONV3x3: TC_LAUNCH16_TALL(TC_GATHER_CONV3x3); break;
-        default: TC_LAUNCH16_TALL(TC_GATHER_CONVT3); break;
-      }
-#undef TC_LAUNCH16_TALL
-      return 1;
+  tc_with_gather(p.gather, [&](auto g) {
+    constexpr int G = decltype(g)::value;
+    if (r.wm == 4) {
+      if (r.ilv == 1) hipLaunchKernelGGL((gemm16_kernel<G, false, false, 0, 1, 4>), grid, block, 0, s, p, order);
+      else if (r.ilv == 2) hipLaunchKernelGGL((gemm16_kernel<G, false, false, 0, 2, 4>), grid, block, 0, s, p, order);
+      else hipLaunchKernelGGL((gemm16_kernel<G, false, false, 0, 0, 4>), grid, block, 0, s, p, order);
     }
-  }
-  if ((ilv == 1 || ilv == 2) && !stats && ilv_ok) {
-#define TC_LAUNCH16_ILV(G)                                                                                       \
-  do {                                                                                                           \
-    if (ilv == 1) hipLaunchKernelGGL((gemm16_kernel<G, false, false, 0, 1>), grid, block, 0, s, p, order);       \
-    else hipLaunchKernelGGL((gemm16_kernel<G, false, false, 0, 2>), grid, block, 0, s, p, order);                \
-  } while (0)
-    switch (p.gather) {
-      case TC_GATHER_LINEAR: TC_LAUNCH16_ILV(TC_GATHER_LINEAR); break;
-      case TC_GATHER_CONV3x3: TC_LAUNCH16_ILV(TC_GATHER_CONV3x3); break;
-      default: TC_LAUNCH16_ILV(TC_GATHER_CONVT3); break;
-    }
-#undef TC_LAUNCH16_ILV
-    return 1;
-  }
-#define TC_LAUNCH16(G)                                                                              \
-  do {                                                                                              \
-    if (stats) hipLaunchKernelGGL((gemm16_kernel<G, false, true>), grid, block, 0, s, p, order);    \
-    else if (pipe) hipLaunchKernelGGL((gemm16_kernel<G, true, false>), grid, block, 0, s, p, order); \
-    else hipLaunchKernelGGL((gemm16_kernel<G, false, false>), grid, block, 0, s, p, order);         \
-  } while (0)
-  switch (p.gather) {
-    case TC_GATHER_LINEAR: TC_LAUNCH16(TC_GATHER_LINEAR); break;
-    case TC_GATHER_CONV3x3: TC_LAUNCH16(TC_GATHER_CONV3x3); break;
-    default: TC_LAUNCH16(TC_GATHER_CONVT3); break;
-  }
-#undef TC_LAUNCH16
-  return 1;
+    else if (r.ilv == 1) hipLaunchKernelGGL((gemm16_kernel<G, false, false, 0, 1>), grid, block, 0, s, p, order);
+    else if (r.ilv == 2) hipLaunchKernelGGL((gemm16_kernel<G, false, false, 0, 2>), grid, block, 0, s, p, order);
+    else if (r.stats) hipLaunchKernelGGL((gemm16_kernel<G, false, true>), grid, block, 0, s, p, order);
+    else if (r.pipe) hipLaunchKernelGGL((gemm16_kernel<G, true, false>), grid, block, 0, s, p, order);
+    else hipLaunchKernelGGL((gemm16_kernel<G, false, false>), grid, block, 0, s, p, order);
+  });
 }

@@ -46,11 +46,9 @@
 
 #include <stdlib.h>
 
-#include <type_traits>
-
 namespace {
 
-constexpr int G8_BM = 256, G8_BN = 256, G8_THREADS = 512;
+constexpr int G8_BM = TC_BIG, G8_BN = TC_BIG, G8_THREADS = 512;
 constexpr int G8_HALF = 128 * TC_BK * 2;     // one half-tile: 128 rows x 128 B = 16 KiB
 constexpr int G8_BUF = 4 * G8_HALF;          // A0 | A1 | B0 | B1
 constexpr int G8_WN = 64;                    // columns per wave
@@ -456,61 +454,15 @@ __global__ __launch_bounds__(G8_THREADS, 2) void gemm8_kernel(const TcGemmParams
   if constexpr ((AB & 16) == 0) { if (grp == 0) g8_barrier(); }   // realign: every wave has executed the same number of barriers
 }
 
-int g8_mode() {        // TC_GEMM8 = 0 never | 1 heuristic (default) | 2 whenever the shape allows; read per call (A/B runs)
-  const char* e = getenv("TC_GEMM8");
-  return e ? atoi(e) : 1;
-}
-
 }  // namespace
 
-// Decide whether the 8-wave kernel should take this (already validated) GEMM, and launch it.  1 = launched.
-int tc_gemm8_try(const TcGemmParams& p, int batch, hipStream_t s, bool dry) {
-  const int mode = g8_mode();
-  if (mode == 0) return 0;
-  const bool geglu = p.act == TC_ACT_GEGLU;
-  const int n_out = geglu ? p.n / 2 : p.n;
-  if ((n_out & 7) != 0 || (geglu && (p.n & 31) != 0)) return 0;   // vector epilogue only; GEGLU packs per 32
-  if (p.k <= TC_BK) return 0;                                     // the K-tile stream needs two K-tiles per tile
-  // the epilogue is the common case only (plain or GEGLU, bf16 out): every option it carried was code the wave streams
-  // through once per tile
-  if ((p.act != TC_ACT_NONE && !geglu) || p.alpha != 1.f || p.out_scale != 1.f || p.out_f32) return 0;
-  if (p.gather == TC_GATHER_CONV3x3 && (p.stride != 1 || p.upsample || p.pad != 1)) return 0;   // plain 3x3 only
-  if (p.gather != TC_GATHER_LINEAR && (p.k / TC_BK >= 1024 || p.cin > 4096)) return 0;          // tap = multiply-high
-  const int tiles_n = (p.n + G8_BN - 1) / G8_BN;
-  const int tiles_m = (p.m + G8_BM - 1) / G8_BM;
-  if (mode == 1) {
-    // Measured (profiles/r04_gemm8_bench.txt, interleaved against the default routing): the kernel is ahead where ONE
-    // round of 256x256 tiles fills the chip and K is long -- the level-1 ff2 (20480 x 640 x 2560: 240 tiles,
-    // 1.11-1.21x), square problems from 4096 (1.00-1.07x), the decoder's 512-channel convolutions (1.03x) -- and
-    // behind wherever the tile grid quantises badly on 256 CUs (every UNet width is 320 k, every row count 5 * 2^n:
-    // N = 320 pads to 512, 320 / 160 / 100 tiles run 1.25 / 0.63 / 0.39 rounds) or K is short (K <= 1280: the epilogue
-    // of a 256 x 256 tile -- 128 KiB of stores, for GEGLU as many VALU cycles as the tile's MFMAs -- is not overlapped
-    // with matrix work when a CU holds a single block).  The heuristic takes the first class only.
-    const int64_t tiles = (int64_t)tiles_n * tiles_m * batch;
-    const double n_eff = (double)p.n / ((double)tiles_n * G8_BN);
-    // (one round: linear layers only -- the convolutions of that size are on the 160x160-tile kernel, which the 8-wave
-    // kernel does NOT beat: level-1 3x3 640 -> 640 0.85x, 1920 -> 640 0.80x)
-    const bool one_round = tiles >= 224 && tiles <= 256 && p.gather == TC_GATHER_LINEAR;
-    const bool many = tiles >= 1024 && p.n % G8_BN == 0 && p.n >= 512 && p.k >= 4096;   // (256 -> 256 convolutions: 0.89-0.92x)
-    // GEGLU projections of levels 0 and 1 (81920 x 2560 x 320, 20480 x 5120 x 640: 3200 / 1600 tiles): once the GELU of
-    // the epilogue lost its division sequence (common.h gelu_erf_f) the kernel is ahead there too -- 1.09-1.13x and
-    // 1.06-1.09x (profiles/r04_gelu_ab.txt); level 2 (5120 x 10240 x 1280) stays behind (0.95x)
-    const bool gated = geglu && p.gather == TC_GATHER_LINEAR && tiles >= 1536 && p.k <= 640 && p.n % G8_BN == 0;
-    if (!gated && (geglu || p.k < 2048 || n_eff < 0.8 || !(one_round || many))) return 0;
-  }
-  const int64_t total = (int64_t)tiles_n * tiles_m;
-  if (total > 0x7fffffffLL) return 0;
-  if (dry) return 1;
-  static const int cus = [] { int d = 0, n = 256; if (hipGetDevice(&d) == hipSuccess) hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n; }();
-  const int gmax = [&] { const char* e = getenv("TC_G8_GRID"); const int v = e ? atoi(e) : 0; return v > 0 ? v : cus; }() & ~7;
-  const int g = (int)(total < gmax ? total : gmax);         // a multiple of 8 unless it covers every tile in one round
-  dim3 grid((unsigned)g, 1, (unsigned)batch), block(G8_THREADS);
-  const int tt = (int)total;
-  const int stg = [] { const char* e = getenv("TC_G8_STAGGER"); return e ? atoi(e) : 0; }();
+void tc_gemm8_launch(const TcGemmParams& p, const TcGemmRoute& r, hipStream_t s) {
+  const dim3 grid(r.grid[0], r.grid[1], r.grid[2]), block(r.block);
+  const int tt = r.total_tiles, stg = r.stagger;
 #ifdef TC_TIMING_BUILDS      /* timing ablations: WRONG results by construction, never in the product library */
   const int ab = [] { const char* e = getenv("TC_G8_ABLATE"); return e ? atoi(e) : 0; }();
   if (ab && p.gather == TC_GATHER_LINEAR) {
-#define TC_G8_AB(X) case X: hipLaunchKernelGGL((gemm8_kernel<TC_GATHER_LINEAR, X>), grid, block, 0, s, p, tt, stg); return 1
+#define TC_G8_AB(X) case X: hipLaunchKernelGGL((gemm8_kernel<TC_GATHER_LINEAR, X>), grid, block, 0, s, p, tt, stg); return
     switch (ab) {
       TC_G8_AB(1); TC_G8_AB(2); TC_G8_AB(3); TC_G8_AB(4); TC_G8_AB(6); TC_G8_AB(7); TC_G8_AB(8); TC_G8_AB(16); TC_G8_AB(32); TC_G8_AB(64); TC_G8_AB(65);
       default: break;
@@ -518,10 +470,5 @@ int tc_gemm8_try(const TcGemmParams& p, int batch, hipStream_t s, bool dry) {
 #undef TC_G8_AB
   }
 #endif
-  switch (p.gather) {
-    case TC_GATHER_LINEAR: hipLaunchKernelGGL((gemm8_kernel<TC_GATHER_LINEAR>), grid, block, 0, s, p, tt, stg); break;
-    case TC_GATHER_CONV3x3: hipLaunchKernelGGL((gemm8_kernel<TC_GATHER_CONV3x3>), grid, block, 0, s, p, tt, stg); break;
-    default: hipLaunchKernelGGL((gemm8_kernel<TC_GATHER_CONVT3>), grid, block, 0, s, p, tt, stg); break;
-  }
-  return 1;
+  tc_with_gather(p.gather, [&](auto g) { hipLaunchKernelGGL((gemm8_kernel<decltype(g)::value>), grid, block, 0, s, p, tt, stg); });
 }

@@ -1,10 +1,9 @@
 // Helpers shared by the GEMM kernels (gemm.hip: 128x128 / 64x64 tiles, gemm_wide.hip: 256-row tiles).
 #pragma once
 #include "common.h"
+#include "gemm_route.h"      // TC_BK, the operand extents, TcGemmRoute
 
-#include <stdlib.h>
-
-constexpr int TC_BK = 64;   // K-step of every GEMM kernel: one 128-byte LDS row per tile row
+#include <type_traits>
 
 // Byte offset of 16-byte chunk `chunk` (0..7) of tile row `row` in the LDS image.  Rows are 128 B; the
 // chunk index is XOR-swizzled by (row>>1)&7, which makes the MFMA fragment reads (16 lanes reading
@@ -44,18 +43,6 @@ typedef __amdgpu_buffer_rsrc_t tc_rsrc_t;
 __device__ __forceinline__ tc_rsrc_t make_rsrc(const void* base, int64_t bytes) {
   const int rec = bytes < 0x7ffffff0LL ? (int)bytes : 0x7ffffff0;
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, rec, TC_SRD_FLAGS);
-}
-
-// byte extents of one batch item of A (source rows of the gather) and W
-__host__ __device__ __forceinline__ int64_t tc_a_rows(const TcGemmParams& p) {
-  return p.gather == TC_GATHER_CONV3x3 ? (int64_t)p.frames * p.h_in * p.w_in : (int64_t)p.m;
-}
-__host__ __device__ __forceinline__ int64_t tc_a_extent(const TcGemmParams& p) {
-  const int kc = p.gather == TC_GATHER_LINEAR ? p.k : p.cin;
-  return ((tc_a_rows(p) - 1) * p.lda + kc) * 2;
-}
-__host__ __device__ __forceinline__ int64_t tc_w_extent(const TcGemmParams& p) {
-  return ((int64_t)(p.n - 1) * p.ldw + p.k) * 2;
 }
 
 __device__ __forceinline__ u32x4 buf_load16(tc_rsrc_t rsrc, uint32_t voff, uint32_t soff) {
@@ -113,16 +100,6 @@ __device__ __forceinline__ void tc_tile_of_block(int bid, int tiles_m, int tiles
     tile_n = full + (r - m_local * rem);
   }
   tile_m = m_local * 8 + xcd;
-}
-
-// host side: order 1 when the weight matrix outgrows one XCD's L2 and there are enough N-tiles to chunk
-inline int tc_gemm_tile_order(const TcGemmParams& p, int tiles_n) {
-  // TC_GEMM_ORDER = chunk width in N-tiles (default 8; 0 = always the plain walk); TC_GEMM_ORDER_MIB = weight
-  // size from which the chunked walk is used (default 4 = one XCD's L2)
-  static const int chunk = [] { const char* e = getenv("TC_GEMM_ORDER"); return e ? atoi(e) : 8; }();
-  static const int64_t min_bytes = [] { const char* e = getenv("TC_GEMM_ORDER_MIB");
-                                        return (int64_t)((e ? atof(e) : 4.0) * (1 << 20)); }();
-  return (chunk > 0 && tiles_n >= 2 * chunk && (int64_t)p.n * p.ldw * 2 > min_bytes) ? chunk : 0;
 }
 
 // Lowest source row of A that the tile whose first output row is `tile_row0` can touch (block-uniform; a lower bound).
@@ -251,35 +228,16 @@ struct AGather {
   }
 };
 
-// Host-side guard shared by the launchers: every byte offset a tile load can form must fit the 31-bit range the
-// out-of-range marker relies on.  For A that is the span of ONE block's source rows from its tc_tile_row_lo (tiles of
-// at most 256 output rows), not the tensor.
-inline bool tc_gemm_offsets_fit(const TcGemmParams& p) {
-  int64_t span_rows = 256;
-  if (p.gather == TC_GATHER_CONVT3) span_rows += 2 * (int64_t)p.h_out * p.w_out;
-  else if (p.gather == TC_GATHER_CONV3x3)
-    span_rows = ((int64_t)256 / (p.w_out > 0 ? p.w_out : 1) + 2) * p.stride * p.w_in + 4 * (int64_t)p.w_in + 8;
-  const int64_t a_bytes = (span_rows + 1) * p.lda * 2;
-  const int64_t w_bytes = (int64_t)p.n * p.ldw * 2;
-  return a_bytes < 0x7fffff00LL && w_bytes < 0x7fffff00LL;
+// runtime gather -> template argument: f(std::integral_constant<int, GATHER>{})
+template <class F>
+inline void tc_with_gather(int gather, F&& f) {
+  switch (gather) {
+    case TC_GATHER_LINEAR: f(std::integral_constant<int, TC_GATHER_LINEAR>{}); break;
+    case TC_GATHER_CONV3x3: f(std::integral_constant<int, TC_GATHER_CONV3x3>{}); break;
+    default: f(std::integral_constant<int, TC_GATHER_CONVT3>{}); break;
+  }
 }
 
-// host side: -1 (W-stationary walk) for the lowest-resolution layers (M <= 2048 rows) whose weight matrix outweighs
-// their activation rows.  Measured (profiles/r02_nmajor_ab.txt): +5-7 % on the level-3 convolutions and qkv, neutral
-// on the rest of level 3, 3-7 % SLOWER on the level-2 convolutions (40 M-tiles: the A halo re-reads cost more than
-// the W re-reads the Infinity Cache was already absorbing) -- hence the row limit.
-// TC_GEMM_NMAJOR = 0 never, 1 heuristic (default), 2 always; read per call.
-inline bool tc_gemm_nmajor(const TcGemmParams& p) {
-  const char* e = getenv("TC_GEMM_NMAJOR");
-  const int mode = e ? atoi(e) : 1;
-  if (mode == 0 || (p.batch > 1)) return false;
-  if (mode == 2) return true;
-  return p.m <= 2048 && tc_w_extent(p) > tc_a_extent(p);
-}
-
-// (dry = true: the routing decision only, nothing is launched -- tc_gemm_gn_rows asks every family in tc_gemm_bf16's order)
-int tc_gemm_wide_try(const TcGemmParams& p, int batch, hipStream_t s, bool force, bool dry = false);   // gemm_wide.hip; 1 = launched
-int tc_gemm_tile16_try(const TcGemmParams& p, int batch, hipStream_t s, bool dry = false);   // gemm16.hip; 1 = launched
-int tc_gemm_ws_try(const TcGemmParams& p, int batch, hipStream_t s, bool dry = false);       // gemm_ws.hip (K = 320); 1 = launched
-int tc_gemm8_try(const TcGemmParams& p, int batch, hipStream_t s, bool dry = false);         // gemm8.hip (8-wave 256x256 ping-pong); 1 = launched
-int tc_conv_halo_try(const TcGemmParams& p, int batch, hipStream_t s, bool dry = false);     // conv_halo.hip (tap-reuse patches; TC_CONV_HALO: 1 = the measured routing (default), 0 = never, 2 = strict); 1 = launched, -1 = strict mode declined
+// one launcher per family file: maps the route's variant (gemm_route.h) to the template instance and launches it
+typedef void TcGemmLaunch(const TcGemmParams& p, const TcGemmRoute& r, hipStream_t s);
+TcGemmLaunch tc_gemm_ws_launch, tc_conv_halo_launch, tc_gemm8_launch, tc_gemm_tile16_launch, tc_gemm_wide_launch;

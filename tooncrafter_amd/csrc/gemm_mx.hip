@@ -409,7 +409,7 @@ extern "C" int tc_gemm_mxfp8(const TcGemmMxParams* pp, void* stream) {
   dim3 grid((unsigned)nblk), block(256);
   TcGemmParams half = p;                      // the walk heuristic prices W in bf16 bytes: fp8 rows are half as long
   half.ldw = p.ldw / 2;
-  const int order = tc_gemm_tile_order(half, tiles_n);
+  const int order = tc_gemm_tile_order(half, tiles_n, tc_gemm_switches());
 #define TC_LAUNCH_MX(G)                                                                            \
   do {                                                                                             \
     if (small) hipLaunchKernelGGL((gemm_mx_kernel<G, 1, 1>), grid, block, 0, s, *pp, order);        \

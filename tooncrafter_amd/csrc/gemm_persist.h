@@ -3,7 +3,6 @@
 #pragma once
 #include "gemm_common.h"
 
-#include <type_traits>
 
 namespace {
 

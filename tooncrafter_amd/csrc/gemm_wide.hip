@@ -14,13 +14,9 @@
 // on 16-byte row vectors (bias / row-bias / activation / GEGLU / residual / store).
 #include "gemm_common.h"
 
-#include <stdlib.h>
-
-#include <type_traits>
-
 namespace {
 
-constexpr int WBM = 256;
+constexpr int WBM = TC_BIG;
 constexpr int WTHREADS = 512;
 
 // PIPE: two K-steps of tile loads in flight, counted vmcnt + raw barriers (see gemm.hip)
@@ -285,68 +281,18 @@ __global__ __launch_bounds__(WTHREADS, 2) void gemm_wide_kernel(const TcGemmPara
   epi_pass(integral_constant<int, 1>{}, integral_constant<int, 1>{});
 }
 
-template <int TNW>
-void launch_wide(const TcGemmParams& p, dim3 grid, hipStream_t s) {
-  dim3 block(WTHREADS);
-  const int order = tc_gemm_tile_order(p, (p.n + 64 * TNW - 1) / (64 * TNW));
-  // TC_GEMM_PIPE = 2 only: with one 8-wave block per CU the second barrier per K-step costs more than the deeper
-  // prefetch returns (measured, profiles/r03_pipe_bench.txt: the decoder's 512-channel convolutions 0.91x, the
-  // N = 10240 GEGLU layer 0.95x), so the default keeps the plain loop
-  const bool pipe = [] { const char* e = getenv("TC_GEMM_PIPE"); return e && e[0] == '2'; }();      // per call (A/B runs)
-#define TC_LAUNCH_WIDE(G)                                                                           \
-  do {                                                                                              \
-    if (pipe) hipLaunchKernelGGL((gemm_wide_kernel<G, TNW, true>), grid, block, 0, s, p, order);    \
-    else hipLaunchKernelGGL((gemm_wide_kernel<G, TNW, false>), grid, block, 0, s, p, order);        \
-  } while (0)
-  switch (p.gather) {
-    case TC_GATHER_LINEAR: TC_LAUNCH_WIDE(TC_GATHER_LINEAR); break;
-    case TC_GATHER_CONV3x3: TC_LAUNCH_WIDE(TC_GATHER_CONV3x3); break;
-    default: TC_LAUNCH_WIDE(TC_GATHER_CONVT3); break;
-  }
-#undef TC_LAUNCH_WIDE
-}
-
-int wide_enabled() {        // TC_GEMM_WIDE=0: never (read per call: A/B runs flip it inside one process)
-  const char* e = getenv("TC_GEMM_WIDE");
-  return (e && e[0] == '0') ? 0 : 1;
-}
-
 }  // namespace
 
-// Decide whether the wide kernel should take this (already validated) GEMM, and launch it.
-int tc_gemm_wide_try(const TcGemmParams& p, int batch, hipStream_t s, bool force, bool dry) {
-  if (!wide_enabled()) return 0;
-  const bool geglu = p.act == TC_ACT_GEGLU;
-  const int n_out = geglu ? p.n / 2 : p.n;
-  if ((n_out & 7) != 0 || (p.n & 31) != 0) return 0;       // vector epilogue only; GEGLU packs per 32
-  int tnw;
-  if (p.n % 320 == 0) tnw = 5;
-  else if (p.n >= 256) tnw = 4;
-  else if (p.n >= 128) tnw = 2;
-  else return 0;
-  const int bn = 64 * tnw;
-  const int tiles_n = (p.n + bn - 1) / bn;
-  const int tiles_m = (p.m + WBM - 1) / WBM;
-  const int64_t blocks = (int64_t)tiles_n * tiles_m * batch;
-  // measured on MI355X (profiles/r01_v6_gemm_tile_sweep.txt): one 8-wave block per CU has no second block
-  // to hide its prologue/epilogue behind, so the 256-row tile only wins with long K and either many
-  // rounds of blocks (the decoder's 256/512-channel 3x3 convolutions) or a grid that fits the 256 CUs
-  // once; wide GEGLU layers (N = 10240) win from K = 1280 because the 256x320 tile halves their
-  // L2->LDS traffic
-  if (!force) {
-    const bool fits = blocks >= 192 && blocks <= 256;
-    const bool conv_like = p.n >= 256 && p.k >= 2048 && (blocks >= 1024 || fits);
-    // (r02: wide GEGLU layers -- N = 10240, K = 1280 -- took the 256x320 tile; with two K-steps in flight the 128x128 kernel
-    // is ahead there too: 157-160 us vs 163-171 us, profiles/r03_pipe_bench.txt / r03_two_tiles_per_block_ab.txt)
-    const bool wide_geglu = false;
-    if (!conv_like && !wide_geglu) return 0;
-  }
-  const int64_t nblk = (int64_t)tiles_n * 8 * ((tiles_m + 7) / 8);
-  if (nblk > 0x7fffffffLL) return 0;
-  if (dry) return 1;
-  dim3 grid((unsigned)nblk, 1, (unsigned)batch);
-  if (tnw == 5) launch_wide<5>(p, grid, s);
-  else if (tnw == 4) launch_wide<4>(p, grid, s);
-  else launch_wide<2>(p, grid, s);
-  return 1;
+void tc_gemm_wide_launch(const TcGemmParams& p, const TcGemmRoute& r, hipStream_t s) {
+  const dim3 grid(r.grid[0], r.grid[1], r.grid[2]), block(r.block);
+  const auto go = [&](auto g, auto t) {
+    constexpr int G = decltype(g)::value, TNW = decltype(t)::value;
+    if (r.pipe) hipLaunchKernelGGL((gemm_wide_kernel<G, TNW, true>), grid, block, 0, s, p, r.order);
+    else hipLaunchKernelGGL((gemm_wide_kernel<G, TNW, false>), grid, block, 0, s, p, r.order);
+  };
+  tc_with_gather(p.gather, [&](auto g) {
+    if (r.tnw == 5) go(g, std::integral_constant<int, 5>{});
+    else if (r.tnw == 4) go(g, std::integral_constant<int, 4>{});
+    else go(g, std::integral_constant<int, 2>{});
+  });
 }

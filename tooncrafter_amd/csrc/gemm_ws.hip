@@ -24,13 +24,11 @@
 // 52 MB A from L2 / Infinity Cache per slab (blocks of one M-chunk share an XCD).
 #include "gemm_common.h"
 
-#include <stdlib.h>
-
 namespace {
 
-constexpr int WS_K = 320;
+constexpr int WS_K = TC_WS_K;
 constexpr int WS_KS = WS_K / 32;                     // K-slices of one 16x16x32 MFMA
-constexpr int WS_ROWS = 64;                          // rows per streamed A tile
+constexpr int WS_ROWS = TC_WS_ROWS;                  // rows per streamed A tile
 constexpr int WS_MT = WS_ROWS / 16;
 constexpr int WS_ROW_BYTES = WS_K * 2;               // 640 B = 40 chunks of 16 B
 constexpr int WS_CHUNKS = WS_ROW_BYTES / 16;
@@ -274,61 +272,13 @@ __global__ __launch_bounds__(256, 1) void gemm_ws_kernel(const TcGemmParams p, c
   wait_vmcnt<0>();        // the two run-ahead DMA requests target this block's LDS: drain them before it is released
 }
 
-int ws_mode() {            // TC_GEMM_WS = 0 never | 1 heuristic (default) | 2 whenever the shape allows | 3 = 2 + vmcnt(0) waits | 4 = 2 + deeper store window | 5 = 1 + deeper store window
-  const char* e = getenv("TC_GEMM_WS");      // read per call: the parity tests flip it inside one process
-  return e ? atoi(e) : 1;
-}
-
 }  // namespace
 
-// Would the weight-stationary kernel take this (validated) problem?  One definition for the launcher and for the host
-// layer that decides whether a LayerNorm may be folded into its consumer (tc_gemm_ws_eligible).
-static bool ws_shape_ok(const TcGemmParams& p, int batch, int mode) {
-  // TC_GEMM_TILE forces a tile family: tc_gemm_bf16 then never comes here, so the host must not be told that a
-  // LayerNorm may be folded into this launch (the two rules disagreed under forced-tile sweeps)
-  if (const char* e = getenv("TC_GEMM_TILE")) { if (e[0]) return false; }
-  if (mode == 0 || batch != 1 || p.gather != TC_GATHER_LINEAR || p.k != WS_K || p.lda < WS_K) return false;
-  if (p.row_bias || p.alpha != 1.f || p.out_scale != 1.f || p.out_f32) return false;
-  const bool geglu = p.act == TC_ACT_GEGLU;
-  if (!geglu && p.act != TC_ACT_NONE) return false;
-  if (p.n % (geglu ? 256 : 320) != 0) return false;
-  if (p.residual && geglu) return false;
-  // Heuristic (profiles/r03_ws_bench_hipblaslt_yardstick.txt, B = 2 shapes): the N = 320 projections are HBM-bound and gain
-  // 1.15x (plain / + residual) to 1.53x (LayerNorm prologue instead of a LayerNorm launch); with more than one N-slab the
-  // single wave per SIMD serialises LayerNorm, MFMAs and epilogue and the kernel LOSES to the tiled one (qkv 0.89x,
-  // 0.67x with the prologue; GEGLU 0.61x / 0.50x), and at M = 40960 it only ties -- so: one slab, plain, M >= 64K rows.
-  if ((mode == 1 || mode == 5) && (p.m < 65536 || geglu || p.n != 320)) return false;
-  if ((int64_t)p.m * p.lda * 2 >= 0x7fffff00LL) return false;       // this kernel addresses A from the tensor base
-  if ((int64_t)p.m * p.ldc * 2 >= 0x7fffff00LL || (p.residual && (int64_t)p.m * p.ldr * 2 >= 0x7fffff00LL)) return false;
-  return true;
-}
-
-extern "C" int tc_gemm_ws_eligible(const TcGemmParams* p) {
-  if (!p) return 0;
-  return ws_shape_ok(*p, p->batch > 0 ? p->batch : 1, ws_mode()) ? 1 : 0;
-}
-
-// 1 = launched
-int tc_gemm_ws_try(const TcGemmParams& p, int batch, hipStream_t s, bool dry) {
-  const int mode = ws_mode();
-  if (!ws_shape_ok(p, batch, mode)) return 0;
-  if (dry) return 1;
-  const bool geglu = p.act == TC_ACT_GEGLU;
-  const int slabs = p.n / (geglu ? 256 : 320);
-  const int ntiles = (p.m + WS_ROWS - 1) / WS_ROWS;
-  int nchunks = 256 / slabs;                                    // one block per CU
-  if (nchunks < 1) nchunks = 1;
-  if (nchunks > ntiles) nchunks = ntiles;
-  const int grid = slabs * 8 * ((nchunks + 7) / 8);
-  // wait mode: the heuristic (1) runs with the deeper store window (+1-6 %, profiles/r03_ws_bench_hipblaslt_yardstick.txt);
-  // 2 = counted waits that also retire the stores of two tiles ago, 3 = vmcnt(0) everywhere (parity tests)
-  const int safe = mode == 3 ? 1 : (mode == 2 ? 0 : 2);
-  const bool res = p.residual != nullptr, ln = p.a_norm != 0;
-  dim3 g((unsigned)grid), b(256);
-#define TC_WS_LAUNCH(NT, G, R, L) hipLaunchKernelGGL((gemm_ws_kernel<NT, G, R, L>), g, b, 0, s, p, nchunks, safe)
-  if (geglu) { if (ln) TC_WS_LAUNCH(4, true, false, true); else TC_WS_LAUNCH(4, true, false, false); }
-  else if (res) { if (ln) TC_WS_LAUNCH(5, false, true, true); else TC_WS_LAUNCH(5, false, true, false); }
-  else { if (ln) TC_WS_LAUNCH(5, false, false, true); else TC_WS_LAUNCH(5, false, false, false); }
+void tc_gemm_ws_launch(const TcGemmParams& p, const TcGemmRoute& r, hipStream_t s) {
+  const dim3 g(r.grid[0]), b(r.block);
+#define TC_WS_LAUNCH(NT, G, R, L) hipLaunchKernelGGL((gemm_ws_kernel<NT, G, R, L>), g, b, 0, s, p, r.nchunks, r.safe)
+  if (r.geglu) { if (r.ln) TC_WS_LAUNCH(4, true, false, true); else TC_WS_LAUNCH(4, true, false, false); }
+  else if (r.res) { if (r.ln) TC_WS_LAUNCH(5, false, true, true); else TC_WS_LAUNCH(5, false, true, false); }
+  else { if (r.ln) TC_WS_LAUNCH(5, false, false, true); else TC_WS_LAUNCH(5, false, false, false); }
 #undef TC_WS_LAUNCH
-  return 1;
 }
