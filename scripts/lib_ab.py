@@ -1,18 +1,34 @@
 #!/usr/bin/env python3
-"""usage: lib_ab.py <other libtooncrafter_hip.so>  -- the in-tree library against another BUILD of it (e.g. the previous
-commit's, kept under scripts/bin/prev/), interleaved in one process on the UNet's GEMM shapes at B = 2 under the default
-routing; checks that both builds give the same bits."""
-import ctypes as C, os, sys
+"""usage: lib_ab.py <other libtooncrafter_hip.so> [--new <another build>] [--edges]
+The in-tree library against another BUILD of it (e.g. the previous commit's, kept under scripts/bin/prev/), interleaved in
+one process on the UNet's GEMM shapes and fused launches at B = 2 under the default routing; checks that both builds give the same bits.
+
+  --new PATH   take PATH instead of the in-tree library as "new" (the other build in BOTH roles: what two runs of the same
+               code differ by -- the noise of the timing columns, the determinism of the battery)
+  --edges      no timing: the same old / new "same bits" check at the smallest shapes where each path of the kernel
+               families can go wrong (ragged M, N tails, a ragged last K-step, every epilogue option), the family forced by
+               its routing switch, inputs from a seeded CPU generator
+"""
+import contextlib, ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from tooncrafter_amd import _lib, ops
-from tooncrafter_amd._lib import ACT_GEGLU, ACT_NONE
+from tooncrafter_amd._lib import ACT_GEGLU, ACT_NONE, ACT_SILU
 dev, BF = "cuda", torch.bfloat16
-hip = ops.backend()
+hip = ops.HipOps()       # the ctypes binding: its library handle is swapped per arm (the custom-op layer is linked to the in-tree build)
+
+def load(path):
+    lib = C.CDLL(os.path.abspath(path))
+    for name, (res, args) in _lib.SYMBOLS.items():
+        fn = getattr(lib, name); fn.restype = res; fn.argtypes = args
+    return lib
+
+args = [a for a in sys.argv[1:] if a != "--edges"]
+edges = "--edges" in sys.argv[1:]
 new = hip.lib
-old = C.CDLL(os.path.abspath(sys.argv[1]))
-for name, (res, args) in _lib.SYMBOLS.items():
-    fn = getattr(old, name); fn.restype = res; fn.argtypes = args
+if "--new" in args:
+    i = args.index("--new"); new = load(args[i + 1]); del args[i:i + 2]
+old = load(args[0])
 assert old.tc_abi_version() == new.tc_abi_version()
 
 def timeit(fn, iters=20, reps=3):
@@ -51,9 +67,153 @@ def conv(frames, h, w, cin, cout, tag, t3=False):
     ab(lambda: hip.gemm(x, wt, b, conv=geom, residual=res), 2.0 * frames * h * w * cout * taps * cin,
        f"{'convT3' if t3 else 'conv3x3'} {tag} {cin}->{cout}")
 
+# ---------------------------------------------------------------- --edges
+_seed = [0]
+def rnd(*shape, scale=1.0, dtype=BF):
+    _seed[0] += 1
+    g = torch.Generator(device="cpu").manual_seed(_seed[0])
+    return (torch.randn(*shape, generator=g) * scale).to(dtype).to(dev)
+
+@contextlib.contextmanager
+def env(**kv):                      # the library reads its switches per call
+    kv = {k: str(v) for k, v in kv.items()}
+    was = {k: os.environ.get(k) for k in kv}
+    os.environ.update(kv)
+    gn_was, hip.gn_part = hip.gn_part, kv.get("TC_GN_PART") == "1"
+    try:
+        yield " ".join(f"{k}={v}" for k, v in kv.items())
+    finally:
+        hip.gn_part = gn_was
+        for k, v in was.items():
+            if v is None: os.environ.pop(k, None)
+            else: os.environ[k] = v
+
+bad, counts = [], {}
+def same(fn, tag, want=1):
+    """fn() -> tensor or tuple of tensors (None allowed), under both builds; a call the route refuses is refused by both.
+    want: tensors the case is about (2 with gn_stats: the output and the sums) -- fewer means the route dropped the part
+    under test, and the case is reported as not covered, never as the same bits"""
+    outs = {}
+    for name, lib in (("old", old), ("new", new)):
+        hip.lib = lib
+        try:
+            o = fn()
+            outs[name] = tuple(t for t in (o if isinstance(o, tuple) else (o,)) if t is not None)
+        except _lib.TooncrafterHipError as e:
+            outs[name] = str(e)
+    hip.lib = new
+    torch.cuda.synchronize()
+    o, n = outs["old"], outs["new"]
+    if isinstance(o, str) or isinstance(n, str):
+        verdict = f"skipped, the route refuses it ({o})" if o == n else "DIFFERENT BITS (one build refuses the call)"
+    elif len(o) == len(n) and len(o) < want:
+        verdict = "NOT COVERED: the route emits no statistics for this call"
+    else:
+        verdict = "same bits" if len(o) == len(n) and all(torch.equal(x, y) for x, y in zip(o, n)) else "DIFFERENT BITS"
+        verdict += f" ({len(o)} tensor{'s' if len(o) != 1 else ''})"
+    if verdict.startswith("DIFFERENT"): bad.append(tag)
+    kind = next(k for k in ("same bits", "skipped", "NOT COVERED", "DIFFERENT BITS") if verdict.startswith(k))
+    counts[kind] = counts.get(kind, 0) + 1
+    print(f"{tag:118s} {verdict}", flush=True)
+
+def epilogue_sets(m, n, geglu, which):
+    """(a) everything at once: bias, row bias with a row_div no tile height is a multiple of, SiLU, alpha, out_scale, residual
+    as a column slice (ldr > n) -- a GEGLU launch carries no row bias, residual or second activation;  (b) bias, fp32 output;
+    (c) what the 8-wave kernel takes: bias, row bias, sliced residual;  (d) bias alone, bf16 (statistics cases: an fp32 output
+    carries none)"""
+    n_out = n // 2 if geglu else n
+    rb = dict(row_bias=rnd((m + 47) // 48, n, dtype=torch.float32), row_div=48, residual=rnd(m, n_out + 16)[:, 8:8 + n_out])
+    sets = {"a": dict(alpha=0.9, out_scale=1.1) if geglu else dict(rb, act=ACT_SILU, alpha=0.9, out_scale=1.1),
+            "b": dict(out_f32=True), "c": rb, "d": {}}
+    return [(s, sets[s]) for s in which]
+
+def gemm_outs(a, w, b, kw, gn):
+    o = hip.gemm(a, w, b, gn_stats=gn, **kw)
+    return (o[0], o[1].sums if o[1] is not None else None) if gn else o
+
+def e_lin(sw, m, n, k, geglu=False, gn=False, which="ab"):
+    a, w, b = rnd(m, k), rnd(n, k, scale=k ** -0.5), rnd(n, dtype=torch.float32)
+    for s, kw in epilogue_sets(m, n, geglu, which):
+        if geglu: kw = dict(kw, act=ACT_GEGLU)
+        with env(**sw) as tag:
+            same(lambda: gemm_outs(a, w, b, kw, gn), want=2 if gn else 1, tag=f"linear{' GEGLU' if geglu else ''}{' +gn_stats' if gn else ''} {m}x{n}x{k} ({s}) {tag}")
+
+def e_conv(sw, frames, h, w_, cin, cout, t3=False):
+    m, taps = frames * h * w_, 3 if t3 else 9
+    x, wt, b = rnd(m, cin), rnd(cout, taps * cin, scale=(taps * cin) ** -0.5), rnd(cout, dtype=torch.float32)
+    geom = dict(kind="t3", frames=frames, t_len=16, cin=cin, h_out=h, w_out=w_) if t3 else \
+        dict(kind="3x3", frames=frames, cin=cin, h_in=h, w_in=w_, h_out=h, w_out=w_, stride=1, upsample=False)
+    for s, kw in epilogue_sets(m, cout, False, "ab"):
+        with env(**sw) as tag:
+            same(lambda: hip.gemm(x, wt, b, conv=geom, **kw), f"{'convT3' if t3 else 'conv3x3'} {frames}x{h}x{w_} {cin}->{cout} ({s}) {tag}")
+
+def run_edges():
+    for tile in (11, 22):
+        for pipe in (0, 1):
+            sw = dict(TC_GEMM_TILE=tile, TC_GEMM_PIPE=pipe)
+            e_lin(sw, 200, 136, 200)                 # ragged M, N tail inside a tile, 4 K-steps with a ragged last
+            e_lin(sw, 200, 12, 200)                  # the scalar tail path
+            e_lin(sw, 200, 256, 200, geglu=True)
+    # GroupNorm sums of the 128 x 128 tile: a forced tile never emits them (tuning runs only: gemm_route.cpp), so the route is left
+    # to itself at the smallest kind of shape it sends there WITH statistics -- at least 384 tiles, n no multiple of 160;
+    # ragged M, an N tail, a ragged last K-step
+    for pipe in (0, 1): e_lin(dict(TC_GN_PART=1, TC_GEMM_PIPE=pipe), 6200, 1032, 200, gn=True, which="abd")
+    e_lin(dict(TC_GEMM_SPLITK=2), 64, 64, 1024)
+    for pipe in (1, 2):
+        sw = dict(TC_GEMM_TILE="wide", TC_GEMM_PIPE=pipe)
+        for n in (160, 256, 320): e_lin(sw, 300, n, 200)
+        e_lin(sw, 300, 256, 200, geglu=True)
+    for pipe in (1, 2):
+        for tall in (0, 2):
+            sw = dict(TC_GEMM_TILE16=2, TC_GEMM_PIPE=pipe, TC_G16_TALL=tall)
+            e_lin(sw, 200, 320, 200)
+            e_lin(dict(sw, TC_GN_PART=1), 200, 320, 200, gn=True, which="abd")
+    for ks in (0, 2):
+        for tall in (0, 2):
+            sw = dict(TC_CONV_HALO=2, TC_CONV_HALO_KSPLIT=ks, TC_CONV_HALO_TALL=tall)
+            e_conv(sw, 1, 20 if tall else 10, 16, 256 if ks else 64, 160)
+            e_conv(sw, 16, 2, 5, 256 if ks else 64, 160, t3=True)
+    e_lin(dict(TC_GEMM8=2), 300, 264, 200, which="c")           # the 8-wave kernel takes neither (a) nor (b)
+    for n in (288, 384):                                         # GEGLU: bias only (288 is no multiple of 128: refused; 384 has an N tail)
+        a, w, b = rnd(300, 200), rnd(n, 200, scale=200 ** -0.5), rnd(n, dtype=torch.float32)
+        with env(TC_GEMM8=2) as tag:
+            same(lambda: hip.gemm(a, w, b, act=ACT_GEGLU), f"linear GEGLU 300x{n}x200 (bias) {tag}")
+    for heads in (1, 3):                                         # one and three K-steps; x a column slice, ldx > c
+        c = 64 * heads
+        x, wq, bq = rnd(16 * 8, c + 64)[:, 32:32 + c], rnd(3 * c, c, scale=1.4 * c ** -0.5), rnd(3 * c, scale=0.2, dtype=torch.float32)
+        same(lambda: hip.temporal_qkv_attn(x, wq, bq, b=1, t=16, hw=8, heads=heads), f"temporal_qkv_attn b=1 t=16 hw=8 heads={heads} ldx={c + 64}")
+    c = 320
+    x, wq, bq = rnd(16 * 8, c), rnd(3 * c, c, scale=1.4 * c ** -0.5), rnd(3 * c, scale=0.2, dtype=torch.float32)
+    wo, bo = rnd(c, c, scale=c ** -0.5), rnd(c, scale=0.2, dtype=torch.float32)
+    with env(TC_TB_FUSED=1) as tag:
+        same(lambda: hip.temporal_attn_fused(x, wq, bq, wo, bo, b=1, t=16, hw=8, heads=5, ln_eps=1e-5), f"temporal_attn_fused b=1 t=16 hw=8 c=320 {tag}")
+    x, w1, b1 = rnd(100, c), rnd(2 * 1280, c, scale=c ** -0.5), rnd(2 * 1280, scale=0.2, dtype=torch.float32)
+    w2, b2 = rnd(c, 1280, scale=1280 ** -0.5), rnd(c, scale=0.2, dtype=torch.float32)
+    same(lambda: hip.ff_geglu_fused(x, w1, b1, w2, b2, ln_eps=1e-5), "ff_geglu_fused m=100 c=320 hidden=1280")
+    print("edges: " + ", ".join(f"{v} {k}" for k, v in counts.items()), flush=True)
+    print(f"edges: {'no case with different bits' if not bad else f'{len(bad)} DIFFERENT: ' + '; '.join(bad)}", flush=True)
+    return 1 if bad else 0
+
+if edges:
+    sys.exit(run_edges())
 lin(81920, 960, 320, "L0 qkv", res=False); lin(81920, 640, 320, "L0 640"); lin(20480, 640, 640, "L1 proj"); lin(20480, 1920, 640, "L1 qkv", res=False)
 lin(20480, 640, 2560, "L1 ff2"); lin(5120, 1280, 1280, "L2 proj"); lin(5120, 3840, 1280, "L2 qkv", res=False); lin(5120, 1280, 5120, "L2 ff2")
 lin(5120, 10240, 1280, "L2 geglu", act=ACT_GEGLU); lin(1280, 1280, 1280, "L3 proj"); lin(777, 520, 1288, "ragged")
 conv(32, 10, 16, 1280, 1280, "L2"); conv(32, 10, 16, 2560, 1280, "L2"); conv(32, 5, 8, 1280, 1280, "L3")
 conv(32, 10, 16, 1280, 1280, "L2", t3=True); conv(32, 5, 8, 1280, 1280, "L3", t3=True)
 conv(16, 40, 64, 512, 512, "decoder")
+# the fused launches of the temporal / feed-forward blocks at their UNet shapes (B = 2)
+def fused():
+    c = 320; m = 81920
+    x, w1, b1 = rnd(m, c), rnd(2 * 1280, c, scale=c ** -0.5), rnd(2 * 1280, scale=0.2, dtype=torch.float32)
+    w2, b2 = rnd(c, 1280, scale=1280 ** -0.5), rnd(c, scale=0.2, dtype=torch.float32)
+    ab(lambda: hip.ff_geglu_fused(x, w1, b1, w2, b2, ln_eps=1e-5), 2.0 * m * c * 1280 * 3, f"ff_geglu_fused L0 {m}x{c}x1280")
+    wq, bq = rnd(3 * c, c, scale=1.4 * c ** -0.5), rnd(3 * c, scale=0.2, dtype=torch.float32)
+    wo, bo = rnd(c, c, scale=c ** -0.5), rnd(c, scale=0.2, dtype=torch.float32)
+    with env(TC_TB_FUSED=1):
+        ab(lambda: hip.temporal_attn_fused(x, wq, bq, wo, bo, b=2, t=16, hw=2560, heads=5, ln_eps=1e-5), 2.0 * m * c * c * 4, f"temporal_attn_fused L0 {m}x{c}")
+    for hw, heads in ((2560, 5), (640, 10), (160, 20)):
+        c = 64 * heads; m = 2 * 16 * hw
+        x, wq, bq = rnd(m, c), rnd(3 * c, c, scale=1.4 * c ** -0.5), rnd(3 * c, scale=0.2, dtype=torch.float32)
+        ab(lambda: hip.temporal_qkv_attn(x, wq, bq, b=2, t=16, hw=hw, heads=heads), 2.0 * m * c * c * 3, f"temporal_qkv_attn {m}x{c}")
+fused()

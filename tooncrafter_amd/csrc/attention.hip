@@ -18,12 +18,6 @@
 
 namespace {
 
-// v_exp_f32 directly: exp2f() expands to six instructions per value (denormal-range test, two selects, add, exp,
-// ldexp) -- with 32 scores per lane per tile that alone was 200 of the ~900 VALU instructions per tile of a kernel
-// the counters show VALU-bound (29 VALU per MFMA, profiles/r02_pmc_attention.json).  Arguments here are <= 0 and
-// results below 2^-126 may flush to zero: exactly what a masked or negligible probability should be.
-__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
 constexpr int KT = 64;            // keys per tile
 constexpr int K_STRIDE = 144;     // bytes per K row in LDS (128 + 16 pad): conflict-free ds_read_b128
 constexpr int VT_STRIDE = 136;    // bytes per V^T row (64 keys * 2 + 8 pad): conflict-free ds_read_b64

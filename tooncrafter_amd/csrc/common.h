@@ -113,6 +113,44 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// v_exp_f32 directly: exp2f() expands to six instructions per value (denormal-range test, two selects, add, exp,
+// ldexp) -- with 32 scores per lane per tile that alone was 200 of the ~900 VALU instructions per tile of the attention
+// kernels, which the counters show VALU-bound (29 VALU per MFMA, profiles/r02_pmc_attention.json).  Arguments there are <= 0 and
+// results below 2^-126 may flush to zero: exactly what a masked or negligible probability should be.
+__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
+
+// counted wait: at most N of this wave's vector-memory requests (LDS-DMA pieces included) may still be in flight
+template <int N>
+__device__ __forceinline__ void tc_wait_vmcnt() {
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
+// v_permlane16_swap / v_permlane32_swap with both operands = x: every lane gets (a, b) = the values its 16-lane row pair
+// (lanes l and l ^ 16) / its half pair (l and l ^ 32) hold, lower row's first -- a cross-row exchange on the VALU instead of a
+// ds_bpermute round trip through LDS
+__device__ __forceinline__ void tc_swap16(uint32_t x, uint32_t& a, uint32_t& b) {
+  const auto r = __builtin_amdgcn_permlane16_swap(x, x, false, false);
+  a = r[0]; b = r[1];
+}
+__device__ __forceinline__ void tc_swap32(uint32_t x, uint32_t& a, uint32_t& b) {
+  const auto r = __builtin_amdgcn_permlane32_swap(x, x, false, false);
+  a = r[0]; b = r[1];
+}
+__device__ __forceinline__ float tc_max_rows(float x) {         // max over the four lanes l15 + 16 g
+  uint32_t a, b;
+  tc_swap16(__builtin_bit_cast(uint32_t, x), a, b);
+  x = fmaxf(__builtin_bit_cast(float, a), __builtin_bit_cast(float, b));
+  tc_swap32(__builtin_bit_cast(uint32_t, x), a, b);
+  return fmaxf(__builtin_bit_cast(float, a), __builtin_bit_cast(float, b));
+}
+__device__ __forceinline__ float tc_sum_rows(float x) {         // ... and their sum
+  uint32_t a, b;
+  tc_swap16(__builtin_bit_cast(uint32_t, x), a, b);
+  x = __builtin_bit_cast(float, a) + __builtin_bit_cast(float, b);
+  tc_swap32(__builtin_bit_cast(uint32_t, x), a, b);
+  return __builtin_bit_cast(float, a) + __builtin_bit_cast(float, b);
+}
+
 static inline bool tc_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 #define TC_LAUNCH_CHECK()                         \

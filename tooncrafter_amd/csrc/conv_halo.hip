@@ -35,11 +35,12 @@
 //     cost the second resident block (LDS: 28 KiB halo + 2 x 20 KiB W stages = 68 KiB, two blocks per CU).
 //   * W tiles: LDS-DMA from inline asm into two stages, one K-step ahead (gemm_persist.h g8_dma16), vmcnt(0) + barrier
 //     per step -- the plain loop; the interleaved loops of gemm16 can follow once this one is measured.
-//   * Epilogue: gemm16's (per-wave fp32 slab, 16-byte row vectors, bias / row bias / activation / residual), with the
-//     tile row -> output row map of the patch.
+//   * Epilogue: gemm16's (gemm_epilogue.h epi_slab_pass16: per-wave fp32 slab, 16-byte row vectors, bias / row bias /
+//     activation / residual), with the tile row -> output row map of the patch.
 // Summation order over K differs from the implicit GEMM's (chunk-major instead of tap-major): results agree to fp32
 // rounding of the accumulators, not bit for bit.
 #include "gemm_persist.h"
+#include "gemm_epilogue.h"
 
 #include "conv_halo_index.h"
 
@@ -237,62 +238,16 @@ __global__ __launch_bounds__(128 * WM * KS, (WM == 2 && KS == 1) ? 2 : 1) void c
         for (int r = 0; r < 4; ++r) acc[i][j][r] += red[((i * CH_NT + j) * 4 + r) * 64];
   }
 
-  // ---- epilogue: per wave, five passes of one 16-row MFMA block through a private fp32 slab [16][80] (gemm16.hip),
+  // ---- epilogue: per wave, five passes of one 16-row MFMA block through a private fp32 slab [16][80] (epi_slab_pass16),
   // tile row 16 y + x -> output row m00 + y ys + x xs
   float* slab = reinterpret_cast<float*>(smem) + wave * (16 * CH_WT);
   const bf16_t* res_base = p.residual ? reinterpret_cast<const bf16_t*>(p.residual) + bz * p.stride_c : nullptr;
   char* c_base = reinterpret_cast<char*>(p.c) + bz * p.stride_c * (p.out_f32 ? 4 : 2);
   const int col_w0 = tile_n * CH_BN + wn * CH_WT;
-  constexpr int VPR = CH_WT / 8;                           // 10 vectors of 8 columns per slab row
   auto epi_pass = [&](auto I_) {
     constexpr int i = decltype(I_)::value;
-    // C/D layout of the 16x16 MFMA: col = lane & 15, row = 4 (lane >> 4) + reg
-#pragma unroll
-    for (int j = 0; j < CH_NT; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) slab[(fq * 4 + r) * CH_WT + j * 16 + frow] = acc[i][j][r];
-    // the same wave reads back (LDS operations of one wave complete in order): 160 vectors over 64 lanes
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      const int v = lane + 64 * q;
-      const int lr = v / VPR, vc = v - lr * VPR;
-      const int m = (int)chx::out_row(pt, wm, i, lr);
-      const int n0 = col_w0 + vc * 8;
-      if (v < 16 * VPR && m < p.m && n0 < p.n) {
-        const f32x4 lo = *reinterpret_cast<const f32x4*>(slab + lr * CH_WT + vc * 8);
-        const f32x4 hi = *reinterpret_cast<const f32x4*>(slab + lr * CH_WT + vc * 8 + 4);
-        float x[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        float bv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (p.bias) {
-          const f32x4 b0 = *reinterpret_cast<const f32x4*>(p.bias + n0);
-          const f32x4 b1 = *reinterpret_cast<const f32x4*>(p.bias + n0 + 4);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { bv[e] = b0[e]; bv[4 + e] = b1[e]; }
-        }
-        if (p.row_bias) {
-          const float* rp = p.row_bias + (int64_t)(m / p.row_div) * p.ldrb + n0;
-          const f32x4 r0 = *reinterpret_cast<const f32x4*>(rp);
-          const f32x4 r1 = *reinterpret_cast<const f32x4*>(rp + 4);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { bv[e] += r0[e]; bv[4 + e] += r1[e]; }
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) x[e] = apply_act(x[e] * p.alpha + bv[e], p.act) * p.out_scale;
-        if (res_base) {
-          float rf[8];
-          unpack8(*reinterpret_cast<const u32x4*>(res_base + (int64_t)m * p.ldr + n0), rf);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) x[e] += rf[e];
-        }
-        if (p.out_f32) {
-          float* op = reinterpret_cast<float*>(c_base) + (int64_t)m * p.ldc + n0;
-          *reinterpret_cast<f32x4*>(op) = f32x4{x[0], x[1], x[2], x[3]};
-          *reinterpret_cast<f32x4*>(op + 4) = f32x4{x[4], x[5], x[6], x[7]};
-        } else {
-          *reinterpret_cast<u32x4*>(reinterpret_cast<bf16_t*>(c_base) + (int64_t)m * p.ldc + n0) = pack8(x);
-        }
-      }
-    }
+    epi_slab_pass16<CH_NT>(p, slab, acc[i], lane, frow, fq, col_w0, c_base, res_base,
+                           [&](int lr) { return (int)chx::out_row(pt, wm, i, lr); }, [](int, const u32x4&) {});
   };
   epi_pass(ic<0>{});
   epi_pass(ic<1>{});

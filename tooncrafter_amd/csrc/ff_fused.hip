@@ -27,8 +27,8 @@
 // Order of the fp32 sums: ff1 over K in ascending 16-slices, ff2 over the hidden index in ascending 16-slices -- the
 // order of the tiled kernels, so the result equals LayerNorm -> tc_gemm_bf16(GEGLU) -> tc_gemm_bf16(+residual) up to the
 // LayerNorm's own rounding.
-#include "gemm_common.h"
 #include "gemm_persist.h"
+#include "gemm_epilogue.h"
 
 #include <stdlib.h>
 
@@ -58,9 +58,6 @@ struct FfArgs {
   int tiles;
   unsigned long long* trace;     // TC_FF_TRACE (ABL bit 16 build): s_memtime after every barrier of block 0's waves 0 and 4
 };
-
-template <int N>
-__device__ __forceinline__ void ff_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // LA: W1 K-tiles requested ahead (2 or 3 of the ring's 4 stages; 4 = three ahead with the requests issued in the MFMA segment,
 // between the MFMAs, instead of in the read segment: 274-280 us against 265-268, profiles/r04_ff_fused_bench.txt -- kept as a switch).  ABL: timing ablations (TC_FF_ABLATE; wrong results) --
@@ -160,7 +157,7 @@ __global__ __launch_bounds__(FF_THREADS, 2) void ff_fused_kernel(const FfArgs p)
   dma_w1(0);
   dma_w1(1);
   if constexpr (LA >= 3) dma_w1(2);
-  ff_wait_vmcnt<0>();
+  tc_wait_vmcnt<0>();
   g8_barrier();
 
   const float* bl = reinterpret_cast<const float*>(smem + FF_B_OFF);
@@ -243,21 +240,21 @@ __global__ __launch_bounds__(FF_THREADS, 2) void ff_fused_kernel(const FfArgs p)
         // the K-tile the NEXT step reads has landed (this wave's pieces; the barrier makes it everybody's): the counts are
         // the requests issued after it -- see the table above the steps
         if constexpr (LA == 2) {
-          if (s == 0) ff_wait_vmcnt<2>();
-          else if (s == 2) ff_wait_vmcnt<5>();
-          else ff_wait_vmcnt<4>();
+          if (s == 0) tc_wait_vmcnt<2>();
+          else if (s == 2) tc_wait_vmcnt<5>();
+          else tc_wait_vmcnt<4>();
         } else if constexpr (LA == 3) {
-          if (s == 0) ff_wait_vmcnt<2>();
-          else if (s == 1) ff_wait_vmcnt<6>();
-          else if (s == 3) ff_wait_vmcnt<8>();
-          else ff_wait_vmcnt<7>();
+          if (s == 0) tc_wait_vmcnt<2>();
+          else if (s == 1) tc_wait_vmcnt<6>();
+          else if (s == 3) tc_wait_vmcnt<8>();
+          else tc_wait_vmcnt<7>();
         } else {
           // requests in the MFMA segments: M_s issues W1(q + 3) (two pieces), then piece s of this chunk's W2 slice.  The
           // tile the next step reads was requested two MFMA segments ago, first there; behind it: that segment's W2 piece
           // and the last segment's three requests (across the chunk seam everything was drained at the end of G)
-          if (s == 0) ff_wait_vmcnt<0>();
-          else if (s == 1) ff_wait_vmcnt<3>();
-          else ff_wait_vmcnt<4>();
+          if (s == 0) tc_wait_vmcnt<0>();
+          else if (s == 1) tc_wait_vmcnt<3>();
+          else tc_wait_vmcnt<4>();
         }
         bar();
         __builtin_amdgcn_s_setprio(1);
@@ -385,35 +382,10 @@ __global__ __launch_bounds__(FF_THREADS, 2) void ff_fused_kernel(const FfArgs p)
     // its own group reads, and this group's last read of them is behind it
     {
       float* slab = reinterpret_cast<float*>(smem + FF_H_OFF + wn * FF_H_BYTES + wm * 32 * 128);
-      const int vc = lane & 7, lr0 = lane >> 3;
-      auto pass = [&](auto J0_, auto NJ_, auto HALF_) {
+      auto pass = [&](auto J0_, auto NJ_, auto HALF_) {            // gemm_epilogue.h epi_fused_out_pass
         constexpr int j0 = decltype(J0_)::value, nj = decltype(NJ_)::value, half = decltype(HALF_)::value;
-#pragma unroll
-        for (int j = 0; j < nj; ++j)
-#pragma unroll
-          for (int qq = 0; qq < 8; ++qq) {
-            const int r = 8 * half + qq;
-            const int lr = (r & 3) + 4 * fhalf + 8 * ((r >> 2) & 1);
-            slab[lr * 64 + j * 32 + frow] = out_acc[j0 + j][r];
-          }
-        const int n0 = wn * 160 + j0 * 32 + vc * 8;
-        if (vc * 8 < nj * 32) {
-#pragma unroll
-          for (int qq = 0; qq < 2; ++qq) {
-            const int lr = lr0 + 8 * qq;
-            const int m = tile * FF_BM + wm * 32 + half * 16 + lr;
-            const f32x4 lo = *reinterpret_cast<const f32x4*>(slab + lr * 64 + vc * 8);
-            const f32x4 hi = *reinterpret_cast<const f32x4*>(slab + lr * 64 + vc * 8 + 4);
-            if (m < p.m) {
-              float xv[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-              float rf[8];
-              unpack8(*reinterpret_cast<const u32x4*>(p.x + (int64_t)m * p.ldx + n0), rf);
-#pragma unroll
-              for (int e = 0; e < 8; ++e) xv[e] = (xv[e] + bl[2 * FF_H + n0 + e]) + rf[e];
-              *reinterpret_cast<u32x4*>(p.out + (int64_t)m * p.ldo + n0) = pack8(xv);
-            }
-          }
-        }
+        epi_fused_out_pass<half, nj>(slab, out_acc + j0, lane, wn * 160 + j0 * 32, bl + 2 * FF_H, p.x, p.ldx, p.out, p.ldo,
+                                     [&](int lr, int64_t& m) { m = tile * FF_BM + wm * 32 + half * 16 + lr; return m < p.m; });
       };
       pass(ic<0>{}, ic<2>{}, ic<0>{});
       pass(ic<0>{}, ic<2>{}, ic<1>{});
@@ -423,7 +395,7 @@ __global__ __launch_bounds__(FF_THREADS, 2) void ff_fused_kernel(const FfArgs p)
       pass(ic<4>{}, ic<1>{}, ic<1>{});
     }
   }
-  ff_wait_vmcnt<0>();                               // the stream ran ahead: nothing may land in LDS after the block is gone
+  tc_wait_vmcnt<0>();                               // the stream ran ahead: nothing may land in LDS after the block is gone
 }
 
 int ff_mode() {        // TC_FF_FUSED = 0 never | 1 (default) whenever the shape is the level-0 block's; read per call

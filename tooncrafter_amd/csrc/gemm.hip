@@ -35,10 +35,9 @@ constexpr int BK = TC_BK;
 // low-resolution layers whose 128-tiles would not fill the 256 CUs; the big-M layers go to the
 // 256-row kernel of gemm_wide.hip.
 
-// PIPE: the K loop keeps TWO K-steps of tile loads in flight (both LDS stages requested before the first wait, stage k
-// re-requested as soon as every wave has consumed it) with counted s_waitcnt vmcnt + raw s_barrier -- a __syncthreads()
-// would drain the LDS-DMA queue (cdna_hip_programming.md, "Pipelining across barriers").  The plain loop has ONE K-step
-// in flight behind vmcnt(0) + barrier: with K = 320-1280 a tile's life is mostly exposed load latency.
+// PIPE: the K loop keeps TWO K-steps of tile loads in flight (gemm_common.h tc_kloop_pipe, where the protocol is stated).
+// The plain loop (tc_kloop_plain) has ONE K-step in flight behind vmcnt(0) + barrier: with K = 320-1280 a tile's life is
+// mostly exposed load latency.
 // (A per-wave epilogue -- private swizzled slabs, no block barrier, GEGLU evaluated in the accumulator layout after
 // v_permlane16_swap so that only the product crosses LDS -- was built, bit-identical in 12 epilogue cases, and measured
 // 1.01-1.02x on the GEGLU layers and 0.84-0.99x on the plain ones (128-byte instead of 256-byte row segments per store
@@ -51,11 +50,6 @@ constexpr int BK = TC_BK;
 // (0.73-1.02x: co-resident blocks are not in lock-step), and two output tiles per block back to back so that the first
 // tile's store acknowledgements arrive under the second K loop (0.90-1.09x where the grid stays >= 512 blocks, 0.57-0.85x
 // where it does not).)
-template <int N>
-__device__ __forceinline__ void gemm_wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 template <int GATHER, int TM, int TN, bool PIPE>
 __global__ __launch_bounds__(256, 2) void gemm_kernel(const TcGemmParams pin, const int splits, const int order,
                                                       const int late_epi) {
@@ -189,9 +183,6 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const TcGemmParams pin, co
     __builtin_amdgcn_sched_barrier(0);
   };
 
-  // LDS-DMA data is visible to a ds_read only after the issuing wave's vmcnt wait AND a barrier the
-  // reader has passed (MI355X_MICROARCH.md); the same barrier also retires the reads of the stage the
-  // next iteration overwrites.
   const int nk_all = (p.k + BK - 1) / BK;
   const int per = (nk_all + splits - 1) / splits;
   const int kb0 = blockIdx.y * per;
@@ -208,38 +199,11 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const TcGemmParams pin, co
     if (geglu) epi_load_bias<true, BM, BN>(p, tid, tile_n, pre);
     else epi_load_bias<false, BM, BN>(p, tid, tile_n, pre);
   }
-  if (PIPE) {
-    if (kb0 < nk) {
-      load_tile(kb0, 0);
-      if (kb0 + 1 < nk) load_tile(kb0 + 1, 1);
-      for (int kb = kb0; kb < nk; ++kb) {
-        const int st = (kb - kb0) & 1;
-        // stage st has landed: this wave's pieces (the RA + RB requests of the other stage may stay in flight), then
-        // everybody's (barrier)
-        if (kb + 1 < nk) gemm_wait_vmcnt<RA + RB>();
-        else gemm_wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        if (kb + 1 == nk && early && !geglu && p.residual) epi_load_residual<BM, BN>(p, tid, tile_m, tile_n, bz, pre);
-        compute(st);
-        if (kb + 2 < nk) {
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          __builtin_amdgcn_s_barrier();          // every wave is done reading stage st (its fragments are in registers)
-          load_tile(kb + 2, st);
-        }
-      }
-      __syncthreads();                           // the epilogue reuses the stage buffers
-    }
-  } else if (kb0 < nk) {
-    load_tile(kb0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    for (int kb = kb0; kb < nk; ++kb) {
-      if (kb + 1 < nk) load_tile(kb + 1, (kb + 1 - kb0) & 1);
-      else if (early && !geglu && p.residual) epi_load_residual<BM, BN>(p, tid, tile_m, tile_n, bz, pre);
-      compute((kb - kb0) & 1);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-    }
+  // the K loop (gemm_common.h); a split-K slice may have no steps.  The residual rows go in front of the last K-step
+  auto load_res = [&] { if (early && !geglu && p.residual) epi_load_residual<BM, BN>(p, tid, tile_m, tile_n, bz, pre); };
+  if (kb0 < nk) {
+    if (PIPE) tc_kloop_pipe<RA + RB>(kb0, nk, load_tile, compute, [&](int kb) { if (kb + 1 == nk) load_res(); });
+    else tc_kloop_plain(kb0, nk, load_tile, compute, load_res);
   }
 
   // ---- epilogue: accumulators -> LDS fp32 [BM][BN] -> row vectors

@@ -17,6 +17,7 @@
 // time, and finishes on 16-byte row vectors (bias / row bias / activation / residual / store).  GEGLU layers
 // (weights packed per 32 columns) stay on the 128x128 / 256x320 kernels.
 #include "gemm_persist.h"
+#include "gemm_epilogue.h"
 
 #include <stdlib.h>
 
@@ -29,7 +30,7 @@ constexpr int T16_WT = 80;                                   // wave tile
 constexpr int T16_NT = T16_WT / 16;                          // 5 MFMA tiles per wave-tile side
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
-// PIPE: two K-steps of tile loads in flight, counted vmcnt + raw barriers (see gemm.hip)
+// PIPE: two K-steps of tile loads in flight (gemm_common.h tc_kloop_pipe); otherwise one (tc_kloop_plain)
 // STATS (ABI 9, TcGemmParams.gn_part): the epilogue also emits, per output column, the sum and the sum of squares of
 // the tile's 160 rows of bf16-rounded outputs.  Vector v = lane + 64 q of a 16-row pass is (row v / 10, column group
 // v % 10) in EVERY pass, so a lane keeps one accumulator set per q (3 x 16 registers) and the walk of the plain
@@ -275,7 +276,7 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void gemm16_kernel(const
       if (nk > 1) {
         prep(1, 1);
         issue_all();
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(RA + RB) : "memory");         // step 0 has landed, step 1 may be in flight
+        tc_wait_vmcnt<RA + RB>();         // step 0 has landed, step 1 may be in flight
       } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
@@ -306,31 +307,9 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void gemm16_kernel(const
     }
     __syncthreads();                               // the epilogue slabs reuse the stage buffers
   } else if (PIPE) {
-    load_tile(0, 0);
-    if (nk > 1) load_tile(1, 1);
-    for (int kb = 0; kb < nk; ++kb) {
-      // stage kb & 1 has landed (the RA + RB requests of the other stage may stay in flight), for every wave
-      if (kb + 1 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(RA + RB) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      compute(kb & 1);
-      if (kb + 2 < nk) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();            // every wave has its fragments of this stage in registers
-        load_tile(kb + 2, kb & 1);
-      }
-    }
-    __syncthreads();                             // the epilogue slabs reuse the stage buffers
+    tc_kloop_pipe<RA + RB>(0, nk, load_tile, compute);       // gemm_common.h; the last barrier frees the stage buffers for the slabs
   } else {
-    load_tile(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    for (int kb = 0; kb < nk; ++kb) {
-      if (kb + 1 < nk) load_tile(kb + 1, (kb + 1) & 1);
-      compute(kb & 1);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-    }
+    tc_kloop_plain(0, nk, load_tile, compute);
   }
 
   // ---- epilogue: per wave, five passes of one 16-row tile row through a private fp32 slab [16][80]
@@ -344,63 +323,18 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void gemm16_kernel(const
   for (int q = 0; q < 3; ++q)
 #pragma unroll
     for (int e = 0; e < 8; ++e) { gs[q][e] = 0.f; gq[q][e] = 0.f; }
-  auto epi_pass = [&](auto I_) {
+  auto epi_pass = [&](auto I_) {                       // gemm_epilogue.h: spill, 160 vectors over 64 lanes, finisher
     constexpr int i = decltype(I_)::value;
-    // C/D layout of the 16x16 MFMA: col = lane & 15, row = 4 (lane >> 4) + reg
-#pragma unroll
-    for (int j = 0; j < T16_NT; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) slab[(fq * 4 + r) * T16_WT + j * 16 + frow] = acc[i][j][r];
-    // the same wave reads back (LDS operations of one wave complete in order): 160 vectors over 64 lanes
     const int row_base = tile_m * BM + wm * T16_WT + i * 16;
+    epi_slab_pass16<T16_NT>(p, slab, acc[i], lane, frow, fq, col_w0, c_base, res_base, [&](int lr) { return row_base + lr; },
+                            [&](int q, const u32x4& packed) {
+                              if (STATS) {
+                                float fr[8];
+                                unpack8(packed, fr);                     // what GroupNorm will read back: the rounded values
 #pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      const int v = lane + 64 * q;
-      const int lr = v / VPR, vc = v - lr * VPR;
-      const int m = row_base + lr;
-      const int n0 = col_w0 + vc * 8;
-      if (v < 16 * VPR && m < p.m && n0 < p.n) {
-        const f32x4 lo = *reinterpret_cast<const f32x4*>(slab + lr * T16_WT + vc * 8);
-        const f32x4 hi = *reinterpret_cast<const f32x4*>(slab + lr * T16_WT + vc * 8 + 4);
-        float x[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        float bv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (p.bias) {
-          const f32x4 b0 = *reinterpret_cast<const f32x4*>(p.bias + n0);
-          const f32x4 b1 = *reinterpret_cast<const f32x4*>(p.bias + n0 + 4);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { bv[e] = b0[e]; bv[4 + e] = b1[e]; }
-        }
-        if (p.row_bias) {
-          const float* rp = p.row_bias + (int64_t)(m / p.row_div) * p.ldrb + n0;
-          const f32x4 r0 = *reinterpret_cast<const f32x4*>(rp);
-          const f32x4 r1 = *reinterpret_cast<const f32x4*>(rp + 4);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { bv[e] += r0[e]; bv[4 + e] += r1[e]; }
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) x[e] = apply_act(x[e] * p.alpha + bv[e], p.act) * p.out_scale;
-        if (res_base) {
-          float rf[8];
-          unpack8(*reinterpret_cast<const u32x4*>(res_base + (int64_t)m * p.ldr + n0), rf);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) x[e] += rf[e];
-        }
-        if (p.out_f32) {
-          float* op = reinterpret_cast<float*>(c_base) + (int64_t)m * p.ldc + n0;
-          *reinterpret_cast<f32x4*>(op) = f32x4{x[0], x[1], x[2], x[3]};
-          *reinterpret_cast<f32x4*>(op + 4) = f32x4{x[4], x[5], x[6], x[7]};
-        } else {
-          const u32x4 packed = pack8(x);
-          *reinterpret_cast<u32x4*>(reinterpret_cast<bf16_t*>(c_base) + (int64_t)m * p.ldc + n0) = packed;
-          if (STATS) {
-            float fr[8];
-            unpack8(packed, fr);                     // what GroupNorm will read back: the rounded values
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { gs[q][e] += fr[e]; gq[q][e] += fr[e] * fr[e]; }
-          }
-        }
-      }
-    }
+                                for (int e = 0; e < 8; ++e) { gs[q][e] += fr[e]; gq[q][e] += fr[e] * fr[e]; }
+                              }
+                            });
   };
   using std::integral_constant;
   epi_pass(integral_constant<int, 0>{});

@@ -41,8 +41,8 @@
 // barrier, and -- because group 1 runs an interval behind -- starts under the other group's last MFMAs and ends under
 // its first.  Per wave: eight passes of 16 rows through the slab, 16-byte row vectors (bias / row bias / activation /
 // GEGLU / residual / store), the global operands of pass n+1 requested before pass n is computed.
-#include "gemm_common.h"
 #include "gemm_persist.h"
+#include "gemm_epilogue.h"
 
 #include <stdlib.h>
 
@@ -284,15 +284,7 @@ __global__ __launch_bounds__(G8_THREADS, 2) void gemm8_kernel(const TcGemmParams
     const int row_w0 = tm * G8_BM + grp * 128;
     auto spill = [&](auto I_, auto H_) {                 // accumulators of pass (i, half) -> slab
       constexpr int i = decltype(I_)::value, half = decltype(H_)::value;
-      // accumulator registers r = 8*half .. 8*half+7 hold local rows (r&3) + 4*fhalf + 8*((r>>2)&1)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const int r = 8 * half + q;
-          const int lr = (r & 3) + 4 * fhalf + 8 * ((r >> 2) & 1);
-          slab[lr * G8_WN + j * 32 + frow] = acc[i][j][r];
-        }
+      epi_spill32_half<half, 2, G8_WN>(slab, acc[i], frow, fhalf);
     };
     if (!geglu) {
       // lane -> vector column vc = lane & 7 (8 columns), slab rows lane>>3 and 8 + (lane>>3): the lane's 8 output
@@ -396,11 +388,7 @@ __global__ __launch_bounds__(G8_THREADS, 2) void gemm8_kernel(const TcGemmParams
         float x[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
         const float gt[8] = {glo[0], glo[1], glo[2], glo[3], ghi[0], ghi[1], ghi[2], ghi[3]};
 #pragma unroll
-        for (int e = 0; e < 8; e += 2) {        // pairs: packed fp32 arithmetic (common.h gelu_erf_f2)
-          const tc_f32x2 v = {x[e] + bv[e], x[e + 1] + bv[e + 1]};
-          const tc_f32x2 h = v * gelu_erf_f2(tc_f32x2{gt[e] + bg[e], gt[e + 1] + bg[e + 1]});
-          x[e] = h[0]; x[e + 1] = h[1];
-        }
+        for (int e = 0; e < 8; e += 2) epi_geglu_pair<true>(p, x + e, gt + e, bv + e, bg + e);     // (alpha = out_scale = 1: host)
         if (m < p.m && col_ok)
           *reinterpret_cast<u32x4*>(reinterpret_cast<bf16_t*>(c_base) + (int64_t)m * p.ldc + n0) = pack8(x);
       };

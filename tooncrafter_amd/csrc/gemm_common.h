@@ -57,6 +57,63 @@ __device__ __forceinline__ void glds16(tc_rsrc_t rsrc, char* lds, uint32_t voff,
   __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds, 16, voff, soff, 0, 0);
 }
 
+// ---- the K loops of the 4-wave skeleton (gemm.hip, gemm_wide.hip, gemm16.hip, qkv_attn.hip) over two LDS stages.
+// The invariant (MI355X_MICROARCH.md): LDS-DMA data is visible to a ds_read only after the ISSUING wave's vmcnt wait AND a
+// barrier the reader has passed; the same barrier retires the reads of the stage the next request overwrites.
+//   load_tile(kb, stage): request K-step kb into `stage` (REQS pieces per wave);  compute(stage): fragment reads + MFMAs.
+// Both loops run K-steps [kb0, nk), kb0 < nk (a caller that may have no steps guards the call), stage = (kb - kb0) & 1,
+// and end with a block barrier: the caller's epilogue may reuse the stage memory.
+//
+// Pipelined: TWO K-steps in flight.  Both stages are requested before the first wait; a counted vmcnt (the REQS requests
+// of the other stage may stay in flight) + a raw s_barrier makes a stage visible to everybody; lgkmcnt(0) + a barrier --
+// every wave has its fragments of the stage in registers -- come before the stage is re-requested.  Raw barriers: a
+// __syncthreads() would drain the DMA queue (cdna_hip_programming.md, "Pipelining across barriers").
+// before_compute(kb) runs behind the barrier of K-step kb, in front of its MFMAs (gemm.hip: the residual rows of the
+// epilogue in front of the last step).
+template <int REQS, class Load, class Compute, class Before>
+__device__ __forceinline__ void tc_kloop_pipe(int kb0, int nk, Load&& load_tile, Compute&& compute, Before&& before_compute) {
+  load_tile(kb0, 0);
+  if (kb0 + 1 < nk) load_tile(kb0 + 1, 1);
+  for (int kb = kb0; kb < nk; ++kb) {
+    const int st = (kb - kb0) & 1;
+    if (kb + 1 < nk) tc_wait_vmcnt<REQS>();
+    else tc_wait_vmcnt<0>();
+    __builtin_amdgcn_s_barrier();
+    before_compute(kb);
+    compute(st);
+    if (kb + 2 < nk) {
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      load_tile(kb + 2, st);
+    }
+  }
+  __syncthreads();
+}
+template <int REQS, class Load, class Compute>
+__device__ __forceinline__ void tc_kloop_pipe(int kb0, int nk, Load&& load_tile, Compute&& compute) {
+  tc_kloop_pipe<REQS>(kb0, nk, load_tile, compute, [](int) {});
+}
+
+// Plain: ONE K-step in flight behind vmcnt(0) + barrier -- step kb + 1 is requested, step kb computed, then everything
+// waits.  last_step() runs in the last K-step, where there is nothing left to request.
+template <class Load, class Compute, class Last>
+__device__ __forceinline__ void tc_kloop_plain(int kb0, int nk, Load&& load_tile, Compute&& compute, Last&& last_step) {
+  load_tile(kb0, 0);
+  tc_wait_vmcnt<0>();
+  __syncthreads();
+  for (int kb = kb0; kb < nk; ++kb) {
+    if (kb + 1 < nk) load_tile(kb + 1, (kb + 1 - kb0) & 1);
+    else last_step();
+    compute((kb - kb0) & 1);
+    tc_wait_vmcnt<0>();
+    __syncthreads();
+  }
+}
+template <class Load, class Compute>
+__device__ __forceinline__ void tc_kloop_plain(int kb0, int nk, Load&& load_tile, Compute&& compute) {
+  tc_kloop_plain(kb0, nk, load_tile, compute, [] {});
+}
+
 // Block -> output tile.  Blocks are dealt round-robin to the 8 XCDs (blockIdx & 7), each with its own L2, so
 // M-tile t always lives on XCD t & 7 and its A rows are fetched into one L2 only.  Within an XCD:
 //   order 0: all N-tiles of an M-tile back to back (A stays hot; W is re-streamed once per M-tile -- fine

@@ -1,8 +1,159 @@
-// Epilogues over the fp32 output tile staged in LDS, shared by the bf16 (gemm.hip) and MX-fp8 (gemm_mx.hip)
-// 4-wave kernels: bias / row bias / activation / GEGLU / residual on 16-byte row vectors.
+// The epilogue arithmetic of the GEMM kernels, stated once: bias / row bias / activation / GEGLU / residual on 16-byte row
+// vectors.  Two groups: first the pieces the per-wave epilogues share (the GEGLU pair, the row-vector finisher, the
+// accumulator -> slab passes: gemm_wide.hip, gemm16.hip, conv_halo.hip, gemm8.hip, ff_fused.hip, tb_fused.hip), then the
+// epilogues over the whole fp32 tile staged in LDS of the 4-wave kernels (gemm.hip, gemm_mx.hip), which use the pair too.
 #pragma once
 #include "gemm_common.h"
 
+// ---- GEGLU on a pair of columns: x <- v . gelu(g), v = x alpha + bv, g = gt alpha + bg, times out_scale; pairs because
+// the arithmetic is packed fp32 (common.h gelu_erf_f2).  PLAIN: alpha = out_scale = 1, the multiplies are not emitted.
+// The TC_ABLATE & 8 hook (scripts/ablate_gemm.sh: no erf) sits here and so in every caller's PLAIN path; only gemm.hip is
+// ever compiled with TC_ABLATE, the other callers (gemm_wide.hip, gemm8.hip, gemm_mx.hip) never see the macro.
+template <bool PLAIN>
+__device__ __forceinline__ void epi_geglu_pair(const TcGemmParams& p, float* x, const float* gt, const float* bv, const float* bg) {
+#if defined(TC_ABLATE) && (TC_ABLATE & 8)      // scripts/ablate_gemm.sh: the GEGLU epilogue without its erf
+  if (PLAIN) { x[0] = (x[0] + bv[0]) * (gt[0] + bg[0]); x[1] = (x[1] + bv[1]) * (gt[1] + bg[1]); }
+#else
+  if (PLAIN) {
+    const tc_f32x2 v = {x[0] + bv[0], x[1] + bv[1]};
+    const tc_f32x2 h = v * gelu_erf_f2(tc_f32x2{gt[0] + bg[0], gt[1] + bg[1]});
+    x[0] = h[0]; x[1] = h[1];
+  }
+#endif
+  else {
+    const tc_f32x2 v = {x[0] * p.alpha + bv[0], x[1] * p.alpha + bv[1]};
+    const tc_f32x2 h = v * gelu_erf_f2(tc_f32x2{gt[0] * p.alpha + bg[0], gt[1] * p.alpha + bg[1]}) * p.out_scale;
+    x[0] = h[0]; x[1] = h[1];
+  }
+}
+
+// ---- Row-vector finisher: 8 consecutive columns n0.. of output row m, raw accumulators in x:
+//     out = act(alpha x + (bias + row_bias[m / row_div])) out_scale + residual,   stored as bf16 or fp32.
+// Every operand is fetched here; c_base / res_base are the batch item's.  stored(packed) is called with the bf16 vector
+// that went to memory (the GroupNorm statistics of gemm16.hip sum the ROUNDED values); nothing is called for fp32 output.
+// ORDER OF ADDITIONS.  There are two in this library and both are part of their kernels' bits:
+//   x alpha + (bias + row_bias)   -- this finisher: gemm_wide.hip (non-GEGLU), gemm16.hip, conv_halo.hip;
+//   (x alpha + bias) + row_bias   -- the staged-tile path below (epilogue_fast / epilogue_tail: gemm.hip, gemm_mx.hip),
+//                                    splitk_reduce_kernel (gemm.hip) and gemm8.hip, which keep their own prefetch structure.
+template <class Stored>
+__device__ __forceinline__ void epi_finish_row8(const TcGemmParams& p, char* c_base, const bf16_t* res_base, int m, int n0,
+                                                float (&x)[8], Stored&& stored) {
+  float bv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (p.bias) {
+    const f32x4 b0 = *reinterpret_cast<const f32x4*>(p.bias + n0);
+    const f32x4 b1 = *reinterpret_cast<const f32x4*>(p.bias + n0 + 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { bv[e] = b0[e]; bv[4 + e] = b1[e]; }
+  }
+  if (p.row_bias) {
+    const float* rp = p.row_bias + (int64_t)(m / p.row_div) * p.ldrb + n0;
+    const f32x4 r0 = *reinterpret_cast<const f32x4*>(rp);
+    const f32x4 r1 = *reinterpret_cast<const f32x4*>(rp + 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { bv[e] += r0[e]; bv[4 + e] += r1[e]; }
+  }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) x[e] = apply_act(x[e] * p.alpha + bv[e], p.act) * p.out_scale;
+  if (res_base) {
+    float rf[8];
+    unpack8(*reinterpret_cast<const u32x4*>(res_base + (int64_t)m * p.ldr + n0), rf);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) x[e] += rf[e];
+  }
+  if (p.out_f32) {
+    float* op = reinterpret_cast<float*>(c_base) + (int64_t)m * p.ldc + n0;
+    *reinterpret_cast<f32x4*>(op) = f32x4{x[0], x[1], x[2], x[3]};
+    *reinterpret_cast<f32x4*>(op + 4) = f32x4{x[4], x[5], x[6], x[7]};
+  } else {
+    const u32x4 packed = pack8(x);
+    *reinterpret_cast<u32x4*>(reinterpret_cast<bf16_t*>(c_base) + (int64_t)m * p.ldc + n0) = packed;
+    stored(packed);
+  }
+}
+__device__ __forceinline__ void epi_finish_row8(const TcGemmParams& p, char* c_base, const bf16_t* res_base, int m, int n0,
+                                                float (&x)[8]) {
+  epi_finish_row8(p, c_base, res_base, m, n0, x, [](const u32x4&) {});
+}
+
+// ---- 16-row slab pass of the 16x16 MFMA layout (gemm16.hip, conv_halo.hip): one tile row of a wave -- NT accumulator
+// tiles `acc`, C/D layout col = lane & 15, row = 4 (lane >> 4) + reg -- goes to the wave's private fp32 slab [16][16 NT];
+// the same wave reads it back (LDS operations of one wave complete in order) as 16 x 2 NT vectors of 8 columns walked
+// over 64 lanes, vector v = lane + 64 q = (slab row v / VPR, column group v % VPR), and finishes each (epi_finish_row8).
+// frow = lane & 15, fq = lane >> 4: the kernel's own values (its fragment addressing uses them; formed afresh here they
+// fold into other address arithmetic and the spill loses its paired LDS writes).
+// row_of(slab row) -> output row;  col_w0: first output column of the wave;  stored(q, packed): see the finisher.
+template <int NT, class RowOf, class Stored>
+__device__ __forceinline__ void epi_slab_pass16(const TcGemmParams& p, float* slab, const f32x4 (&acc)[NT], int lane, int frow,
+                                                int fq, int col_w0, char* c_base, const bf16_t* res_base, RowOf&& row_of,
+                                                Stored&& stored) {
+  constexpr int WT = 16 * NT, VPR = WT / 8;
+#pragma unroll
+  for (int j = 0; j < NT; ++j)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) slab[(fq * 4 + r) * WT + j * 16 + frow] = acc[j][r];
+#pragma unroll
+  for (int q = 0; q < (16 * VPR + 63) / 64; ++q) {
+    const int v = lane + 64 * q;
+    const int lr = v / VPR, vc = v - lr * VPR;
+    const int m = row_of(lr);
+    const int n0 = col_w0 + vc * 8;
+    if (v < 16 * VPR && m < p.m && n0 < p.n) {
+      const f32x4 lo = *reinterpret_cast<const f32x4*>(slab + lr * WT + vc * 8);
+      const f32x4 hi = *reinterpret_cast<const f32x4*>(slab + lr * WT + vc * 8 + 4);
+      float x[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+      epi_finish_row8(p, c_base, res_base, m, n0, x, [&](const u32x4& packed) { stored(q, packed); });
+    }
+  }
+}
+
+// ---- half-accumulator spill of the 32x32 MFMA layout (gemm_wide.hip, gemm8.hip, ff_fused.hip, tb_fused.hip): registers
+// r = 8 HALF .. 8 HALF + 7 of NJ accumulator blocks side by side hold local rows (r & 3) + 4 fhalf + 8 ((r >> 2) & 1),
+// column frow of their block -> a 16-row fp32 slab with rows of LD floats.  HALF is a template argument so that the
+// accumulator indices stay static (a run-time index would send the whole accumulator file to scratch).
+template <int HALF, int NJ, int LD>
+__device__ __forceinline__ void epi_spill32_half(float* slab, const f32x16* acc, int frow, int fhalf) {
+#pragma unroll
+  for (int j = 0; j < NJ; ++j)
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int r = 8 * HALF + q;
+      const int lr = (r & 3) + 4 * fhalf + 8 * ((r >> 2) & 1);
+      slab[lr * LD + j * 32 + frow] = acc[j][r];
+    }
+}
+
+// ---- output pass of the level-0 fused kernels (ff_fused.hip, tb_fused.hip): 16 rows x (32 NJ <= 64) columns of a wave's
+// output accumulators through its private slab [16][64]; out = (acc + bias) + residual, the residual being the block's own
+// input rows x, as bf16.  n0w: first output column of the pass;  bias: the output bias (LDS);  row_of(slab row, m) ->
+// whether the row exists, and its row m of x / out (a flag beside the row, not a negative row: tb_fused.hip's rows always
+// exist, its constant `true` folds away, and a sentinel would cost that kernel a compare and a branch per row).
+template <int HALF, int NJ, class RowOf>
+__device__ __forceinline__ void epi_fused_out_pass(float* slab, const f32x16* acc, int lane, int n0w, const float* bias,
+                                                   const bf16_t* x, int ldx, bf16_t* out, int ldo, RowOf&& row_of) {
+  epi_spill32_half<HALF, NJ, 64>(slab, acc, lane & 31, lane >> 5);
+  const int vc = lane & 7, lr0 = lane >> 3;
+  const int n0 = n0w + vc * 8;
+  if (vc * 8 < NJ * 32) {
+#pragma unroll
+    for (int qq = 0; qq < 2; ++qq) {
+      const int lr = lr0 + 8 * qq;
+      int64_t m;
+      const bool ok = row_of(lr, m);
+      const f32x4 lo = *reinterpret_cast<const f32x4*>(slab + lr * 64 + vc * 8);
+      const f32x4 hi = *reinterpret_cast<const f32x4*>(slab + lr * 64 + vc * 8 + 4);
+      if (ok) {
+        float xv[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        float rf[8];
+        unpack8(*reinterpret_cast<const u32x4*>(x + m * ldx + n0), rf);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) xv[e] = (xv[e] + bias[n0 + e]) + rf[e];
+        *reinterpret_cast<u32x4*>(out + m * ldo + n0) = pack8(xv);
+      }
+    }
+  }
+}
+
+// ======== the 4-wave kernels' epilogue over the whole fp32 tile staged in LDS (gemm.hip, gemm_mx.hip) ========
 // The operands of the epilogue that come from global memory -- bias vectors and the residual rows -- are requested EARLY
 // (EpiPrefetch): the bias before the K loop, the residual in front of the last K-step, so their latency runs under the
 // MFMAs instead of standing between the K loop and the stores.  With K as short as 320-640 a tile's life is a dependent
@@ -129,22 +280,7 @@ __device__ __forceinline__ void epilogue_fast(const TcGemmParams& p, const float
 #pragma unroll
       for (int e = 0; e < 4; ++e) { gt[e] = lo[e]; gt[4 + e] = hi[e]; }
 #pragma unroll
-      for (int e = 0; e < 8; e += 2) {          // pairs: packed fp32 arithmetic (common.h gelu_erf_f2)
-#if defined(TC_ABLATE) && (TC_ABLATE & 8)      // scripts/ablate_gemm.sh: the GEGLU epilogue without its erf
-        if (PLAIN) { x[e] = (x[e] + bv[e]) * (gt[e] + bg[e]); x[e + 1] = (x[e + 1] + bv[e + 1]) * (gt[e + 1] + bg[e + 1]); }
-#else
-        if (PLAIN) {
-          const tc_f32x2 v = {x[e] + bv[e], x[e + 1] + bv[e + 1]};
-          const tc_f32x2 h = v * gelu_erf_f2(tc_f32x2{gt[e] + bg[e], gt[e + 1] + bg[e + 1]});
-          x[e] = h[0]; x[e + 1] = h[1];
-        }
-#endif
-        else {
-          const tc_f32x2 v = {x[e] * p.alpha + bv[e], x[e + 1] * p.alpha + bv[e + 1]};
-          const tc_f32x2 h = v * gelu_erf_f2(tc_f32x2{gt[e] * p.alpha + bg[e], gt[e + 1] * p.alpha + bg[e + 1]}) * p.out_scale;
-          x[e] = h[0]; x[e + 1] = h[1];
-        }
-      }
+      for (int e = 0; e < 8; e += 2) epi_geglu_pair<PLAIN>(p, x + e, gt + e, bv + e, bg + e);
     } else {
 #pragma unroll
       for (int e = 0; e < 8; ++e) {

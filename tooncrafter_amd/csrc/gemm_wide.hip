@@ -12,14 +12,14 @@
 // of K-step k+1 in flight under the 40 MFMAs per wave of K-step k, one barrier per K-step.  Epilogue: each wave
 // transposes its accumulators through a private 10 KiB LDS slab, 16 rows at a time, and finishes
 // on 16-byte row vectors (bias / row-bias / activation / GEGLU / residual / store).
-#include "gemm_common.h"
+#include "gemm_epilogue.h"
 
 namespace {
 
 constexpr int WBM = TC_BIG;
 constexpr int WTHREADS = 512;
 
-// PIPE: two K-steps of tile loads in flight, counted vmcnt + raw barriers (see gemm.hip)
+// PIPE: two K-steps of tile loads in flight (gemm_common.h tc_kloop_pipe); otherwise one (tc_kloop_plain)
 template <int GATHER, int TNW, bool PIPE>
 __global__ __launch_bounds__(WTHREADS, 2) void gemm_wide_kernel(const TcGemmParams p, const int order) {
   constexpr int BN = 64 * TNW;
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(WTHREADS, 2) void gemm_wide_kernel(const TcGemmPara
   const int64_t bz = blockIdx.z;
   const tc_rsrc_t w_rsrc = make_rsrc(reinterpret_cast<const bf16_t*>(p.w) + bz * p.stride_w, tc_w_extent(p));
 
-  // tile loads go global -> LDS directly (buffer_load_dwordx4 ... lds, see gemm.hip): lane l of a wave
+  // tile loads go global -> LDS directly (buffer_load_dwordx4 ... lds: gemm_common.h glds16): lane l of a wave
   // instruction lands at byte 16 l of a 1-KiB piece = (row l>>3, physical chunk l&7) of 8 tile rows, so
   // the XOR swizzle is applied to the source chunk the lane fetches
   const int lrow = tid >> 3;     // 0..63
@@ -133,35 +133,10 @@ __global__ __launch_bounds__(WTHREADS, 2) void gemm_wide_kernel(const TcGemmPara
     }
   };
 
-  // LDS-DMA data is visible to a ds_read only after the issuing wave's vmcnt wait AND a barrier the
-  // reader has passed; the same barrier retires the reads of the stage the next iteration overwrites.
+  // the K loop (gemm_common.h); its last barrier frees the stage buffers for the epilogue slabs
   const int nk = (p.k + TC_BK - 1) / TC_BK;
-  if (PIPE) {
-    load_tile(0, 0);
-    if (nk > 1) load_tile(1, 1);
-    for (int kb = 0; kb < nk; ++kb) {
-      if (kb + 1 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(RA + RB) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      compute(kb & 1);
-      if (kb + 2 < nk) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();            // every wave has its fragments of this stage in registers
-        load_tile(kb + 2, kb & 1);
-      }
-    }
-    __syncthreads();                             // the epilogue slabs reuse the stage buffers
-  } else {
-    load_tile(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    for (int kb = 0; kb < nk; ++kb) {
-      if (kb + 1 < nk) load_tile(kb + 1, (kb + 1) & 1);
-      compute(kb & 1);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-    }
-  }
+  if (PIPE) tc_kloop_pipe<RA + RB>(0, nk, load_tile, compute);
+  else tc_kloop_plain(0, nk, load_tile, compute);
 
   // ---- epilogue: per wave, 4 passes of 16 rows through a private fp32 slab
   const bool geglu = p.act == TC_ACT_GEGLU;
@@ -175,15 +150,7 @@ __global__ __launch_bounds__(WTHREADS, 2) void gemm_wide_kernel(const TcGemmPara
   // (a runtime index would send the whole accumulator file to scratch)
   auto epi_pass = [&](auto I_, auto H_) {
     constexpr int i = decltype(I_)::value, half = decltype(H_)::value;
-    // accumulator registers r = 8*half .. 8*half+7 hold local rows (r&3) + 4*fhalf + 8*((r>>2)&1)
-#pragma unroll
-    for (int j = 0; j < TNW; ++j)
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int r = 8 * half + q;
-        const int lr = (r & 3) + 4 * fhalf + 8 * ((r >> 2) & 1);
-        slab[lr * WN + j * 32 + frow] = acc[i][j][r];
-      }
+    epi_spill32_half<half, TNW, WN>(slab, acc[i], frow, fhalf);
     // same wave reads back: LDS operations of one wave complete in order
     const int row_base = tile_m * WBM + wm * 64 + i * 32 + half * 16;
     if (!geglu) {
@@ -199,35 +166,7 @@ __global__ __launch_bounds__(WTHREADS, 2) void gemm_wide_kernel(const TcGemmPara
         const f32x4 hi = *reinterpret_cast<const f32x4*>(slab + lr * WN + vc * 8 + 4);
         if (m < p.m && n0 < p.n) {
           float x[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-          float bv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-          if (p.bias) {
-            const f32x4 b0 = *reinterpret_cast<const f32x4*>(p.bias + n0);
-            const f32x4 b1 = *reinterpret_cast<const f32x4*>(p.bias + n0 + 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { bv[e] = b0[e]; bv[4 + e] = b1[e]; }
-          }
-          if (p.row_bias) {
-            const float* rp = p.row_bias + (int64_t)(m / p.row_div) * p.ldrb + n0;
-            const f32x4 r0 = *reinterpret_cast<const f32x4*>(rp);
-            const f32x4 r1 = *reinterpret_cast<const f32x4*>(rp + 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { bv[e] += r0[e]; bv[4 + e] += r1[e]; }
-          }
-#pragma unroll
-          for (int e = 0; e < 8; ++e) x[e] = apply_act(x[e] * p.alpha + bv[e], p.act) * p.out_scale;
-          if (res_base) {
-            float rf[8];
-            unpack8(*reinterpret_cast<const u32x4*>(res_base + (int64_t)m * p.ldr + n0), rf);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) x[e] += rf[e];
-          }
-          if (p.out_f32) {
-            float* op = reinterpret_cast<float*>(c_base) + (int64_t)m * p.ldc + n0;
-            *reinterpret_cast<f32x4*>(op) = f32x4{x[0], x[1], x[2], x[3]};
-            *reinterpret_cast<f32x4*>(op + 4) = f32x4{x[4], x[5], x[6], x[7]};
-          } else {
-            *reinterpret_cast<u32x4*>(reinterpret_cast<bf16_t*>(c_base) + (int64_t)m * p.ldc + n0) = pack8(x);
-          }
+          epi_finish_row8(p, c_base, res_base, m, n0, x);
         }
       }
     } else {
@@ -258,11 +197,7 @@ __global__ __launch_bounds__(WTHREADS, 2) void gemm_wide_kernel(const TcGemmPara
             for (int e = 0; e < 4; ++e) { bv[e] = b0[e]; bv[4 + e] = b1[e]; bg[e] = g0[e]; bg[4 + e] = g1[e]; }
           }
 #pragma unroll
-          for (int e = 0; e < 8; e += 2) {      // pairs: packed fp32 arithmetic (common.h gelu_erf_f2)
-            const tc_f32x2 v = {x[e] * p.alpha + bv[e], x[e + 1] * p.alpha + bv[e + 1]};
-            const tc_f32x2 h = v * gelu_erf_f2(tc_f32x2{gt[e] * p.alpha + bg[e], gt[e + 1] * p.alpha + bg[e + 1]}) * p.out_scale;
-            x[e] = h[0]; x[e + 1] = h[1];
-          }
+          for (int e = 0; e < 8; e += 2) epi_geglu_pair<false>(p, x + e, gt + e, bv + e, bg + e);
           if (p.out_f32) {
             float* op = reinterpret_cast<float*>(c_base) + (int64_t)m * p.ldc + n0;
             *reinterpret_cast<f32x4*>(op) = f32x4{x[0], x[1], x[2], x[3]};

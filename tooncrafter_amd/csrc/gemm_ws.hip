@@ -37,11 +37,6 @@ constexpr int WS_STAGES = 3;
 constexpr int WS_LOADS = WS_TILE_BYTES / 1024 / 4;   // LDS-DMA instructions per wave per tile (10)
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 template <int NT, bool GEGLU, bool RES, bool LN>
 __global__ __launch_bounds__(256, 1) void gemm_ws_kernel(const TcGemmParams p, const int nchunks, const int safe_wait) {
   constexpr int WCOLS = NT * 16;                     // W rows (= accumulator columns) per wave
@@ -150,10 +145,10 @@ __global__ __launch_bounds__(256, 1) void gemm_ws_kernel(const TcGemmParams p, c
     // residual loads (t-1), stores (t-1)].  The default count lets the newest LOADS + (2 | 1) * STORES of them stay in
     // flight -- which also retires the stores of iteration t-2; safe_wait = 2 keeps those in flight as well (their
     // write acknowledgements can take longer than one ~1.5 us iteration: measured by scripts/ws_bench.py).
-    if (safe_wait == 1) wait_vmcnt<0>();
-    else if (t == 0) wait_vmcnt<WS_LOADS>();
-    else if (safe_wait == 2 && t > 1) wait_vmcnt<WS_LOADS + (RES ? 4 : 2) * STORES>();
-    else wait_vmcnt<WS_LOADS + (RES ? 2 : 1) * STORES>();
+    if (safe_wait == 1) tc_wait_vmcnt<0>();
+    else if (t == 0) tc_wait_vmcnt<WS_LOADS>();
+    else if (safe_wait == 2 && t > 1) tc_wait_vmcnt<WS_LOADS + (RES ? 4 : 2) * STORES>();
+    else tc_wait_vmcnt<WS_LOADS + (RES ? 2 : 1) * STORES>();
     __builtin_amdgcn_s_barrier();
     // the barrier also says: every wave is done reading stage (t + 2) % 3 (tile t - 1): refill it
     load_tile(t + 2, (t + 2) % WS_STAGES);
@@ -269,7 +264,7 @@ __global__ __launch_bounds__(256, 1) void gemm_ws_kernel(const TcGemmParams p, c
       }
     }
   }
-  wait_vmcnt<0>();        // the two run-ahead DMA requests target this block's LDS: drain them before it is released
+  tc_wait_vmcnt<0>();        // the two run-ahead DMA requests target this block's LDS: drain them before it is released
 }
 
 }  // namespace

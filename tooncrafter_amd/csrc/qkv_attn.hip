@@ -16,9 +16,9 @@
 //  * a block owns 8 consecutive pixels x 16 frames = 128 GATHERED rows (tile row = pixel * 16 + frame; a pixel's frames are
 //    HW rows apart in memory) and ONE head: a 128 x 192 output tile [q_h | k_h | v_h] over K = C, on the 4-wave skeleton
 //    of csrc/gemm.hip -- tiles global -> LDS by buffer_load ... lds (XOR swizzle on the source side), two K-steps in
-//    flight with counted vmcnt + raw s_barrier, waves 2 x 2, each 64 x 96 = 2 x 3 v_mfma_f32_32x32x16_bf16 sub-tiles;
+//    flight (gemm_common.h tc_kloop_pipe), waves 2 x 2, each 64 x 96 = 2 x 3 v_mfma_f32_32x32x16_bf16 sub-tiles;
 //  * epilogue: + bias, bf16 (the roundings of the projection's own output), q and k row-major, v TRANSPOSED into the stage
-//    memory; then every wave runs the attention of two pixels on 16x16x32 MFMAs exactly as tb_fused.hip does (S^T = K Q^T:
+//    memory; then every wave runs the attention of two pixels on 16x16x32 MFMAs (attn_frames16.h tc_attn_frames16, shared with tb_fused.hip; S^T = K Q^T:
 //    a lane owns one query, softmax in-lane + two cross-row swaps, P re-laid as the A operand by permlane swaps, O = P V),
 //    writes O as bf16 over its pixels' q rows and stores those rows itself: 128 contiguous bytes per row, no block barrier
 //    after the attention;
@@ -29,6 +29,7 @@
 // tc_gemm_bf16 + tc_attn_temporal differ in ONE place (tc_attn_temporal keeps its softmax weights in fp32), as
 // tb_fused.hip does.
 #include "gemm_common.h"
+#include "attn_frames16.h"
 
 #include <stdlib.h>
 
@@ -51,33 +52,6 @@ struct QaArgs {
   float scale_log2e;
   int tiles, tiles_per_b;
 };
-
-template <int N>
-__device__ __forceinline__ void qa_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-// cross-row exchanges on the VALU (tb_fused.hip): every lane gets the values its 16-lane row pair / its half pair hold
-__device__ __forceinline__ void qa_swap16(uint32_t x, uint32_t& a, uint32_t& b) {
-  const auto r = __builtin_amdgcn_permlane16_swap(x, x, false, false);
-  a = r[0]; b = r[1];
-}
-__device__ __forceinline__ void qa_swap32(uint32_t x, uint32_t& a, uint32_t& b) {
-  const auto r = __builtin_amdgcn_permlane32_swap(x, x, false, false);
-  a = r[0]; b = r[1];
-}
-__device__ __forceinline__ float qa_max_rows(float x) {          // max over the four lanes l15 + 16 g
-  uint32_t a, b;
-  qa_swap16(__builtin_bit_cast(uint32_t, x), a, b);
-  x = fmaxf(__builtin_bit_cast(float, a), __builtin_bit_cast(float, b));
-  qa_swap32(__builtin_bit_cast(uint32_t, x), a, b);
-  return fmaxf(__builtin_bit_cast(float, a), __builtin_bit_cast(float, b));
-}
-__device__ __forceinline__ float qa_sum_rows(float x) {
-  uint32_t a, b;
-  qa_swap16(__builtin_bit_cast(uint32_t, x), a, b);
-  x = __builtin_bit_cast(float, a) + __builtin_bit_cast(float, b);
-  qa_swap32(__builtin_bit_cast(uint32_t, x), a, b);
-  return __builtin_bit_cast(float, a) + __builtin_bit_cast(float, b);
-}
 
 __global__ __launch_bounds__(QA_THREADS, 2) void qkv_attn_kernel(const QaArgs p) {
   __shared__ __attribute__((aligned(1024))) char smem[QA_LDS];
@@ -175,24 +149,8 @@ __global__ __launch_bounds__(QA_THREADS, 2) void qkv_attn_kernel(const QaArgs p)
     __builtin_amdgcn_sched_barrier(0);
   };
 
-  // ---- K loop (csrc/gemm.hip, PIPE): both stages requested before the first wait, a stage re-requested as soon as every
-  // wave has its fragments in registers; counted vmcnt + raw s_barrier (a __syncthreads() would drain the DMA queue)
-  const int nk = p.c / TC_BK;
-  load_tile(0, 0);
-  if (nk > 1) load_tile(1, 1);
-  for (int kb = 0; kb < nk; ++kb) {
-    const int st = kb & 1;
-    if (kb + 1 < nk) qa_wait_vmcnt<QA_RA + QA_RB>();
-    else qa_wait_vmcnt<0>();
-    __builtin_amdgcn_s_barrier();
-    compute(st);
-    if (kb + 2 < nk) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      load_tile(kb + 2, st);
-    }
-  }
-  __syncthreads();                                  // the epilogue reuses the stage memory
+  // ---- K loop: two K-steps in flight (gemm_common.h tc_kloop_pipe); its last barrier frees the stage memory for the epilogue
+  tc_kloop_pipe<QA_RA + QA_RB>(0, p.c / TC_BK, load_tile, compute);
 
   // ---- write-out of the projection: + bias, bf16.  Accumulator register r of a lane = row cr = (r & 3) + 8 (r >> 2)
   // + 4 fhalf of the 32-row block, column frow.  q / k: row-major [128][64], chunks swizzled by (row >> 1) & 7;
@@ -228,69 +186,11 @@ __global__ __launch_bounds__(QA_THREADS, 2) void qkv_attn_kernel(const QaArgs p)
   }
   __syncthreads();
 
-  // ---- attention: wave w takes pixels 2 w and 2 w + 1 (tile rows pr .. pr + 16 = the pixel's 16 frames), 16x16x32 MFMAs
-  const int l15 = lane & 15, g4 = lane >> 4;
-  typedef float f32x4_t __attribute__((ext_vector_type(4)));
+  // ---- attention: wave w takes pixels 2 w and 2 w + 1 (tile rows pr .. pr + 16 = the pixel's 16 frames); O lands as bf16
+  // over the pixel's q rows (dead: this wave alone read them)
 #pragma unroll
-  for (int pp = 0; pp < 2; ++pp) {
-    const int pr = wave_u * 32 + pp * 16;
-    const int row = pr + l15;
-    const int sw = (row >> 1) & 7;
-    const char* qrow = smem + QA_Q_OFF + row * 128;
-    const char* krow = smem + QA_K_OFF + row * 128;
-    f32x4_t st = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {                // S^T[key][query] = sum_d K[key][d] Q[query][d]
-      const int c = ((ks * 4 + g4) ^ sw) << 4;
-      const bf16x8 ka = *reinterpret_cast<const bf16x8*>(krow + c);
-      const bf16x8 qb = *reinterpret_cast<const bf16x8*>(qrow + c);
-      st = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka, qb, st, 0, 0, 0);
-    }
-    // lane: query l15, keys 4 g4 + r.  Softmax over the 16 keys: in-lane over r, across g4 by two swaps
-    float mx = fmaxf(fmaxf(st[0], st[1]), fmaxf(st[2], st[3]));
-    mx = qa_max_rows(mx);
-    float e[4], sum = 0.f;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { e[r] = __builtin_amdgcn_exp2f((st[r] - mx) * p.scale_log2e); sum += e[r]; }
-    sum = qa_sum_rows(sum);
-    const float inv = __builtin_amdgcn_rcpf(sum);
-    const uint32_t pk0 = pack2(e[0] * inv, e[1] * inv), pk1 = pack2(e[2] * inv, e[3] * inv);
-    // P as the A operand of P.V (rows = queries, k = keys 8 g' .. +7; keys 16..31 of the 32-deep slice are zero):
-    // lane (query, g' = 0) <- keys 0..3 (own) | 4..7 (lane + 16); (query, 1) <- 8..11 (lane + 16) | 12..15 (lane + 32)
-    uint32_t a0, b0, a1, b1, lo, hi, c0, d0, c1, d1;
-    qa_swap16(pk0, a0, b0);
-    qa_swap16(pk1, a1, b1);
-    qa_swap32(pk0, lo, hi);
-    qa_swap16(hi, c0, d0);
-    qa_swap32(pk1, lo, hi);
-    qa_swap16(hi, c1, d1);
-    const bool r0 = g4 == 0, r1 = g4 == 1;
-    u32x4 pw;
-    pw[0] = r0 ? a0 : (r1 ? c0 : 0u);
-    pw[1] = r0 ? a1 : (r1 ? c1 : 0u);
-    pw[2] = r0 ? b0 : (r1 ? d0 : 0u);
-    pw[3] = r0 ? b1 : (r1 ? d1 : 0u);
-    const bf16x8 pa = __builtin_bit_cast(bf16x8, pw);
-    // O[query][d] = sum_key P[query][key] V[key][d]: B operand from v^T (lane: dim db*16 + l15, keys 8 g' .. +7 of the
-    // pixel; g' >= 2 meets the zero half of P: it re-reads the valid half, never uninitialised bytes)
-    const char* vt = smem + QA_VT_OFF + l15 * QA_VT_LD + (pr + 8 * (g4 & 1)) * 2;
-    f32x4_t od[4];
-#pragma unroll
-    for (int db = 0; db < 4; ++db) {
-      const bf16x8 vb = *reinterpret_cast<const bf16x8*>(vt + db * 16 * QA_VT_LD);
-      od[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa, vb, f32x4_t{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-    }
-    // lane: dim db*16 + l15, queries 4 g4 + r -> bf16 over the pixel's q rows (dead: this wave alone read them, above)
-#pragma unroll
-    for (int db = 0; db < 4; ++db)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int orow = pr + 4 * g4 + r;
-        const int d = db * 16 + l15;
-        char* dst = smem + QA_Q_OFF + orow * 128 + (((d >> 3) ^ ((orow >> 1) & 7)) << 4) + (d & 7) * 2;
-        *reinterpret_cast<bf16_t*>(dst) = (bf16_t)od[db][r];
-      }
-  }
+  for (int pp = 0; pp < 2; ++pp)
+    tc_attn_frames16(smem + QA_Q_OFF, smem + QA_K_OFF, smem + QA_VT_OFF, QA_VT_LD, wave_u * 32 + pp * 16, lane, p.scale_log2e);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // this wave's 32 output rows are in LDS (written by this wave only)
 
   // ---- store: the wave's 32 rows x 64 columns, 8 lanes per row (128 contiguous bytes), 8 rows per pass

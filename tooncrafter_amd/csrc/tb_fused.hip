@@ -15,9 +15,10 @@
 //    of Wqkv: stage A = the head's 64 q rows | its 64 k rows (waves wn = 0 produce q, wn = 1 produce k, 8 MFMAs per K-step),
 //    stage B = its 64 v rows (waves wn = 0 only).  q and k go to LDS row-major, v TRANSPOSED ([64 dims][128 rows], the B
 //    operand of P.V); then every wave runs the attention of ONE pixel (wave (wm, wn): pixel 2 wm + wn) on 16x16x32 MFMAs:
-//    S^T = K Q^T (a lane owns one query: softmax reductions in-lane + two shuffles), P re-laid as the A operand by four
-//    ds_bpermute, O = P V, written as bf16 in A layout over the head's q rows; then 20 MFMAs of the output projection
-//    against Wo's [320 x 64] slice into the wave's 32 x 160 output accumulators, which live across the heads;
+//    S^T = K Q^T (a lane owns one query: softmax reductions in-lane + two cross-row swaps), P re-laid as the A operand by
+//    permlane swaps, O = P V, written as bf16 in A layout over the head's q rows (attn_frames16.h tc_attn_frames16); then
+//    20 MFMAs of the output projection against Wo's [320 x 64] slice into the wave's 32 x 160 output accumulators, which
+//    live across the heads;
 //  * weights (819 KB, L2-resident) stream by LDS-DMA from inline asm: Wqkv K-tiles through a ring of three 16 KiB stages
 //    (requested two steps ahead; the stream runs on across heads and tiles), Wo's slice once per head in five pieces;
 //    every wait is a hand-counted vmcnt;
@@ -26,8 +27,9 @@
 // LDS: W ring 48 KiB | Wo slice 40 | q (then the head's output) 16 | k 16 | v^T 17 | biases 5 | parked A fragments 12 = 154 KiB.
 // Roundings: LayerNorm output, q / k / v, the softmax weights and the attention output in bf16, sums in fp32 -- the
 // roundings of the four launches (tc_attn_temporal keeps its softmax weights in fp32: the one difference).
-#include "gemm_common.h"
 #include "gemm_persist.h"
+#include "gemm_epilogue.h"
+#include "attn_frames16.h"
 
 #include <stdlib.h>
 
@@ -61,35 +63,6 @@ struct TbArgs {
   unsigned long long* trace;   // TC_TB_TRACE (with TC_TB_ABLATE bit 8): s_memtime after every barrier of block 0's waves 0 and 4
   int stagger;      // TC_TB_STAGGER: block i starts (i & 3) * stagger * ~3.4 us late (de-phases the blocks' memory phases)
 };
-
-// v_permlane16_swap / v_permlane32_swap with both operands = x: every lane gets (a, b) = the values its 16-lane row pair
-// (lanes l and l ^ 16) / its half pair (l and l ^ 32) hold, lower row's first -- a cross-row exchange on the VALU instead of a
-// ds_bpermute round trip through LDS
-__device__ __forceinline__ void tb_swap16(uint32_t x, uint32_t& a, uint32_t& b) {
-  const auto r = __builtin_amdgcn_permlane16_swap(x, x, false, false);
-  a = r[0]; b = r[1];
-}
-__device__ __forceinline__ void tb_swap32(uint32_t x, uint32_t& a, uint32_t& b) {
-  const auto r = __builtin_amdgcn_permlane32_swap(x, x, false, false);
-  a = r[0]; b = r[1];
-}
-__device__ __forceinline__ float tb_max_rows(float x) {         // max over the four lanes l15 + 16 g
-  uint32_t a, b;
-  tb_swap16(__builtin_bit_cast(uint32_t, x), a, b);
-  x = fmaxf(__builtin_bit_cast(float, a), __builtin_bit_cast(float, b));
-  tb_swap32(__builtin_bit_cast(uint32_t, x), a, b);
-  return fmaxf(__builtin_bit_cast(float, a), __builtin_bit_cast(float, b));
-}
-__device__ __forceinline__ float tb_sum_rows(float x) {
-  uint32_t a, b;
-  tb_swap16(__builtin_bit_cast(uint32_t, x), a, b);
-  x = __builtin_bit_cast(float, a) + __builtin_bit_cast(float, b);
-  tb_swap32(__builtin_bit_cast(uint32_t, x), a, b);
-  return __builtin_bit_cast(float, a) + __builtin_bit_cast(float, b);
-}
-
-template <int N>
-__device__ __forceinline__ void tb_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 template <bool TRACE>
 __global__ __launch_bounds__(TB_THREADS, 2) void tb_fused_kernel(const TbArgs p) {
@@ -169,7 +142,7 @@ __global__ __launch_bounds__(TB_THREADS, 2) void tb_fused_kernel(const TbArgs p)
   int q = 0;                                        // K-tile stream position consumed next
   dma_w(0);
   dma_w(1);
-  tb_wait_vmcnt<0>();
+  tc_wait_vmcnt<0>();
   g8_barrier();
 
   const float* bl = reinterpret_cast<const float*>(smem + TB_B_OFF);
@@ -253,7 +226,7 @@ __global__ __launch_bounds__(TB_THREADS, 2) void tb_fused_kernel(const TbArgs p)
         if (stage == 1 && s >= 2) dma_wo(h, s);
         constexpr int pos = stage * 5 + s;
         constexpr int keep = pos <= 2 ? 2 : (pos <= 5 ? 1 : (pos == 6 ? 3 : 4));
-        tb_wait_vmcnt<keep>();
+        tc_wait_vmcnt<keep>();
         bar();
         __builtin_amdgcn_s_setprio(1);
         if (act) {
@@ -346,68 +319,8 @@ __global__ __launch_bounds__(TB_THREADS, 2) void tb_fused_kernel(const TbArgs p)
       // (The other group's Wo pieces are only known to have landed after ITS drain, one interval behind this one: this
       // interval separates that drain from the output projection's reads, as the empty interval of ff_fused.hip does.)
       {
-        const int gl = lane_now();
-        const int l15 = gl & 15, g4 = gl >> 4;
-        const int pr = wm * 32 + wn * 16;
-        const int row = pr + l15;
-        const int sw = (row >> 1) & 7;
-        const char* qrow = smem + TB_Q_OFF + row * 128;
-        const char* krow = smem + TB_K_OFF + row * 128;
-        typedef float f32x4_t __attribute__((ext_vector_type(4)));
-        f32x4_t st = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {               // S^T[key][query] = sum_d K[key][d] Q[query][d]
-          const int c = ((ks * 4 + g4) ^ sw) << 4;
-          const bf16x8 ka = *reinterpret_cast<const bf16x8*>(krow + c);
-          const bf16x8 qb = *reinterpret_cast<const bf16x8*>(qrow + c);
-          st = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka, qb, st, 0, 0, 0);
-        }
-        // lane: query l15, keys 4 g4 + r.  Softmax over the 16 keys: in-lane over r, across g4 by two shuffles
-        float mx = fmaxf(fmaxf(st[0], st[1]), fmaxf(st[2], st[3]));
-        mx = tb_max_rows(mx);
-        float e[4], sum = 0.f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { e[r] = __builtin_amdgcn_exp2f((st[r] - mx) * p.scale_log2e); sum += e[r]; }
-        sum = tb_sum_rows(sum);
-        const float inv = __builtin_amdgcn_rcpf(sum);
-        const uint32_t pk0 = pack2(e[0] * inv, e[1] * inv), pk1 = pack2(e[2] * inv, e[3] * inv);
-        // P as the A operand of P.V (rows = queries, k = keys 8 g' .. +7, keys 16..31 of the 32-deep slice are zero):
-        // lane (query, g' = 0) <- keys 0..3 (own) | 4..7 (lane + 16); (query, 1) <- 8..11 (lane + 16) | 12..15 (lane + 32)
-        // (rows of 16 lanes r0..r3 = g4: swap16(x) gives row 0 (x.r0, x.r1); swap32(x)'s second value brings rows 2, 3 down
-        // to rows 0, 1, and swap16 of THAT gives row 1 (x.r2, x.r3))
-        uint32_t a0, b0, a1, b1, lo, hi, c0, d0, c1, d1;
-        tb_swap16(pk0, a0, b0);
-        tb_swap16(pk1, a1, b1);
-        tb_swap32(pk0, lo, hi);
-        tb_swap16(hi, c0, d0);
-        tb_swap32(pk1, lo, hi);
-        tb_swap16(hi, c1, d1);
-        const bool r0 = g4 == 0, r1 = g4 == 1;
-        u32x4 pw;
-        pw[0] = r0 ? a0 : (r1 ? c0 : 0u);
-        pw[1] = r0 ? a1 : (r1 ? c1 : 0u);
-        pw[2] = r0 ? b0 : (r1 ? d0 : 0u);
-        pw[3] = r0 ? b1 : (r1 ? d1 : 0u);
-        const bf16x8 pa = __builtin_bit_cast(bf16x8, pw);
-        // O[query][d] = sum_key P[query][key] V[key][d]: B operand from v^T (lane: dim db*16 + l15, keys 8 g' .. +7 of the
-        // pixel; g' >= 2 meets the zero half of P: it re-reads the valid half, never uninitialised bytes)
-        const char* vt = smem + TB_VT_OFF + l15 * TB_VT_LD + (pr + 8 * (g4 & 1)) * 2;
-        f32x4_t od[4];
-#pragma unroll
-        for (int db = 0; db < 4; ++db) {
-          const bf16x8 vb = *reinterpret_cast<const bf16x8*>(vt + db * 16 * TB_VT_LD);
-          od[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa, vb, f32x4_t{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-        }
-        // lane: dim db*16 + l15, queries 4 g4 + r -> the head's output over its q rows, A layout of the projection
-#pragma unroll
-        for (int db = 0; db < 4; ++db)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int orow = pr + 4 * g4 + r;
-            const int d = db * 16 + l15;
-            char* dst = smem + TB_Q_OFF + orow * 128 + (((d >> 3) ^ ((orow >> 1) & 7)) << 4) + (d & 7) * 2;
-            *reinterpret_cast<bf16_t*>(dst) = (bf16_t)od[db][r];
-          }
+        // attn_frames16.h: S^T = K Q^T, softmax, O = P V, the head's output over its q rows in the A layout of the projection
+        tc_attn_frames16(smem + TB_Q_OFF, smem + TB_K_OFF, smem + TB_VT_OFF, TB_VT_LD, wm * 32 + wn * 16, lane_now(), p.scale_log2e);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         bar();
       }
@@ -447,33 +360,10 @@ __global__ __launch_bounds__(TB_THREADS, 2) void tb_fused_kernel(const TbArgs p)
     // buffers (dead: the last head's attention is behind every wave)
     {
       float* slab = reinterpret_cast<float*>(smem + TB_K_OFF + wave_u * 4096);
-      const int vc = lane & 7, lr0 = lane >> 3;
-      auto pass = [&](auto J0_, auto NJ_, auto HALF_) {
+      auto pass = [&](auto J0_, auto NJ_, auto HALF_) {            // gemm_epilogue.h epi_fused_out_pass
         constexpr int j0 = decltype(J0_)::value, nj = decltype(NJ_)::value, half = decltype(HALF_)::value;
-#pragma unroll
-        for (int j = 0; j < nj; ++j)
-#pragma unroll
-          for (int qq = 0; qq < 8; ++qq) {
-            const int r = 8 * half + qq;
-            const int lr = (r & 3) + 4 * fhalf + 8 * ((r >> 2) & 1);
-            slab[lr * 64 + j * 32 + frow] = out_acc[j0 + j][r];
-          }
-        const int n0 = wn * 160 + j0 * 32 + vc * 8;
-        if (vc * 8 < nj * 32) {
-#pragma unroll
-          for (int qq = 0; qq < 2; ++qq) {
-            const int lr = lr0 + 8 * qq;
-            const int64_t m = grow(wm * 32 + half * 16 + lr);
-            const f32x4 lo = *reinterpret_cast<const f32x4*>(slab + lr * 64 + vc * 8);
-            const f32x4 hi = *reinterpret_cast<const f32x4*>(slab + lr * 64 + vc * 8 + 4);
-            float xv[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-            float rf[8];
-            unpack8(*reinterpret_cast<const u32x4*>(p.x + m * p.ldx + n0), rf);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) xv[e] = (xv[e] + bl[3 * TB_C + n0 + e]) + rf[e];
-            *reinterpret_cast<u32x4*>(p.out + m * p.ldo + n0) = pack8(xv);
-          }
-        }
+        epi_fused_out_pass<half, nj>(slab, out_acc + j0, lane, wn * 160 + j0 * 32, bl + 3 * TB_C, p.x, p.ldx, p.out, p.ldo,
+                                     [&](int lr, int64_t& m) { m = grow(wm * 32 + half * 16 + lr); return true; });
       };
       if (!(p.abl & 4)) {
         pass(ic<0>{}, ic<2>{}, ic<0>{});
@@ -485,7 +375,7 @@ __global__ __launch_bounds__(TB_THREADS, 2) void tb_fused_kernel(const TbArgs p)
       }
     }
   }
-  tb_wait_vmcnt<0>();                               // the stream ran ahead: nothing may land in LDS after the block is gone
+  tc_wait_vmcnt<0>();                               // the stream ran ahead: nothing may land in LDS after the block is gone
 }
 
 // TC_TB_FUSED = 1 whenever the shape is the level-0 block's | 0 never (the DEFAULT since round 6); read per call.
