@@ -182,16 +182,28 @@ int tc_temporal_attn_fused_eligible(const TcTbParams* p);
 int tc_temporal_attn_fused(const TcTbParams* p, void* stream);
 
 /* ABI 13 -- the fused q / k / v projection of a temporal self-attention and the attention itself as ONE launch
- * (lvdm/modules/attention.py:81-144: to_q / to_k / to_v at :96-102, the per-head softmax(q k^T * scale) v over the T = 16
+ * (lvdm/modules/attention.py:81-144: to_q / to_k / to_v at :96-102, the per-head softmax(q k^T * scale) v over the T
  * frames of a pixel at :103-134 -- called with context = None from TemporalTransformer, attention.py:365-412):
  *     out[:, h*64 .. h*64+63] = Attn_frames(x . wqkv[q_h | k_h | v_h]^T + bqkv),     every head h
  * i.e. tc_gemm_bf16(x, wqkv) followed by tc_attn_temporal, without the [rows, 3c] tensor between them reaching HBM.
- * `out` is what to_out (a tc_gemm_bf16 with bias and residual) takes next.  t = 16, c = heads * 64, hw % 8 == 0
- * (tc_temporal_qkv_attn_eligible): every level of the UNet (c = 320 ... 1280; since round 6 level 0 takes LayerNorm -> this ->
- * to_out by default, tc_temporal_attn_fused only with TC_TB_FUSED=1).
+ * `out` is what to_out (a tc_gemm_bf16 with bias and residual) takes next.
+ * Domain (tc_temporal_qkv_attn_eligible; anything else returns TC_ESHAPE and launches nothing): c = heads * 64; ldx, ldo >= c
+ * and multiples of 8; a block's rows within 31 bits of its first; and
+ *   t = 16                       hw % 8 == 0 (csrc/qkv_attn.hip): every level of the UNet (c = 320 ... 1280; since round 6
+ *                                level 0 takes LayerNorm -> this -> to_out by default, tc_temporal_attn_fused only with
+ *                                TC_TB_FUSED=1);
+ *   17 <= t <= TC_TEMPORAL_MAX_FRAMES   hw % (128 / TT) == 0 with TT = 32 for t <= 32, else 64 (csrc/qkv_attn_long.hip).  The
+ *                                frame count is padded to TT slots inside the kernel: a padded slot reads zeros (never
+ *                                the next clip's rows, nor anything behind x), takes no part in any softmax, and is never
+ *                                stored -- x and out hold exactly b*t*hw rows.
+ *   t < 16 and t > TC_TEMPORAL_MAX_FRAMES are refused: tc_gemm_bf16 + tc_attn_temporal take them.
+ * TC_QKV_ATTN (environment, read per call): 0 = never eligible; 1 (default) = 16 frames, plus the 17 .. 64-frame shapes
+ * that measured ahead of the two launches: c = 320 or 640 with t >= 24 (t <= 32) or t >= 48 (t > 32), c = 1280
+ * with t = 32 or t = 64; 2 = every shape above.
  *   x     [b*t*hw, ldx] bf16, row = (batch * t + frame) * hw + pixel: the projection's input (the LayerNorm's output);
  *   wqkv  [3*c, c] bf16: rows [0, c) = to_q, [c, 2c) = to_k, [2c, 3c) = to_v (head h at h*64) -- tc_gemm_bf16's operand;
- *   bqkv  [3*c] fp32 or NULL (the reference's projections have no bias);   out [b*t*hw, ldo] bf16;   scale = 64^-0.5. */
+ *   bqkv  [3*c] fp32 or NULL (the reference's projections have no bias);   out [b*t*hw, ldo] bf16;   scale = 64^-0.5.
+ * `out` must not alias `x`: a block stores its rows while other blocks (the other heads of the same rows) still read x. */
 typedef struct TcTqaParams {
   const tc_bf16* x; const tc_bf16* wqkv; const float* bqkv; tc_bf16* out;
   int32_t b, t, hw, c, heads, ldx, ldo;

@@ -99,7 +99,7 @@ class TcTbParams(C.Structure):
 
 
 class TcTqaParams(C.Structure):
-    """ABI 13: temporal qkv projection + attention as one launch (csrc/qkv_attn.hip)."""
+    """ABI 13: temporal qkv projection + attention as one launch (csrc/qkv_attn.hip; 17 .. 64 frames: csrc/qkv_attn_long.hip)."""
     _fields_ = [
         ("x", C.c_void_p), ("wqkv", C.c_void_p), ("bqkv", C.c_void_p), ("out", C.c_void_p),
         ("b", C.c_int32), ("t", C.c_int32), ("hw", C.c_int32), ("c", C.c_int32), ("heads", C.c_int32),

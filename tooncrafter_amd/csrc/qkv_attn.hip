@@ -28,30 +28,12 @@
 // live in the stage memory.  Roundings: q / k / v, the softmax weights and the attention output in bf16, sums in fp32 --
 // tc_gemm_bf16 + tc_attn_temporal differ in ONE place (tc_attn_temporal keeps its softmax weights in fp32), as
 // tb_fused.hip does.
-#include "gemm_common.h"
+#include "qkv_attn_tile.h"     // the tile's geometry, the LDS places of q / k / v^T, QaArgs (shared with qkv_attn_long.hip)
 #include "attn_frames16.h"
 
 #include <stdlib.h>
 
 namespace {
-
-constexpr int QA_BM = 128, QA_BN = 192, QA_THREADS = 256, QA_T = 16;
-constexpr int QA_A_BYTES = QA_BM * TC_BK * 2;                 // 16 KiB
-constexpr int QA_STAGE = (QA_BM + QA_BN) * TC_BK * 2;         // 40 KiB
-constexpr int QA_LDS = 2 * QA_STAGE;                          // 80 KiB
-constexpr int QA_Q_OFF = 0;                                   // [128 rows][64] bf16, 16-byte chunks XOR-swizzled by (row >> 1) & 7
-constexpr int QA_K_OFF = 128 * 128;
-constexpr int QA_VT_OFF = 2 * 128 * 128;                      // [64 dims][128 rows + 8] bf16: 272-byte rows
-constexpr int QA_VT_LD = 272;
-static_assert(QA_VT_OFF + 64 * QA_VT_LD <= QA_LDS, "epilogue buffers live in the stage memory");
-constexpr int QA_RA = QA_BM / 32, QA_RB = QA_BN / 32;         // loader rows per thread: 4 + 6 requests per K-step
-
-struct QaArgs {
-  const bf16_t* x; const bf16_t* w; const float* bias; bf16_t* out;
-  int hw, c, heads, ldx, ldo;
-  float scale_log2e;
-  int tiles, tiles_per_b;
-};
 
 __global__ __launch_bounds__(QA_THREADS, 2) void qkv_attn_kernel(const QaArgs p) {
   __shared__ __attribute__((aligned(1024))) char smem[QA_LDS];
@@ -204,15 +186,22 @@ __global__ __launch_bounds__(QA_THREADS, 2) void qkv_attn_kernel(const QaArgs p)
   }
 }
 
-int qa_mode() {        // TC_QKV_ATTN = 0 never | 1 (default) wherever eligible and tb_fused.hip does not take the block; read per call
+// TC_QKV_ATTN, read per call: 0 never | 1 (default) 16 frames wherever eligible, 17 .. 64 frames where the measured rule of
+// qkv_attn_long.hip admits the shape | 2 every shape either kernel can take
+int qa_mode() {
   const char* e = getenv("TC_QKV_ATTN");
   return e ? atoi(e) : 1;
 }
 
 }  // namespace
 
+// 17 .. TC_TEMPORAL_MAX_FRAMES frames: csrc/qkv_attn_long.hip (its own shape rule, and what mode 1 admits of it)
+int qkv_attn_long_eligible(const TcTqaParams* p, int mode);
+int qkv_attn_long_launch(const TcTqaParams* p, hipStream_t stream);
+
 extern "C" int tc_temporal_qkv_attn_eligible(const TcTqaParams* p) {
   if (!p || qa_mode() == 0) return 0;
+  if (p->t > QA_T) return qkv_attn_long_eligible(p, qa_mode());
   if (p->t != QA_T || p->b <= 0 || p->hw <= 0 || (p->hw & 7)) return 0;
   if (p->heads <= 0 || p->c != p->heads * 64) return 0;
   if (p->ldx < p->c || p->ldo < p->c || (p->ldx & 7) || (p->ldo & 7)) return 0;
@@ -228,6 +217,7 @@ extern "C" int tc_temporal_qkv_attn(const TcTqaParams* p, void* stream) {
   if (!p || !p->x || !p->wqkv || !p->out) return TC_EINVAL;
   if (!tc_temporal_qkv_attn_eligible(p)) return TC_ESHAPE;
   if (!tc_aligned16(p->x) || !tc_aligned16(p->wqkv) || !tc_aligned16(p->out)) return TC_EALIGN;
+  if (p->t > QA_T) return qkv_attn_long_launch(p, reinterpret_cast<hipStream_t>(stream));
   QaArgs a;
   a.x = reinterpret_cast<const bf16_t*>(p->x); a.w = reinterpret_cast<const bf16_t*>(p->wqkv); a.bias = p->bqkv;
   a.out = reinterpret_cast<bf16_t*>(p->out);

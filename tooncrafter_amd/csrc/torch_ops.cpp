@@ -351,7 +351,7 @@ Tensor temporal_attn_fused_meta(const Tensor& x, const Tensor&, const Tensor&, c
   return at::empty({x.size(0), x.size(1)}, x.options());
 }
 
-// ABI 13: the temporal q / k / v projection and its attention as one launch (csrc/qkv_attn.hip)
+// ABI 13: the temporal q / k / v projection and its attention as one launch (csrc/qkv_attn.hip; 17 .. 64 frames: csrc/qkv_attn_long.hip -- any t is passed through, the library decides)
 Tensor temporal_qkv_attn_cuda(const Tensor& x, const Tensor& wqkv, const optional<Tensor>& bqkv, int64_t b, int64_t t, int64_t hw,
                               int64_t heads, double scale) {
   check_rows(x, "temporal_qkv_attn: x");

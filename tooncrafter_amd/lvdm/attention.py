@@ -198,9 +198,13 @@ class CrossAttention(PackedModule):
     # -- self attention over the T frames at each pixel
     def forward_temporal_self(self, x_norm, residual, act: Act, ln=None):
         pk = self.pk
-        # levels 1-3: the fused projection and the 16 x 16 attentions as ONE launch (csrc/qkv_attn.hip, ABI 13) -- the
-        # [rows, 3C] tensor between them never reaches HBM; the library's own rule decides (16 frames, hw % 8 == 0).
-        # Any other frame count takes the projection + tc_attn_temporal (17 .. 64 frames: csrc/attention_temporal_long.hip)
+        # every level: the fused projection and the attentions over the frames as ONE launch (ABI 13) -- the [rows, 3C]
+        # tensor between them never reaches HBM.  The library's own rule decides (tc_temporal_qkv_attn_eligible): 16
+        # frames with hw % 8 == 0 (csrc/qkv_attn.hip); 17 .. 64 frames with hw % (128 / TT) == 0, TT = 32 | 64
+        # (csrc/qkv_attn_long.hip) where TC_QKV_ATTN admits the shape -- mode 1, the default, what measured ahead;
+        # mode 2 every shape the kernel takes.  Everything else takes the projection + tc_attn_temporal (17 .. 64 frames:
+        # csrc/attention_temporal_long.hip), and so does a LayerNorm folded into the projection (ln is not None: the
+        # one-launch kernels read normalised rows).
         fused = getattr(ops.backend(), "temporal_qkv_attn_eligible", None) if ln is None and torch.is_tensor(x_norm) else None
         if fused is not None and fused(b=act.b, t=act.t, hw=act.hw, c=x_norm.shape[1], heads=self.heads, ldx=x_norm.stride(0)):
             a = ops.temporal_qkv_attn(x_norm, pk["wqkv"], None, b=act.b, t=act.t, hw=act.hw, heads=self.heads, scale=self.scale)

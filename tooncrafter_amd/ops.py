@@ -340,8 +340,10 @@ class HipOps:
         return p
 
     def temporal_qkv_attn_eligible(self, *, b, t, hw, c, heads, ldx=None) -> bool:
-        """Would `temporal_qkv_attn` be accepted?  The library's own rule (tc_temporal_qkv_attn_eligible: 16 frames,
-        c = heads * 64, hw % 8 == 0, TC_QKV_ATTN != 0); never on the MXFP8 route (which quantises the projection's input)."""
+        """Would `temporal_qkv_attn` be accepted?  The library's own rule (tc_temporal_qkv_attn_eligible: c = heads * 64;
+        16 frames with hw % 8 == 0, or 17 .. 64 frames with hw % (128 / TT) == 0, TT = 32 | 64, where TC_QKV_ATTN admits
+        the shape -- 0 never, 1 what measured ahead, 2 everything; any t is passed through, the library decides); never on
+        the MXFP8 route (which quantises the projection's input)."""
         if self.fp8 is not None:
             return False
         p = self._tqa_params(b, t, hw, c, heads, c if ldx is None else ldx, c, None)
@@ -350,7 +352,8 @@ class HipOps:
     def temporal_qkv_attn(self, x, wqkv, bqkv=None, *, b, t, hw, heads, scale=None, out=None):
         """Attn_frames(x . wqkv^T + bqkv) -> [rows, c] as ONE launch: `gemm(x, wqkv, bqkv)` + `attention_temporal` without the
         [rows, 3c] tensor between them (reference attention.py:96-134 over the frames of a pixel, TemporalTransformer
-        attention.py:365-412).  x: the projection's input (LayerNorm output) rows; the result feeds to_out."""
+        attention.py:365-412).  x: the projection's input (LayerNorm output) rows; the result feeds to_out.  `out` must
+        not alias `x`."""
         m, c = x.shape
         _dev(x, BF16, "temporal_qkv_attn x", contiguous=False)
         _dev(wqkv, BF16, "temporal_qkv_attn wqkv")
