@@ -384,6 +384,27 @@ typedef struct TcDdimParams {
 int64_t tc_ddim_workspace(int32_t b);
 int tc_ddim_step(const TcDdimParams* p, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Pinned-frame blend and forward noising of the samplers, one elementwise launch (additive within ABI 14: one struct,
+ * one symbol).  Replaces the mask / x0 blend at the top of a sampling step (ddim.py:173-180, ddim_multiplecond.py:177-184),
+ * q_sample (ddpm3d.py:306-309) and the last line of stochastic_encode (ddim.py:316-317):
+ *   orig = noise ? sqrt_ac * x0 + sqrt_1m_ac * noise : x0          (noise == NULL: clean_cond)
+ *   out  = mask  ? orig * mask + (1 - mask) * x      : orig        (mask == NULL: q_sample / stochastic_encode)
+ * in fp32 with every product, the subtraction and every sum rounded on its own (no FMA contraction), i.e. the bits of the
+ * reference's separate torch ops.  Any n >= 1; pointers need only the 4-byte alignment of a float (16-byte vectors are
+ * used when every pointer allows it).  No workspace, no synchronisation.
+ * Aliasing: `out` may be EXACTLY `x` (the blend in place); any other overlap of `out` with x, x0, noise or mask --
+ * partial overlap with x included -- returns TC_EINVAL.  Also TC_EINVAL: NULL x0 / out, b <= 0, n <= 0, mask without x. */
+typedef struct TcDdimBlendParams {
+  const float* x;      /* current latent (B, n) fp32; required when mask != NULL */
+  const float* x0;     /* known latent (B, n) */
+  const float* noise;  /* N(0,1) draw, or NULL: x0 is taken as it is (clean_cond) */
+  const float* mask;   /* (B, n) weights, or NULL: out = noised x0 (q_sample / stochastic_encode) */
+  float* out;          /* may be exactly x (in place) */
+  int32_t b; int64_t n;
+  float sqrt_ac, sqrt_1m_ac;
+} TcDdimBlendParams;
+int tc_ddim_blend(const TcDdimBlendParams* p, void* stream);
+
 /* introspection */
 int tc_abi_version(void);
 const char* tc_build_info(void);

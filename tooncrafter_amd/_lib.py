@@ -80,6 +80,15 @@ class TcDdimParams(C.Structure):
     ]
 
 
+class TcDdimBlendParams(C.Structure):
+    """Pinned-frame blend / forward noising (tc_ddim_blend; additive within ABI 14)."""
+    _fields_ = [
+        ("x", C.c_void_p), ("x0", C.c_void_p), ("noise", C.c_void_p), ("mask", C.c_void_p), ("out", C.c_void_p),
+        ("b", C.c_int32), ("n", C.c_int64),
+        ("sqrt_ac", C.c_float), ("sqrt_1m_ac", C.c_float),
+    ]
+
+
 # name -> (restype, argtypes): every symbol include/tooncrafter_hip.h declares
 class TcFfParams(C.Structure):
     _fields_ = [
@@ -156,6 +165,7 @@ SYMBOLS = {
     "tc_video_to_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "tc_ddim_workspace": (C.c_int64, [C.c_int32]),
     "tc_ddim_step": (C.c_int, [C.POINTER(TcDdimParams), C.c_void_p, C.c_int64, C.c_void_p]),
+    "tc_ddim_blend": (C.c_int, [C.POINTER(TcDdimBlendParams), C.c_void_p]),
     "tc_gemm_ws_eligible": (C.c_int, [C.POINTER(TcGemmParams)]),
     "tc_gemm_gn_rows": (C.c_int, [C.POINTER(TcGemmParams)]),
     "tc_groupnorm_part": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,

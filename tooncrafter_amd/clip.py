@@ -1,7 +1,7 @@
 """One clip, end to end, as three separable stages over the HIP-backed mirror:
 
     cond    = Conditions.build(model, videos, ...)       # embedders + first / last frame through the encoder
-    latents = sample(model, cond, plan)                  # DDIM (two- or three-way guidance)
+    latents = sample(model, cond, plan)                  # DDIM (two- or three-way guidance; pinned= holds extra keyframes)
     video   = decode_spliced(model, latents, cond.refs)  # 16-frame decode + 14-frame re-decode, centre frames spliced
 
 `bench.py` times the second and third stage on resident conditioning; `synthesize` chains all three.  The caller the
@@ -100,15 +100,34 @@ class SamplingPlan:
     extra: dict = field(default_factory=dict)
 
 
-def sample(model, cond: Conditions, plan: SamplingPlan, latent_shape, x_T=None):
-    """Latents (b, 4, t, h, w) of one clip batch."""
+def pin_frames(model, frames, t):
+    """Extra keyframes for `sample(..., pinned=...)`: `frames` maps a frame index to (b, 3, H, W) pixels in [-1, 1].  They
+    go through the first-stage encoder (one call) and come back as the sampler's pair: x0 (b, 4, t, h, w), zero away from
+    those frames, and mask (b, 1, t, 1, 1), one on them."""
+    index = sorted(int(i) for i in frames)
+    if not index or index[0] < 0 or index[-1] >= t:
+        raise IndexError(f"keyframe indices {index} for a clip of {t} frames")
+    z = model.encode_first_stage(torch.stack([frames[i] for i in index], dim=2)).to(torch.float32)     # (b, 4, k, h, w)
+    x0 = z.new_zeros((z.shape[0], z.shape[1], t, *z.shape[3:]))
+    mask = z.new_zeros((z.shape[0], 1, t, 1, 1))
+    x0[:, :, index] = z
+    mask[:, :, index] = 1.0
+    return x0, mask
+
+
+def sample(model, cond: Conditions, plan: SamplingPlan, latent_shape, x_T=None, pinned=None):
+    """Latents (b, 4, t, h, w) of one clip batch.  `pinned`: an (x0, mask) pair (`pin_frames`) -- where mask is one the
+    latent is held at x0, noised to each step's level, while the rest is sampled (the reference's `mask` / `x0`).  As there,
+    the returned latents are not blended once more: pinned frames come out close to x0, not equal to it."""
     check_frames(latent_shape[2])
     sampler = (ThreeWaySampler if cond.three_way else DDIMSampler)(model)
     extra = dict(plan.extra)
     x_T = extra.pop("x_T", x_T)                    # the reference's callers hand the start noise over among their **kwargs
+    x0, mask = pinned if pinned is not None else (None, None)
+    x0, mask = extra.pop("x0", x0), extra.pop("mask", mask)       # ... and `mask` / `x0` likewise
     out, _ = sampler.sample(S=plan.steps, conditioning=cond.positive, batch_size=latent_shape[0], shape=tuple(latent_shape[1:]),
                             verbose=False, unconditional_guidance_scale=plan.scale, unconditional_conditioning=cond.negative,
-                            eta=plan.eta, cfg_img=plan.image_scale, mask=None, x0=None, fs=cond.fs,
+                            eta=plan.eta, cfg_img=plan.image_scale, mask=mask, x0=x0, fs=cond.fs,
                             timestep_spacing=plan.spacing, guidance_rescale=plan.rescale, x_T=x_T,
                             unconditional_conditioning_img_nonetext=cond.image_only, **extra)
     return out
@@ -130,11 +149,14 @@ def decode_spliced(model, latents, refs, marks=None):
 
 
 def synthesize(model, videos, latent_shape, *, plan: SamplingPlan, prompts=None, fs=24, three_way=False, hold_endpoints=True,
-               variants=1):
-    """(b, variants, 3, t, H, W) pixels in [-1, 1]."""
+               variants=1, keyframes=None):
+    """(b, variants, 3, t, H, W) pixels in [-1, 1].  `keyframes`: {frame index: (b, 3, H, W) pixels} held in place between
+    the endpoints while the rest is sampled (`pin_frames`; encoded once for all variants).  The concat conditioning stays
+    endpoints-only: that is what the model was trained on."""
     cond = Conditions.build(model, videos, prompts=prompts, fs=fs, guided=plan.scale != 1.0,
                             three_way=three_way, image_branch=plan.image_scale != 1.0, hold_endpoints=hold_endpoints)
-    clips = [decode_spliced(model, sample(model, cond, plan, latent_shape), cond.refs) for _ in range(variants)]
+    pinned = pin_frames(model, keyframes, latent_shape[2]) if keyframes else None
+    clips = [decode_spliced(model, sample(model, cond, plan, latent_shape, pinned=pinned), cond.refs) for _ in range(variants)]
     return torch.stack(clips, dim=1)
 
 

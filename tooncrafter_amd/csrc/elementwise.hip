@@ -245,6 +245,53 @@ __global__ __launch_bounds__(256) void ddim_apply_kernel(TcDdimParams p, const d
   }
 }
 
+// Pinned-frame blend / forward noising (tc_ddim_blend), flat over the b * n elements.  Every product, the subtraction and every
+// sum is rounded on its own, where the reference's separate torch ops round (ddim.py:176-180, ddpm3d.py:306-309): the
+// library is built with -ffp-contract=on, which would turn `a * b + c * d` into a multiply and an FMA.
+__device__ __forceinline__ float ddim_blend_one(float x0, float nz, float m, float x, float sqrt_ac, float sqrt_1m_ac,
+                                                bool noised, bool masked) {
+#pragma clang fp contract(off)
+  float orig = x0;
+  if (noised) {
+    const float a = sqrt_ac * x0, c = sqrt_1m_ac * nz;
+    orig = a + c;
+  }
+  if (!masked) return orig;
+  const float keep = orig * m, inv = 1.0f - m;
+  const float rest = inv * x;
+  return keep + rest;
+}
+
+// VEC: every pointer is 16-byte aligned -- float4 body, then the total % 4 tail as scalars.  `out` may be exactly `x`:
+// each element is read and then written by the same thread, so neither pointer is __restrict__.
+template <bool VEC>
+__global__ __launch_bounds__(256) void ddim_blend_kernel(const float* x, const float* __restrict__ x0,
+                                                         const float* __restrict__ noise, const float* __restrict__ mask,
+                                                         float* out, int64_t total, float sqrt_ac, float sqrt_1m_ac) {
+  const bool noised = noise != nullptr, masked = mask != nullptr;
+  const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+  int64_t done = 0;
+  if (VEC) {
+    const int64_t vecs = total >> 2;
+    for (int64_t i = tid; i < vecs; i += stride) {
+      const float4 a = reinterpret_cast<const float4*>(x0)[i];
+      const float4 z = noised ? reinterpret_cast<const float4*>(noise)[i] : float4{0.f, 0.f, 0.f, 0.f};
+      const float4 m = masked ? reinterpret_cast<const float4*>(mask)[i] : float4{0.f, 0.f, 0.f, 0.f};
+      const float4 v = masked ? reinterpret_cast<const float4*>(x)[i] : float4{0.f, 0.f, 0.f, 0.f};
+      float4 r;
+      r.x = ddim_blend_one(a.x, z.x, m.x, v.x, sqrt_ac, sqrt_1m_ac, noised, masked);
+      r.y = ddim_blend_one(a.y, z.y, m.y, v.y, sqrt_ac, sqrt_1m_ac, noised, masked);
+      r.z = ddim_blend_one(a.z, z.z, m.z, v.z, sqrt_ac, sqrt_1m_ac, noised, masked);
+      r.w = ddim_blend_one(a.w, z.w, m.w, v.w, sqrt_ac, sqrt_1m_ac, noised, masked);
+      reinterpret_cast<float4*>(out)[i] = r;
+    }
+    done = vecs << 2;
+  }
+  for (int64_t i = done + tid; i < total; i += stride)
+    out[i] = ddim_blend_one(x0[i], noised ? noise[i] : 0.f, masked ? mask[i] : 0.f, masked ? x[i] : 0.f, sqrt_ac, sqrt_1m_ac,
+                            noised, masked);
+}
+
 // (b, 3, t, hw) fp32 -> (b, t, hw, 3) uint8: one thread per pixel reads its three channel planes
 // (coalesced per plane) and writes 3 consecutive bytes.
 __global__ __launch_bounds__(256) void video_to_u8_kernel(const float* __restrict__ x, uint8_t* __restrict__ out,
@@ -383,6 +430,32 @@ extern "C" int tc_ddim_step(const TcDdimParams* pp, void* workspace, int64_t wor
     TC_LAUNCH_CHECK();
   }
   hipLaunchKernelGGL(ddim_apply_kernel, dim3(grid_for(p.n, 256, 256), p.b), dim3(256), 0, s, p, part);
+  TC_LAUNCH_CHECK();
+  return TC_OK;
+}
+
+extern "C" int tc_ddim_blend(const TcDdimBlendParams* pp, void* stream) {
+  if (!pp) return TC_EINVAL;
+  const TcDdimBlendParams& p = *pp;
+  if (!p.x0 || !p.out || p.b <= 0 || p.n <= 0 || (p.mask && !p.x)) return TC_EINVAL;
+  const int64_t total = (int64_t)p.b * p.n;
+  const uintptr_t bytes = (uintptr_t)total * sizeof(float), o = reinterpret_cast<uintptr_t>(p.out);
+  const float* x = p.mask ? p.x : nullptr;                 // x is read only under a mask
+  const float* in[4] = {x, p.x0, p.noise, p.mask};
+  bool vec = (o & 15) == 0;
+  for (int k = 0; k < 4; ++k) {
+    if (!in[k]) continue;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(in[k]);
+    if (a < o + bytes && o < a + bytes && !(k == 0 && a == o)) return TC_EINVAL;   // overlap other than out == x
+    vec = vec && (a & 15) == 0;
+  }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (vec)
+    hipLaunchKernelGGL(ddim_blend_kernel<true>, dim3(grid_for((total + 3) >> 2, 256)), dim3(256), 0, s, x, p.x0, p.noise, p.mask,
+                       p.out, total, p.sqrt_ac, p.sqrt_1m_ac);
+  else
+    hipLaunchKernelGGL(ddim_blend_kernel<false>, dim3(grid_for(total, 256)), dim3(256), 0, s, x, p.x0, p.noise, p.mask, p.out,
+                       total, p.sqrt_ac, p.sqrt_1m_ac);
   TC_LAUNCH_CHECK();
   return TC_OK;
 }

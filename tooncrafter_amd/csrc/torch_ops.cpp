@@ -2,7 +2,7 @@
 //
 // The reference binds ATen / xformers operators from Python (utils/utils.py:27-42 instantiates lvdm classes whose
 // forward methods call torch ops); this registers the MI355X kernels as first-class torch operators instead:
-//   torch.ops.tooncrafter.gemm / quant_mxfp8 / gemm_mx / attention / attention_temporal / groupnorm(_pf) / layernorm(_pf) / ddim_step /
+//   torch.ops.tooncrafter.gemm / quant_mxfp8 / gemm_mx / attention / attention_temporal / groupnorm(_pf) / layernorm(_pf) / ddim_step / ddim_blend /
 //   ff_geglu_fused / temporal_attn_fused / temporal_qkv_attn / attention_q8
 // with (i) a CUDA(HIP)-key implementation that validates the tensors, allocates the result from the caching allocator,
 // picks up the CURRENT stream and calls the same extern "C" entry point the ctypes binding calls, and (ii) a Meta-key
@@ -418,6 +418,30 @@ std::tuple<Tensor, Tensor> ddim_step_meta(const Tensor& x, const Tensor&, const 
   return std::make_tuple(at::empty_like(x), at::empty_like(x));
 }
 
+Tensor ddim_blend_cuda(const optional<Tensor>& x, const Tensor& x0, const optional<Tensor>& noise, const optional<Tensor>& mask,
+                       double sqrt_ac, double sqrt_1m_ac) {
+  auto ok = [&](const Tensor& t) {
+    return t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.sizes() == x0.sizes();
+  };
+  TORCH_CHECK(x0.dim() >= 1 && ok(x0) && (!x.has_value() || ok(*x)) && (!noise.has_value() || ok(*noise)) &&
+              (!mask.has_value() || ok(*mask)), "ddim_blend: contiguous fp32 CUDA tensors of one shape (B, ...)");
+  Tensor out = at::empty_like(x0);
+  TcDdimBlendParams p = {};
+  p.x = x.has_value() ? x->data_ptr<float>() : nullptr;
+  p.x0 = x0.data_ptr<float>();
+  p.noise = noise.has_value() ? noise->data_ptr<float>() : nullptr;
+  p.mask = mask.has_value() ? mask->data_ptr<float>() : nullptr;
+  p.out = out.data_ptr<float>();
+  p.b = (int32_t)x0.size(0); p.n = p.b ? x0.numel() / x0.size(0) : 0;
+  p.sqrt_ac = (float)sqrt_ac; p.sqrt_1m_ac = (float)sqrt_1m_ac;
+  check_rc(tc_ddim_blend(&p, cur_stream()), "tc_ddim_blend");
+  return out;
+}
+
+Tensor ddim_blend_meta(const optional<Tensor>&, const Tensor& x0, const optional<Tensor>&, const optional<Tensor>&, double, double) {
+  return at::empty_like(x0);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(tooncrafter, m) {
@@ -440,6 +464,7 @@ TORCH_LIBRARY(tooncrafter, m) {
   m.def("ddim_step(Tensor x, Tensor e_cond, Tensor? e_uncond, Tensor? noise, Tensor? e_uncond_img, float cfg_scale, "
         "float cfg_img, float guidance_rescale, float sqrt_ac, float sqrt_1m_ac, float sqrt_a_prev, float dir_coef, "
         "float sigma, float x0_rescale) -> (Tensor, Tensor)");
+  m.def("ddim_blend(Tensor? x, Tensor x0, Tensor? noise, Tensor? mask, float sqrt_ac, float sqrt_1m_ac) -> Tensor");
   m.def("abi_version() -> int");
 }
 
@@ -455,6 +480,7 @@ TORCH_LIBRARY_IMPL(tooncrafter, CUDA, m) {
   m.impl("groupnorm_pf", groupnorm_pf_cuda);
   m.impl("layernorm_pf", layernorm_pf_cuda);
   m.impl("ddim_step", ddim_step_cuda);
+  m.impl("ddim_blend", ddim_blend_cuda);
   m.impl("ff_geglu_fused", ff_geglu_fused_cuda);
   m.impl("temporal_attn_fused", temporal_attn_fused_cuda);
   m.impl("temporal_qkv_attn", temporal_qkv_attn_cuda);
@@ -472,6 +498,7 @@ TORCH_LIBRARY_IMPL(tooncrafter, Meta, m) {
   m.impl("groupnorm_pf", groupnorm_pf_meta);
   m.impl("layernorm_pf", layernorm_pf_meta);
   m.impl("ddim_step", ddim_step_meta);
+  m.impl("ddim_blend", ddim_blend_meta);
   m.impl("ff_geglu_fused", ff_geglu_fused_meta);
   m.impl("temporal_attn_fused", temporal_attn_fused_meta);
   m.impl("temporal_qkv_attn", temporal_qkv_attn_meta);

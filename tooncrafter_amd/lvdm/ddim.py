@@ -2,8 +2,9 @@
 
 Interface of reference lvdm/models/samplers/ddim.py: DDIMSampler.__init__ (11-16),
 register_buffer (18-22), make_schedule (24-57), sample (60-132), ddim_sampling
-(135-203), p_sample_ddim (206-279) -- same signatures, kwargs and return values, so
-scripts/evaluation/inference.py:244-259 and funcs.py:61-76 call it unchanged.
+(135-203), p_sample_ddim (206-279), decode (282-301), stochastic_encode (304-317) -- same
+signatures, kwargs and return values, so scripts/evaluation/inference.py:244-259 and
+funcs.py:61-76 call it unchanged.
 
 What is different underneath:
   * the per-step algebra (CFG combine, guidance rescale with its two unbiased
@@ -14,6 +15,9 @@ What is different underneath:
   * conditional and unconditional UNet passes run as one B=2 call when the model
     offers `apply_model_cfg` (every normalisation in the UNet is per-sample, so this is
     exact), reading the 2.9 GB of weights once per step instead of twice.
+  * pinned frames (`mask` / `x0`, ddim.py:173-180) are noised by `model.q_sample` and blended
+    into the latent by tc_ddim_blend at the top of each step, with the bits of the
+    reference's separate torch ops; the mask is made dense fp32 once per call.
 """
 from __future__ import annotations
 
@@ -32,6 +36,16 @@ def noise_like(shape, device, repeat=False):
     if repeat:
         return torch.randn((1, *shape[1:]), device=device).repeat(shape[0], *((1,) * (len(shape) - 1)))
     return torch.randn(shape, device=device)
+
+
+def subset_timesteps(ddim_timesteps, timesteps):
+    """The steps a partial run walks (ddim.py:152-156): the lowest `subset_end` entries of the DDIM sequence, where the
+    reference's rule ends ONE short of `timesteps` (S = 5: timesteps=3 -> two steps, timesteps >= 5 -> four)."""
+    if timesteps is None:
+        return ddim_timesteps
+    n = ddim_timesteps.shape[0]
+    subset_end = int(min(timesteps / n, 1) * n) - 1
+    return ddim_timesteps[:subset_end]
 
 
 class DDIMSampler(object):
@@ -121,23 +135,34 @@ class DDIMSampler(object):
                       log_every_t=100, temperature=1., noise_dropout=0., score_corrector=None,
                       corrector_kwargs=None, unconditional_guidance_scale=1., unconditional_conditioning=None,
                       verbose=True, precision=None, fs=None, guidance_rescale=0.0, **kwargs):
-        if ddim_use_original_steps or timesteps is not None or quantize_denoised or score_corrector is not None:
+        if ddim_use_original_steps or quantize_denoised or score_corrector is not None:
             raise NotImplementedError("only the DDIM-subsequence sampling path the scripts use")
-        if mask is not None:
-            raise NotImplementedError("mask blending (ddim.py:174-180) is unused by the interpolation scripts")
         device = self.model.betas.device
         b = shape[0]
         img = torch.randn(shape, device=device) if x_T is None else x_T
         img = img.to(torch.float32).contiguous()
-        steps = self.ddim_timesteps
+        steps = subset_timesteps(self.ddim_timesteps, timesteps)
         total_steps = steps.shape[0]
         intermediates = {'x_inter': [img], 'pred_x0': [img]}
         time_range = np.flip(steps)
         iterator = tqdm(time_range, desc='DDIM Sampler', total=total_steps) if verbose else time_range
-        kwargs.pop("clean_cond", False)
+        clean_cond = kwargs.pop("clean_cond", False)
+        if mask is not None:
+            assert x0 is not None
+            # once per call: whatever broadcasts to the latent (a (1,1,T,1,1) bool frame selector, a dense weight map)
+            # becomes the dense fp32 operand of the blend kernel
+            mask = torch.as_tensor(mask).to(device=device, dtype=torch.float32).expand(tuple(img.shape)).contiguous()
+            x0 = x0.to(device=device, dtype=torch.float32).expand(tuple(img.shape)).contiguous()
         for i, step in enumerate(iterator):
             index = total_steps - i - 1
             ts = torch.full((b,), int(step), device=device, dtype=torch.long)
+            if mask is not None:
+                # ddim.py:173-180: known latents, noised to THIS step's level (the q_sample draw comes before the step's
+                # noise_like draw), replace the masked part of the latent.  The timestep goes over as a host integer:
+                # q_sample then reads its two coefficients from host tables.  Never in place: `img` may be the caller's
+                # x_T or an entry of `intermediates`.
+                img_orig = x0 if clean_cond else self.model.q_sample(x0, int(step))
+                img = ops.ddim_blend(img, img_orig, None, mask)
             img, pred_x0 = self.p_sample_ddim(img, cond, ts, index=index, temperature=temperature,
                                               noise_dropout=noise_dropout,
                                               unconditional_guidance_scale=unconditional_guidance_scale,
@@ -185,3 +210,46 @@ class DDIMSampler(object):
                                         noise, cfg_scale=unconditional_guidance_scale,
                                         guidance_rescale=guidance_rescale if use_cfg else 0.0, **sc)
         return x_prev, pred_x0
+
+    @torch.no_grad()
+    def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
+               use_original_steps=False, callback=None):
+        """The last `t_start` steps of the DDIM sequence from `x_latent` (ddim.py:282-301); `make_schedule` first.  Like the
+        reference it hands p_sample_ddim neither `fs` nor a guidance rescale (the UNet falls back to its default_fs)."""
+        if use_original_steps:
+            raise NotImplementedError("only the DDIM-subsequence sampling path the scripts use")
+        timesteps = self.ddim_timesteps[:t_start]
+        time_range = np.flip(timesteps)
+        total_steps = timesteps.shape[0]
+        print(f"Running DDIM Sampling with {total_steps} timesteps")
+        x_dec = x_latent.to(torch.float32).contiguous()
+        for i, step in enumerate(tqdm(time_range, desc='Decoding image', total=total_steps)):
+            index = total_steps - i - 1
+            ts = torch.full((x_latent.shape[0],), int(step), device=x_latent.device, dtype=torch.long)
+            x_dec, _ = self.p_sample_ddim(x_dec, cond, ts, index=index,
+                                          unconditional_guidance_scale=unconditional_guidance_scale,
+                                          unconditional_conditioning=unconditional_conditioning, _step=int(step))
+            if callback:
+                callback(i)
+        return x_dec
+
+    @torch.no_grad()
+    def stochastic_encode(self, x0, t, use_original_steps=False, noise=None):
+        """x0 noised to the level of DDIM index `t` (ddim.py:304-317): fast, not an exact inversion.  `t` indexes the DDIM
+        tables, one entry per sample; the coefficients are rounded where the reference rounds them (fp32 ddim_alphas, then
+        an fp32 sqrt; fp32 sqrt(1 - ddim_alphas))."""
+        if use_original_steps:
+            raise NotImplementedError("only the DDIM-subsequence sampling path the scripts use")
+        if noise is None:
+            noise = torch.randn_like(x0)
+        idx = [int(v) for v in (t.reshape(-1).tolist() if torch.is_tensor(t) else np.atleast_1d(t).tolist())]
+        assert len(idx) == x0.shape[0], "one DDIM index per sample"
+        sqrt_a = torch.sqrt(torch.as_tensor(self.ddim_alphas, dtype=torch.float32))
+        xs, nz = x0.to(torch.float32).contiguous(), noise.to(torch.float32).contiguous()
+        coef = lambda i: dict(sqrt_ac=float(sqrt_a[i]), sqrt_1m_ac=float(self.ddim_sqrt_one_minus_alphas[i]))
+        if len(set(idx)) == 1:
+            return ops.ddim_blend(None, xs, nz, None, **coef(idx[0]))
+        out = torch.empty_like(xs)
+        for k, i in enumerate(idx):
+            ops.ddim_blend(None, xs[k:k + 1], nz[k:k + 1], None, out=out[k:k + 1], **coef(i))
+        return out

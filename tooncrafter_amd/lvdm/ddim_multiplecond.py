@@ -10,6 +10,9 @@ and "image kept, text dropped" (`kwargs['unconditional_conditioning_img_nonetext
 before the usual guidance rescale against e_cond, v-parameterisation and DDIM update.
 scripts/evaluation/funcs.py:61-76 selects it with `multiple_cond_cfg=True`.
 
+`ddim_sampling` -- pinned frames (`mask` / `x0`, :177-184), `clean_cond`, partial runs (`timesteps=`) -- `decode` and
+`stochastic_encode` are inherited from the mirror of samplers/ddim.py, as they are the same code in the reference.
+
 Here the three passes are one batch-3B UNet call (`apply_model_multi`) and the combination is part
 of the fused tc_ddim_step kernel (TcDdimParams.e_uncond_img / cfg_img).
 """

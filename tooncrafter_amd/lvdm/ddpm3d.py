@@ -1,6 +1,6 @@
 """Pipeline model: schedule buffers, apply_model, v-parameterisation algebra,
 decode_first_stage.  Interface of reference lvdm/models/ddpm3d.py -- DDPM (41-463:
-register_schedule 124-187, predict_* 240-252), LatentDiffusion (465-1039: scale_arr
+register_schedule 124-187, predict_* 240-252, q_sample 306-309), LatentDiffusion (465-1039: scale_arr
 523-528, decode_core 647-679, apply_model 735-750), LatentVisualDiffusion
 (1041-1240), DiffusionWrapper (1243-1310, `hybrid` branch) -- restricted to what the
 inference scripts touch.  Training, losses, logging and EMA are out of scope.
@@ -128,6 +128,28 @@ class DDPM(_DeviceModule):
 
     def predict_eps_from_z_and_v(self, x_t, t, v):
         return self._at(self.sqrt_alphas_cumprod, t, x_t) * v + self._at(self.sqrt_one_minus_alphas_cumprod, t, x_t) * x_t
+
+    def q_sample(self, x_start, t, noise=None):
+        """x_start noised to timestep t (ddpm3d.py:306-309): sqrt_ac[t] * x_start + sqrt_1m_ac[t] * noise in fp32, one
+        tc_ddim_blend launch.  `t`: the reference's (b,) LongTensor, or a Python int for one timestep shared by the batch --
+        what the samplers pass, so that their loop reads nothing back from the device (the two coefficients come from host
+        copies of the schedule buffers).  A tensor `t` is read to the host; samples that differ in t are noised one by one."""
+        if noise is None:
+            noise = torch.randn_like(x_start)
+        tab = getattr(self, "_q_host", None)
+        src = (self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod)
+        if tab is None or any(a is not b0 or a._version != v for a, (b0, v) in zip(src, tab[0])):
+            tab = self._q_host = ([(a, a._version) for a in src], [a.detach().to(torch.float32).cpu() for a in src])
+        sa, s1 = tab[1]
+        idx = [int(t)] if not torch.is_tensor(t) else [int(v) for v in t.reshape(-1).tolist()]
+        xs, nz = x_start.to(torch.float32).contiguous(), noise.to(torch.float32).contiguous()
+        if len(set(idx)) == 1:
+            return ops.ddim_blend(None, xs, nz, None, sqrt_ac=float(sa[idx[0]]), sqrt_1m_ac=float(s1[idx[0]]))
+        assert len(idx) == xs.shape[0], "one timestep per sample"
+        out = torch.empty_like(xs)
+        for k, i in enumerate(idx):
+            ops.ddim_blend(None, xs[k:k + 1], nz[k:k + 1], None, sqrt_ac=float(sa[i]), sqrt_1m_ac=float(s1[i]), out=out[k:k + 1])
+        return out
 
 
 class LatentDiffusion(DDPM):

@@ -23,7 +23,7 @@ import torch
 
 from . import _lib
 from ._lib import (ACT_GEGLU, ACT_GELU, ACT_NONE, ACT_SILU, GATHER_CONV3x3, GATHER_CONVT3,
-                   GATHER_LINEAR, TcAttnParams, TcAttnQ8Params, TcDdimParams, TcFfParams, TcGemmMxParams, TcGemmParams, TcTbParams, TcTqaParams)
+                   GATHER_LINEAR, TcAttnParams, TcAttnQ8Params, TcDdimBlendParams, TcDdimParams, TcFfParams, TcGemmMxParams, TcGemmParams, TcTbParams, TcTqaParams)
 
 BF16 = torch.bfloat16
 
@@ -767,6 +767,28 @@ class HipOps:
         ws = self._workspace(nbytes, x.device)
         _lib.check(self.lib.tc_ddim_step(C.byref(p), ws.data_ptr(), nbytes, _stream()), "tc_ddim_step")
         return x_prev, x0
+
+    def ddim_blend(self, x, x0, noise, mask, *, sqrt_ac=1.0, sqrt_1m_ac=0.0, out=None):
+        """orig = sqrt_ac * x0 + sqrt_1m_ac * noise (noise None: x0 itself); result = orig * mask + (1 - mask) * x (mask None:
+        orig) -- the pinned-frame blend of ddim.py:176-180, q_sample and stochastic_encode, every operation rounded on its own.
+        Tensors of one shape (B, ...), fp32, contiguous.  `out` may be `x` itself (in place); default: a new tensor."""
+        for tns in (x, x0, noise, mask, out):
+            if tns is not None and (tns.dtype != torch.float32 or not tns.is_contiguous() or not tns.is_cuda):
+                raise ValueError("ddim_blend: contiguous fp32 CUDA tensors")
+        for tns in (x, noise, mask, out):
+            if tns is not None and tns.shape != x0.shape:
+                raise ValueError(f"ddim_blend: shape {tuple(tns.shape)} against x0 {tuple(x0.shape)}")
+        if x0.dim() < 1:
+            raise ValueError("ddim_blend: tensors of shape (B, ...)")
+        if out is None:
+            out = torch.empty_like(x0)
+        b = x0.shape[0]
+        p = TcDdimBlendParams()
+        p.x, p.x0, p.noise, p.mask, p.out = _ptr(x), x0.data_ptr(), _ptr(noise), _ptr(mask), out.data_ptr()
+        p.b, p.n = b, (x0.numel() // b if b else 0)
+        p.sqrt_ac, p.sqrt_1m_ac = float(sqrt_ac), float(sqrt_1m_ac)
+        _lib.check(self.lib.tc_ddim_blend(C.byref(p), _stream()), "tc_ddim_blend")
+        return out
 
 
 _backend = None

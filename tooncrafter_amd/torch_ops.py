@@ -124,3 +124,8 @@ class TorchLibOps(HipOps):
                                   float(cfg_scale if cfg_img is None else cfg_img), float(guidance_rescale), float(sqrt_ac),
                                   float(sqrt_1m_ac), float(sqrt_a_prev), float(dir_coef), float(sigma), float(x0_rescale))
         return xp, (x0 if want_x0 else None)
+
+    def ddim_blend(self, x, x0, noise, mask, *, sqrt_ac=1.0, sqrt_1m_ac=0.0, out=None):
+        if out is not None:                                  # an explicit result buffer (in place): the ctypes method
+            return super().ddim_blend(x, x0, noise, mask, sqrt_ac=sqrt_ac, sqrt_1m_ac=sqrt_1m_ac, out=out)
+        return self.t.ddim_blend(x, x0, noise, mask, float(sqrt_ac), float(sqrt_1m_ac))
