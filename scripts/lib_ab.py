@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
-"""usage: lib_ab.py <other libtooncrafter_hip.so> [--new <another build>] [--edges]
+"""usage: lib_ab.py <other libtooncrafter_hip.so> [--new <another build>] [--edges | --fused]
 The in-tree library against another BUILD of it (e.g. the previous commit's, kept under scripts/bin/prev/), interleaved in
 one process on the UNet's GEMM shapes and fused launches at B = 2 under the default routing; checks that both builds give the same bits.
 
   --new PATH   take PATH instead of the in-tree library as "new" (the other build in BOTH roles: what two runs of the same
                code differ by -- the noise of the timing columns, the determinism of the battery)
+  --fused      time only the fused launches and the temporal attention (the last section), not the GEMM / convolution shapes
   --edges      no timing: the same old / new "same bits" check at the smallest shapes where each path of the kernel
                families can go wrong (ragged M, N tails, a ragged last K-step, every epilogue option), the family forced by
                its routing switch, inputs from a seeded CPU generator
@@ -23,7 +24,7 @@ def load(path):
         fn = getattr(lib, name); fn.restype = res; fn.argtypes = args
     return lib
 
-args = [a for a in sys.argv[1:] if a != "--edges"]
+args = [a for a in sys.argv[1:] if a not in ("--edges", "--fused")]
 edges = "--edges" in sys.argv[1:]
 new = hip.lib
 if "--new" in args:
@@ -50,7 +51,9 @@ def ab(fn, flops, tag):
     hip.lib = new
     same = torch.equal(outs["old"], outs["new"])
     a, b = min(r["old"]) * 1e3, min(r["new"]) * 1e3
-    print(f"{tag:40s} old {a:7.1f} us {flops / a / 1e6:7.1f} TF/s | new {b:7.1f} us {flops / b / 1e6:7.1f} TF/s | x{a / b:5.3f} | {'same bits' if same else 'DIFFERENT BITS'}", flush=True)
+    spread = (max(r["old"]) - min(r["old"])) / min(r["old"])          # what two timings of the SAME code differ by, this row
+    print(f"{tag:40s} old {a:7.1f} us {flops / a / 1e6:7.1f} TF/s | new {b:7.1f} us {flops / b / 1e6:7.1f} TF/s | x{a / b:5.3f} | "
+          f"old repeats {100 * spread:4.1f} % apart | {'same bits' if same else 'DIFFERENT BITS'}", flush=True)
 
 def lin(m, n, k, tag, act=ACT_NONE, res=True):
     a = torch.randn(m, k, device=dev).to(BF); w = (torch.randn(n, k, device=dev) * k ** -0.5).to(BF)
@@ -182,6 +185,26 @@ def run_edges():
         c = 64 * heads
         x, wq, bq = rnd(16 * 8, c + 64)[:, 32:32 + c], rnd(3 * c, c, scale=1.4 * c ** -0.5), rnd(3 * c, scale=0.2, dtype=torch.float32)
         same(lambda: hip.temporal_qkv_attn(x, wq, bq, b=1, t=16, hw=8, heads=heads), f"temporal_qkv_attn b=1 t=16 hw=8 heads={heads} ldx={c + 64}")
+    # 17 .. 64 frames (TC_QKV_ATTN=2: every shape reaches the kernel): frames padded to TT = 32 | 64 slots, PX = 128 / TT pixels
+    # per tile.  t just above a boundary and at it; hw = PX (one tile per clip) and 12 (three tiles at TT = 32, six at 64);
+    # b = 2, so that a tile's padded slots sit against the next clip's rows; one and five K-steps; with and without bias
+    def e_tqa(t, hw, heads, bias, pitch=0):
+        c = 64 * heads
+        x, wq = rnd(2 * t * hw, c + pitch)[:, pitch // 2:pitch // 2 + c], rnd(3 * c, c, scale=1.4 * c ** -0.5)
+        bq = rnd(3 * c, scale=0.2, dtype=torch.float32) if bias else None
+        with env(TC_QKV_ATTN=2) as tag:
+            same(lambda: hip.temporal_qkv_attn(x, wq, bq, b=2, t=t, hw=hw, heads=heads),
+                 f"temporal_qkv_attn b=2 t={t} hw={hw} heads={heads} {'bias' if bias else 'no bias'} ldx={c + pitch} {tag}")
+    for t in (17, 32, 33, 64):
+        for hw in (4 if t <= 32 else 2, 12):
+            for heads in (1, 5):
+                for bias in (True, False): e_tqa(t, hw, heads, bias)
+    e_tqa(33, 12, 5, True, pitch=64)
+    # tc_attn_temporal at the same lengths: one wave per (clip, pixel, head), four to a block -- 14 and 70 waves: a tail wave
+    for t in (17, 32, 33, 64):
+        for heads in (1, 5):
+            qkv = rnd(2 * t * 7, 3 * 64 * heads)
+            same(lambda: hip.attention_temporal(qkv, b=2, t=t, hw=7, heads=heads), f"attention_temporal b=2 t={t} hw=7 heads={heads}")
     c = 320
     x, wq, bq = rnd(16 * 8, c), rnd(3 * c, c, scale=1.4 * c ** -0.5), rnd(3 * c, scale=0.2, dtype=torch.float32)
     wo, bo = rnd(c, c, scale=c ** -0.5), rnd(c, scale=0.2, dtype=torch.float32)
@@ -196,12 +219,13 @@ def run_edges():
 
 if edges:
     sys.exit(run_edges())
-lin(81920, 960, 320, "L0 qkv", res=False); lin(81920, 640, 320, "L0 640"); lin(20480, 640, 640, "L1 proj"); lin(20480, 1920, 640, "L1 qkv", res=False)
-lin(20480, 640, 2560, "L1 ff2"); lin(5120, 1280, 1280, "L2 proj"); lin(5120, 3840, 1280, "L2 qkv", res=False); lin(5120, 1280, 5120, "L2 ff2")
-lin(5120, 10240, 1280, "L2 geglu", act=ACT_GEGLU); lin(1280, 1280, 1280, "L3 proj"); lin(777, 520, 1288, "ragged")
-conv(32, 10, 16, 1280, 1280, "L2"); conv(32, 10, 16, 2560, 1280, "L2"); conv(32, 5, 8, 1280, 1280, "L3")
-conv(32, 10, 16, 1280, 1280, "L2", t3=True); conv(32, 5, 8, 1280, 1280, "L3", t3=True)
-conv(16, 40, 64, 512, 512, "decoder")
+def gemms():
+    lin(81920, 960, 320, "L0 qkv", res=False); lin(81920, 640, 320, "L0 640"); lin(20480, 640, 640, "L1 proj"); lin(20480, 1920, 640, "L1 qkv", res=False)
+    lin(20480, 640, 2560, "L1 ff2"); lin(5120, 1280, 1280, "L2 proj"); lin(5120, 3840, 1280, "L2 qkv", res=False); lin(5120, 1280, 5120, "L2 ff2")
+    lin(5120, 10240, 1280, "L2 geglu", act=ACT_GEGLU); lin(1280, 1280, 1280, "L3 proj"); lin(777, 520, 1288, "ragged")
+    conv(32, 10, 16, 1280, 1280, "L2"); conv(32, 10, 16, 2560, 1280, "L2"); conv(32, 5, 8, 1280, 1280, "L3")
+    conv(32, 10, 16, 1280, 1280, "L2", t3=True); conv(32, 5, 8, 1280, 1280, "L3", t3=True)
+    conv(16, 40, 64, 512, 512, "decoder")
 # the fused launches of the temporal / feed-forward blocks at their UNet shapes (B = 2)
 def fused():
     c = 320; m = 81920
@@ -216,4 +240,16 @@ def fused():
         c = 64 * heads; m = 2 * 16 * hw
         x, wq, bq = rnd(m, c), rnd(3 * c, c, scale=1.4 * c ** -0.5), rnd(3 * c, scale=0.2, dtype=torch.float32)
         ab(lambda: hip.temporal_qkv_attn(x, wq, bq, b=2, t=16, hw=hw, heads=heads), 2.0 * m * c * c * 3, f"temporal_qkv_attn {m}x{c}")
+    # long clips: the four level geometries of scripts/long_clip_bench.py --qkv-attn at 32 and 64 frames -- the one launch
+    # (TC_QKV_ATTN=2: every shape reaches the kernel) and tc_attn_temporal on a qkv tensor of the same geometry
+    for hw, heads in ((2560, 5), (640, 10), (160, 20), (40, 20)):
+        for t in (32, 64):
+            c = 64 * heads; m = 2 * t * hw
+            x, wq, bq = rnd(m, c), rnd(3 * c, c, scale=1.4 * c ** -0.5), rnd(3 * c, scale=0.2, dtype=torch.float32)
+            with env(TC_QKV_ATTN=2):
+                ab(lambda: hip.temporal_qkv_attn(x, wq, bq, b=2, t=t, hw=hw, heads=heads), 2.0 * m * c * c * 3, f"temporal_qkv_attn t={t} {m}x{c}")
+            qkv = rnd(m, 3 * c)
+            ab(lambda: hip.attention_temporal(qkv, b=2, t=t, hw=hw, heads=heads), 4.0 * m * t * c, f"attention_temporal t={t} {m}x{c}")
+if "--fused" not in sys.argv[1:]:
+    gemms()
 fused()

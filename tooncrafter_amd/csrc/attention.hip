@@ -548,10 +548,6 @@ extern "C" int tc_attn_d64(const TcAttnParams* pp, void* stream) {
   return TC_OK;
 }
 
-// 17 .. TC_TEMPORAL_MAX_FRAMES frames: csrc/attention_temporal_long.hip (MFMA, frames padded to 32 | 64)
-int attn_temporal_long_launch(const bf16_t* qkv, bf16_t* out, int32_t b, int32_t t, int32_t hw, int32_t heads, float scale,
-                              hipStream_t stream);
-
 extern "C" int tc_attn_temporal(const tc_bf16* qkv, tc_bf16* out, int32_t b, int32_t t, int32_t hw,
                                 int32_t heads, float scale, void* stream) {
   if (!qkv || !out || b <= 0 || t <= 0 || hw <= 0 || heads <= 0) return TC_EINVAL;

@@ -11,9 +11,9 @@
 //    bytes of one qkv row): 4 k-steps over d = 64, TT / 32 key blocks per 32-query block.  A lane then owns ONE query and
 //    its keys lie along its 16 accumulator registers and the two lane halves -- keys >= t are set to -inf, the softmax
 //    max / sum are in-lane plus one exchange between the lane halves;
-//  * P^T is rounded to bf16 in registers and fed straight in as the B operand of O^T = V^T P^T; the k order inside a step
-//    of an accumulator-as-operand is permuted (k-slot (half, j) of step s = key 16 s + 8 (j >> 2) + 4 half + (j & 3)),
-//    and the V^T fragments are read from LDS in that same order (attention.hip's attn_d64_kernel does the same);
+//  * P^T is rounded to bf16 in registers and fed straight in as the B operand of O^T = V^T P^T, the V^T fragments read
+//    from LDS in the accumulator's permuted key order (attn_frames_long.h tc_attn_frames_long, shared with
+//    qkv_attn_long.hip, states the permutation);
 //  * O^T has dims on registers and the query on the lane: one permlane32_swap per dword pair turns two 8-byte halves
 //    into one 16-byte row store; padded query rows (>= t) are never stored.
 //
@@ -22,14 +22,9 @@
 // softmax weights in fp32).  Every row address is formed in 64 bits: at T = 64 the level-0 qkv of one guided clip is
 // 0.63 GB, a batch of four crosses 2^31 bytes.
 #include "gemm_common.h"
+#include "attn_frames_long.h"
 
 namespace {
-
-// max / sum of a lane and lane ^ 32.  (A permlane32_swap(x, x) would be one VALU op, but hipcc, with this file's flags,
-// folded its two results into one -- the listing took x + x -- so the cross-half step is a plain shuffle; it runs twice
-// per 32 queries.)
-__device__ __forceinline__ float tl_half_max(float x) { return fmaxf(x, __shfl_xor(x, 32, 64)); }
-__device__ __forceinline__ float tl_half_sum(float x) { return x + __shfl_xor(x, 32, 64); }
 
 template <int TT>
 __global__ __launch_bounds__(256) void attn_temporal_long_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
@@ -112,51 +107,9 @@ __global__ __launch_bounds__(256) void attn_temporal_long_kernel(const bf16_t* _
 #pragma unroll
       for (int kk = 0; kk < 4; ++kk) st[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[kb][kk], qf[kk], st[kb], 0, 0, 0);
     }
-    float mx = -INFINITY;
-#pragma unroll
-    for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int key = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-        st[kb][r] = key < t_len ? st[kb][r] : -INFINITY;
-        mx = fmaxf(mx, st[kb][r]);
-      }
-    mx = tl_half_max(mx);                          // key 0 is always valid: mx is finite
-    float sum = 0.f;
-#pragma unroll
-    for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float e = __builtin_amdgcn_exp2f((st[kb][r] - mx) * scale_log2e);   // masked: exp2(-inf) = 0
-        st[kb][r] = e;
-        sum += e;
-      }
-    sum = tl_half_sum(sum);
-    const float inv = __builtin_amdgcn_rcpf(sum);
-
-    // O^T[dim][query] = sum_key V^T[dim][key] P^T[key][query]: P^T in bf16 as the B operand (k-step s of key block kb =
-    // registers 8 s .. 8 s + 7), V^T (lane: dim db*32 + l31) read in the same permuted key order
+    // masked softmax, P^T in bf16, O^T = V^T P^T (attn_frames_long.h)
     f32x16 oacc[2];
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) oacc[db][r] = 0.f;
-#pragma unroll
-    for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        bf16x8 pf;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) pf[j] = (bf16_t)(st[kb][8 * s + j] * inv);
-#pragma unroll
-        for (int db = 0; db < 2; ++db) {
-          const char* vrow = vts + (db * 32 + l31) * VT_LD + (kb * 32 + 16 * s + 4 * half) * 2;
-          const u32x2 lo = *reinterpret_cast<const u32x2*>(vrow);        // keys +0..3
-          const u32x2 hi = *reinterpret_cast<const u32x2*>(vrow + 16);   // keys +8..11
-          const u32x4 vv = {lo[0], lo[1], hi[0], hi[1]};
-          oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vv), pf, oacc[db], 0, 0, 0);
-        }
-      }
+    tc_attn_frames_long<NKB>(st, oacc, t_len, scale_log2e, vts, VT_LD, l31, half);
 
     // ---- store: oacc[db][4 g + i] = O[q][db*32 + 8 g + 4 half + i].  For each group pair (g, g + 1) one permlane32_swap
     // per dword leaves lanes 0-31 with dims 8 g .. 8 g + 7 and lanes 32-63 with 8 g + 8 .. 8 g + 15: 16-byte stores.

@@ -151,6 +151,11 @@ __device__ __forceinline__ float tc_sum_rows(float x) {         // ... and their
   return __builtin_bit_cast(float, a) + __builtin_bit_cast(float, b);
 }
 
+// tc_attn_temporal at 17 .. TC_TEMPORAL_MAX_FRAMES frames (csrc/attention_temporal_long.hip: MFMA, frames padded to 32 | 64);
+// the caller (csrc/attention.hip) has checked the pointers and t
+int attn_temporal_long_launch(const bf16_t* qkv, bf16_t* out, int32_t b, int32_t t, int32_t hw, int32_t heads, float scale,
+                              hipStream_t stream);
+
 static inline bool tc_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 #define TC_LAUNCH_CHECK()                         \
