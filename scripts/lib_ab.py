@@ -5,10 +5,12 @@ one process on the UNet's GEMM shapes and fused launches at B = 2 under the defa
 
   --new PATH   take PATH instead of the in-tree library as "new" (the other build in BOTH roles: what two runs of the same
                code differ by -- the noise of the timing columns, the determinism of the battery)
-  --fused      time only the fused launches and the temporal attention (the last section), not the GEMM / convolution shapes
+  --fused      time only the fused launches, the temporal and spatial attention, the MXFP8 quantiser and the LayerNorm that
+               carries it (the last two sections), not the GEMM / convolution shapes
   --edges      no timing: the same old / new "same bits" check at the smallest shapes where each path of the kernel
                families can go wrong (ragged M, N tails, a ragged last K-step, every epilogue option), the family forced by
-               its routing switch, inputs from a seeded CPU generator
+               its routing switch, inputs from a seeded CPU generator.  TC_ATTN_STAGE is latched per process: run --edges a
+               second time with TC_ATTN_STAGE=reg in the environment for the register-staged attention kernel
 """
 import contextlib, ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -150,6 +152,73 @@ def e_conv(sw, frames, h, w_, cin, cout, t3=False):
         with env(**sw) as tag:
             same(lambda: hip.gemm(x, wt, b, conv=geom, **kw), f"{'convT3' if t3 else 'conv3x3'} {frames}x{h}x{w_} {cin}->{cout} ({s}) {tag}")
 
+@contextlib.contextmanager
+def fp8_linear(min_k=None):         # the fp8 routing of ops.HipOps with its row floor lifted: a LayerNorm's consumer is taken at any M
+    was = hip.fp8, hip.fp8_min_m, hip.fp8_min_k                     # min_k: the routing's floor for K lowered too (c = 320 rows)
+    hip.fp8, hip.fp8_min_m, hip.fp8_min_k = "linear", 1, was[2] if min_k is None else min_k
+    try: yield
+    finally: hip.fp8, hip.fp8_min_m, hip.fp8_min_k = was
+
+def e_spatial_and_norms():
+    """The spatial attention kernels (under TC_ATTN_STAGE=reg in the environment of the process: the register-staged one),
+    the 8-bit attention, the MXFP8 quantiser alone and inside LayerNorm, and every GroupNorm / LayerNorm launch form."""
+    stage = os.environ.get("TC_ATTN_STAGE", "dma")
+    def kv_rows(batch, lk, div): return ((batch + div - 1) // div) * lk
+    # a tail block of queries, ragged key tiles, shared K/V, two query blocks, one query and one key
+    for batch, heads, lq, lk, div in ((2, 1, 40, 40, 1), (4, 2, 64, 77, 2), (2, 3, 130, 65, 1), (1, 1, 1, 1, 1)):
+        c = 64 * heads
+        q, k, v = rnd(batch * lq, c), rnd(kv_rows(batch, lk, div), c), rnd(kv_rows(batch, lk, div), c)
+        same(lambda: hip.attention(q, k, v, batch=batch, heads=heads, lq=lq, lk=lk, kv_bdiv=div),
+             f"attention b={batch} heads={heads} lq={lq} lk={lk} kv_bdiv={div} stage={stage}")
+    qkv = rnd(2 * 100, 3 * 128)                                  # q / k / v as column slices: row stride 3c
+    same(lambda: hip.attention(qkv[:, :128], qkv[:, 128:256], qkv[:, 256:], batch=2, heads=2, lq=100, lk=100),
+         f"attention b=2 heads=2 lq=100 lk=100 q/k/v slices of [rows, 3c] stage={stage}")
+    q, k, v, base = rnd(2 * 96, 128), rnd(2 * 200, 128), rnd(2 * 200, 128), rnd(2 * 96, 128)
+    k[150] = q[7] * 4.0                                          # one key far above the rest, late: the rescale runs
+    same(lambda: hip.attention(q, k, v, batch=2, heads=2, lq=96, lk=200, out=base.clone(), accumulate=True),
+         f"attention b=2 heads=2 lq=96 lk=200 accumulate, spiked key stage={stage}")
+    for batch, heads, lq, lk, div, lk2, div2 in ((8, 2, 100, 77, 4, 16, 1), (2, 3, 130, 200, 1, 65, 2), (3, 1, 1, 1, 1, 1, 1)):
+        c = 64 * heads
+        q, kv, kv2 = rnd(batch * lq, c), rnd(kv_rows(batch, lk, div), 2 * c), rnd(kv_rows(batch, lk2, div2), 2 * c)
+        same(lambda: hip.attention(q, kv[:, :c], kv[:, c:], batch=batch, heads=heads, lq=lq, lk=lk, kv_bdiv=div,
+                                   k2=kv2[:, :c], v2=kv2[:, c:], lk2=lk2, kv2_bdiv=div2),
+             f"attention dual b={batch} heads={heads} lq={lq} lk={lk}/{div} lk2={lk2}/{div2}")
+    for batch, heads, lq, lk in ((1, 2, 200, 200), (2, 1, 130, 65)):          # ragged tiles, two query blocks
+        c = 64 * heads
+        q, k, v = rnd(batch * lq, c), rnd(batch * lk, c), rnd(batch * lk, c)
+        same(lambda: hip.attention_q8(q, k, v, batch=batch, heads=heads, lq=lq, lk=lk), f"attention_q8 b={batch} heads={heads} lq={lq} lk={lk}")
+    for rows, k, ld in ((64, 32, 64), (5, 96, 96), (33, 2560, 2688)):        # ld > k; scale padding columns (k = 32, 96, 2560: lds = 4, 4, 80)
+        x = rnd(rows, ld, scale=3.0)
+        same(lambda: hip.quant_mxfp8(x, k), f"quant_mxfp8 rows={rows} k={k} ld={ld}", want=2)
+    def ln_mx(x, g, b):
+        o = hip.layernorm(x, g, b, mx_for=(4 * x.shape[1], 4 * x.shape[1]))
+        return (o.q, o.scales) if isinstance(o, ops.MxRows) else o           # one tensor only: not covered
+    # (NV, R) = (2, 2) twice -- 960 pads its scales -- and (4, 1); then (1, 4), c <= 512: a tail group of rows, 320 pads its scales
+    for rows, c in ((77, 640), (33, 960), (5, 2048), (9, 320), (130, 512)):
+        x, g, b = rnd(rows, c, scale=3.0), rnd(c, scale=0.1, dtype=torch.float32) + 1.0, rnd(c, scale=0.1, dtype=torch.float32)
+        with fp8_linear(min_k=320):
+            same(lambda: ln_mx(x, g, b), f"layernorm -> MXFP8 {rows}x{c}", want=2)
+    for rows, c in ((5, 1280), (333, 512)):
+        x, g, b = rnd(rows, c, scale=3.0), rnd(c, scale=0.1, dtype=torch.float32) + 1.0, rnd(c, scale=0.1, dtype=torch.float32)
+        same(lambda: hip.layernorm(x, g, b), f"layernorm {rows}x{c}")
+    w_pf = rnd(1024, 1024)                                                   # 2 MiB: above the prefetch rule's floor
+    # c = 320: a unit is 5 vectors, 51 rows per pass of 256 threads -- 4 vectors a thread up to 204 rows, 13 up to 663; 7000 rows
+    # of one sample are 8 slabs and 4.5 MB: the three launches
+    for samples, rows, what in ((3, 100, "one pass NV=4"), (2, 500, "one pass NV=13"), (1, 7000, "three launches")):
+        x, g, b = rnd(samples * rows, 320, scale=2.0) + 0.5, rnd(320, scale=0.1, dtype=torch.float32) + 1.0, rnd(320, scale=0.1, dtype=torch.float32)
+        for silu in (False, True):
+            same(lambda: hip.groupnorm(x, g, b, samples=samples, rows=rows, eps=1e-5, silu=silu), f"groupnorm {samples}x{rows}x320 silu={int(silu)} ({what})")
+        same(lambda: hip.groupnorm(x, g, b, samples=samples, rows=rows, eps=1e-5, silu=True, prefetch=[w_pf]),
+             f"groupnorm {samples}x{rows}x320 silu=1 prefetch 2 MiB ({what})")
+    # tc_groupnorm_part: the producer's sums (per block of 160 rows and per channel: sum, sum of squares) stated on the CPU
+    samples, rows = 2, 320
+    x, g, b = rnd(samples * rows, 320, scale=2.0) + 0.5, rnd(320, scale=0.1, dtype=torch.float32) + 1.0, rnd(320, scale=0.1, dtype=torch.float32)
+    xb = x.float().cpu().view(-1, 160, 320)
+    part = ops.GnPart(torch.stack([xb.sum(1), (xb * xb).sum(1)], 1).contiguous().to(dev), 160, x)
+    for silu in (False, True):
+        with env(TC_GN_PART=1) as tag:
+            same(lambda: hip.groupnorm(x, g, b, samples=samples, rows=rows, eps=1e-5, silu=silu, part=part), f"groupnorm_part {samples}x{rows}x320 silu={int(silu)} {tag}")
+
 def run_edges():
     for tile in (11, 22):
         for pipe in (0, 1):
@@ -213,6 +282,7 @@ def run_edges():
     x, w1, b1 = rnd(100, c), rnd(2 * 1280, c, scale=c ** -0.5), rnd(2 * 1280, scale=0.2, dtype=torch.float32)
     w2, b2 = rnd(c, 1280, scale=1280 ** -0.5), rnd(c, scale=0.2, dtype=torch.float32)
     same(lambda: hip.ff_geglu_fused(x, w1, b1, w2, b2, ln_eps=1e-5), "ff_geglu_fused m=100 c=320 hidden=1280")
+    e_spatial_and_norms()
     print("edges: " + ", ".join(f"{v} {k}" for k, v in counts.items()), flush=True)
     print(f"edges: {'no case with different bits' if not bad else f'{len(bad)} DIFFERENT: ' + '; '.join(bad)}", flush=True)
     return 1 if bad else 0
@@ -250,6 +320,22 @@ def fused():
                 ab(lambda: hip.temporal_qkv_attn(x, wq, bq, b=2, t=t, hw=hw, heads=heads), 2.0 * m * c * c * 3, f"temporal_qkv_attn t={t} {m}x{c}")
             qkv = rnd(m, 3 * c)
             ab(lambda: hip.attention_temporal(qkv, b=2, t=t, hw=hw, heads=heads), 4.0 * m * t * c, f"attention_temporal t={t} {m}x{c}")
+# the spatial attention kernels, the MXFP8 quantiser and the LayerNorm that carries it, at their UNet shapes (B = 2)
+def spatial():
+    for batch, heads, l in ((32, 5, 2560), (32, 10, 640)):
+        c = 64 * heads
+        q, k, v = rnd(batch * l, c), rnd(batch * l, c), rnd(batch * l, c)
+        ab(lambda: hip.attention(q, k, v, batch=batch, heads=heads, lq=l, lk=l), 4.0 * batch * heads * l * l * 64, f"attention {batch}x{heads} {l}x{l}")
+        if l == 2560:
+            ab(lambda: hip.attention_q8(q, k, v, batch=batch, heads=heads, lq=l, lk=l), 4.0 * batch * heads * l * l * 64, f"attention_q8 {batch}x{heads} {l}x{l}")
+    q, kv, kv2 = rnd(32 * 2560, 320), rnd(2 * 77, 640), rnd(32 * 16, 640)
+    ab(lambda: hip.attention(q, kv[:, :320], kv[:, 320:], batch=32, heads=5, lq=2560, lk=77, kv_bdiv=16, k2=kv2[:, :320], v2=kv2[:, 320:],
+                             lk2=16, kv2_bdiv=1), 4.0 * 32 * 5 * 2560 * 93 * 64, "attention dual 32x5 2560x(77/16+16/1)")
+    x, g, b = rnd(81920, 320, scale=3.0), rnd(320, scale=0.1, dtype=torch.float32) + 1.0, rnd(320, scale=0.1, dtype=torch.float32)
+    ab(lambda: hip.quant_mxfp8(x)[0], 81920.0 * 320, "quant_mxfp8 81920x320")
+    with fp8_linear(min_k=320):                                  # k = 320 is below the routing's floor for K: lowered for the row
+        ab(lambda: hip.layernorm(x, g, b, mx_for=(1280, 1280)).q, 81920.0 * 320, "layernorm -> MXFP8 81920x320")
 if "--fused" not in sys.argv[1:]:
     gemms()
 fused()
+spatial()

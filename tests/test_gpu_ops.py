@@ -261,6 +261,54 @@ def test_attention_accumulate_and_spike(hip, emu):
     check(o, r, "attention accumulate + max spike", rel=8e-3)
 
 
+def _attn_cases():
+    """(name, q, k, v, keywords, base) of the register-staged test: three shapes of test_attention_d64 (a tail block of
+    queries, a ragged key tile with shared K/V, two query blocks) and the case of test_attention_accumulate_and_spike.
+    Seeded on the CPU: the child process and the test build the same tensors."""
+    out = []
+    for batch, heads, lq, lk, kv_bdiv in ((2, 1, 40, 40, 1), (4, 2, 64, 77, 2), (2, 3, 130, 65, 1)):
+        c = heads * 64
+        q, kv = rnd(batch * lq, c, seed=30), rnd(((batch + kv_bdiv - 1) // kv_bdiv) * lk, 2 * c, seed=31)
+        out.append((f"b{batch} h{heads} lq{lq} lk{lk} div{kv_bdiv}", q, kv[:, :c], kv[:, c:],
+                    dict(batch=batch, heads=heads, lq=lq, lk=lk, kv_bdiv=kv_bdiv), None))
+    q, k, v = rnd(2 * 96, 128, seed=32), rnd(2 * 200, 128, seed=33), rnd(2 * 200, 128, seed=34)
+    k[150] = q[7] * 4.0
+    out.append(("accumulate + max spike", q, k, v, dict(batch=2, heads=2, lq=96, lk=200, accumulate=True), rnd(2 * 96, 128, seed=35)))
+    return out
+
+
+_ATTN_REG_CHILD = """
+import sys, torch
+sys.path[:0] = [sys.argv[1], sys.argv[1] + "/tests"]
+import test_gpu_ops as t
+from tooncrafter_amd.ops import HipOps
+hip, outs = HipOps(), {}
+for name, q, k, v, kw, base in t._attn_cases():
+    outs[name] = hip.attention(q, k, v, out=None if base is None else base.clone(), **kw).cpu()
+torch.cuda.synchronize()
+torch.save(outs, sys.argv[2])
+"""
+
+
+def test_attention_register_staged_kernel(emu, tmp_path):
+    """TC_ATTN_STAGE=reg (attn_d64_kernel, the A/B arm of the DMA-staged default) is latched at a process's first attention
+    call, so it is run in ONE fresh child process; the outputs are judged here, as test_attention_d64 judges the default's."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    path = tmp_path / "attn_reg.pt"
+    r = subprocess.run([sys.executable, "-c", _ATTN_REG_CHILD, root, str(path)], capture_output=True, text=True,
+                       env=dict(os.environ, TC_ATTN_STAGE="reg"), timeout=300)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    got = torch.load(path)
+    cases = _attn_cases()
+    assert sorted(got) == sorted(c[0] for c in cases)
+    for name, q, k, v, kw, base in cases:
+        ref = emu.attention(q, k, v, out=None if base is None else base.clone(), **kw)
+        check(got[name].to(DEV), ref, f"register-staged attention {name}", rel=8e-3)
+
+
 @pytest.mark.parametrize("b,t,hw,heads", [(1, 16, 40, 5), (2, 4, 64, 1), (1, 16, 7, 8), (2, 3, 5, 2), (1, 1, 9, 1)])
 def test_attention_temporal(hip, emu, b, t, hw, heads):
     qkv = rnd(b * t * hw, 3 * heads * 64, seed=36)

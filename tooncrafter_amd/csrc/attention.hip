@@ -3,15 +3,15 @@
 // attn_d64_kernel: flash-style softmax(q k^T * scale) v.  One block = 128 query rows of one
 // (batch, head): 4 waves x 32 rows.  Per 64-key tile the block stages K row-major and V
 // TRANSPOSED ([d][key]) in LDS; each wave then computes S^T = K Q^T with
-// v_mfma_f32_32x32x16_bf16 ("swapped" product: every lane owns ONE query column, so the
-// softmax row reductions are in-lane plus a single lane^32 exchange), exponentiates in
-// registers, and feeds the probabilities straight back as the B operand of
-// O^T += V^T P^T -- the accumulator-to-operand key permutation is absorbed by reading the
-// V^T fragments with the same permutation, so P never touches LDS.
+// v_mfma_f32_32x32x16_bf16, exponentiates in registers, and feeds the probabilities straight
+// back as the B operand of O^T += V^T P^T.  Who owns which query, key and output dim, and the
+// key permutation of an accumulator fed back as an operand: csrc/attn_tile64.h, which also holds
+// the softmax and the output pass; this file holds the staging and the MFMA loops.
 //
 // attn_temporal_kernel: 16-frame (or shorter) self-attention at every pixel; the whole
 // problem is 16x16x64 per (pixel, head), done on the VALU by one wave.  Longer clips (17 .. 64
 // frames) go to csrc/attention_temporal_long.hip.
+#include "attn_tile64.h"
 #include "gemm_common.h"
 
 #include <stdlib.h>
@@ -39,13 +39,8 @@ __global__ __launch_bounds__(256) void attn_d64_kernel(const TcAttnParams p) {
   bf16_t* ob = reinterpret_cast<bf16_t*>(p.o) + (int64_t)b * p.o_sb + h * 64;
 
   const int q_row = blockIdx.x * 128 + wave * 32 + l31;
-  const int q_ld = q_row < p.lq ? q_row : p.lq - 1;   // clamp: tail rows compute garbage, never stored
-
-  // Q fragments: B operand of S^T = K Q^T -> lane holds Q[q][16 kk + 8 half + j]
   bf16x8 qf[4];
-#pragma unroll
-  for (int kk = 0; kk < 4; ++kk)
-    qf[kk] = *reinterpret_cast<const bf16x8*>(qb + (int64_t)q_ld * p.q_ss + kk * 16 + half * 8);
+  tc_tile64_load_q(qf, qb, q_row, p.lq, p.q_ss, half);
 
   const float c = p.scale * 1.4426950408889634f;   // softmax in base 2
   float m_run = -1e30f, l_run = 0.f;
@@ -101,102 +96,38 @@ __global__ __launch_bounds__(256) void attn_d64_kernel(const TcAttnParams p) {
     __syncthreads();
     if (kt + 1 < n_tiles) load_kv(kt + 1);
 
-    // ---- S^T = K Q^T : two 32-key blocks
+    // ---- S^T = K Q^T : two 32-key blocks (the first product takes the inline constant 0 as its C operand)
     f32x16 st[2];
+    const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int kbk = 0; kbk < 2; ++kbk) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) st[kbk][r] = 0.f;
-#pragma unroll
       for (int kk = 0; kk < 4; ++kk) {
         const bf16x8 kf = *reinterpret_cast<const bf16x8*>(ks + (kbk * 32 + l31) * K_STRIDE + kk * 32 + half * 16);
-        st[kbk] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[kk], st[kbk], 0, 0, 0);
+        st[kbk] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[kk], kk == 0 ? zero16 : st[kbk], 0, 0, 0);
       }
     }
-    // lane owns query l31; st[kbk][r] is key  key0 + kbk*32 + (r&3) + 8*(r>>2) + 4*half.
-    // The softmax is kept lean (it, not the MFMAs, bounds this kernel): masking only on the ragged
-    // last tile, the scale folded into one fma per element, and the O/l rescale skipped whenever no
-    // row of the wave raised its running maximum (exact: alpha would be 1).
-    if (key0 + KT > p.lk) {
-#pragma unroll
-      for (int kbk = 0; kbk < 2; ++kbk)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int key = key0 + kbk * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-          st[kbk][r] = key < p.lk ? st[kbk][r] : -1e30f;
-        }
-    }
-    float mx = st[0][0];
-#pragma unroll
-    for (int kbk = 0; kbk < 2; ++kbk)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mx = fmaxf(mx, st[kbk][r]);
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float m_new = fmaxf(m_run, mx * c);         // c > 0: max commutes with the scale
-    if (!__all(m_new == m_run)) {
-      const float alpha = fast_exp2(m_run - m_new);
-      l_run *= alpha;
-#pragma unroll
-      for (int d = 0; d < 2; ++d)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) oacc[d][r] *= alpha;
-      m_run = m_new;
-    }
-    float rs = 0.f;
-#pragma unroll
-    for (int kbk = 0; kbk < 2; ++kbk)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float pv = fast_exp2(fmaf(st[kbk][r], c, -m_run));   // masked keys: exp2(-huge) = 0
-        st[kbk][r] = pv;
-        rs += pv;
-      }
-    rs += __shfl_xor(rs, 32, 64);
-    l_run += rs;
+    tc_tile64_mask(st, key0, p.lk, half, -1e30f);
+    tc_tile64_softmax(st, c, m_run, l_run, oacc);
 
-    // ---- O^T += V^T P^T.  MFMA k-slot (half, j) of slab s in key block kbk carries key
-    //      kbk*32 + 16 s + 8 (j>>2) + 4 half + (j&3)  -- for BOTH operands.
+    // ---- O^T += V^T P^T: the V^T side of k-step s is keys +0..3 and +8..11 of the lane's slab
 #pragma unroll
     for (int kbk = 0; kbk < 2; ++kbk)
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
-        bf16x8 pf;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) pf[j] = (bf16_t)st[kbk][8 * s + j];
+        const bf16x8 pf = tc_tile64_pack_p(st[kbk], s);
 #pragma unroll
         for (int d = 0; d < 2; ++d) {
           const char* vrow = vts + (d * 32 + l31) * VT_STRIDE + (kbk * 32 + 16 * s + 4 * half) * 2;
-          const u32x2 lo = *reinterpret_cast<const u32x2*>(vrow);        // keys +0..3
-          const u32x2 hi = *reinterpret_cast<const u32x2*>(vrow + 16);   // keys +8..11
+          const u32x2 lo = *reinterpret_cast<const u32x2*>(vrow);
+          const u32x2 hi = *reinterpret_cast<const u32x2*>(vrow + 16);
           u32x4 vv = {lo[0], lo[1], hi[0], hi[1]};
           oacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vv), pf, oacc[d], 0, 0, 0);
         }
       }
   }
 
-  // ---- normalise and store.  oacc[d][r] = O[q = l31][dim = d*32 + (r&3) + 8*(r>>2) + 4*half]
-  if (q_row < p.lq) {
-    const float inv = 1.0f / l_run;
-    bf16_t* orow = ob + (int64_t)q_row * p.o_ss;
-#pragma unroll
-    for (int d = 0; d < 2; ++d)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int dim = d * 32 + 8 * g + 4 * half;
-        float x0 = oacc[d][4 * g + 0] * inv, x1 = oacc[d][4 * g + 1] * inv;
-        float x2 = oacc[d][4 * g + 2] * inv, x3 = oacc[d][4 * g + 3] * inv;
-        u32x2* dst = reinterpret_cast<u32x2*>(orow + dim);
-        if (p.accumulate) {
-          const u32x2 old = *dst;
-          x0 += __uint_as_float(old[0] << 16);
-          x1 += __uint_as_float(old[0] & 0xffff0000u);
-          x2 += __uint_as_float(old[1] << 16);
-          x3 += __uint_as_float(old[1] & 0xffff0000u);
-        }
-        u32x2 out = {pack2(x0, x1), pack2(x2, x3)};
-        *dst = out;
-      }
-  }
+  if (q_row < p.lq) tc_tile64_store(oacc, l_run, ob + (int64_t)q_row * p.o_ss, half, p.accumulate);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -237,11 +168,8 @@ __global__ __launch_bounds__(256) void attn_d64_dma_kernel(const TcAttnParams p)
   bf16_t* ob = reinterpret_cast<bf16_t*>(p.o) + (int64_t)b * p.o_sb + h * 64;
 
   const int q_row = blockIdx.x * 128 + wave * 32 + l31;
-  const int q_ld = q_row < p.lq ? q_row : p.lq - 1;   // clamp: tail rows compute garbage, never stored
   bf16x8 qf[4];
-#pragma unroll
-  for (int kk = 0; kk < 4; ++kk)
-    qf[kk] = *reinterpret_cast<const bf16x8*>(qb + (int64_t)q_ld * p.q_ss + kk * 16 + half * 8);
+  tc_tile64_load_q(qf, qb, q_row, p.lq, p.q_ss, half);
 
   // ---- fragment read offsets (per lane, fixed for the whole kernel)
   // K (A operand of S^T = K Q^T): lane (key l31 of block kbk, k = 16 kk + 8 half ..): 16-byte chunk 2 kk + half of its row
@@ -322,52 +250,15 @@ __global__ __launch_bounds__(256) void attn_d64_dma_kernel(const TcAttnParams p)
           st[kbk] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[kk], kk == 0 ? zero16 : st[kbk], 0, 0, 0);
         }
       }
-      if (key0 + KT > lk) {
-#pragma unroll
-        for (int kbk = 0; kbk < 2; ++kbk)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int key = key0 + kbk * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-            st[kbk][r] = key < lk ? st[kbk][r] : -1e30f;
-          }
-      }
-      float mx = st[0][0];
-#pragma unroll
-      for (int kbk = 0; kbk < 2; ++kbk)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) mx = fmaxf(mx, st[kbk][r]);
-      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-      const float m_new = fmaxf(m_run, mx * c);
-      if (!__all(m_new == m_run)) {
-        const float alpha = fast_exp2(m_run - m_new);
-        l_run *= alpha;
-#pragma unroll
-        for (int d = 0; d < 2; ++d)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) oacc[d][r] *= alpha;
-        m_run = m_new;
-      }
-      float rs = 0.f;
-#pragma unroll
-      for (int kbk = 0; kbk < 2; ++kbk)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float pv = fast_exp2(fmaf(st[kbk][r], c, -m_run));
-          st[kbk][r] = pv;
-          rs += pv;
-        }
-      rs += __shfl_xor(rs, 32, 64);
-      l_run += rs;
+      tc_tile64_mask(st, key0, lk, half, -1e30f);
+      tc_tile64_softmax(st, c, m_run, l_run, oacc);
 
-      // O^T += V^T P^T: k-slot (half, j) of slab s in key block kbk carries key kbk*32 + 16 s + 8 (j>>2) + 4 half + (j&3)
-      // for both operands; the V side is two transposing reads (keys +0..3 and +8..11 of the slab) per fragment
+      // O^T += V^T P^T: the V^T side of k-step s is two transposing reads (keys +0..3 and +8..11 of the lane's slab)
 #pragma unroll
       for (int kbk = 0; kbk < 2; ++kbk)
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-          bf16x8 pf;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) pf[j] = (bf16_t)st[kbk][8 * s + j];
+          const bf16x8 pf = tc_tile64_pack_p(st[kbk], s);
           const int kbase = (kbk * 32 + 16 * s + 4 * half) * 128;
 #pragma unroll
           for (int d = 0; d < 2; ++d) {
@@ -402,29 +293,7 @@ __global__ __launch_bounds__(256) void attn_d64_dma_kernel(const TcAttnParams p)
                reinterpret_cast<const bf16_t*>(p.v2) + (int64_t)kvb2 * p.v2_sb + h * 64, p.lk2, p.k2_ss, p.v2_ss);
   }
 
-  if (q_row < p.lq) {
-    const float inv = 1.0f / l_run;
-    bf16_t* orow = ob + (int64_t)q_row * p.o_ss;
-#pragma unroll
-    for (int d = 0; d < 2; ++d)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int dim = d * 32 + 8 * g + 4 * half;
-        float x0 = oacc[d][4 * g + 0] * inv, x1 = oacc[d][4 * g + 1] * inv;
-        float x2 = oacc[d][4 * g + 2] * inv, x3 = oacc[d][4 * g + 3] * inv;
-        if (DUAL) { x0 += o1[d][4 * g + 0]; x1 += o1[d][4 * g + 1]; x2 += o1[d][4 * g + 2]; x3 += o1[d][4 * g + 3]; }
-        u32x2* dst = reinterpret_cast<u32x2*>(orow + dim);
-        if (p.accumulate) {
-          const u32x2 old = *dst;
-          x0 += __uint_as_float(old[0] << 16);
-          x1 += __uint_as_float(old[0] & 0xffff0000u);
-          x2 += __uint_as_float(old[1] << 16);
-          x3 += __uint_as_float(old[1] & 0xffff0000u);
-        }
-        u32x2 out = {pack2(x0, x1), pack2(x2, x3)};
-        *dst = out;
-      }
-  }
+  if (q_row < p.lq) tc_tile64_store<DUAL>(oacc, o1, l_run, ob + (int64_t)q_row * p.o_ss, half, p.accumulate);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -519,15 +388,14 @@ extern "C" int tc_attn_d64(const TcAttnParams* pp, void* stream) {
   const TcAttnParams& p = *pp;
   if (!p.q || !p.k || !p.v || !p.o) return TC_EINVAL;
   if (p.batch <= 0 || p.heads <= 0 || p.lq <= 0 || p.lk <= 0 || p.kv_bdiv <= 0) return TC_EINVAL;
-  if (!tc_aligned16(p.q) || !tc_aligned16(p.k) || !tc_aligned16(p.v) || !tc_aligned16(p.o)) return TC_EALIGN;
-  if ((p.q_ss & 7) || (p.k_ss & 7) || (p.v_ss & 7) || (p.o_ss & 7)) return TC_EALIGN;
-  if ((p.q_sb & 7) || (p.k_sb & 7) || (p.v_sb & 7) || (p.o_sb & 7)) return TC_EALIGN;
+  if (!tc_tile64_aligned(p.q, p.q_ss, p.q_sb) || !tc_tile64_aligned(p.k, p.k_ss, p.k_sb) ||
+      !tc_tile64_aligned(p.v, p.v_ss, p.v_sb) || !tc_tile64_aligned(p.o, p.o_ss, p.o_sb))
+    return TC_EALIGN;
   if (p.heads > 65535 || p.batch > 65535) return TC_ESHAPE;
   const bool dual = p.k2 != nullptr;
   if (dual) {
     if (!p.v2 || p.lk2 <= 0 || p.kv2_bdiv <= 0) return TC_EINVAL;
-    if (!tc_aligned16(p.k2) || !tc_aligned16(p.v2) || (p.k2_ss & 7) || (p.v2_ss & 7) || (p.k2_sb & 7) || (p.v2_sb & 7))
-      return TC_EALIGN;
+    if (!tc_tile64_aligned(p.k2, p.k2_ss, p.k2_sb) || !tc_tile64_aligned(p.v2, p.v2_ss, p.v2_sb)) return TC_EALIGN;
   }
   dim3 grid((p.lq + 127) / 128, p.heads, p.batch), block(256);
   // TC_ATTN_STAGE=reg selects the register-staged kernel (A/B runs); the DMA-staged one needs 31-bit row offsets

@@ -26,10 +26,11 @@
 //
 // attn_d64_q8_kernel: the structure of attn_d64_dma_kernel<false> (attention.hip) -- 128 queries per block, 4 waves,
 // double-buffered 64-key tiles staged by DMA, swapped S^T = K Q^T so each lane owns one query column, P kept in
-// registers as the next MFMA's operand:
+// registers as the next MFMA's operand; the lane / register / key layout, the mask, the rescale and the output pass are
+// those of csrc/attn_tile64.h:
 //   * S^T on v_mfma_i32_32x32x32_i8: two instructions per 32x32 score tile (bf16 needs four).  A (K) and B (Q) carry the
 //     same d in the same byte of the same lane half, so the product needs no other knowledge of the k order.  The int32
-//     result has the shape-determined C layout: register r of lane (q, h) is key (r&3) + 8 (r>>2) + 4 h.
+//     result has the shape-determined C layout of the header.
 //     Score = float(acc) * s_k[key] * s_q: the key scale is per register (one multiply), the query scale is folded with
 //     scale * log2(e) into the per-lane multiplier of the exp2 argument.
 //   * O^T += V^T P^T on v_mfma_scale_f32_32x32x64_f8f6f4 with K = 64 keys = one tile.  Measured layout of that
@@ -37,8 +38,10 @@
 //     scale byte is block h's.  Score tile kbk = 0 (registers 0..15) fills bytes 0..15 and kbk = 1 bytes 16..31, so block
 //     kbk is keys 32 kbk .. 32 kbk + 31 -- the V^T fragments are stored in that same key order.  The block max needs one
 //     lane^32 exchange per block.
-//   * P is packed with v_cvt_pk_fp8_f32 (round to nearest even).
+//   * P is packed by mx_pack4 (csrc/mx_quant.h: round to nearest even).
+#include "attn_tile64.h"
 #include "gemm_common.h"
+#include "mx_quant.h"
 
 namespace {
 
@@ -127,20 +130,13 @@ __global__ __launch_bounds__(256) void attn_q8_quant_kv_kernel(const TcAttnQ8Par
       amax = max(amax, bits[j] & 0x7fffu);
     }
     amax = max(amax, (uint32_t)__shfl_xor((int)amax, 1, 64));
-    // shared exponent = floor(log2(amax)) - 8 (e4m3 emax), clamped to E8M0's range: tc_quant_mxfp8's formula
-    const int e8 = (int)(amax >> 7);
-    const int byte = e8 - 8 < 0 ? 0 : (e8 - 8 > 254 ? 254 : e8 - 8);
-    const float inv = __uint_as_float((uint32_t)(254 - byte) << 23);   // 2^-(byte - 127), exact
+    const int byte = mx_scale_byte(amax);
+    const float inv = mx_inv_scale(byte);
     u32x4 out;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float f[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) f[e] = fminf(fmaxf(__uint_as_float(bits[4 * i + e] << 16) * inv, -448.f), 448.f);
-      int w = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], 0, false);
-      w = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], w, true);
-      out[i] = (uint32_t)w;
-    }
+    for (int i = 0; i < 4; ++i)
+      out[i] = mx_quant4(bf16_bits_to_f32(bits[4 * i]), bf16_bits_to_f32(bits[4 * i + 1]), bf16_bits_to_f32(bits[4 * i + 2]),
+                         bf16_bits_to_f32(bits[4 * i + 3]), inv);
     const int d0 = d >> 5;
     *reinterpret_cast<u32x4*>(rec + REC_V + ((d0 * 2 + blk) * 64 + hh * 32 + (d & 31)) * 16) = out;
     if (hh == 0) reinterpret_cast<uint8_t*>(rec + REC_VS)[d * 2 + blk] = (uint8_t)byte;
@@ -221,7 +217,7 @@ __global__ __launch_bounds__(256) void attn_d64_q8_kernel(const TcAttnQ8Params p
         const i32x4 kf = *reinterpret_cast<const i32x4*>(rec + ((kbk * 2 + kk) * 64 + lane) * 16);
         sacc[kbk] = __builtin_amdgcn_mfma_i32_32x32x32_i8(kf, qf[kk], kk == 0 ? izero : sacc[kbk], 0, 0, 0);
       }
-    // scores with the key scales: register r of block kbk is key 32 kbk + (r&3) + 8 (r>>2) + 4 half
+    // scores with the key scales of the registers' keys
     const float* ks = reinterpret_cast<const float*>(rec + REC_KS);
     float s[2][16];
 #pragma unroll
@@ -232,15 +228,7 @@ __global__ __launch_bounds__(256) void attn_d64_q8_kernel(const TcAttnQ8Params p
 #pragma unroll
         for (int i = 0; i < 4; ++i) s[kbk][4 * g + i] = (float)sacc[kbk][4 * g + i] * sk[i];
       }
-    if (key0 + KT > p.lk) {
-#pragma unroll
-      for (int kbk = 0; kbk < 2; ++kbk)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int key = key0 + kbk * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-          s[kbk][r] = key < p.lk ? s[kbk][r] : -INFINITY;
-        }
-    }
+    tc_tile64_mask(s, key0, p.lk, half, -INFINITY);
     float bmx[2];
 #pragma unroll
     for (int kbk = 0; kbk < 2; ++kbk) {
@@ -249,16 +237,7 @@ __global__ __launch_bounds__(256) void attn_d64_q8_kernel(const TcAttnQ8Params p
       for (int r = 1; r < 16; ++r) mx = fmaxf(mx, s[kbk][r]);
       bmx[kbk] = fmaxf(mx, __shfl_xor(mx, 32, 64));
     }
-    const float m_new = fmaxf(m_run, fmaxf(bmx[0], bmx[1]) * cq);   // cq > 0: max commutes with the scale
-    if (!__all(m_new == m_run)) {
-      const float alpha = fast_exp2(m_run - m_new);
-      l_run *= alpha;
-#pragma unroll
-      for (int d = 0; d < 2; ++d)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) oacc[d][r] *= alpha;
-      m_run = m_new;
-    }
+    tc_tile64_raise_max(fmaxf(m_run, fmaxf(bmx[0], bmx[1]) * cq), m_run, l_run, oacc);   // cq > 0: max commutes with the scale
     // P in e4m3 with one E8M0 exponent per query and 32-key block; l from the fp32 values
     i32x8 pf;
     float rs = 0.f;
@@ -278,11 +257,7 @@ __global__ __launch_bounds__(256) void attn_d64_q8_kernel(const TcAttnQ8Params p
       }
       rs += ldexpf(rsb, (int)e);
 #pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        int x = __builtin_amdgcn_cvt_pk_fp8_f32(pv[4 * w], pv[4 * w + 1], 0, false);
-        x = __builtin_amdgcn_cvt_pk_fp8_f32(pv[4 * w + 2], pv[4 * w + 3], x, true);
-        pf[4 * kbk + w] = x;
-      }
+      for (int w = 0; w < 4; ++w) pf[4 * kbk + w] = (int)mx_pack4(pv[4 * w], pv[4 * w + 1], pv[4 * w + 2], pv[4 * w + 3]);
     }
     rs += __shfl_xor(rs, 32, 64);
     l_run += rs;
@@ -300,20 +275,7 @@ __global__ __launch_bounds__(256) void attn_d64_q8_kernel(const TcAttnQ8Params p
     }
   }
 
-  // ---- normalise and store.  oacc[d][r] = O[q = l31][dim = d*32 + (r&3) + 8*(r>>2) + 4*half]
-  if (q_row < p.lq) {
-    const float inv = 1.0f / l_run;
-    bf16_t* orow = ob + (int64_t)q_row * p.o_ss;
-#pragma unroll
-    for (int d = 0; d < 2; ++d)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int dim = d * 32 + 8 * g + 4 * half;
-        u32x2 out = {pack2(oacc[d][4 * g + 0] * inv, oacc[d][4 * g + 1] * inv),
-                     pack2(oacc[d][4 * g + 2] * inv, oacc[d][4 * g + 3] * inv)};
-        *reinterpret_cast<u32x2*>(orow + dim) = out;
-      }
-  }
+  if (q_row < p.lq) tc_tile64_store(oacc, l_run, ob + (int64_t)q_row * p.o_ss, half, false);
 }
 
 int q8_check(const TcAttnQ8Params* pp, bool need_q) {
@@ -323,12 +285,10 @@ int q8_check(const TcAttnQ8Params* pp, bool need_q) {
   if (!(p.scale > 0.f) || !(p.scale < INFINITY)) return TC_EINVAL;
   if (need_q) {
     if (!p.q || !p.o) return TC_EINVAL;
-    if (!tc_aligned16(p.q) || !tc_aligned16(p.o) || (p.q_ss & 7) || (p.o_ss & 7) || (p.q_sb & 7) || (p.o_sb & 7))
-      return TC_EALIGN;
+    if (!tc_tile64_aligned(p.q, p.q_ss, p.q_sb) || !tc_tile64_aligned(p.o, p.o_ss, p.o_sb)) return TC_EALIGN;
   } else {
     if (!p.k || !p.v) return TC_EINVAL;
-    if (!tc_aligned16(p.k) || !tc_aligned16(p.v) || (p.k_ss & 7) || (p.v_ss & 7) || (p.k_sb & 7) || (p.v_sb & 7))
-      return TC_EALIGN;
+    if (!tc_tile64_aligned(p.k, p.k_ss, p.k_sb) || !tc_tile64_aligned(p.v, p.v_ss, p.v_sb)) return TC_EALIGN;
   }
   if (!tc_aligned16(p.workspace)) return TC_EALIGN;
   if (p.heads > 65535 || p.batch > 65535) return TC_ESHAPE;

@@ -98,7 +98,7 @@ __global__ __launch_bounds__(256) void attn_temporal_long_kernel(const bf16_t* _
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) qf[kk] = *reinterpret_cast<const bf16x8*>(qp + kk * 16);
 
-    // S^T[key][query]: lane = query q, register r of key block kb = key kb*32 + (r & 3) + 8 (r >> 2) + 4 half
+    // S^T[key][query]: lane = query q, registers = keys (the layout of attn_tile64.h)
     f32x16 st[NKB];
 #pragma unroll
     for (int kb = 0; kb < NKB; ++kb) {

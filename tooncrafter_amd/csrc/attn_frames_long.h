@@ -12,16 +12,14 @@ namespace {
 __device__ __forceinline__ float tc_half_max(float x) { return fmaxf(x, __shfl_xor(x, 32, 64)); }
 __device__ __forceinline__ float tc_half_sum(float x) { return x + __shfl_xor(x, 32, 64); }
 
-// st: the raw S^T = K Q^T accumulators of the NKB = TT / 32 key blocks (frames padded to TT = 32 | 64 slots).  A lane
-// (l31 = lane & 31, half = lane >> 5) owns ONE query; register r of key block kb = key kb*32 + (r & 3) + 8 (r >> 2) + 4 half.
+// st: the raw S^T = K Q^T accumulators of the NKB = TT / 32 key blocks (frames padded to TT = 32 | 64 slots), in the layout
+// that attn_tile64.h states: a lane (l31 = lane & 31, half = lane >> 5) owns ONE query, a register is a key of its block.
 // Keys >= t are set to -inf; max and sum are in-lane plus one exchange between the lane halves; P^T is rounded to bf16 in
-// registers (st is overwritten) and fed straight in as the B operand of O^T = V^T P^T.  THE KEY PERMUTATION: the k order
-// inside a step of an accumulator-as-operand is permuted,
-//     k-slot (half, j) of step s = key 16 s + 8 (j >> 2) + 4 half + (j & 3),
-// and the V^T fragments are read from LDS in that same order (attention.hip's attn_d64_kernel does the same).
+// registers (st is overwritten) and fed straight in as the B operand of O^T = V^T P^T, whose k order is permuted as stated
+// there; the V^T fragments are read from LDS in that same order.
 // vt: V^T of the pixel in LDS, [64 dims][keys] bf16 with rows of `vt_ld` bytes, pointing at the pixel's key 0; keys
 // t .. TT - 1 must hold finite values (their P is 0: 0 * garbage could still be NaN).
-// oacc[db][4 g + i] = O[query][db*32 + 8 g + 4 half + i]: how O leaves is the caller's.
+// oacc comes out in that header's O layout: how O leaves is the caller's.
 template <int NKB>
 __device__ __forceinline__ void tc_attn_frames_long(f32x16 (&st)[NKB], f32x16 (&oacc)[2], int t, float scale_log2e,
                                                     const char* vt, int vt_ld, int l31, int half) {

@@ -20,6 +20,7 @@
 // K-slice), issued with the tile loads of the step they belong to.
 #include "gemm_common.h"
 #include "gemm_epilogue.h"
+#include "mx_quant.h"
 
 namespace {
 
@@ -311,26 +312,16 @@ __global__ __launch_bounds__(256) void quant_mx_kernel(const bf16_t* __restrict_
       const uint32_t lo = v[i][e] & 0x7fffu, hi = (v[i][e] >> 16) & 0x7fffu;
       amax = max(amax, max(lo, hi));
     }
-  // shared exponent = floor(log2(amax)) - 8 (e4m3 emax), clamped to E8M0's [-127, 127]; as a biased byte:
-  const int e8 = (int)(amax >> 7);                       // bf16 exponent field of amax
-  const int byte = e8 - 8 < 0 ? 0 : (e8 - 8 > 254 ? 254 : e8 - 8);
-  const float inv = __uint_as_float((uint32_t)(254 - byte) << 23);   // 2^-(byte - 127), exact
+  const int byte = mx_scale_byte(amax);
+  const float inv = mx_inv_scale(byte);
   uint32_t out[8];
 #pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int e = 0; e < 4; e += 2) {
-      float f[4];
-      f[0] = __uint_as_float(v[i][e] << 16);
-      f[1] = __uint_as_float(v[i][e] & 0xffff0000u);
-      f[2] = __uint_as_float(v[i][e + 1] << 16);
-      f[3] = __uint_as_float(v[i][e + 1] & 0xffff0000u);
-#pragma unroll
-      for (int t = 0; t < 4; ++t) f[t] = fminf(fmaxf(f[t] * inv, -448.f), 448.f);   // saturate, then RNE to e4m3
-      int w = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], 0, false);
-      w = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], w, true);
-      out[i * 2 + e / 2] = (uint32_t)w;
-    }
+  for (int i = 0; i < 4; ++i) {
+    float f[8];
+    unpack8(v[i], f);
+    out[i * 2] = mx_quant4(f[0], f[1], f[2], f[3], inv);
+    out[i * 2 + 1] = mx_quant4(f[4], f[5], f[6], f[7], inv);
+  }
   u32x4* dst = reinterpret_cast<u32x4*>(q + row * ldq + blk * 32);
   dst[0] = u32x4{out[0], out[1], out[2], out[3]};
   dst[1] = u32x4{out[4], out[5], out[6], out[7]};

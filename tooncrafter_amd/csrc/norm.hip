@@ -21,6 +21,7 @@
 // Algorithmic traffic: read x twice, write y once (the second read mostly hits the 256 MiB
 // Infinity Cache for UNet-sized tensors).
 #include "common.h"
+#include "mx_quant.h"
 
 #include <stdlib.h>
 
@@ -441,13 +442,12 @@ __global__ __launch_bounds__(T) void gn_onepass_kernel(const bf16_t* __restrict_
 // latency-bound (4.1 TB/s).
 // MX = true (tc_layernorm_mxfp8): the normalised row leaves as MXFP8 -- e4m3 bytes q[row, ldq] plus one E8M0 scale per
 // 32 channels s[row, lds] -- instead of bf16: exactly tc_quant_mxfp8 applied to the bf16 result (the value is rounded
-// to bf16 first), without the bf16 round trip through HBM.  A 32-channel block is 4 adjacent lanes.
-template <int NV, int R, bool MX = false>
+// to bf16 first; both call csrc/mx_quant.h), without the bf16 round trip through HBM.  A 32-channel block is 4 adjacent lanes.
+template <int NV, int R, bool MX>
 __global__ __launch_bounds__(256) void layernorm_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y,
                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                       int rows, int c, float eps, uint8_t* __restrict__ q = nullptr,
-                                                       int ldq = 0, uint8_t* __restrict__ sc = nullptr, int lds = 0,
-                                                       const PfArgs pf = PfArgs{}) {
+                                                       int rows, int c, float eps, uint8_t* __restrict__ q, int ldq,
+                                                       uint8_t* __restrict__ sc, int lds, const PfArgs pf) {
   if (blockIdx.y) {                                           // a weight-prefetch plane (ABI 12)
     pf_run(pf, (blockIdx.y - 1) * gridDim.x + blockIdx.x, (gridDim.y - 1) * gridDim.x, threadIdx.x, 256);
     return;
@@ -515,23 +515,17 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const bf16_t* __restrict
           if (!MX) {
             *reinterpret_cast<u32x4*>(y + (int64_t)(row0 + r) * c + v * 8) = packed;
           } else {
-            uint32_t amax = 0;                               // |value| as bf16 bits, as in quant_mx_kernel
+            uint32_t amax = 0;                               // |value| as bf16 bits, over the block's four lanes
 #pragma unroll
             for (int e = 0; e < 4; ++e) amax = max(amax, max(packed[e] & 0x7fffu, (packed[e] >> 16) & 0x7fffu));
             amax = max(amax, (uint32_t)__shfl_xor((int)amax, 1, 64));
             amax = max(amax, (uint32_t)__shfl_xor((int)amax, 2, 64));
-            const int e8 = (int)(amax >> 7);
-            const int byte = e8 - 8 < 0 ? 0 : (e8 - 8 > 254 ? 254 : e8 - 8);
-            const float inv = __uint_as_float((uint32_t)(254 - byte) << 23);
+            const int byte = mx_scale_byte(amax);
+            const float inv = mx_inv_scale(byte);
             float t[8];
             unpack8(packed, t);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) t[e] = fminf(fmaxf(t[e] * inv, -448.f), 448.f);
-            int w0 = __builtin_amdgcn_cvt_pk_fp8_f32(t[0], t[1], 0, false);
-            w0 = __builtin_amdgcn_cvt_pk_fp8_f32(t[2], t[3], w0, true);
-            int w1 = __builtin_amdgcn_cvt_pk_fp8_f32(t[4], t[5], 0, false);
-            w1 = __builtin_amdgcn_cvt_pk_fp8_f32(t[6], t[7], w1, true);
-            *reinterpret_cast<u32x2*>(q + (int64_t)(row0 + r) * ldq + v * 8) = u32x2{(uint32_t)w0, (uint32_t)w1};
+            *reinterpret_cast<u32x2*>(q + (int64_t)(row0 + r) * ldq + v * 8) =
+                u32x2{mx_quant4(t[0], t[1], t[2], t[3], inv), mx_quant4(t[4], t[5], t[6], t[7], inv)};
             if ((v & 3) == 0) sc[(int64_t)(row0 + r) * lds + (v >> 2)] = (uint8_t)byte;
           }
         }
@@ -632,18 +626,40 @@ extern "C" int64_t tc_groupnorm_workspace(int32_t samples, int32_t rows, int32_t
   return ((int64_t)samples * nch * 64 + (int64_t)samples * 64) * sizeof(float);
 }
 
-static int groupnorm_impl(const tc_bf16* x, tc_bf16* y, const float* gamma, const float* beta,
-                          int32_t samples, int32_t rows, int32_t c, float eps, int32_t silu,
-                          void* workspace, int64_t workspace_bytes, const TcPrefetch* prefetch, void* stream) {
+// what every GroupNorm entry point asks of its arguments; pf: the prefetch list as kernel arguments (none: prefetch == nullptr)
+static int gn_check(const tc_bf16* x, tc_bf16* y, const float* gamma, const float* beta, int32_t samples, int32_t rows,
+                    int32_t c, void* workspace, int64_t workspace_bytes, const TcPrefetch* prefetch, PfArgs* pf) {
   if (!x || !y || !gamma || !beta || !workspace || samples <= 0 || rows <= 0 || c <= 0) return TC_EINVAL;
-  PfArgs pf;
-  if (const int rc = pf_args(prefetch, &pf)) return rc;
+  if (const int rc = pf_args(prefetch, pf)) return rc;
   if ((c % 32) != 0 || c > GN_MAX_SLOTS * GN_THREADS * 8 || c > 4096) return TC_ESHAPE;
-  if ((c % 8) != 0) return TC_ESHAPE;
   if (!tc_aligned16(x) || !tc_aligned16(y)) return TC_EALIGN;
   if (workspace_bytes < tc_groupnorm_workspace(samples, rows, c)) return TC_EWORKSPACE;
   if (samples > 65535) return TC_ESHAPE;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  return TC_OK;
+}
+
+// SILU is a template parameter of both kernels: the one place that turns the run-time flag into it
+struct GnIo {
+  const bf16_t* x; bf16_t* y; const float* gamma; const float* beta;
+  int rows, c; bool silu; hipStream_t s;
+};
+static void gn_apply_launch(const GnIo& io, dim3 grid, const float* stats, int chunk_rows, const PfArgs& pf) {
+  const auto k = io.silu ? gn_apply_kernel<true> : gn_apply_kernel<false>;
+  hipLaunchKernelGGL(k, grid, dim3(GN_THREADS), 0, io.s, io.x, io.y, io.gamma, io.beta, stats, io.rows, io.c, chunk_rows, pf);
+}
+template <int T, int NV>
+static void gn_onepass_launch(const GnIo& io, dim3 grid, int vu, float eps, const PfArgs& pf) {
+  const auto k = io.silu ? gn_onepass_kernel<T, NV, true> : gn_onepass_kernel<T, NV, false>;
+  hipLaunchKernelGGL(k, grid, dim3(T), 0, io.s, io.x, io.y, io.gamma, io.beta, io.rows, io.c, vu, eps, pf);
+}
+
+static int groupnorm_impl(const tc_bf16* x, tc_bf16* y, const float* gamma, const float* beta,
+                          int32_t samples, int32_t rows, int32_t c, float eps, int32_t silu,
+                          void* workspace, int64_t workspace_bytes, const TcPrefetch* prefetch, void* stream) {
+  PfArgs pf;
+  if (const int rc = gn_check(x, y, gamma, beta, samples, rows, c, workspace, workspace_bytes, prefetch, &pf)) return rc;
+  const GnIo io = {reinterpret_cast<const bf16_t*>(x), reinterpret_cast<bf16_t*>(y), gamma, beta, rows, c, silu != 0,
+                   reinterpret_cast<hipStream_t>(stream)};
   {
     // single-pass kernel when a (sample, unit) slab fits the registers of one block (TC_GN_ONEPASS=0: never)
     static const bool onepass = [] { const char* e = getenv("TC_GN_ONEPASS"); return !(e && e[0] == '0'); }();
@@ -654,8 +670,6 @@ static int groupnorm_impl(const tc_bf16* x, tc_bf16* y, const float* gamma, cons
     if (onepass && (c % u) == 0 && gu <= 4 && vu <= 64 && tc_aligned16(gamma) && tc_aligned16(beta)) {
       const int64_t nvec = (int64_t)rows * vu;
       const dim3 grid(c / u, samples, 1 + pf_planes(pf, (int64_t)(c / u) * samples));
-      const bf16_t* xb = reinterpret_cast<const bf16_t*>(x);
-      bf16_t* yb = reinterpret_cast<bf16_t*>(y);
       auto fits = [&](int t, int nv) { return (int64_t)((rows + t / vu - 1) / (t / vu)) <= nv; };
       // measured (profiles/r02_gn_onepass_ab.txt): wins 13-32 % where the grid fills the chip (per-frame norms of levels
       // 1-3) or the tensor is tiny (level-3 clip-wide, 3 MB); LOSES with 64 blocks on a 13 MB tensor (level-2
@@ -663,14 +677,8 @@ static int groupnorm_impl(const tc_bf16* x, tc_bf16* y, const float* gamma, cons
       const int64_t nblk = (int64_t)(c / u) * samples;
       const int64_t bytes = nvec * 16 * samples * (c / u);
       bool done = nblk >= 128 || bytes <= (4 << 20);
-      if (!done) {}
-      else if (fits(256, 4)) {
-        if (silu) hipLaunchKernelGGL((gn_onepass_kernel<256, 4, true>), grid, dim3(256), 0, s, xb, yb, gamma, beta, rows, c, vu, eps, pf);
-        else hipLaunchKernelGGL((gn_onepass_kernel<256, 4, false>), grid, dim3(256), 0, s, xb, yb, gamma, beta, rows, c, vu, eps, pf);
-      } else if (fits(256, 13)) {
-        if (silu) hipLaunchKernelGGL((gn_onepass_kernel<256, 13, true>), grid, dim3(256), 0, s, xb, yb, gamma, beta, rows, c, vu, eps, pf);
-        else hipLaunchKernelGGL((gn_onepass_kernel<256, 13, false>), grid, dim3(256), 0, s, xb, yb, gamma, beta, rows, c, vu, eps, pf);
-      }
+      if (done && fits(256, 4)) gn_onepass_launch<256, 4>(io, grid, vu, eps, pf);
+      else if (done && fits(256, 13)) gn_onepass_launch<256, 13>(io, grid, vu, eps, pf);
       else done = false;
       // (round 6: a 768-thread / 17-vector instance -- slabs of up to 204 KiB in ONE block's registers: the per-frame norms
       // of level 0, 256 slabs = one per CU, and the clip-wide norms of level 2 -- was built, passed its tests and LOST:
@@ -689,17 +697,13 @@ static int groupnorm_impl(const tc_bf16* x, tc_bf16* y, const float* gamma, cons
   float* part = reinterpret_cast<float*>(workspace);
   float* stats = part + (int64_t)samples * nch * 64;
   dim3 grid(nch, samples), block(GN_THREADS);
-  hipLaunchKernelGGL(gn_stats_kernel, grid, block, 0, s, reinterpret_cast<const bf16_t*>(x), part, rows, c, nch, cr);
+  hipLaunchKernelGGL(gn_stats_kernel, grid, block, 0, io.s, io.x, part, rows, c, nch, cr);
   TC_LAUNCH_CHECK();
-  hipLaunchKernelGGL(gn_finalize_kernel, dim3((samples * 32 + 3) / 4), block, 0, s, part, stats, samples, rows, c, nch,
+  hipLaunchKernelGGL(gn_finalize_kernel, dim3((samples * 32 + 3) / 4), block, 0, io.s, part, stats, samples, rows, c, nch,
                      eps);
   TC_LAUNCH_CHECK();
   // the weight-prefetch planes ride on the LAST of the three launches: the one right in front of the consumer
-  const dim3 agrid(nch, samples, 1 + pf_planes(pf, (int64_t)nch * samples));
-  if (silu) hipLaunchKernelGGL(gn_apply_kernel<true>, agrid, block, 0, s, reinterpret_cast<const bf16_t*>(x),
-                               reinterpret_cast<bf16_t*>(y), gamma, beta, stats, rows, c, cr, pf);
-  else hipLaunchKernelGGL(gn_apply_kernel<false>, agrid, block, 0, s, reinterpret_cast<const bf16_t*>(x),
-                          reinterpret_cast<bf16_t*>(y), gamma, beta, stats, rows, c, cr, pf);
+  gn_apply_launch(io, dim3(nch, samples, 1 + pf_planes(pf, (int64_t)nch * samples)), stats, cr, pf);
   TC_LAUNCH_CHECK();
   return TC_OK;
 }
@@ -719,24 +723,32 @@ extern "C" int tc_groupnorm_pf(const tc_bf16* x, tc_bf16* y, const float* gamma,
 extern "C" int tc_groupnorm_part(const tc_bf16* x, tc_bf16* y, const float* gamma, const float* beta, const float* part,
                                  int32_t part_rows, int32_t samples, int32_t rows, int32_t c, float eps, int32_t silu,
                                  void* workspace, int64_t workspace_bytes, void* stream) {
-  if (!x || !y || !gamma || !beta || !part || !workspace || samples <= 0 || rows <= 0 || c <= 0 || part_rows <= 0) return TC_EINVAL;
-  if ((c % 32) != 0 || (c % 8) != 0 || c > GN_MAX_SLOTS * GN_THREADS * 8 || c > 4096 || samples > 65535) return TC_ESHAPE;
+  if (!part || part_rows <= 0) return TC_EINVAL;
+  PfArgs pf;                                                     // stays empty: this entry point takes no prefetch list
+  if (const int rc = gn_check(x, y, gamma, beta, samples, rows, c, workspace, workspace_bytes, nullptr, &pf)) return rc;
   if ((rows % part_rows) != 0) return TC_ESHAPE;                 // a block of partial sums may not straddle two samples
-  if (!tc_aligned16(x) || !tc_aligned16(y)) return TC_EALIGN;
-  if (workspace_bytes < tc_groupnorm_workspace(samples, rows, c)) return TC_EWORKSPACE;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const GnIo io = {reinterpret_cast<const bf16_t*>(x), reinterpret_cast<bf16_t*>(y), gamma, beta, rows, c, silu != 0,
+                   reinterpret_cast<hipStream_t>(stream)};
   int nch, cr;
   gn_chunking(samples, rows, &nch, &cr);
   float* stats = reinterpret_cast<float*>(workspace) + (int64_t)samples * nch * 64;
-  hipLaunchKernelGGL(gn_finalize_part_kernel, dim3(samples * 32), dim3(256), 0, s, part, stats, samples, rows, c,
+  hipLaunchKernelGGL(gn_finalize_part_kernel, dim3(samples * 32), dim3(256), 0, io.s, part, stats, samples, rows, c,
                      part_rows, eps);
   TC_LAUNCH_CHECK();
-  if (silu) hipLaunchKernelGGL(gn_apply_kernel<true>, dim3(nch, samples), dim3(GN_THREADS), 0, s, reinterpret_cast<const bf16_t*>(x),
-                               reinterpret_cast<bf16_t*>(y), gamma, beta, stats, rows, c, cr, PfArgs{});
-  else hipLaunchKernelGGL(gn_apply_kernel<false>, dim3(nch, samples), dim3(GN_THREADS), 0, s, reinterpret_cast<const bf16_t*>(x),
-                          reinterpret_cast<bf16_t*>(y), gamma, beta, stats, rows, c, cr, PfArgs{});
+  gn_apply_launch(io, dim3(nch, samples), stats, cr, pf);
   TC_LAUNCH_CHECK();
   return TC_OK;
+}
+
+// LayerNorm: (NV, R) by the row width, for both forms of the result
+template <bool MX>
+static void ln_launch(const tc_bf16* x, tc_bf16* y, const float* gamma, const float* beta, int32_t rows, int32_t c, float eps,
+                      uint8_t* q, int32_t ldq, uint8_t* sc, int32_t lds, const PfArgs& pf, void* stream) {
+  const int rpb = c <= 512 ? 16 : (c <= 1024 ? 8 : 4);       // rows per block
+  const unsigned blocks = (unsigned)((rows + rpb - 1) / rpb);
+  const auto k = c <= 512 ? layernorm_kernel<1, 4, MX> : (c <= 1024 ? layernorm_kernel<2, 2, MX> : layernorm_kernel<4, 1, MX>);
+  hipLaunchKernelGGL(k, dim3(blocks, 1 + pf_planes(pf, blocks)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                     reinterpret_cast<const bf16_t*>(x), reinterpret_cast<bf16_t*>(y), gamma, beta, rows, c, eps, q, ldq, sc, lds, pf);
 }
 
 static int layernorm_impl(const tc_bf16* x, tc_bf16* y, const float* gamma, const float* beta,
@@ -746,18 +758,7 @@ static int layernorm_impl(const tc_bf16* x, tc_bf16* y, const float* gamma, cons
   if (!tc_aligned16(x) || !tc_aligned16(y) || !tc_aligned16(gamma) || !tc_aligned16(beta)) return TC_EALIGN;
   PfArgs pf;
   if (const int rc = pf_args(prefetch, &pf)) return rc;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const bf16_t* xb = reinterpret_cast<const bf16_t*>(x);
-  bf16_t* yb = reinterpret_cast<bf16_t*>(y);
-  const int rpb = c <= 512 ? 16 : (c <= 1024 ? 8 : 4);       // rows per block
-  const unsigned blocks = (unsigned)((rows + rpb - 1) / rpb);
-  const dim3 grid(blocks, 1 + pf_planes(pf, blocks));
-  if (c <= 512)
-    hipLaunchKernelGGL((layernorm_kernel<1, 4>), grid, dim3(256), 0, st, xb, yb, gamma, beta, rows, c, eps, nullptr, 0, nullptr, 0, pf);
-  else if (c <= 1024)
-    hipLaunchKernelGGL((layernorm_kernel<2, 2>), grid, dim3(256), 0, st, xb, yb, gamma, beta, rows, c, eps, nullptr, 0, nullptr, 0, pf);
-  else
-    hipLaunchKernelGGL((layernorm_kernel<4, 1>), grid, dim3(256), 0, st, xb, yb, gamma, beta, rows, c, eps, nullptr, 0, nullptr, 0, pf);
+  ln_launch<false>(x, y, gamma, beta, rows, c, eps, nullptr, 0, nullptr, 0, pf, stream);
   TC_LAUNCH_CHECK();
   return TC_OK;
 }
@@ -780,14 +781,7 @@ extern "C" int tc_layernorm_mxfp8(const tc_bf16* x, uint8_t* q, int32_t ldq, uin
   const int vpr = c >> 3, pad = lds - (c >> 5);
   const int nv = c <= 512 ? 1 : (c <= 1024 ? 2 : 4);
   if (vpr + pad > 64 * nv) return TC_ESHAPE;               // no idle lanes left to zero the scale padding
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const bf16_t* xb = reinterpret_cast<const bf16_t*>(x);
-  if (c <= 512)
-    hipLaunchKernelGGL((layernorm_kernel<1, 4, true>), dim3((rows + 15) / 16), dim3(256), 0, st, xb, nullptr, gamma, beta, rows, c, eps, q, ldq, sc, lds);
-  else if (c <= 1024)
-    hipLaunchKernelGGL((layernorm_kernel<2, 2, true>), dim3((rows + 7) / 8), dim3(256), 0, st, xb, nullptr, gamma, beta, rows, c, eps, q, ldq, sc, lds);
-  else
-    hipLaunchKernelGGL((layernorm_kernel<4, 1, true>), dim3((rows + 3) / 4), dim3(256), 0, st, xb, nullptr, gamma, beta, rows, c, eps, q, ldq, sc, lds);
+  ln_launch<true>(x, nullptr, gamma, beta, rows, c, eps, q, ldq, sc, lds, PfArgs{}, stream);
   TC_LAUNCH_CHECK();
   return TC_OK;
 }
