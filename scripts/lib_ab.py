@@ -274,14 +274,33 @@ def run_edges():
         for heads in (1, 5):
             qkv = rnd(2 * t * 7, 3 * 64 * heads)
             same(lambda: hip.attention_temporal(qkv, b=2, t=t, hw=7, heads=heads), f"attention_temporal b=2 t={t} hw=7 heads={heads}")
+    # the level-0 fused kernels (csrc/fused_l0.h is their shared skeleton; both read their switches per call)
     c = 320
-    x, wq, bq = rnd(16 * 8, c), rnd(3 * c, c, scale=1.4 * c ** -0.5), rnd(3 * c, scale=0.2, dtype=torch.float32)
+    wq, bq = rnd(3 * c, c, scale=1.4 * c ** -0.5), rnd(3 * c, scale=0.2, dtype=torch.float32)
     wo, bo = rnd(c, c, scale=c ** -0.5), rnd(c, scale=0.2, dtype=torch.float32)
-    with env(TC_TB_FUSED=1) as tag:
-        same(lambda: hip.temporal_attn_fused(x, wq, bq, wo, bo, b=1, t=16, hw=8, heads=5, ln_eps=1e-5), f"temporal_attn_fused b=1 t=16 hw=8 c=320 {tag}")
-    x, w1, b1 = rnd(100, c), rnd(2 * 1280, c, scale=c ** -0.5), rnd(2 * 1280, scale=0.2, dtype=torch.float32)
+    def e_tb(b, hw, ln_eps=1e-5, pitch=c, **sw):
+        x = rnd(b * 16 * hw, pitch)[:, :c]
+        with env(TC_TB_FUSED=1, **sw) as tag:
+            same(lambda: hip.temporal_attn_fused(x, wq, bq, wo, bo, b=b, t=16, hw=hw, heads=5, ln_eps=ln_eps),
+                 f"temporal_attn_fused b={b} t=16 hw={hw} c=320 ldx={pitch} ln_eps={ln_eps} {tag}")
+    e_tb(1, 8)                                                   # one tile
+    e_tb(1, 24, TC_TB_GRID=1)                                    # three tiles in one block: the stream crosses tile seams
+    e_tb(3, 40, TC_TB_GRID=4)                                    # 15 tiles of three clips on 4 blocks: 4, 4, 4 and 3 rounds
+    e_tb(1, 8, ln_eps=None)
+    e_tb(1, 8, pitch=960)
+    e_tb(3, 40, TC_TB_STAGGER=1)
+    w1, b1 = rnd(2 * 1280, c, scale=c ** -0.5), rnd(2 * 1280, scale=0.2, dtype=torch.float32)
     w2, b2 = rnd(c, 1280, scale=1280 ** -0.5), rnd(c, scale=0.2, dtype=torch.float32)
-    same(lambda: hip.ff_geglu_fused(x, w1, b1, w2, b2, ln_eps=1e-5), "ff_geglu_fused m=100 c=320 hidden=1280")
+    def e_ff(m, ln_eps=1e-5, pitch=c, **sw):
+        x = rnd(m, pitch)[:, :c]
+        with env(**sw) as tag:
+            same(lambda: hip.ff_geglu_fused(x, w1, b1, w2, b2, ln_eps=ln_eps), f"ff_geglu_fused m={m} c=320 hidden=1280 ldx={pitch} ln_eps={ln_eps} {tag}")
+    e_ff(100)                                                    # fewer rows than a tile
+    e_ff(677, TC_FF_GRID=2)                                      # 6 tiles, 3 per block: tile seams in the stream, a ragged last tile
+    e_ff(100, ln_eps=None)
+    e_ff(677, pitch=960)
+    for sw in (dict(TC_FF_LOOKAHEAD=2), dict(TC_FF_LOOKAHEAD=4), dict(TC_FF_GILP=2)):       # with the default: the four product instances
+        e_ff(677, TC_FF_GRID=2, **sw)
     e_spatial_and_norms()
     print("edges: " + ", ".join(f"{v} {k}" for k, v in counts.items()), flush=True)
     print(f"edges: {'no case with different bits' if not bad else f'{len(bad)} DIFFERENT: ' + '; '.join(bad)}", flush=True)

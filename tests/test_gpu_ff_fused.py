@@ -83,6 +83,23 @@ def test_fused_vs_chain_and_emulation(hip, weights, tag, m, pitch, ln):
     assert torch.equal(out, again), "repeated launch differs"
 
 
+def test_tile_arithmetic_is_independent_of_grid_and_lookahead(hip, weights, monkeypatch):
+    """A tile's arithmetic does not depend on which block runs it, on how far ahead the weight stream is requested or on
+    how the GEGLU stores are grouped: at m = 677 (6 tiles, the last ragged) two blocks of three tiles and each of the
+    other product instances of the kernel give the bits of the default launch."""
+    x = _x(677)
+    run = lambda: hip.ff_geglu_fused(x, *weights["folded"], weights["w2"], weights["b2"], ln_eps=1e-5)
+    for name in ("TC_FF_GRID", "TC_FF_LOOKAHEAD", "TC_FF_GILP"):
+        monkeypatch.delenv(name, raising=False)
+    out = run()
+    check(out, _chain(hip, x, weights, True), "m = 677: fused vs the three launches", rel=1.5e-3)
+    for name, value in (("TC_FF_GRID", "2"), ("TC_FF_LOOKAHEAD", "2"), ("TC_FF_LOOKAHEAD", "4"), ("TC_FF_GILP", "2")):
+        with monkeypatch.context() as mp:
+            mp.setenv(name, value)
+            got = run()
+        assert torch.equal(got, out), f"{name}={value} differs from the default launch"
+
+
 def test_fused_vs_fp64_reference_block(hip, weights):
     """x + Linear(GEGLU(LayerNorm(x))) exactly as the reference spells it (attention.py:244-246, 415-442), fp64."""
     w1, b1, w2, b2, gamma, beta = (t.double().cpu() for t in weights["raw"])

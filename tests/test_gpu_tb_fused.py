@@ -88,6 +88,25 @@ def test_fused_vs_chain_and_emulation(hip, weights, tag, b, hw, pitch, ln):
     assert torch.equal(out, again), "repeated launch differs"
 
 
+def test_tile_arithmetic_is_independent_of_grid_and_stagger(hip, weights, monkeypatch):
+    """A tile's arithmetic does not depend on which block runs it or on when that block starts: at b = 3, hw = 40 (15 tiles)
+    one block walking all tiles, four blocks in ragged rounds and staggered block starts give the bits of the default
+    launch (one tile per block)."""
+    b, hw = 3, 40
+    x = _x(b, hw)
+    kw = dict(b=b, t=T, hw=hw, heads=HEADS, ln_eps=1e-5)
+    run = lambda: hip.temporal_attn_fused(x, *weights["folded"], weights["wo"], weights["bo"], **kw)
+    for name in ("TC_TB_GRID", "TC_TB_STAGGER"):
+        monkeypatch.delenv(name, raising=False)
+    out = run()
+    check(out, _chain(hip, x, weights, True, b, hw), "b = 3, hw = 40: fused vs the four launches", rel=3e-3)
+    for name, value in (("TC_TB_GRID", "1"), ("TC_TB_GRID", "4"), ("TC_TB_STAGGER", "1")):
+        with monkeypatch.context() as mp:
+            mp.setenv(name, value)
+            got = run()
+        assert torch.equal(got, out), f"{name}={value} differs from the default launch"
+
+
 def test_fused_vs_fp64_reference_block(hip, weights):
     """x + to_out(softmax(q k^T / 8) v) over the frames of every pixel, q / k / v = Linear(LayerNorm(x)), in fp64."""
     raw, wo, bo, gamma, beta = (t.double().cpu() for t in weights["raw"])

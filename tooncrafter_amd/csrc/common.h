@@ -158,6 +158,12 @@ int attn_temporal_long_launch(const bf16_t* qkv, bf16_t* out, int32_t b, int32_t
 
 static inline bool tc_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// compute units of the current device (256 where it cannot be asked), read once: what the persistent grids are sized by
+static inline int tc_cu_count() {
+  static const int cus = [] { int d = 0, n = 256; if (hipGetDevice(&d) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n; }();
+  return cus;
+}
+
 #define TC_LAUNCH_CHECK()                         \
   do {                                            \
     hipError_t e__ = hipGetLastError();           \

@@ -26,29 +26,24 @@
 // LDS: W1 ring 64 KiB | W2 slice 40 KiB | hidden chunk 2 x 16 KiB (also the epilogue slabs) | biases 12 KiB = 148 KiB.
 // Order of the fp32 sums: ff1 over K in ascending 16-slices, ff2 over the hidden index in ascending 16-slices -- the
 // order of the tiled kernels, so the result equals LayerNorm -> tc_gemm_bf16(GEGLU) -> tc_gemm_bf16(+residual) up to the
-// LayerNorm's own rounding.
-#include "gemm_persist.h"
-#include "gemm_epilogue.h"
-
-#include <stdlib.h>
+// LayerNorm's own rounding.  What this kernel shares with tb_fused.hip is stated in csrc/fused_l0.h; here: the LDS map,
+// the weight-stream schedule with its counted waits, and the GEGLU between the two products.
+#include "fused_l0.h"
 
 namespace {
 
-constexpr int FF_C = 320, FF_H = 1280, FF_BM = 128, FF_THREADS = 512;
+constexpr int FF_C = L0_C, FF_H = 1280, FF_BM = L0_BM, FF_THREADS = L0_THREADS;
 constexpr int FF_CH = 64;                       // hidden columns per chunk = 128 packed W1 rows
 constexpr int FF_NCH = FF_H / FF_CH;            // 20 chunks
-constexpr int FF_KT = FF_C / TC_BK;             // 5 K-steps of ff1 per chunk
-constexpr int FF_W1_STAGE = 128 * 128;          // 16 KiB: 128 packed rows x 64 k
+constexpr int FF_KT = L0_KT;                    // 5 K-steps of ff1 per chunk
+constexpr int FF_W1_STAGE = L0_W_STAGE;         // 16 KiB: 128 packed rows x 64 k
 constexpr int FF_W1_OFF = 0;                    // ring of 4
 constexpr int FF_W2_OFF = 4 * FF_W1_STAGE;      // 40 KiB: 320 rows x 64 k
-constexpr int FF_W2_BYTES = 320 * 128;
-constexpr int FF_H_OFF = FF_W2_OFF + FF_W2_BYTES;   // 2 x 16 KiB: 128 rows x 64 hidden
-constexpr int FF_H_BYTES = 128 * 128;
+constexpr int FF_H_OFF = FF_W2_OFF + L0_W2_BYTES;   // 2 x 16 KiB: 128 rows x 64 hidden
+constexpr int FF_H_BYTES = L0_BUF_BYTES;
 constexpr int FF_B_OFF = FF_H_OFF + 2 * FF_H_BYTES; // b1 (2560 fp32) | b2 (320 fp32)
-constexpr int FF_P_OFF = FF_B_OFF + (2 * FF_H + FF_C) * 4;   // FF_NPARK parked A fragments: [slot][wm][lane] x 16 B
-constexpr int FF_NPARK = 3;                     // the last K-slices of the normalised rows live in LDS, not in registers
-constexpr int FF_NRES = 20 - FF_NPARK;
-constexpr int FF_LDS = FF_P_OFF + FF_NPARK * 4096;
+constexpr int FF_P_OFF = FF_B_OFF + (2 * FF_H + FF_C) * 4;   // the parked A fragments
+constexpr int FF_LDS = FF_P_OFF + L0_PARK_BYTES;
 static_assert(FF_LDS <= 160 * 1024, "LDS");
 
 struct FfArgs {
@@ -77,24 +72,17 @@ __global__ __launch_bounds__(FF_THREADS, 2) void ff_fused_kernel(const FfArgs p)
   const g8_srd_t w2_srd = g8_make_srd(p.w2, (int64_t)FF_C * FF_H * 2);
   const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
 
-  // biases into LDS once (no global load may sit inside the chunk loop: hipcc would wait vmcnt(0) for it and drain the stream)
-  {
-    float* bl = reinterpret_cast<float*>(smem + FF_B_OFF);
-    for (int i = tid; i < 2 * FF_H; i += FF_THREADS) bl[i] = p.b1[i];
-    for (int i = tid; i < FF_C; i += FF_THREADS) bl[2 * FF_H + i] = p.b2[i];
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");     // ... and in LDS before the first barrier
-  }
+  l0_stage_biases(reinterpret_cast<float*>(smem + FF_B_OFF), p.b1, 2 * FF_H, p.b2, FF_C, tid);
 
-  // ---- weight stream: thread -> (row lrow + 64 i, 16-byte chunk) of a 64-row pass; the XOR swizzle on the SOURCE chunk
-  const int lrow = tid >> 3;
-  const int sch = (tid & 7) ^ ((lrow >> 1) & 7);
+  // ---- weight stream (lane map: fused_l0.h)
+  const int lrow = l0_stream_row(tid);
   // W1 arrives in the GEMM's GEGLU packing (lvdm/common.py pack_geglu: every 32 rows = 16 value rows | their 16 gate rows);
   // the stage wants, per 64 rows, [32 values | 32 gates], so that a value and its gate meet in one lane of the two 32 x 32
   // accumulator blocks -- a permutation of the SOURCE row, free in the request's address
   const int w1_src = ((lrow & 31) >> 4) * 32 + (lrow >> 5) * 16 + (lrow & 15);
-  const uint32_t v1 = (uint32_t)(w1_src * FF_C * 2 + sch * 16);       // W1: + soffset (packed row block, K-step, pass)
-  const uint32_t v2 = (uint32_t)(lrow * FF_H * 2 + sch * 16);         // W2: + soffset (hidden chunk, pass)
-  const uint32_t dma_dst = lds0 + wave_u * 1024;
+  const uint32_t v1 = l0_stream_voff(w1_src, FF_C, tid);              // W1: + soffset (packed row block, K-step, pass)
+  const uint32_t v2 = l0_stream_voff(lrow, FF_H, tid);                // W2: + soffset (hidden chunk, pass)
+  const uint32_t dma_dst = l0_stream_dst(lds0, wave_u);
   auto dma_w1 = [&](int q) {                                          // W1 K-tile q of the cyclic stream -> ring stage q & 3
     if constexpr (ABL & 2) return;
     const int qq = q % (FF_NCH * FF_KT);
@@ -118,20 +106,15 @@ __global__ __launch_bounds__(FF_THREADS, 2) void ff_fused_kernel(const FfArgs p)
     g8_dma16(w2_srd, dma_dst + FF_W2_OFF + piece * 8192, v2, so);
   };
 
-  // ---- fragment addressing (32x32x16 MFMA): lane holds row lane & 31, k = 8 (lane >> 5) .. of slice kk -> chunk 2 kk + (lane >> 5)
-  // (computed where they are used, from the lane id: the kernel lives at the register limit -- 80 A-fragment + 80 output +
-  // 32 ff1 accumulator + 32 B-fragment registers -- and every address kept across the chunk loop is a spill into scratch,
-  // i.e. a vector-memory load inside the counted LDS-DMA stream)
-  auto coff = [&](int kk) { return ((kk * 2 + fhalf) ^ ((frow >> 1) & 7)) << 4; };
+  // ---- fragment addressing (layout: fused_l0.h), computed where it is used, from the lane id: the kernel lives at the
+  // register limit -- 80 A-fragment + 80 output + 32 ff1 accumulator + 32 B-fragment registers -- and every address kept
+  // across the chunk loop is a spill into scratch, i.e. a vector-memory load inside the counted LDS-DMA stream
   auto w1_row = [&]() { return (wn * 64 + frow) * 128; };          // + j * 4096 (value / gate block)
   auto h_row = [&]() { return (wm * 32 + frow) * 128; };
   auto w2_row = [&]() { return (wn * 160 + frow) * 128; };         // + j * 4096
 
-  // the tile's normalised rows, A fragments of ff1: K-slices 0 .. FF_NRES-1 in registers, the last FF_NPARK in LDS (both
-  // N-waves of a row group write the same bytes).  80 + 80 + 32 + 32 registers of fragments and accumulators do not
-  // leave room for addressing under the 256 a wave of an 8-wave block gets; the parked slices are read in the MFMA
-  // segment of the last K-step into B-fragment registers its first MFMAs have just released.
-  bf16x8 xa[FF_NRES];
+  // the tile's normalised rows, A fragments of ff1: K-slices 0 .. L0_NRES-1 in registers, the last L0_NPARK in LDS
+  bf16x8 xa[L0_NRES];
   char* const park = smem + FF_P_OFF + wm * 1024 + lane * 16;
   f32x16 out_acc[5];
   f32x16 acc_v, acc_g;
@@ -140,16 +123,7 @@ __global__ __launch_bounds__(FF_THREADS, 2) void ff_fused_kernel(const FfArgs p)
   // shader clock after every barrier -> trace[wave >> 2][n]
   int tr_n = 0;
   bool tr_on = false;
-  auto bar = [&]() {
-    g8_barrier();
-    if constexpr (ABL & 16) {
-      if (tr_on && tr_n < 64) {
-        const unsigned long long t = __builtin_amdgcn_s_memtime();
-        if (lane == 0) p.trace[(wave_u >> 2) * 64 + tr_n] = t;
-        ++tr_n;
-      }
-    }
-  };
+  auto bar = [&]() { l0_bar<(ABL & 16) != 0>(p.trace, wave_u, lane, tr_on, tr_n); };
   int q = 0;                                          // W1 K-tile stream position consumed next (cyclic)
   int cw2 = 0;                                        // hidden chunk whose W2 slice is requested next (cyclic): the one
                                                       // the CURRENT chunk's ff2 reads -- requested during its ff1 steps
@@ -166,59 +140,13 @@ __global__ __launch_bounds__(FF_THREADS, 2) void ff_fused_kernel(const FfArgs p)
     // ---- the wave's 32 rows: raw -> LayerNorm -> A fragments
     const int row = tile * FF_BM + wm * 32 + frow;
     const bool rok = row < p.m;
-    {
-      u32x4 raw[20];
-      const bf16_t* xr = p.x + (int64_t)(rok ? row : p.m - 1) * p.ldx + 8 * fhalf;       // rows past M: a valid row, never stored
-#pragma unroll
-      for (int s = 0; s < 20; ++s) raw[s] = *reinterpret_cast<const u32x4*>(xr + 16 * s);
-      if (p.ln) {
-        float sum = 0.f;
-#pragma unroll
-        for (int s = 0; s < 20; ++s) {
-          float f[8];
-          unpack8(raw[s], f);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) sum += f[e];
-        }
-        sum += __shfl_xor(sum, 32, 64);
-        const float mean = sum * (1.0f / FF_C);
-        float sq = 0.f;
-#pragma unroll
-        for (int s = 0; s < 20; ++s) {
-          float f[8];
-          unpack8(raw[s], f);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) { const float d = f[e] - mean; sq += d * d; }
-        }
-        sq += __shfl_xor(sq, 32, 64);
-        const float rstd = rsqrtf(sq * (1.0f / FF_C) + p.eps);
-#pragma unroll
-        for (int s = 0; s < 20; ++s) {
-          float f[8];
-          unpack8(raw[s], f);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) f[e] = (f[e] - mean) * rstd;
-          raw[s] = pack8(f);
-        }
-      }
-#pragma unroll
-      for (int s = 0; s < 20; ++s) {
-        if (s < FF_NRES) xa[s] = __builtin_bit_cast(bf16x8, raw[s]);
-        else *reinterpret_cast<u32x4*>(park + (s - FF_NRES) * 4096) = raw[s];
-      }
-      // without LayerNorm nothing has consumed the row loads yet: a load still "pending" at the chunk loop's header makes
-      // the compiler wait vmcnt(0) at its first use INSIDE the loop, every chunk -- so they are consumed here, once
-#pragma unroll
-      for (int s = 0; s < FF_NRES; ++s) asm volatile("" ::"v"(xa[s]));
-    }
+    l0_rows_prologue(p.x + (int64_t)(rok ? row : p.m - 1) * p.ldx, fhalf, true, p.ln, p.eps, xa, park);   // rows past M: a valid row, never stored
 #pragma unroll
     for (int j = 0; j < 5; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) out_acc[j][r] = 0.f;
 
-    // the stagger, per tile: group 1 runs one barrier interval behind group 0 through the chunks (and is let catch up
-    // before the epilogue, so that the two groups' epilogues and row loads -- long, barrier-free -- run side by side)
-    if (grp == 1) g8_barrier();
+    l0_stagger(grp);
     for (int c = 0; c < FF_NCH; ++c) {
       if constexpr (ABL & 16) tr_on = blockIdx.x == 0 && (wave_u & 3) == 0 && tile == (int)(blockIdx.x + gridDim.x) && c < 3;
 #pragma unroll
@@ -228,10 +156,7 @@ __global__ __launch_bounds__(FF_THREADS, 2) void ff_fused_kernel(const FfArgs p)
         constexpr int s = decltype(S_)::value;
         const char* st = smem + FF_W1_OFF + (q & 3) * FF_W1_STAGE + w1_row();
         bf16x8 bw[2][4];
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int kk = 0; kk < 4; ++kk) bw[j][kk] = *reinterpret_cast<const bf16x8*>(st + j * 4096 + coff(kk));
+        l0_read_bw(st, frow, fhalf, bw);
         if constexpr (LA != 4) {
           dma_w1(q + LA);
           if (s == 1) { dma_w2(cw2, 0); dma_w2(cw2, 1); }
@@ -258,20 +183,7 @@ __global__ __launch_bounds__(FF_THREADS, 2) void ff_fused_kernel(const FfArgs p)
         }
         bar();
         __builtin_amdgcn_s_setprio(1);
-        auto mm = [&](auto KK_) {
-          constexpr int kk = decltype(KK_)::value, ks = 4 * s + kk;
-          if constexpr (ABL & 4) {
-            asm volatile("" : "+v"(acc_v), "+v"(acc_g) : "v"(bw[0][kk]), "v"(bw[1][kk]));
-          } else if constexpr (ks < FF_NRES) {
-            acc_v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[ks], bw[0][kk], acc_v, 0, 0, 0);
-            acc_g = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[ks], bw[1][kk], acc_g, 0, 0, 0);
-          } else {
-            const bf16x8 pa = *reinterpret_cast<const bf16x8*>(park + (ks - FF_NRES) * 4096);
-            acc_v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa, bw[0][kk], acc_v, 0, 0, 0);
-            acc_g = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa, bw[1][kk], acc_g, 0, 0, 0);
-          }
-          if constexpr (s == 4) __builtin_amdgcn_sched_barrier(0);
-        };
+        auto mm = [&](auto KK_) { l0_mm<s, decltype(KK_)::value, (ABL & 4) != 0>(xa, park, bw, acc_v, acc_g); };
         if constexpr (LA == 4) {
           mm(ic<0>{});
           __builtin_amdgcn_sched_barrier(0);
@@ -287,10 +199,7 @@ __global__ __launch_bounds__(FF_THREADS, 2) void ff_fused_kernel(const FfArgs p)
           __builtin_amdgcn_sched_barrier(0);
           mm(ic<3>{});
         } else {
-          mm(ic<0>{});
-          mm(ic<1>{});
-          mm(ic<2>{});
-          mm(ic<3>{});
+          l0_mm4<s, (ABL & 4) != 0>(xa, park, bw, acc_v, acc_g);
         }
         __builtin_amdgcn_s_setprio(0);
         bar();
@@ -311,31 +220,20 @@ __global__ __launch_bounds__(FF_THREADS, 2) void ff_fused_kernel(const FfArgs p)
       ff1_step(ic<4>{});
       // ---- G: GEGLU on the accumulators -> the wave's 32 x 32 hidden values, bf16, into the chunk buffer (A layout of ff2)
       {
-        // the lane id is taken afresh (and opaquely): an address hoisted out of the chunk loop is a register the loop does
-        // not have, i.e. a scratch reload, i.e. a compiler "s_waitcnt vmcnt(0)" at the top of every G draining the stream
-        int gl = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-        asm volatile("" : "+v"(gl));
+        const int gl = l0_lane_now();                               // afresh: nothing hoisted out of the chunk loop
         const int frow = gl & 31, fhalf = gl >> 5;
         const int pr = c * 128 + wn * 64 + (frow >> 4) * 32 + (frow & 15);   // pack_geglu row of this lane's value; gate 16 on
         const float bv = bl[pr], bg = bl[pr + 16];
-        // accumulator register r of a lane is row cr = (r & 3) + 8 (r >> 2) (+ 4 fhalf) of the wave's 32, column frow; its
-        // place in the chunk buffer (row-major [128][64] bf16, 16-byte chunks XOR-swizzled by (row >> 1) & 7):
-        //     row * 128 + (((hcol >> 3) ^ ((row >> 1) & 7)) << 4) + (hcol & 7) * 2,     hcol = wn * 32 + frow
-        // (row >> 1) & 7 = kr | 2 fhalf with kr = (cr >> 1) & 7 in {0, 1, 4, 5}: four lane-dependent bases, the rest immediates
-        const int hcol = wn * 32 + frow;
-        char* const hrow = smem + FF_H_OFF + (c & 1) * FF_H_BYTES + (wm * 32 + 4 * fhalf) * 128 + (hcol & 7) * 2;
-        const int a2 = (hcol >> 3) ^ (2 * fhalf);
-        char* const hbase[4] = {hrow + (a2 << 4), hrow + ((a2 ^ 1) << 4), hrow + ((a2 ^ 4) << 4), hrow + ((a2 ^ 5) << 4)};
+        // the wave's block is columns wn * 32 .. + 32 of the chunk buffer (fused_l0.h L0Scatter)
+        const L0Scatter sc(smem + FF_H_OFF + (c & 1) * FF_H_BYTES + wm * 32 * 128, wn * 32 + frow, fhalf);
 #pragma unroll
-        for (int r = 0; r < 16; r += 2) {                             // register pairs: packed fp32 arithmetic
-          const int cr = (r & 3) + 8 * (r >> 2);                      // row of r; r + 1 is the next row (r is even)
-          const int kr = (cr >> 1) & 7;                               // 0, 1, 4 or 5 -- the same for both
+        for (int r = 0; r < 16; r += 2) {                             // register pairs (rows cr, cr + 1): packed fp32 arithmetic
           const tc_f32x2 v = {acc_v[r] + bv, acc_v[r + 1] + bv};
           const tc_f32x2 g = {acc_g[r] + bg, acc_g[r + 1] + bg};
           const tc_f32x2 h = (ABL & 1) ? v * g : v * gelu_erf_f2(g);
-          char* const dst = hbase[(kr & 1) + (kr >> 2) * 2] + cr * 128;
-          *reinterpret_cast<bf16_t*>(dst) = (bf16_t)h[0];
-          *reinterpret_cast<bf16_t*>(dst + 128) = (bf16_t)h[1];
+          bf16_t* const dst = sc.at(r);
+          dst[0] = (bf16_t)h[0];
+          dst[64] = (bf16_t)h[1];                                     // the next row: + 128 bytes
           if ((r + 2) % GI == 0) __builtin_amdgcn_sched_barrier(0);   // GI values in flight: the chain of a GELU is ~20 dependent instructions
         }
         ++cw2;
@@ -349,58 +247,25 @@ __global__ __launch_bounds__(FF_THREADS, 2) void ff_fused_kernel(const FfArgs p)
       {
         const char* hb = smem + FF_H_OFF + (c & 1) * FF_H_BYTES + h_row();
         const char* wb = smem + FF_W2_OFF + w2_row();
-        bf16x8 ha[4], b2[2][4];
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) ha[kk] = *reinterpret_cast<const bf16x8*>(hb + coff(kk));
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int kk = 0; kk < 4; ++kk) b2[j][kk] = *reinterpret_cast<const bf16x8*>(wb + j * 4096 + coff(kk));
-        bar();
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int j = 0; j < 5; ++j) {
-#pragma unroll
-          for (int kk = 0; kk < 4; ++kk)
-            if constexpr (ABL & 8) asm volatile("" : "+v"(out_acc[j]) : "v"(ha[kk]), "v"(b2[j & 1][kk]));
-            else out_acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ha[kk], b2[j & 1][kk], out_acc[j], 0, 0, 0);
-          __builtin_amdgcn_sched_barrier(0);
-          if (j + 2 < 5) {                            // the set just consumed is refilled two blocks ahead
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) b2[j & 1][kk] = *reinterpret_cast<const bf16x8*>(wb + (j + 2) * 4096 + coff(kk));
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        __builtin_amdgcn_s_setprio(0);
-        bar();
+        l0_second_product<(ABL & 8) != 0>(hb, wb, frow, fhalf, out_acc, bar);
       }
     }
 
-    if (grp == 0) g8_barrier();                     // realign: every wave has executed the same number of barriers
+    l0_realign(grp);
     // ---- epilogue: + b2 + residual (the raw rows), bf16.  Per wave six passes of (16 rows x 64 columns) through a
     // private 4 KiB slab carved from the hidden-chunk buffers: wave (wm, wn) takes buffer wn, rows wm*32..+32 -- rows only
     // its own group reads, and this group's last read of them is behind it
     {
       float* slab = reinterpret_cast<float*>(smem + FF_H_OFF + wn * FF_H_BYTES + wm * 32 * 128);
-      auto pass = [&](auto J0_, auto NJ_, auto HALF_) {            // gemm_epilogue.h epi_fused_out_pass
-        constexpr int j0 = decltype(J0_)::value, nj = decltype(NJ_)::value, half = decltype(HALF_)::value;
-        epi_fused_out_pass<half, nj>(slab, out_acc + j0, lane, wn * 160 + j0 * 32, bl + 2 * FF_H, p.x, p.ldx, p.out, p.ldo,
-                                     [&](int lr, int64_t& m) { m = tile * FF_BM + wm * 32 + half * 16 + lr; return m < p.m; });
-      };
-      pass(ic<0>{}, ic<2>{}, ic<0>{});
-      pass(ic<0>{}, ic<2>{}, ic<1>{});
-      pass(ic<2>{}, ic<2>{}, ic<0>{});
-      pass(ic<2>{}, ic<2>{}, ic<1>{});
-      pass(ic<4>{}, ic<1>{}, ic<0>{});
-      pass(ic<4>{}, ic<1>{}, ic<1>{});
+      l0_epilogue(slab, out_acc, lane, wm, wn, bl + 2 * FF_H, p.x, p.ldx, p.out, p.ldo,
+                  [&](int tr, int64_t& m) { m = tile * FF_BM + tr; return m < p.m; });
     }
   }
   tc_wait_vmcnt<0>();                               // the stream ran ahead: nothing may land in LDS after the block is gone
 }
 
 int ff_mode() {        // TC_FF_FUSED = 0 never | 1 (default) whenever the shape is the level-0 block's; read per call
-  const char* e = getenv("TC_FF_FUSED");
-  return e ? atoi(e) : 1;
+  return l0_env_int("TC_FF_FUSED", 1);
 }
 
 }  // namespace
@@ -408,36 +273,27 @@ int ff_mode() {        // TC_FF_FUSED = 0 never | 1 (default) whenever the shape
 extern "C" int tc_ff_geglu_fused_eligible(const TcFfParams* p) {
   if (!p || ff_mode() == 0) return 0;
   if (p->c != FF_C || p->hidden != FF_H || p->m <= 0) return 0;
-  if (p->ldx < FF_C || p->ldo < FF_C || (p->ldx & 7) || (p->ldo & 7)) return 0;
-  if ((int64_t)p->m * p->ldx * 2 >= 0x7fffffffLL * 64) return 0;
-  return 1;
+  return l0_rows_ok(p->ldx, p->ldo, p->m, p->ldx);
 }
 
 extern "C" int tc_ff_geglu_fused(const TcFfParams* p, void* stream) {
-  if (!p || !p->x || !p->w1 || !p->b1 || !p->w2 || !p->b2 || !p->out) return TC_EINVAL;
-  if (!tc_ff_geglu_fused_eligible(p)) return TC_ESHAPE;
-  if (!tc_aligned16(p->x) || !tc_aligned16(p->w1) || !tc_aligned16(p->w2) || !tc_aligned16(p->out)) return TC_EALIGN;
+  if (!p) return TC_EINVAL;
+  if (const int rc = l0_check_call(p->x, p->w1, p->b1, p->w2, p->b2, p->out, tc_ff_geglu_fused_eligible(p))) return rc;
   FfArgs a;
   a.x = reinterpret_cast<const bf16_t*>(p->x); a.w1 = reinterpret_cast<const bf16_t*>(p->w1); a.b1 = p->b1;
   a.w2 = reinterpret_cast<const bf16_t*>(p->w2); a.b2 = p->b2; a.out = reinterpret_cast<bf16_t*>(p->out);
   a.m = p->m; a.ldx = p->ldx; a.ldo = p->ldo; a.ln = p->ln ? 1 : 0; a.eps = p->ln_eps;
   a.tiles = (p->m + FF_BM - 1) / FF_BM;
 #ifdef TC_TIMING_BUILDS      /* interval trace / timing ablations: WRONG results by construction, never in the product library */
-  a.trace = [&]() -> unsigned long long* { const char* e = getenv("TC_FF_TRACE"); return e ? reinterpret_cast<unsigned long long*>(strtoull(e, nullptr, 0)) : nullptr; }();
+  a.trace = l0_trace_ptr("TC_FF_TRACE");
 #else
   a.trace = nullptr;
 #endif
-  static const int cus = [] { int d = 0, n = 256; if (hipGetDevice(&d) == hipSuccess) hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n; }();
-  const int gmax = [&] { const char* e = getenv("TC_FF_GRID"); const int v = e ? atoi(e) : 0; return v > 0 ? v : cus; }();
-  // every block the same number of tiles: 640 tiles on 256 CUs are three rounds either way, and 214 blocks of three
-  // leave the weight stream (L2 -> LDS, shared by all) less contended than 256 blocks of two or three
-  const int rounds = (a.tiles + gmax - 1) / gmax;
-  const int grid = (a.tiles + rounds - 1) / rounds;
+  const int grid = l0_grid(a.tiles, "TC_FF_GRID");
 #ifdef TC_TIMING_BUILDS
-  const int abl = [&] { const char* e = getenv("TC_FF_ABLATE"); return e ? atoi(e) : 0; }();
+  const int abl = l0_env_int("TC_FF_ABLATE", 0);
 #endif
-  const int gi = [&] { const char* e = getenv("TC_FF_GILP"); return e ? atoi(e) : 8; }();
-  const int la = [&] { const char* e = getenv("TC_FF_LOOKAHEAD"); return e ? atoi(e) : 3; }();
+  const int gi = l0_env_int("TC_FF_GILP", 8), la = l0_env_int("TC_FF_LOOKAHEAD", 3);
   const dim3 g((unsigned)grid), b(FF_THREADS);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 #define FF_LAUNCH(LA_, ABL_) hipLaunchKernelGGL((ff_fused_kernel<LA_, ABL_, 2>), g, b, 0, st, a)

@@ -332,7 +332,7 @@ extern "C" int tc_gemm_bf16(const TcGemmParams* pp, void* stream) {
   if (!pp) return TC_EINVAL;
   const TcGemmParams& p = *pp;
   if (const int rc = tc_gemm_validate(p)) return rc;
-  static const int cus = [] { int d = 0, n = 256; if (hipGetDevice(&d) == hipSuccess) hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n; }();
+  const int cus = tc_cu_count();
   const TcGemmSwitches sw = tc_gemm_switches();
   TcGemmRoute r;
   const int rc = tc_gemm_route(p, sw, cus, &r);

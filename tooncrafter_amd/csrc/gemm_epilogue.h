@@ -122,7 +122,7 @@ __device__ __forceinline__ void epi_spill32_half(float* slab, const f32x16* acc,
     }
 }
 
-// ---- output pass of the level-0 fused kernels (ff_fused.hip, tb_fused.hip): 16 rows x (32 NJ <= 64) columns of a wave's
+// ---- output pass of the level-0 fused kernels (fused_l0.h l0_epilogue: ff_fused.hip, tb_fused.hip): 16 rows x (32 NJ <= 64) columns of a wave's
 // output accumulators through its private slab [16][64]; out = (acc + bias) + residual, the residual being the block's own
 // input rows x, as bf16.  n0w: first output column of the pass;  bias: the output bias (LDS);  row_of(slab row, m) ->
 // whether the row exists, and its row m of x / out (a flag beside the row, not a negative row: tb_fused.hip's rows always

@@ -3,7 +3,7 @@
 // arguments, the projection itself (qa_project: the two kernels differ in the row map they hand it) and the host's
 // shape rule and argument fill.
 #pragma once
-#include "gemm_common.h"
+#include "fused_l0.h"      // L0Scatter: the swizzled [128][64] layout of q / k is the level-0 fused kernels'
 
 // the long-clip route of tc_temporal_qkv_attn (csrc/qkv_attn_long.hip): 17 .. TC_TEMPORAL_MAX_FRAMES frames, its own pixel
 // count per tile, and what TC_QKV_ATTN = 1 admits of it
@@ -145,16 +145,13 @@ __device__ __forceinline__ void qa_project(char* smem, const tc_rsrc_t a_rsrc, c
   // ---- K loop: two K-steps in flight (gemm_common.h tc_kloop_pipe); its last barrier frees the stage memory for the epilogue
   tc_kloop_pipe<QA_RA + QA_RB>(0, c / TC_BK, load_tile, compute);
 
-  // ---- write-out of the projection: + bias, bf16.  Accumulator register r of a lane = row cr = (r & 3) + 8 (r >> 2)
-  // + 4 fhalf of the 32-row block, column frow.  q / k: row-major [128][64], chunks swizzled by (row >> 1) & 7;
-  // v: transposed [64 dims][128 rows], four consecutive rows of a lane as one 8-byte store.
+  // ---- write-out of the projection: + bias, bf16.  q / k: row-major [128][64], chunks swizzled by (row >> 1) & 7 -- the
+  // scatter of a 32 x 32 accumulator block stated in fused_l0.h (L0Scatter);  v: transposed [64 dims][128 rows], four
+  // consecutive rows of a lane (accumulator registers 4 g .. 4 g + 3 = rows 8 g + 4 fhalf + (0..3)) as one 8-byte store.
   auto write_rm = [&](char* buf, const f32x16& a, int i, int colblk, float b) {
-    const int col = colblk * 32 + frow;
+    const L0Scatter sc(buf + (wm * 64 + i * 32) * 128, colblk * 32 + frow, fhalf);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fhalf;
-      *reinterpret_cast<bf16_t*>(buf + row * 128 + (((col >> 3) ^ ((row >> 1) & 7)) << 4) + (col & 7) * 2) = (bf16_t)(a[r] + b);
-    }
+    for (int r = 0; r < 16; ++r) *sc.at(r) = (bf16_t)(a[r] + b);
   };
   auto write_vt = [&](const f32x16& a, int i, int colblk, float b) {
     char* v0 = smem + QA_VT_OFF + (colblk * 32 + frow) * QA_VT_LD + (wm * 64 + i * 32 + 4 * fhalf) * 2;

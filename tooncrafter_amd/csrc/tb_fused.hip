@@ -6,7 +6,7 @@
 // TemporalTransformer, attention.py:365-412, behind norm1 / norm2 of BasicTransformerBlock, attention.py:225-246).  As four
 // launches -- LayerNorm(-prologue) qkv projection (81920 x 960 x 320), tc_attn_temporal, output projection + residual --
 // the block writes a 157 MB qkv tensor and a 52 MB attention output to HBM and reads both back for 0.018 TFLOP of
-// attention arithmetic.  Here neither exists.  The skeleton is csrc/ff_fused.hip's:
+// attention arithmetic.  Here neither exists:
 //
 //  * a block owns 8 consecutive pixels x 16 frames = 128 GATHERED rows (tile row = pixel * 16 + frame; a pixel's frames are
 //    HW rows apart in memory, each row 640 contiguous bytes); wave (wm, wn) of its 8 waves owns rows wm*32..+32 = two pixels.
@@ -22,35 +22,31 @@
 //  * weights (819 KB, L2-resident) stream by LDS-DMA from inline asm: Wqkv K-tiles through a ring of three 16 KiB stages
 //    (requested two steps ahead; the stream runs on across heads and tiles), Wo's slice once per head in five pieces;
 //    every wait is a hand-counted vmcnt;
-//  * the two wave groups (wm >> 1: one wave per SIMD each) run one barrier interval apart, as in ff_fused.hip / gemm8.hip.
+//  * the two wave groups (wm >> 1: one wave per SIMD each) run one barrier interval apart, as in gemm8.hip.
 //
+// What this kernel shares with ff_fused.hip is stated once, in csrc/fused_l0.h; this file keeps the LDS map, the weight-stream
+// schedule with its counted waits, the v^T write-out and the attention between the two products.
 // LDS: W ring 48 KiB | Wo slice 40 | q (then the head's output) 16 | k 16 | v^T 17 | biases 5 | parked A fragments 12 = 154 KiB.
 // Roundings: LayerNorm output, q / k / v, the softmax weights and the attention output in bf16, sums in fp32 -- the
 // roundings of the four launches (tc_attn_temporal keeps its softmax weights in fp32: the one difference).
-#include "gemm_persist.h"
-#include "gemm_epilogue.h"
+#include "fused_l0.h"
 #include "attn_frames16.h"
-
-#include <stdlib.h>
 
 namespace {
 
-constexpr int TB_C = 320, TB_HEADS = 5, TB_T = 16, TB_BM = 128, TB_THREADS = 512;
-constexpr int TB_KT = TB_C / TC_BK;               // 5 K-steps per stage
-constexpr int TB_W_STAGE = 128 * 128;             // 16 KiB: 128 rows x 64 k
+constexpr int TB_C = L0_C, TB_HEADS = 5, TB_T = 16, TB_THREADS = L0_THREADS;
+constexpr int TB_KT = L0_KT;                      // 5 K-steps per stage
+constexpr int TB_W_STAGE = L0_W_STAGE;            // 16 KiB: 128 rows x 64 k
 constexpr int TB_NRING = 3;
 constexpr int TB_W_OFF = 0;
 constexpr int TB_WO_OFF = TB_NRING * TB_W_STAGE;  // 40 KiB: 320 rows x 64 k
-constexpr int TB_WO_BYTES = 320 * 128;
-constexpr int TB_Q_OFF = TB_WO_OFF + TB_WO_BYTES; // [128 rows][64] bf16, 16-byte chunks XOR-swizzled by (row >> 1) & 7
-constexpr int TB_K_OFF = TB_Q_OFF + 128 * 128;
-constexpr int TB_VT_OFF = TB_K_OFF + 128 * 128;   // [64 dims][128 rows + 8] bf16: 272-byte rows (conflict-free 16-lane reads)
+constexpr int TB_Q_OFF = TB_WO_OFF + L0_W2_BYTES; // [128 rows][64] bf16, swizzled (fused_l0.h)
+constexpr int TB_K_OFF = TB_Q_OFF + L0_BUF_BYTES;
+constexpr int TB_VT_OFF = TB_K_OFF + L0_BUF_BYTES;   // [64 dims][128 rows + 8] bf16: 272-byte rows (conflict-free 16-lane reads)
 constexpr int TB_VT_LD = 272;
 constexpr int TB_B_OFF = TB_VT_OFF + 64 * TB_VT_LD;          // bqkv (960 fp32) | bo (320 fp32)
-constexpr int TB_P_OFF = TB_B_OFF + (3 * TB_C + TB_C) * 4;   // parked A fragments: [slot][wm][lane] x 16 B
-constexpr int TB_NPARK = 3;
-constexpr int TB_NRES = 20 - TB_NPARK;
-constexpr int TB_LDS = TB_P_OFF + TB_NPARK * 4096;
+constexpr int TB_P_OFF = TB_B_OFF + (3 * TB_C + TB_C) * 4;   // the parked A fragments
+constexpr int TB_LDS = TB_P_OFF + L0_PARK_BYTES;
 static_assert(TB_LDS <= 160 * 1024, "LDS");
 static_assert(TB_VT_OFF + 64 * TB_VT_LD - TB_K_OFF >= 8 * 4096, "epilogue slabs live in the k / v^T buffers");
 
@@ -79,20 +75,11 @@ __global__ __launch_bounds__(TB_THREADS, 2) void tb_fused_kernel(const TbArgs p)
   const g8_srd_t wo_srd = g8_make_srd(p.wo, (int64_t)TB_C * TB_C * 2);
   const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
 
-  // biases into LDS once (no global load may sit inside the head loop: hipcc would wait vmcnt(0) for it and drain the stream)
-  {
-    float* bl = reinterpret_cast<float*>(smem + TB_B_OFF);
-    for (int i = tid; i < 3 * TB_C; i += TB_THREADS) bl[i] = p.bqkv[i];
-    for (int i = tid; i < TB_C; i += TB_THREADS) bl[3 * TB_C + i] = p.bo[i];
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  }
+  l0_stage_biases(reinterpret_cast<float*>(smem + TB_B_OFF), p.bqkv, 3 * TB_C, p.bo, TB_C, tid);
 
-  // ---- weight stream: thread -> (row lrow of a 64-row piece, 16-byte chunk); the XOR swizzle on the SOURCE chunk.  Wqkv
-  // and Wo both have 320-element rows, so one per-lane offset serves both
-  const int lrow = tid >> 3;
-  const int sch = (tid & 7) ^ ((lrow >> 1) & 7);
-  const uint32_t voff = (uint32_t)(lrow * TB_C * 2 + sch * 16);
-  const uint32_t dma_dst = lds0 + wave_u * 1024;
+  // ---- weight stream (lane map: fused_l0.h).  Wqkv and Wo both have 320-element rows, so one per-lane offset serves both
+  const uint32_t voff = l0_stream_voff(l0_stream_row(tid), TB_C, tid);
+  const uint32_t dma_dst = l0_stream_dst(lds0, wave_u);
   // K-tile q of the cyclic stream (50 per tile: head h = q / 10, stage (q % 10) / 5, K-step q % 5) -> ring stage q % 3.
   // Stage A: rows 0..63 <- the head's q rows (h*64 ..), rows 64..127 <- its k rows (320 + h*64 ..): two pieces per thread;
   // stage B: rows 0..63 <- its v rows (640 + h*64 ..): one piece
@@ -115,10 +102,7 @@ __global__ __launch_bounds__(TB_THREADS, 2) void tb_fused_kernel(const TbArgs p)
     g8_dma16(wo_srd, dma_dst + TB_WO_OFF + piece * 8192, voff, so);
   };
 
-  // ---- fragment addressing (32x32x16 MFMA): lane holds row lane & 31, k = 8 (lane >> 5) .. of slice kk -> chunk 2 kk + (lane >> 5)
-  auto coff = [&](int kk) { return ((kk * 2 + fhalf) ^ ((frow >> 1) & 7)) << 4; };
-
-  bf16x8 xa[TB_NRES];                               // the tile's normalised rows: K-slices 0 .. TB_NRES-1 (the rest parked in LDS)
+  bf16x8 xa[L0_NRES];                               // the tile's normalised rows: K-slices 0 .. L0_NRES-1 (the rest parked in LDS)
   char* const park = smem + TB_P_OFF + wm * 1024 + lane * 16;
   f32x16 out_acc[5];
   f32x16 acc_v, acc_g;                              // the stage's 32 x 64 block of the wave: columns 0..31 | 32..63
@@ -128,16 +112,7 @@ __global__ __launch_bounds__(TB_THREADS, 2) void tb_fused_kernel(const TbArgs p)
   // cycle, its waits are the same)
   int tr_n = 0;
   bool tr_on = false;
-  auto bar = [&]() {
-    g8_barrier();
-    if constexpr (TRACE) {
-      if (tr_on && tr_n < 64) {
-        const unsigned long long t = __builtin_amdgcn_s_memtime();
-        if (lane == 0) p.trace[(wave_u >> 2) * 64 + tr_n] = t;
-        ++tr_n;
-      }
-    }
-  };
+  auto bar = [&]() { l0_bar<TRACE>(p.trace, wave_u, lane, tr_on, tr_n); };
   for (int i = (blockIdx.x & 3) * p.stagger; i > 0; --i) __builtin_amdgcn_s_sleep(127);
   int q = 0;                                        // K-tile stream position consumed next
   dma_w(0);
@@ -152,55 +127,13 @@ __global__ __launch_bounds__(TB_THREADS, 2) void tb_fused_kernel(const TbArgs p)
     const int p0 = (tile - bb * p.tiles_per_b) * 8;
     // tile row lr = pixel * 16 + frame -> memory row (bb * 16 + frame) * hw + p0 + pixel
     auto grow = [&](int lr) { return (int64_t)(bb * TB_T + (lr & 15)) * p.hw + p0 + (lr >> 4); };
-    {
-      u32x4 raw[20];
-      const bf16_t* xr = p.x + grow(wm * 32 + frow) * p.ldx + 8 * fhalf;
-#pragma unroll
-      for (int s = 0; s < 20; ++s) raw[s] = (p.abl & 2) ? u32x4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u} : *reinterpret_cast<const u32x4*>(xr + 16 * s);
-      if (p.ln) {
-        float sum = 0.f;
-#pragma unroll
-        for (int s = 0; s < 20; ++s) {
-          float f[8];
-          unpack8(raw[s], f);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) sum += f[e];
-        }
-        sum += __shfl_xor(sum, 32, 64);
-        const float mean = sum * (1.0f / TB_C);
-        float sq = 0.f;
-#pragma unroll
-        for (int s = 0; s < 20; ++s) {
-          float f[8];
-          unpack8(raw[s], f);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) { const float d = f[e] - mean; sq += d * d; }
-        }
-        sq += __shfl_xor(sq, 32, 64);
-        const float rstd = rsqrtf(sq * (1.0f / TB_C) + p.eps);
-#pragma unroll
-        for (int s = 0; s < 20; ++s) {
-          float f[8];
-          unpack8(raw[s], f);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) f[e] = (f[e] - mean) * rstd;
-          raw[s] = pack8(f);
-        }
-      }
-#pragma unroll
-      for (int s = 0; s < 20; ++s) {
-        if (s < TB_NRES) xa[s] = __builtin_bit_cast(bf16x8, raw[s]);
-        else *reinterpret_cast<u32x4*>(park + (s - TB_NRES) * 4096) = raw[s];
-      }
-#pragma unroll
-      for (int s = 0; s < TB_NRES; ++s) asm volatile("" ::"v"(xa[s]));     // row loads consumed before the head loop (ff_fused.hip)
-    }
+    l0_rows_prologue(p.x + grow(wm * 32 + frow) * p.ldx, fhalf, !(p.abl & 2), p.ln, p.eps, xa, park);
 #pragma unroll
     for (int j = 0; j < 5; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) out_acc[j][r] = 0.f;
 
-    if (grp == 1) g8_barrier();                     // the stagger, per tile (ff_fused.hip)
+    l0_stagger(grp);
     for (int h = (p.abl & 1) ? TB_HEADS : 0; h < TB_HEADS; ++h) {
       if constexpr (TRACE) tr_on = blockIdx.x == 0 && (wave_u & 3) == 0 && tile == (int)(blockIdx.x + gridDim.x) && h < 2;
       // ---- one K-step of a stage: fragments of W K-tile q (ring stage q % 3), K-tile q + 2 and this step's share of Wo's
@@ -215,12 +148,7 @@ __global__ __launch_bounds__(TB_THREADS, 2) void tb_fused_kernel(const TbArgs p)
         const bool act = stage == 0 || wn == 0;       // stage B: the k-side waves have no columns
         const char* st = smem + TB_W_OFF + (q % TB_NRING) * TB_W_STAGE + (wn * 64 + frow) * 128;
         bf16x8 bw[2][4];
-        if (act) {
-#pragma unroll
-          for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) bw[j][kk] = *reinterpret_cast<const bf16x8*>(st + j * 4096 + coff(kk));
-        }
+        if (act) l0_read_bw(st, frow, fhalf, bw);
         dma_w(q + 2);
         if (stage == 1 && s == 1) { dma_wo(h, 0); dma_wo(h, 1); }
         if (stage == 1 && s >= 2) dma_wo(h, s);
@@ -229,56 +157,28 @@ __global__ __launch_bounds__(TB_THREADS, 2) void tb_fused_kernel(const TbArgs p)
         tc_wait_vmcnt<keep>();
         bar();
         __builtin_amdgcn_s_setprio(1);
-        if (act) {
-          auto mm = [&](auto KK_) {
-            constexpr int kk = decltype(KK_)::value, ks = 4 * s + kk;
-            if constexpr (ks < TB_NRES) {
-              acc_v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[ks], bw[0][kk], acc_v, 0, 0, 0);
-              acc_g = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[ks], bw[1][kk], acc_g, 0, 0, 0);
-            } else {
-              const bf16x8 pa = *reinterpret_cast<const bf16x8*>(park + (ks - TB_NRES) * 4096);
-              acc_v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa, bw[0][kk], acc_v, 0, 0, 0);
-              acc_g = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa, bw[1][kk], acc_g, 0, 0, 0);
-            }
-            if constexpr (s == 4) __builtin_amdgcn_sched_barrier(0);
-          };
-          mm(ic<0>{});
-          mm(ic<1>{});
-          mm(ic<2>{});
-          mm(ic<3>{});
-        }
+        if (act) l0_mm4<s>(xa, park, bw, acc_v, acc_g);
         __builtin_amdgcn_s_setprio(0);
         bar();
         ++q;
       };
-      // ---- write-out of a stage's block: + bias, bf16.  q / k: row-major [128][64], 16-byte chunks XOR-swizzled by
-      // (row >> 1) & 7 (accumulator register r of a lane = row cr = (r & 3) + 8 (r >> 2) + 4 fhalf of the wave's 32, column
-      // frow | 32 + frow: (row >> 1) & 7 = kr | 2 fhalf with kr in {0, 1, 4, 5}, so four lane-dependent bases serve all 32
-      // stores -- ff_fused.hip); v: transposed, [64 dims][128 rows], four consecutive rows of a lane as one 8-byte store
-      auto lane_now = [&]() {                          // the lane id afresh and opaque: nothing hoisted out of the head loop
-        int gl = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-        asm volatile("" : "+v"(gl));
-        return gl;
-      };
+      // ---- write-out of a stage's block: + bias, bf16 (the lane id afresh: nothing hoisted out of the head loop).  q / k:
+      // row-major [128][64], swizzled: columns frow | 32 + frow of the wave's rows (fused_l0.h L0Scatter); v: transposed,
+      // [64 dims][128 rows], four consecutive rows of a lane as one 8-byte store
       auto write_qk = [&]() {
-        const int gl = lane_now();
+        const int gl = l0_lane_now();
         const int fr = gl & 31, fh = gl >> 5;
         const float b0 = bl[wn * TB_C + h * 64 + fr], b1 = bl[wn * TB_C + h * 64 + 32 + fr];
-        char* const hrow = smem + (wn ? TB_K_OFF : TB_Q_OFF) + (wm * 32 + 4 * fh) * 128 + (fr & 7) * 2;
-        const int a2 = (fr >> 3) ^ (2 * fh);
-        char* const hb[4] = {hrow + (a2 << 4), hrow + ((a2 ^ 1) << 4), hrow + ((a2 ^ 4) << 4), hrow + ((a2 ^ 5) << 4)};
+        const L0Scatter sc(smem + (wn ? TB_K_OFF : TB_Q_OFF) + wm * 32 * 128, fr, fh);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int cr = (r & 3) + 8 * (r >> 2);
-          const int kr = (cr >> 1) & 7;                // 0, 1, 4 or 5
-          const int i0 = (kr & 1) + (kr >> 2) * 2;      // base of column frow; column 32 + frow: chunk ^ 4 -> kr ^ 4
-          *reinterpret_cast<bf16_t*>(hb[i0] + cr * 128) = (bf16_t)(acc_v[r] + b0);
-          *reinterpret_cast<bf16_t*>(hb[i0 ^ 2] + cr * 128) = (bf16_t)(acc_g[r] + b1);
+          *sc.at(r) = (bf16_t)(acc_v[r] + b0);
+          *sc.at32(r) = (bf16_t)(acc_g[r] + b1);
         }
       };
       auto write_vt = [&]() {
         if (wn != 0) return;
-        const int gl = lane_now();
+        const int gl = l0_lane_now();
         const int fr = gl & 31, fh = gl >> 5;
         const float b0 = bl[2 * TB_C + h * 64 + fr], b1 = bl[2 * TB_C + h * 64 + 32 + fr];
         char* const v0 = smem + TB_VT_OFF + fr * TB_VT_LD + (wm * 32 + 4 * fh) * 2;
@@ -317,10 +217,10 @@ __global__ __launch_bounds__(TB_THREADS, 2) void tb_fused_kernel(const TbArgs p)
 
       // ---- attention of ONE pixel per wave (rows pr .. pr + 16 of the tile = its 16 frames), 16x16x32 MFMAs.
       // (The other group's Wo pieces are only known to have landed after ITS drain, one interval behind this one: this
-      // interval separates that drain from the output projection's reads, as the empty interval of ff_fused.hip does.)
+      // interval separates that drain from the output projection's reads.)
       {
         // attn_frames16.h: S^T = K Q^T, softmax, O = P V, the head's output over its q rows in the A layout of the projection
-        tc_attn_frames16(smem + TB_Q_OFF, smem + TB_K_OFF, smem + TB_VT_OFF, TB_VT_LD, wm * 32 + wn * 16, lane_now(), p.scale_log2e);
+        tc_attn_frames16(smem + TB_Q_OFF, smem + TB_K_OFF, smem + TB_VT_OFF, TB_VT_LD, wm * 32 + wn * 16, l0_lane_now(), p.scale_log2e);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         bar();
       }
@@ -329,50 +229,18 @@ __global__ __launch_bounds__(TB_THREADS, 2) void tb_fused_kernel(const TbArgs p)
       {
         const char* hb = smem + TB_Q_OFF + (wm * 32 + frow) * 128;
         const char* wb = smem + TB_WO_OFF + (wn * 160 + frow) * 128;
-        bf16x8 ha[4], b2[2][4];
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) ha[kk] = *reinterpret_cast<const bf16x8*>(hb + coff(kk));
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int kk = 0; kk < 4; ++kk) b2[j][kk] = *reinterpret_cast<const bf16x8*>(wb + j * 4096 + coff(kk));
-        bar();
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int j = 0; j < 5; ++j) {
-#pragma unroll
-          for (int kk = 0; kk < 4; ++kk)
-            out_acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ha[kk], b2[j & 1][kk], out_acc[j], 0, 0, 0);
-          __builtin_amdgcn_sched_barrier(0);
-          if (j + 2 < 5) {
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) b2[j & 1][kk] = *reinterpret_cast<const bf16x8*>(wb + (j + 2) * 4096 + coff(kk));
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        __builtin_amdgcn_s_setprio(0);
-        bar();
+        l0_second_product(hb, wb, frow, fhalf, out_acc, bar);
       }
     }
 
-    if (grp == 0) g8_barrier();                     // realign: every wave has executed the same number of barriers
+    l0_realign(grp);
     // ---- epilogue: + bo + residual (the raw rows), bf16, through a private 4 KiB slab per wave carved from the k / v^T
     // buffers (dead: the last head's attention is behind every wave)
     {
       float* slab = reinterpret_cast<float*>(smem + TB_K_OFF + wave_u * 4096);
-      auto pass = [&](auto J0_, auto NJ_, auto HALF_) {            // gemm_epilogue.h epi_fused_out_pass
-        constexpr int j0 = decltype(J0_)::value, nj = decltype(NJ_)::value, half = decltype(HALF_)::value;
-        epi_fused_out_pass<half, nj>(slab, out_acc + j0, lane, wn * 160 + j0 * 32, bl + 3 * TB_C, p.x, p.ldx, p.out, p.ldo,
-                                     [&](int lr, int64_t& m) { m = grow(wm * 32 + half * 16 + lr); return true; });
-      };
-      if (!(p.abl & 4)) {
-        pass(ic<0>{}, ic<2>{}, ic<0>{});
-        pass(ic<0>{}, ic<2>{}, ic<1>{});
-        pass(ic<2>{}, ic<2>{}, ic<0>{});
-        pass(ic<2>{}, ic<2>{}, ic<1>{});
-        pass(ic<4>{}, ic<1>{}, ic<0>{});
-        pass(ic<4>{}, ic<1>{}, ic<1>{});
-      }
+      if (!(p.abl & 4))
+        l0_epilogue(slab, out_acc, lane, wm, wn, bl + 3 * TB_C, p.x, p.ldx, p.out, p.ldo,
+                    [&](int tr, int64_t& m) { m = grow(tr); return true; });
     }
   }
   tc_wait_vmcnt<0>();                               // the stream ran ahead: nothing may land in LDS after the block is gone
@@ -386,8 +254,7 @@ __global__ __launch_bounds__(TB_THREADS, 2) void tb_fused_kernel(const TbArgs p)
 // tried: +0.57 % and +0.38 % (profiles/r06_l0_chain_vs_tb_fused_forward_ab*.txt).  This kernel is LDS-bandwidth-bound
 // (header); the chain's launches are HBM-bound and each runs near its own roof.  Kept, tested, one switch away.
 int tb_mode() {
-  const char* e = getenv("TC_TB_FUSED");
-  return e ? atoi(e) : 0;
+  return l0_env_int("TC_TB_FUSED", 0);
 }
 
 }  // namespace
@@ -395,15 +262,12 @@ int tb_mode() {
 extern "C" int tc_temporal_attn_fused_eligible(const TcTbParams* p) {
   if (!p || tb_mode() == 0) return 0;
   if (p->c != TB_C || p->heads != TB_HEADS || p->t != TB_T || p->b <= 0 || p->hw <= 0 || (p->hw & 7)) return 0;
-  if (p->ldx < TB_C || p->ldo < TB_C || (p->ldx & 7) || (p->ldo & 7)) return 0;
-  if ((int64_t)p->b * p->t * p->hw * (p->ldx > p->ldo ? p->ldx : p->ldo) * 2 >= 0x7fffffffLL * 64) return 0;
-  return 1;
+  return l0_rows_ok(p->ldx, p->ldo, (int64_t)p->b * p->t * p->hw, p->ldx > p->ldo ? p->ldx : p->ldo);
 }
 
 extern "C" int tc_temporal_attn_fused(const TcTbParams* p, void* stream) {
-  if (!p || !p->x || !p->wqkv || !p->bqkv || !p->wo || !p->bo || !p->out) return TC_EINVAL;
-  if (!tc_temporal_attn_fused_eligible(p)) return TC_ESHAPE;
-  if (!tc_aligned16(p->x) || !tc_aligned16(p->wqkv) || !tc_aligned16(p->wo) || !tc_aligned16(p->out)) return TC_EALIGN;
+  if (!p) return TC_EINVAL;
+  if (const int rc = l0_check_call(p->x, p->wqkv, p->bqkv, p->wo, p->bo, p->out, tc_temporal_attn_fused_eligible(p))) return rc;
   TbArgs a;
   a.x = reinterpret_cast<const bf16_t*>(p->x); a.wqkv = reinterpret_cast<const bf16_t*>(p->wqkv); a.bqkv = p->bqkv;
   a.wo = reinterpret_cast<const bf16_t*>(p->wo); a.bo = p->bo; a.out = reinterpret_cast<bf16_t*>(p->out);
@@ -411,19 +275,16 @@ extern "C" int tc_temporal_attn_fused(const TcTbParams* p, void* stream) {
   a.scale_log2e = p->scale * 1.44269504088896340736f;
   a.tiles_per_b = p->hw / 8;
   a.tiles = p->b * a.tiles_per_b;
-  static const int cus = [] { int d = 0, n = 256; if (hipGetDevice(&d) == hipSuccess) hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n; }();
 #ifdef TC_TIMING_BUILDS      /* timing ablations / interval trace: WRONG results by construction, never in the product library */
-  a.abl = [&] { const char* e = getenv("TC_TB_ABLATE"); return e ? atoi(e) : 0; }();
-  a.trace = [&]() -> unsigned long long* { const char* e = getenv("TC_TB_TRACE"); return e ? reinterpret_cast<unsigned long long*>(strtoull(e, nullptr, 0)) : nullptr; }();
+  a.abl = l0_env_int("TC_TB_ABLATE", 0);
+  a.trace = l0_trace_ptr("TC_TB_TRACE");
   if (!a.trace) a.abl &= ~8;
 #else
   a.abl = 0;
   a.trace = nullptr;
 #endif
-  a.stagger = [&] { const char* e = getenv("TC_TB_STAGGER"); return e ? atoi(e) : 0; }();
-  const int gmax = [&] { const char* e = getenv("TC_TB_GRID"); const int v = e ? atoi(e) : 0; return v > 0 ? v : cus; }();
-  const int rounds = (a.tiles + gmax - 1) / gmax;
-  const int grid = (a.tiles + rounds - 1) / rounds;
+  a.stagger = l0_env_int("TC_TB_STAGGER", 0);
+  const int grid = l0_grid(a.tiles, "TC_TB_GRID");
 #ifdef TC_TIMING_BUILDS
   if (a.abl & 8) hipLaunchKernelGGL(tb_fused_kernel<true>, dim3((unsigned)grid), dim3(TB_THREADS), 0, reinterpret_cast<hipStream_t>(stream), a);
   else
