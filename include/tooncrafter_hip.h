@@ -384,6 +384,14 @@ typedef struct TcDdimParams {
 int64_t tc_ddim_workspace(int32_t b);
 int tc_ddim_step(const TcDdimParams* p, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* The same step for an eps-parameterised model (additive within ABI 14: one symbol, the struct and the workspace of
+ * tc_ddim_step).  The model output after CFG and rescale_noise_cfg is e_t itself (samplers/ddim.py:231-234), so
+ *   pred_x0 = (x - sqrt_1m_ac * e_t) / sqrt_ac                     (ddim.py:257-258, a true fp32 division)
+ * and dynamic rescale, dir_coef * e_t, the noise term and x_prev follow as in tc_ddim_step (ddim.py:262-277).  The
+ * callers pass sqrt_ac = sqrt(ddim_alphas[index]) and sqrt_1m_ac = ddim_sqrt_one_minus_alphas[index], the tables this
+ * branch of the reference reads (ddim.py:251-254).  TC_EINVAL also for sqrt_ac == 0 (a zero-terminal-SNR step). */
+int tc_ddim_step_eps(const TcDdimParams* p, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Pinned-frame blend and forward noising of the samplers, one elementwise launch (additive within ABI 14: one struct,
  * one symbol).  Replaces the mask / x0 blend at the top of a sampling step (ddim.py:173-180, ddim_multiplecond.py:177-184),
  * q_sample (ddpm3d.py:306-309) and the last line of stochastic_encode (ddim.py:316-317):

@@ -165,6 +165,7 @@ SYMBOLS = {
     "tc_video_to_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "tc_ddim_workspace": (C.c_int64, [C.c_int32]),
     "tc_ddim_step": (C.c_int, [C.POINTER(TcDdimParams), C.c_void_p, C.c_int64, C.c_void_p]),
+    "tc_ddim_step_eps": (C.c_int, [C.POINTER(TcDdimParams), C.c_void_p, C.c_int64, C.c_void_p]),
     "tc_ddim_blend": (C.c_int, [C.POINTER(TcDdimBlendParams), C.c_void_p]),
     "tc_gemm_ws_eligible": (C.c_int, [C.POINTER(TcGemmParams)]),
     "tc_gemm_gn_rows": (C.c_int, [C.POINTER(TcGemmParams)]),

@@ -204,46 +204,54 @@ __global__ __launch_bounds__(256) void ddim_stats_kernel(TcDdimParams p, double*
         red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
-__global__ __launch_bounds__(256) void ddim_apply_kernel(TcDdimParams p, const double* __restrict__ part) {
-  __shared__ float factor_s;
-  const int b = blockIdx.y;
-  const bool cfg = p.e_uncond != nullptr;
-  const bool resc = cfg && p.guidance_rescale > 0.f;
-  if (threadIdx.x == 0) {
-    float factor = 1.f;
-    if (resc) {
-      double s[4] = {0, 0, 0, 0};
-      for (int k = 0; k < DDIM_PARTS; ++k)
-        for (int j = 0; j < 4; ++j) s[j] += part[((int64_t)b * DDIM_PARTS + k) * 4 + j];
-      const double n = (double)p.n;
-      const double var_t = (s[1] - s[0] * s[0] / n) / (n - 1.0);
-      const double var_c = (s[3] - s[2] * s[2] / n) / (n - 1.0);
-      const float std_t = (float)sqrt(var_t > 0 ? var_t : 0.0);
-      const float std_c = (float)sqrt(var_c > 0 ? var_c : 0.0);
-      factor = std_t / std_c;
-    }
-    factor_s = factor;
-  }
-  __syncthreads();
-  const float factor = factor_s;
-  const int64_t base = (int64_t)b * p.n;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < p.n; i += (int64_t)gridDim.x * 256) {
-    const float x = p.x[base + i];
-    float v = p.e_cond[base + i];
-    if (cfg) {
-      v = p.e_uncond_img ? cfg_combine3(v, p.e_uncond[base + i], p.e_uncond_img[base + i], p.cfg_scale, p.cfg_img)
-                         : cfg_combine(v, p.e_uncond[base + i], p.cfg_scale);
-      if (resc) v = p.guidance_rescale * (v * factor) + (1.f - p.guidance_rescale) * v;
-    }
-    const float e_t = p.sqrt_ac * v + p.sqrt_1m_ac * x;
-    float x0 = p.sqrt_ac * x - p.sqrt_1m_ac * v;
-    x0 *= p.x0_rescale;
-    float xp = p.sqrt_a_prev * x0 + p.dir_coef * e_t;
-    if (p.noise) xp += p.sigma * p.noise[base + i];
-    p.x_prev[base + i] = xp;
-    if (p.pred_x0) p.pred_x0[base + i] = x0;
-  }
+// EPS = false: the model output is v (ddim.py:232, 260).  EPS = true: it is e_t itself (ddim.py:234) and
+// pred_x0 = (x - sqrt_1m_ac * e_t) / sqrt_ac, a true division as on ddim.py:258.  One text, two kernels.  A macro and not
+// a template body inlined into two kernels: through the inlined form the compiler orders two scalar address adds of the
+// v kernel differently, and that kernel is to stay the instructions it was (scripts/isa_compare.py).
+#define TC_DDIM_APPLY_KERNEL(NAME, EPS)                                                                            \
+__global__ __launch_bounds__(256) void NAME(TcDdimParams p, const double* __restrict__ part) {                     \
+  __shared__ float factor_s;                                                                                       \
+  const int b = blockIdx.y;                                                                                        \
+  const bool cfg = p.e_uncond != nullptr;                                                                          \
+  const bool resc = cfg && p.guidance_rescale > 0.f;                                                               \
+  if (threadIdx.x == 0) {                                                                                          \
+    float factor = 1.f;                                                                                            \
+    if (resc) {                                                                                                    \
+      double s[4] = {0, 0, 0, 0};                                                                                  \
+      for (int k = 0; k < DDIM_PARTS; ++k)                                                                         \
+        for (int j = 0; j < 4; ++j) s[j] += part[((int64_t)b * DDIM_PARTS + k) * 4 + j];                           \
+      const double n = (double)p.n;                                                                                \
+      const double var_t = (s[1] - s[0] * s[0] / n) / (n - 1.0);                                                   \
+      const double var_c = (s[3] - s[2] * s[2] / n) / (n - 1.0);                                                   \
+      const float std_t = (float)sqrt(var_t > 0 ? var_t : 0.0);                                                    \
+      const float std_c = (float)sqrt(var_c > 0 ? var_c : 0.0);                                                    \
+      factor = std_t / std_c;                                                                                      \
+    }                                                                                                              \
+    factor_s = factor;                                                                                             \
+  }                                                                                                                \
+  __syncthreads();                                                                                                 \
+  const float factor = factor_s;                                                                                   \
+  const int64_t base = (int64_t)b * p.n;                                                                           \
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < p.n; i += (int64_t)gridDim.x * 256) {              \
+    const float x = p.x[base + i];                                                                                 \
+    float v = p.e_cond[base + i];                                                                                  \
+    if (cfg) {                                                                                                     \
+      v = p.e_uncond_img ? cfg_combine3(v, p.e_uncond[base + i], p.e_uncond_img[base + i], p.cfg_scale, p.cfg_img) \
+                         : cfg_combine(v, p.e_uncond[base + i], p.cfg_scale);                                      \
+      if (resc) v = p.guidance_rescale * (v * factor) + (1.f - p.guidance_rescale) * v;                            \
+    }                                                                                                              \
+    const float e_t = EPS ? v : p.sqrt_ac * v + p.sqrt_1m_ac * x;                                                  \
+    float x0 = EPS ? (x - p.sqrt_1m_ac * v) / p.sqrt_ac : p.sqrt_ac * x - p.sqrt_1m_ac * v;                        \
+    x0 *= p.x0_rescale;                                                                                            \
+    float xp = p.sqrt_a_prev * x0 + p.dir_coef * e_t;                                                              \
+    if (p.noise) xp += p.sigma * p.noise[base + i];                                                                \
+    p.x_prev[base + i] = xp;                                                                                       \
+    if (p.pred_x0) p.pred_x0[base + i] = x0;                                                                       \
+  }                                                                                                                \
 }
+TC_DDIM_APPLY_KERNEL(ddim_apply_kernel, false)
+TC_DDIM_APPLY_KERNEL(ddim_apply_eps_kernel, true)
+#undef TC_DDIM_APPLY_KERNEL
 
 // Pinned-frame blend / forward noising (tc_ddim_blend), flat over the b * n elements.  Every product, the subtraction and every
 // sum is rounded on its own, where the reference's separate torch ops round (ddim.py:176-180, ddpm3d.py:306-309): the
@@ -416,7 +424,7 @@ extern "C" int tc_video_to_u8(const float* x, uint8_t* out, int32_t b, int32_t t
 
 extern "C" int64_t tc_ddim_workspace(int32_t b) { return b > 0 ? (int64_t)b * DDIM_PARTS * 4 * sizeof(double) : 0; }
 
-extern "C" int tc_ddim_step(const TcDdimParams* pp, void* workspace, int64_t workspace_bytes, void* stream) {
+static int ddim_step_launch(const TcDdimParams* pp, void* workspace, int64_t workspace_bytes, void* stream, bool eps) {
   if (!pp) return TC_EINVAL;
   const TcDdimParams& p = *pp;
   if (!p.x || !p.e_cond || !p.x_prev || p.b <= 0 || p.n <= 1) return TC_EINVAL;
@@ -429,9 +437,22 @@ extern "C" int tc_ddim_step(const TcDdimParams* pp, void* workspace, int64_t wor
     hipLaunchKernelGGL(ddim_stats_kernel, dim3(DDIM_PARTS, p.b), dim3(256), 0, s, p, part);
     TC_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(ddim_apply_kernel, dim3(grid_for(p.n, 256, 256), p.b), dim3(256), 0, s, p, part);
+  const dim3 grid(grid_for(p.n, 256, 256), p.b);
+  if (eps)
+    hipLaunchKernelGGL(ddim_apply_eps_kernel, grid, dim3(256), 0, s, p, part);
+  else
+    hipLaunchKernelGGL(ddim_apply_kernel, grid, dim3(256), 0, s, p, part);
   TC_LAUNCH_CHECK();
   return TC_OK;
+}
+
+extern "C" int tc_ddim_step(const TcDdimParams* pp, void* workspace, int64_t workspace_bytes, void* stream) {
+  return ddim_step_launch(pp, workspace, workspace_bytes, stream, false);
+}
+
+extern "C" int tc_ddim_step_eps(const TcDdimParams* pp, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (pp && pp->sqrt_ac == 0.f) return TC_EINVAL;          // eps divides by sqrt_ac: a zero-terminal-SNR step has no eps form
+  return ddim_step_launch(pp, workspace, workspace_bytes, stream, true);
 }
 
 extern "C" int tc_ddim_blend(const TcDdimBlendParams* pp, void* stream) {

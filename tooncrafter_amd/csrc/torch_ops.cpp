@@ -2,7 +2,7 @@
 //
 // The reference binds ATen / xformers operators from Python (utils/utils.py:27-42 instantiates lvdm classes whose
 // forward methods call torch ops); this registers the MI355X kernels as first-class torch operators instead:
-//   torch.ops.tooncrafter.gemm / quant_mxfp8 / gemm_mx / attention / attention_temporal / groupnorm(_pf) / layernorm(_pf) / ddim_step / ddim_blend /
+//   torch.ops.tooncrafter.gemm / quant_mxfp8 / gemm_mx / attention / attention_temporal / groupnorm(_pf) / layernorm(_pf) / ddim_step(_eps) / ddim_blend /
 //   ff_geglu_fused / temporal_attn_fused / temporal_qkv_attn / attention_q8
 // with (i) a CUDA(HIP)-key implementation that validates the tensors, allocates the result from the caching allocator,
 // picks up the CURRENT stream and calls the same extern "C" entry point the ctypes binding calls, and (ii) a Meta-key
@@ -389,10 +389,11 @@ Tensor layernorm_cuda(const Tensor& x, const Tensor& gamma, const Tensor& beta, 
 Tensor like_meta3(const Tensor& x, const Tensor&, const Tensor&, int64_t, int64_t, double, bool) { return at::empty_like(x); }
 Tensor like_meta_ln(const Tensor& x, const Tensor&, const Tensor&, double) { return at::empty_like(x); }
 
-std::tuple<Tensor, Tensor> ddim_step_cuda(const Tensor& x, const Tensor& e_cond, const optional<Tensor>& e_uncond,
-                                          const optional<Tensor>& noise, const optional<Tensor>& e_uncond_img, double cfg_scale,
-                                          double cfg_img, double guidance_rescale, double sqrt_ac, double sqrt_1m_ac,
-                                          double sqrt_a_prev, double dir_coef, double sigma, double x0_rescale) {
+template <bool EPS>
+std::tuple<Tensor, Tensor> ddim_step_any(const Tensor& x, const Tensor& e_cond, const optional<Tensor>& e_uncond,
+                                         const optional<Tensor>& noise, const optional<Tensor>& e_uncond_img, double cfg_scale,
+                                         double cfg_img, double guidance_rescale, double sqrt_ac, double sqrt_1m_ac,
+                                         double sqrt_a_prev, double dir_coef, double sigma, double x0_rescale) {
   auto ok = [](const Tensor& t) { return t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous(); };
   TORCH_CHECK(ok(x) && ok(e_cond) && (!e_uncond.has_value() || ok(*e_uncond)) && (!noise.has_value() || ok(*noise)) &&
               (!e_uncond_img.has_value() || ok(*e_uncond_img)), "ddim_step: contiguous fp32 CUDA tensors");
@@ -409,7 +410,10 @@ std::tuple<Tensor, Tensor> ddim_step_cuda(const Tensor& x, const Tensor& e_cond,
   p.dir_coef = (float)dir_coef; p.sigma = (float)sigma; p.x0_rescale = (float)x0_rescale;
   const int64_t nbytes = tc_ddim_workspace(p.b);
   Tensor ws = at::empty({nbytes > 16 ? nbytes : 16}, x.options().dtype(at::kByte));
-  check_rc(tc_ddim_step(&p, ws.data_ptr(), nbytes, cur_stream()), "tc_ddim_step");
+  if (EPS)
+    check_rc(tc_ddim_step_eps(&p, ws.data_ptr(), nbytes, cur_stream()), "tc_ddim_step_eps");
+  else
+    check_rc(tc_ddim_step(&p, ws.data_ptr(), nbytes, cur_stream()), "tc_ddim_step");
   return std::make_tuple(x_prev, x0);
 }
 
@@ -464,6 +468,9 @@ TORCH_LIBRARY(tooncrafter, m) {
   m.def("ddim_step(Tensor x, Tensor e_cond, Tensor? e_uncond, Tensor? noise, Tensor? e_uncond_img, float cfg_scale, "
         "float cfg_img, float guidance_rescale, float sqrt_ac, float sqrt_1m_ac, float sqrt_a_prev, float dir_coef, "
         "float sigma, float x0_rescale) -> (Tensor, Tensor)");
+  m.def("ddim_step_eps(Tensor x, Tensor e_cond, Tensor? e_uncond, Tensor? noise, Tensor? e_uncond_img, float cfg_scale, "
+        "float cfg_img, float guidance_rescale, float sqrt_ac, float sqrt_1m_ac, float sqrt_a_prev, float dir_coef, "
+        "float sigma, float x0_rescale) -> (Tensor, Tensor)");
   m.def("ddim_blend(Tensor? x, Tensor x0, Tensor? noise, Tensor? mask, float sqrt_ac, float sqrt_1m_ac) -> Tensor");
   m.def("abi_version() -> int");
 }
@@ -479,7 +486,8 @@ TORCH_LIBRARY_IMPL(tooncrafter, CUDA, m) {
   m.impl("layernorm", layernorm_cuda);
   m.impl("groupnorm_pf", groupnorm_pf_cuda);
   m.impl("layernorm_pf", layernorm_pf_cuda);
-  m.impl("ddim_step", ddim_step_cuda);
+  m.impl("ddim_step", ddim_step_any<false>);
+  m.impl("ddim_step_eps", ddim_step_any<true>);
   m.impl("ddim_blend", ddim_blend_cuda);
   m.impl("ff_geglu_fused", ff_geglu_fused_cuda);
   m.impl("temporal_attn_fused", temporal_attn_fused_cuda);
@@ -498,6 +506,7 @@ TORCH_LIBRARY_IMPL(tooncrafter, Meta, m) {
   m.impl("groupnorm_pf", groupnorm_pf_meta);
   m.impl("layernorm_pf", layernorm_pf_meta);
   m.impl("ddim_step", ddim_step_meta);
+  m.impl("ddim_step_eps", ddim_step_meta);
   m.impl("ddim_blend", ddim_blend_meta);
   m.impl("ff_geglu_fused", ff_geglu_fused_meta);
   m.impl("temporal_attn_fused", temporal_attn_fused_meta);

@@ -1,9 +1,10 @@
-"""First-stage Encoder on the HIP operators (the step right before the loop).
+"""First-stage Encoder and plain image Decoder on the HIP operators (the step right before
+the loop; the Decoder is the first stage of the DynamiCrafter-family configurations).
 
 Mirrors reference lvdm/modules/networks/ae_modules.py -- ResnetBlock (153-213), AttnBlock
-(21-88), Downsample (92-112), Encoder (366-475) -- with the same parameter names
-(`first_stage_model.encoder.*` loads strictly).  It produces the latent moments and the five
-hidden states that become the decoder's `ref_context`.
+(21-88), Downsample (92-112), Encoder (366-475), Decoder (478-590) -- with the same parameter names
+(`first_stage_model.encoder.*` / `first_stage_model.decoder.*` load strictly).  The Encoder produces the
+latent moments and the five hidden states that become the video decoder's `ref_context`.
 
 Same kernels as the decoder: implicit-GEMM 3x3 convolutions, fused GroupNorm+swish, the
 single-head d=C attention as GEMM -> row softmax -> GEMM.  The stride-2 downsample with the
@@ -19,7 +20,7 @@ import torch.nn as nn
 from .. import ops
 from .autoencoder_dualref import MemoryEfficientAttnBlock, Normalize
 from .common import Act, PackedModule, ceil_to, f32, pack_conv3x3, pack_linear
-from .openaimodel3d import _conv_geom
+from .openaimodel3d import Upsample, _conv_geom
 
 
 class ResnetBlock(PackedModule):
@@ -161,3 +162,74 @@ class Encoder(PackedModule):
             return out
         hs = [ops.rows_to_nchw(a.rows, c=a.c, b=n, t=1, h=a.h, w=a.w)[:, :, 0] for a in hidden]
         return out, hs
+
+
+class Decoder(PackedModule):
+    """The plain per-image decoder (ae_modules.py:478-590): conv_in, mid (ResnetBlock, AttnBlock, ResnetBlock), per level
+    num_res_blocks + 1 ResnetBlocks and a nearest-x2 + 3x3 upsample (folded into the conv's row gather, as in the video
+    decoder), norm_out + swish, conv_out.  Frames are independent: a clip is decoded as B*T images in one call."""
+
+    def __init__(self, *, ch, out_ch, ch_mult=(1, 2, 4, 8), num_res_blocks, attn_resolutions, dropout=0.0,
+                 resamp_with_conv=True, in_channels, resolution, z_channels, give_pre_end=False, tanh_out=False,
+                 use_linear_attn=False, attn_type="vanilla", **ignorekwargs):
+        super().__init__()
+        if attn_resolutions or give_pre_end or tanh_out or use_linear_attn:
+            raise NotImplementedError("Decoder variant unused by the config")
+        self.ch, self.num_resolutions, self.num_res_blocks = ch, len(ch_mult), num_res_blocks
+        self.in_channels, self.resolution, self.z_channels, self.out_ch = in_channels, resolution, z_channels, out_ch
+        block_in = ch * ch_mult[-1]
+        self.conv_in = nn.Conv2d(z_channels, block_in, 3, padding=1)
+        self.mid = _Level()
+        self.mid.block_1 = ResnetBlock(in_channels=block_in, out_channels=block_in, temb_channels=0, dropout=dropout)
+        self.mid.attn_1 = AttnBlock(block_in)
+        self.mid.block_2 = ResnetBlock(in_channels=block_in, out_channels=block_in, temb_channels=0, dropout=dropout)
+        self.up = nn.ModuleList()
+        for i_level in reversed(range(self.num_resolutions)):
+            block = nn.ModuleList()
+            block_out = ch * ch_mult[i_level]
+            for _ in range(num_res_blocks + 1):
+                block.append(ResnetBlock(in_channels=block_in, out_channels=block_out, temb_channels=0, dropout=dropout))
+                block_in = block_out
+            up = _Level()
+            up.block = block
+            up.attn = nn.ModuleList()
+            if i_level != 0:
+                up.upsample = Upsample(block_in, resamp_with_conv)
+            self.up.insert(0, up)
+        self.norm_out = Normalize(block_in)
+        self.conv_out = nn.Conv2d(block_in, out_ch, 3, padding=1)
+
+    def _pack(self):
+        return {"wi": pack_conv3x3(self.conv_in.weight), "bi": f32(self.conv_in.bias),
+                "og": f32(self.norm_out.weight), "ob": f32(self.norm_out.bias),
+                "wo": pack_conv3x3(self.conv_out.weight), "bo": f32(self.conv_out.bias)}
+
+    def decode_rows(self, act: Act) -> torch.Tensor:
+        """act: the conv_in input as bf16 rows, channels padded to 64 -> (N, out_ch, 8h, 8w) fp32."""
+        with ops.fp8_scope("decoder"):         # the first stage (pixels <-> latents) stays bf16 under TC_FP8
+            return self._decode_rows(act)
+
+    def _decode_rows(self, act):
+        pk = self.pk
+        n = act.frames
+        geom, _, _ = _conv_geom(act, act.c)
+        act = act.like(ops.gemm(act.rows, pk["wi"], pk["bi"], conv=geom))
+        act = self.mid.block_1(act)
+        act = self.mid.attn_1(act)
+        act = self.mid.block_2(act)
+        for lvl in reversed(range(self.num_resolutions)):
+            for blk in self.up[lvl].block:
+                act = blk(act)
+            if lvl != 0:
+                act = self.up[lvl].upsample(act)
+        hrows = ops.groupnorm(act.rows, pk["og"], pk["ob"], samples=act.frames, rows=act.hw, eps=1e-6, silu=True)
+        geom, _, _ = _conv_geom(act, act.c)
+        y = ops.gemm(hrows, pk["wo"], pk["bo"], conv=geom, out_f32=True)                    # [N*H*W, out_ch] fp32
+        return ops.rows_to_nchw(y, c=self.out_ch, b=n, t=1, h=act.h, w=act.w)[:, :, 0]
+
+    def forward(self, z):
+        """Reference call shape: (N, z_channels, h, w) -> (N, out_ch, 8h, 8w)."""
+        n, zc, h, w = z.shape
+        cpad = ceil_to(zc, 64)
+        rows = ops.nchw_to_rows(z.float().reshape(n, zc, 1, h, w), c_pad=cpad)
+        return self.decode_rows(Act(rows, n, 1, h, w))

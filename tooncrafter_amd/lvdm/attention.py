@@ -150,8 +150,6 @@ class CrossAttention(PackedModule):
             raise NotImplementedError("HIP attention kernels are specialised for head dim 64")
         if relative_position:
             raise NotImplementedError("relative position is unused by inference_512_v1.0.yaml")
-        if image_cross_attention_scale_learnable:
-            raise NotImplementedError("learnable image cross-attention scale is unused by the config")
         inner = dim_head * heads
         self.is_self = context_dim is None
         context_dim = query_dim if context_dim is None else context_dim
@@ -165,9 +163,26 @@ class CrossAttention(PackedModule):
         self.image_cross_attention = image_cross_attention
         self.image_cross_attention_scale = image_cross_attention_scale
         self.text_context_len = text_context_len
+        self.image_cross_attention_scale_learnable = image_cross_attention_scale_learnable
         if image_cross_attention:
             self.to_k_ip = nn.Linear(context_dim, inner, bias=False)
             self.to_v_ip = nn.Linear(context_dim, inner, bias=False)
+            if image_cross_attention_scale_learnable:
+                self.register_parameter('alpha', nn.Parameter(torch.tensor(0.)))
+
+    def _ip_stamp(self):
+        """What the image-branch factor was made from: the scale attribute and, when learnable, `alpha` (object, version)."""
+        a = getattr(self, "alpha", None) if self.image_cross_attention_scale_learnable else None
+        return (float(self.image_cross_attention_scale), None if a is None else (id(a), a._version, a.device))
+
+    def ip_factor(self) -> float:
+        """The weight of the image-token attention in the sum (attention.py:138-142, 203-207):
+        image_cross_attention_scale * (tanh(alpha) + 1) with a learnable alpha, image_cross_attention_scale without;
+        formed in fp32 like the reference's tensor expression."""
+        s = torch.tensor(float(self.image_cross_attention_scale), dtype=torch.float32)
+        if self.image_cross_attention_scale_learnable:
+            s = s * (torch.tanh(self.alpha.detach().to(device="cpu", dtype=torch.float32)) + 1)
+        return float(s)
 
     def _pack(self):
         pk = {"wo": pack_linear(self.to_out[0].weight), "bo": f32(self.to_out[0].bias)}
@@ -177,7 +192,22 @@ class CrossAttention(PackedModule):
             pk["wq"] = pack_linear(self.to_q.weight)
             pk["wkv"] = pack_linear(torch.cat([self.to_k.weight, self.to_v.weight], 0))
             if self.image_cross_attention:
-                pk["wkv_ip"] = pack_linear(torch.cat([self.to_k_ip.weight, self.to_v_ip.weight], 0))
+                # softmax(q k2^T) (s v2) = s softmax(q k2^T) v2: the factor of the image branch is folded, in fp32, into the
+                # V rows of the packed projection -- the attention kernel and its struct know nothing of it.  s == 1 (the
+                # ToonCrafter config; alpha == 0) leaves the weights as they are, bit for bit.
+                s = self.ip_factor()
+                wv = self.to_v_ip.weight if s == 1.0 else self.to_v_ip.weight.detach().float() * s
+                pk["wkv_ip"] = pack_linear(torch.cat([self.to_k_ip.weight.detach().float(), wv.detach().float()], 0))
+                pk["ip_stamp"] = self._ip_stamp()
+        return pk
+
+    def _fresh_pk(self):
+        """The packed dict, rebuilt first if `alpha` or the scale attribute changed since it was made (weights are
+        covered by PackedModule: load_state_dict / .to() / invalidate())."""
+        pk = self.pk
+        if pk.get("ip_stamp", None) is not None and pk["ip_stamp"] != self._ip_stamp():
+            self.invalidate()
+            pk = self.pk
         return pk
 
     # -- self attention over the H*W tokens of each frame
@@ -215,7 +245,7 @@ class CrossAttention(PackedModule):
 
     # -- text + image cross attention: two softmaxes, summed
     def project_context(self, ctx: ContextCache, kv_text=None, kv_img=None):
-        pk = self.pk
+        pk = self._fresh_pk()
         kv_text = ops.gemm(ctx.text_rows, pk["wkv"], out=kv_text)
         if self.image_cross_attention and ctx.img_rows is not None:
             kv_img = ops.gemm(ctx.img_rows, pk["wkv_ip"], out=kv_img)
@@ -224,6 +254,11 @@ class CrossAttention(PackedModule):
     def context_kv(self, ctx):
         root = getattr(ctx, "parent", ctx)                      # a CtxBranch reads row slices of its parent's K/V
         hit = root.kv.get(id(self))
+        pk = self._pk
+        if hit is not None and pk is not None and pk.get("ip_stamp") is not None and pk["ip_stamp"] != self._ip_stamp():
+            # `alpha` or the scale attribute changed in place since the image K/V were projected: repack (the epoch bump
+            # makes captured graphs and every other cached projection stale too) and project again into the same buffers
+            self.project_context(root, hit[1], hit[2])
         if hit is None:
             kv_text, kv_img = self.project_context(root)
             hit = root.kv[id(self)] = (self, kv_text, kv_img)
@@ -235,8 +270,6 @@ class CrossAttention(PackedModule):
         pk = self.pk
         c = self.heads * 64
         kv_text, kv_img = self.context_kv(ctx)
-        if kv_img is not None and self.image_cross_attention_scale != 1.0:
-            raise NotImplementedError("image_cross_attention_scale != 1.0")
         q = ops.gemm(x_norm, pk["wq"]) if ln is None else ops.gemm(x_norm, ln[0], ln[1], a_norm_eps=ln[2])
         if kv_img is not None:
             # text and image softmaxes in ONE launch (attention.py:153-207 runs two attentions and adds them): Q is read

@@ -3,16 +3,18 @@ AutoencoderKL.encode (100-110) / .decode (112-116) and AutoencoderKL_Dualref (23
 the posterior object of lvdm/distributions.py:24-65.
 
 decode is on the hot path `north_star` names; encode runs once per clip
-before the loop and shares the decoder's kernels.
+before the loop and shares the decoder's kernels.  AutoencoderKL (14-116) is the first stage of the DynamiCrafter-family
+configurations (configs/training_512_v1.0, training_1024_v1.0): the same encoder, post_quant_conv and the plain
+per-image Decoder; AutoencoderKL_Dualref swaps the decoder for the dual-reference VideoDecoder, as in the reference.
 """
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
 
-from .ae_modules import Encoder
+from .ae_modules import Decoder, Encoder
 from .autoencoder_dualref import VideoDecoder
-from .common import f32, pack_conv3x3
+from .common import BF16, Act, ceil_to, f32, pack_conv3x3
 
 
 class DiagonalGaussianDistribution(object):
@@ -37,7 +39,9 @@ class DiagonalGaussianDistribution(object):
         return self.mean
 
 
-class AutoencoderKL_Dualref(nn.Module):
+class AutoencoderKL(nn.Module):
+    decoder_cls = Decoder
+
     def __init__(self, ddconfig, lossconfig=None, embed_dim=4, ckpt_path=None, ignore_keys=[], image_key="image",
                  colorize_nlabels=None, monitor=None, test=False, logdir=None, input_dim=4, test_args=None,
                  additional_decode_keys=None, use_checkpoint=False, diff_boost_factor=3.0):
@@ -47,7 +51,7 @@ class AutoencoderKL_Dualref(nn.Module):
         self.embed_dim = embed_dim
         self.image_key = image_key
         self.encoder = Encoder(**dd)
-        self.decoder = VideoDecoder(**dd)
+        self.decoder = self.decoder_cls(**dd)
         # 1x1 convs of the KL autoencoder; post_quant_conv is bypassed by the video decode path
         # (autoencoder.py:113-114) but is part of the checkpoint.
         self.quant_conv = nn.Conv2d(2 * dd["z_channels"], 2 * embed_dim, 1)
@@ -55,13 +59,14 @@ class AutoencoderKL_Dualref(nn.Module):
         if monitor is not None:
             self.monitor = monitor
         self._quant_pack = None
+        self._post_quant_pack = None
 
     @property
     def device(self):
         return next(self.parameters()).device
 
     def _apply(self, fn, recurse=True):
-        self._quant_pack = None
+        self._quant_pack = self._post_quant_pack = None
         return super()._apply(fn, recurse)
 
     def _fused_out_conv(self):
@@ -91,6 +96,45 @@ class AutoencoderKL_Dualref(nn.Module):
             return posterior
         hs = [ops.rows_to_nchw(a.rows, c=a.c, b=n, t=1, h=a.h, w=a.w)[:, :, 0] for a in hidden]
         return posterior, hs
+
+    def _post_quant(self):
+        """post_quant_conv (1x1, embed_dim -> z_channels) as its own GEMM on the 64-column rows conv_in reads: weight and
+        bias zero-padded to 64 x 64, so the columns behind z_channels come out as exact zeros.  NOT composed into conv_in
+        the way quant_conv is composed above: conv_in zero-pads AFTER the 1x1, so the 1x1's bias does not reach the
+        border taps and the composed convolution would be wrong on the image edge."""
+        wt, bs = self.post_quant_conv.weight, self.post_quant_conv.bias
+        key = (wt._version, bs._version, wt.device)
+        if self._post_quant_pack is None or self._post_quant_pack[0] != key:
+            with torch.no_grad():
+                zc, ed = wt.shape[:2]
+                w = torch.zeros((ceil_to(zc, 64), ceil_to(ed, 64)), dtype=BF16, device=wt.device)
+                w[:zc, :ed] = wt[:, :, 0, 0].to(BF16)
+                b = torch.zeros((w.shape[0],), dtype=torch.float32, device=wt.device)
+                b[:zc] = bs.float()
+                self._post_quant_pack = (key, w, b)
+        return self._post_quant_pack[1], self._post_quant_pack[2]
+
+    def decode_images(self, z, scale=1.0):
+        """z: (N, embed_dim, h, w) fp32 -> (N, 3, 8h, 8w) fp32; `scale` multiplies z on the way in (decode_core's
+        1 / scale_factor)."""
+        from .. import ops
+        n, c, h, w = z.shape
+        with ops.fp8_scope("decoder"):
+            wp, bp = self._post_quant()
+            rows = ops.nchw_to_rows(z.float().reshape(n, c, 1, h, w), c_pad=wp.shape[1], scale=scale)
+            act = Act(ops.gemm(rows, wp, bp), n, 1, h, w)
+        return self.decoder.decode_rows(act)
+
+    def decode(self, z, **kwargs):
+        """z: (N, embed_dim, h, w), already divided by scale_factor: post_quant_conv, then the plain decoder
+        (autoencoder.py:112-116).  The plain Decoder takes no decode kwargs (the reference's fails on them)."""
+        if kwargs:
+            raise TypeError(f"{type(self.decoder).__name__}.forward() takes no decode kwargs, got {sorted(kwargs)}")
+        return self.decode_images(z)
+
+
+class AutoencoderKL_Dualref(AutoencoderKL):
+    decoder_cls = VideoDecoder
 
     def decode(self, z, **kwargs):
         """z: (B*T, zc, h, w) already divided by scale_factor.  With kwargs (ref_context,

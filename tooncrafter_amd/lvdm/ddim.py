@@ -8,7 +8,8 @@ funcs.py:61-76 call it unchanged.
 
 What is different underneath:
   * the per-step algebra (CFG combine, guidance rescale with its two unbiased
-    stds, v -> eps/x0, dynamic rescale, x_prev) is ONE fused kernel (tc_ddim_step);
+    stds, v -> eps/x0, dynamic rescale, x_prev) is ONE fused kernel (tc_ddim_step; tc_ddim_step_eps
+    for a model with parameterization "eps", ddim.py:234, 258);
   * its six scalars per step are computed on the host from the schedule tables in the
     reference's exact order/precision, so the loop has no device->host sync (the
     reference reads six device scalars per step, ddim.py:251-264);
@@ -82,6 +83,14 @@ class DDIMSampler(object):
         self._sqrt_ac = m.sqrt_alphas_cumprod.detach().to(torch.float32).cpu()
         self._sqrt_1m_ac = m.sqrt_one_minus_alphas_cumprod.detach().to(torch.float32).cpu()
 
+    def step_kind(self):
+        """What the model predicts, as the fused step takes it: "v" (tc_ddim_step) or "eps" (tc_ddim_step_eps).  The
+        reference's samplers treat "x0" as eps (ddim.py:231-234); that is not reproduced."""
+        par = self.model.parameterization
+        if par not in ("v", "eps"):
+            raise NotImplementedError(f"the fused DDIM step implements the v- and eps-parameterisations, not {par!r}")
+        return par
+
     def step_scalars(self, index: int, t: int):
         """The fp32 scalars of one update, each rounded exactly where the reference's
         `torch.full(size, value)` rounds it (ddim.py:251-266, 271, 277)."""
@@ -92,9 +101,15 @@ class DDIMSampler(object):
         x0_rescale = f32(1.0)
         if self.model.use_dynamic_rescale:
             x0_rescale = self.ddim_scale_arr_prev[index] / self.ddim_scale_arr[index]
-        return dict(sqrt_ac=float(self._sqrt_ac[t]), sqrt_1m_ac=float(self._sqrt_1m_ac[t]),
-                    sqrt_a_prev=float(a_prev.sqrt()), dir_coef=float(dir_coef), sigma=float(sigma),
-                    x0_rescale=float(x0_rescale))
+        sc = dict(sqrt_ac=float(self._sqrt_ac[t]), sqrt_1m_ac=float(self._sqrt_1m_ac[t]),
+                  sqrt_a_prev=float(a_prev.sqrt()), dir_coef=float(dir_coef), sigma=float(sigma),
+                  x0_rescale=float(x0_rescale))
+        if self.model.parameterization != "v":
+            # the eps branch reads the DDIM tables, not the model's per-timestep buffers: a_t = ddim_alphas[index] with an
+            # fp32 sqrt, and ddim_sqrt_one_minus_alphas[index] (ddim.py:251-258).  The "v" call carries no extra keyword.
+            sc.update(sqrt_ac=float(f32(self.ddim_alphas[index]).sqrt()),
+                      sqrt_1m_ac=float(f32(self.ddim_sqrt_one_minus_alphas[index])), parameterization=self.step_kind())
+        return sc
 
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None,
@@ -185,8 +200,7 @@ class DDIMSampler(object):
                       guidance_rescale=0.0, _step=None, **kwargs):
         if use_original_steps or quantize_denoised or score_corrector is not None or noise_dropout > 0.:
             raise NotImplementedError("p_sample_ddim variant unused by the inference scripts")
-        if self.model.parameterization != "v":
-            raise NotImplementedError("the fused DDIM step implements the v-parameterisation of the config")
+        self.step_kind()
         step = int(t[0]) if _step is None else _step
         use_cfg = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.)
         if not use_cfg:

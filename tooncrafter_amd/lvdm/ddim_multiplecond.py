@@ -33,8 +33,7 @@ class DDIMSampler(_DDIMSampler):
                       uc_type=None, cfg_img=None, mask=None, x0=None, guidance_rescale=0.0, _step=None, **kwargs):
         if use_original_steps or quantize_denoised or score_corrector is not None or noise_dropout > 0.:
             raise NotImplementedError("p_sample_ddim variant unused by the inference scripts")
-        if self.model.parameterization != "v":
-            raise NotImplementedError("the fused DDIM step implements the v-parameterisation of the config")
+        self.step_kind()
         if cfg_img is None:
             cfg_img = unconditional_guidance_scale                                  # :217-218
         uc_img = kwargs['unconditional_conditioning_img_nonetext']                   # :220 (KeyError like the reference)

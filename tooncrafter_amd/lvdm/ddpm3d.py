@@ -170,7 +170,10 @@ class LatentDiffusion(DDPM):
         self.noise_strength = noise_strength
         self.use_dynamic_rescale = use_dynamic_rescale
         self.loop_video = loop_video
+        # read only by the training batch builder of the reference (ddpm3d.py:1098, 1124-1127): kept as attributes, nothing
+        # on the inference path depends on them ('fs' and 'fps' models take the same `fs` tensor at sampling time)
         self.fps_condition_type = fps_condition_type
+        self.rand_cond_frame = rand_cond_frame
         self.perframe_ae = perframe_ae
         self.en_and_decode_n_samples_a_time = en_and_decode_n_samples_a_time
         if scale_by_std:
@@ -333,22 +336,25 @@ class LatentDiffusion(DDPM):
         """z: (B, C, T, h, w) latent.  The whole clip batch goes through ONE decoder call with
         timesteps=T (the only geometry in which the dual-reference fusion is well defined for
         B > 1); for B == 1 this is exactly what the reference's
-        `perframe_ae=True` loop computes."""
+        `perframe_ae=True` loop computes.
+
+        A plain first stage (autoencoder.AutoencoderKL, the DynamiCrafter-family configurations) decodes images: a 5-D
+        latent goes through as its B*T frames, a 4-D (N, C, h, w) latent as it is, and the decode kwargs are ignored as
+        the reference's `perframe_ae=True` branch ignores them for a non-video decoder (ddpm3d.py:666-669).  All frames
+        share one call whatever `perframe_ae` says: the frames are independent, so the result is the same tensor."""
+        from .ae_modules import Decoder as PlainDecoder
+        dec = self.first_stage_model.decoder
+        scale = 1.0 / float(self.scale_factor)
+        if isinstance(dec, PlainDecoder):
+            return self._decode_plain(z, scale)
         if z.dim() != 5:
             raise NotImplementedError("decode_first_stage expects a (B, C, T, h, w) video latent")
         ref_context = kwargs.get("ref_context")
-        dec = self.first_stage_model.decoder
-        scale = 1.0 / float(self.scale_factor)
         # B * T frames share every launch (BASELINE configs[3], the call the reference dies on at ddpm3d.py:656-657).
         # The GEMM kernels address activations block-relatively (csrc/gemm_common.h: tc_tile_row_lo), so a tensor may
         # exceed 2 GiB (level 0 of two 320x512 clips: 2.7 GB); what stays 32-bit is the ROW count of a launch.
         b, _, t, h, w = z.shape
-        bmax = max(1, int(0x7fffffff // max(t * (8 * h) * (8 * w), 1)))
-        be = ops.backend()
-        if getattr(be, "fp8", None) is not None and getattr(be, "fp8_decoder", False):
-            # the MXFP8 GEMM still addresses A from the tensor base (csrc/gemm_mx.hip): with TC_FP8_DECODER=1 no
-            # activation may exceed the 31-bit byte range -- the widest one is 128 channels at full resolution
-            bmax = max(1, min(bmax, int(0x7fffff00 // max(t * (8 * h) * (8 * w) * 128 * 2, 1))))
+        bmax = self._decode_batch_max(t, h, w)
         if b <= bmax:
             return dec.decode_clip(z, ref_context, scale=scale)
         outs = []
@@ -356,6 +362,35 @@ class LatentDiffusion(DDPM):
             refs = None if not ref_context else [r[i:i + bmax].contiguous() for r in ref_context]
             outs.append(dec.decode_clip(z[i:i + bmax].contiguous(), refs, scale=scale))
         return torch.cat(outs, 0)
+
+    @staticmethod
+    def _decode_batch_max(t, h, w):
+        """How many clips of t frames of an (h, w) latent one decoder call takes: the row count of a launch is 32-bit."""
+        bmax = max(1, int(0x7fffffff // max(t * (8 * h) * (8 * w), 1)))
+        be = ops.backend()
+        if getattr(be, "fp8", None) is not None and getattr(be, "fp8_decoder", False):
+            # the MXFP8 GEMM still addresses A from the tensor base (csrc/gemm_mx.hip): with TC_FP8_DECODER=1 no
+            # activation may exceed the 31-bit byte range -- the widest one is 128 channels at full resolution
+            bmax = max(1, min(bmax, int(0x7fffff00 // max(t * (8 * h) * (8 * w) * 128 * 2, 1))))
+        return bmax
+
+    def _decode_plain(self, z, scale):
+        """Image decode of a plain first stage: eager (the hipGraph capture of VideoDecoder.decode_clip is built around
+        its reference context and is not shared), under the same row-count chunking as the video decode."""
+        if z.dim() not in (4, 5):
+            raise NotImplementedError("decode_first_stage expects a (B, C, T, h, w) or an (N, C, h, w) latent")
+        frames = z
+        if z.dim() == 5:
+            b, c, t, h, w = z.shape
+            frames = z.permute(0, 2, 1, 3, 4).reshape(b * t, c, h, w)
+        n, _, h, w = frames.shape
+        nmax = self._decode_batch_max(1, h, w)
+        ae = self.first_stage_model
+        outs = [ae.decode_images(frames[i:i + nmax].contiguous(), scale=scale) for i in range(0, n, nmax)]
+        out = outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+        if z.dim() == 5:
+            out = out.reshape(b, t, *out.shape[1:]).permute(0, 2, 1, 3, 4).contiguous()
+        return out
 
 
 class LatentVisualDiffusion(LatentDiffusion):

@@ -744,9 +744,13 @@ class HipOps:
         return out
 
     def ddim_step(self, x, e_cond, e_uncond, noise, *, cfg_scale, guidance_rescale, sqrt_ac, sqrt_1m_ac,
-                  sqrt_a_prev, dir_coef, sigma, x0_rescale, want_x0=True, e_uncond_img=None, cfg_img=None):
+                  sqrt_a_prev, dir_coef, sigma, x0_rescale, want_x0=True, e_uncond_img=None, cfg_img=None,
+                  parameterization="v"):
         """One fused DDIM update.  With `e_uncond_img` the guidance is the three-way form of
-        ddim_multiplecond.py:236 (cfg_img defaults to cfg_scale like the reference)."""
+        ddim_multiplecond.py:236 (cfg_img defaults to cfg_scale like the reference).  `parameterization` says what the
+        model predicts: "v" (tc_ddim_step) or "eps" (tc_ddim_step_eps, ddim.py:234, 258)."""
+        if parameterization not in ("v", "eps"):
+            raise NotImplementedError(f"ddim_step: parameterization {parameterization!r} (the fused step has 'v' and 'eps')")
         for tns in (x, e_cond, e_uncond, noise, e_uncond_img):
             if tns is not None and (tns.dtype != torch.float32 or not tns.is_contiguous() or not tns.is_cuda):
                 raise ValueError("ddim_step: contiguous fp32 CUDA tensors")
@@ -765,7 +769,10 @@ class HipOps:
         p.cfg_img = float(cfg_scale if cfg_img is None else cfg_img)
         nbytes = self.lib.tc_ddim_workspace(b)
         ws = self._workspace(nbytes, x.device)
-        _lib.check(self.lib.tc_ddim_step(C.byref(p), ws.data_ptr(), nbytes, _stream()), "tc_ddim_step")
+        if parameterization == "v":
+            _lib.check(self.lib.tc_ddim_step(C.byref(p), ws.data_ptr(), nbytes, _stream()), "tc_ddim_step")
+        else:
+            _lib.check(self.lib.tc_ddim_step_eps(C.byref(p), ws.data_ptr(), nbytes, _stream()), "tc_ddim_step_eps")
         return x_prev, x0
 
     def ddim_blend(self, x, x0, noise, mask, *, sqrt_ac=1.0, sqrt_1m_ac=0.0, out=None):

@@ -119,10 +119,13 @@ class TorchLibOps(HipOps):
         return self.t.layernorm(x, gamma, beta, float(eps))
 
     def ddim_step(self, x, e_cond, e_uncond, noise, *, cfg_scale, guidance_rescale, sqrt_ac, sqrt_1m_ac, sqrt_a_prev,
-                  dir_coef, sigma, x0_rescale, want_x0=True, e_uncond_img=None, cfg_img=None):
-        xp, x0 = self.t.ddim_step(x, e_cond, e_uncond, noise, e_uncond_img, float(cfg_scale),
-                                  float(cfg_scale if cfg_img is None else cfg_img), float(guidance_rescale), float(sqrt_ac),
-                                  float(sqrt_1m_ac), float(sqrt_a_prev), float(dir_coef), float(sigma), float(x0_rescale))
+                  dir_coef, sigma, x0_rescale, want_x0=True, e_uncond_img=None, cfg_img=None, parameterization="v"):
+        if parameterization not in ("v", "eps"):
+            raise NotImplementedError(f"ddim_step: parameterization {parameterization!r} (the fused step has 'v' and 'eps')")
+        op = self.t.ddim_step if parameterization == "v" else self.t.ddim_step_eps
+        xp, x0 = op(x, e_cond, e_uncond, noise, e_uncond_img, float(cfg_scale),
+                    float(cfg_scale if cfg_img is None else cfg_img), float(guidance_rescale), float(sqrt_ac),
+                    float(sqrt_1m_ac), float(sqrt_a_prev), float(dir_coef), float(sigma), float(x0_rescale))
         return xp, (x0 if want_x0 else None)
 
     def ddim_blend(self, x, x0, noise, mask, *, sqrt_ac=1.0, sqrt_1m_ac=0.0, out=None):
