@@ -268,6 +268,29 @@ int tc_attn_d64_q8(const TcAttnQ8Params* p, void* stream);
 int tc_attn_temporal(const tc_bf16* qkv, tc_bf16* out, int32_t b, int32_t t, int32_t hw,
                      int32_t heads, float scale, void* stream);
 
+/* The same attention with relative position and / or a causal mask (attention.py:20-39 RelativePosition, 103-124 the
+ * two extra einsums and the mask in CrossAttention.forward, 343-345 / 376-390 the tril mask of TemporalTransformer:
+ * use_relative_position / use_causal_attention of the UNet).  Per pixel and head, over the t frames:
+ *     idx(i, j) = clamp(j - i, -max_rel, max_rel) + max_rel
+ *     s[i, j]   = scale * (q_i . k_j + q_i . rel_k[idx(i, j)]),  -inf for j > i when causal
+ *     o_i       = sum_j softmax_j(s[i, :])[j] * (v_j + rel_v[idx(i, j)])
+ * qkv / out as tc_attn_temporal.  rel_k, rel_v: [2*max_rel + 1, 64] bf16 each, shared by every head, 16-byte aligned; both
+ * NULL = mask only (max_rel is then ignored), exactly one NULL: TC_EINVAL.  1 <= t <= TC_TEMPORAL_MAX_FRAMES and, with
+ * tables, 1 <= max_rel <= TC_TEMPORAL_MAX_FRAMES, else TC_ESHAPE: nothing launched, nothing written.  t may exceed
+ * max_rel (distances clamp); the reference's causal mask is [max_rel, max_rel], so causal with t > max_rel has no
+ * counterpart there and is the caller's to refuse.  One MFMA kernel for every t (csrc/attention_temporal_rel.hip), bf16
+ * softmax weights and per-distance sums; with no tables and causal == 0 it is tc_attn_temporal's long-clip arithmetic.
+ * No allocation, no synchronisation, safe under hipGraph capture.  Additive within ABI 14. */
+typedef struct TcAttnTemporalRelParams {
+  const tc_bf16* qkv;
+  tc_bf16* out;
+  const tc_bf16* rel_k;
+  const tc_bf16* rel_v;
+  int32_t b, t, hw, heads, max_rel, causal;
+  float scale;
+} TcAttnTemporalRelParams;
+int tc_attn_temporal_rel(const TcAttnTemporalRelParams* p, void* stream);
+
 /* GroupNorm(32 groups) over channels-last rows, fp32 statistics, optional fused SiLU.
  * x: [samples, rows, C]; statistics over (rows, C/32) per (sample, group): samples = B*T,
  * rows = H*W for the per-frame norms; samples = B, rows = T*H*W for the clip-wide ones.

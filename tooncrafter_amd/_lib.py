@@ -117,6 +117,16 @@ class TcTqaParams(C.Structure):
     ]
 
 
+class TcAttnTemporalRelParams(C.Structure):
+    """Temporal attention with relative position / a causal mask (tc_attn_temporal_rel; additive within ABI 14)."""
+    _fields_ = [
+        ("qkv", C.c_void_p), ("out", C.c_void_p), ("rel_k", C.c_void_p), ("rel_v", C.c_void_p),
+        ("b", C.c_int32), ("t", C.c_int32), ("hw", C.c_int32), ("heads", C.c_int32), ("max_rel", C.c_int32),
+        ("causal", C.c_int32),
+        ("scale", C.c_float),
+    ]
+
+
 TC_PREFETCH_MAX = 4
 
 
@@ -140,6 +150,7 @@ SYMBOLS = {
     "tc_attn_d64_q8": (C.c_int, [C.POINTER(TcAttnQ8Params), C.c_void_p]),
     "tc_attn_temporal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                    C.c_float, C.c_void_p]),
+    "tc_attn_temporal_rel": (C.c_int, [C.POINTER(TcAttnTemporalRelParams), C.c_void_p]),
     "tc_groupnorm_workspace": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "tc_groupnorm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                C.c_float, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),

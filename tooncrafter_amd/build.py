@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libtooncrafter_hip.so")
-SOURCES = ["gemm_route.cpp", "gemm.hip", "gemm_wide.hip", "gemm16.hip", "conv_halo.hip", "gemm8.hip", "ff_fused.hip", "tb_fused.hip", "qkv_attn.hip", "qkv_attn_long.hip", "gemm_ws.hip", "gemm_mx.hip", "attention.hip", "attention_temporal_long.hip", "attention_q8.hip", "norm.hip", "elementwise.hip"]
+SOURCES = ["gemm_route.cpp", "gemm.hip", "gemm_wide.hip", "gemm16.hip", "conv_halo.hip", "gemm8.hip", "ff_fused.hip", "tb_fused.hip", "qkv_attn.hip", "qkv_attn_long.hip", "gemm_ws.hip", "gemm_mx.hip", "attention.hip", "attention_temporal_long.hip", "attention_temporal_rel.hip", "attention_q8.hip", "norm.hip", "elementwise.hip"]
 # every header of csrc/ (sorted) plus the public one: a new header cannot be left out of the source digest
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(ROOT, "include", "tooncrafter_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on",
@@ -27,7 +27,8 @@ if os.environ.get("TC_TIMING_BUILDS") == "1":       # the timing-ablation / inte
 # hipcc parks the score / output accumulators in AGPRs and the in-register softmax then pays 224 v_accvgpr_read/write
 # moves per 64-key tile
 EXTRA_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "attention_q8.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
-               "attention_temporal_long.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
+               "attention_temporal_long.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+               "attention_temporal_rel.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 
 
 def _hipcc() -> str:

@@ -2,7 +2,7 @@
 //
 // The reference binds ATen / xformers operators from Python (utils/utils.py:27-42 instantiates lvdm classes whose
 // forward methods call torch ops); this registers the MI355X kernels as first-class torch operators instead:
-//   torch.ops.tooncrafter.gemm / quant_mxfp8 / gemm_mx / attention / attention_temporal / groupnorm(_pf) / layernorm(_pf) / ddim_step(_eps) / ddim_blend /
+//   torch.ops.tooncrafter.gemm / quant_mxfp8 / gemm_mx / attention / attention_temporal(_rel) / groupnorm(_pf) / layernorm(_pf) / ddim_step(_eps) / ddim_blend /
 //   ff_geglu_fused / temporal_attn_fused / temporal_qkv_attn / attention_q8
 // with (i) a CUDA(HIP)-key implementation that validates the tensors, allocates the result from the caching allocator,
 // picks up the CURRENT stream and calls the same extern "C" entry point the ctypes binding calls, and (ii) a Meta-key
@@ -235,6 +235,37 @@ Tensor attention_temporal_meta(const Tensor& qkv, int64_t b, int64_t t, int64_t 
   return at::empty({b * t * hw, heads * 64}, qkv.options());
 }
 
+// tc_attn_temporal_rel: relative position and / or a causal mask on the temporal attention (reference attention.py:20-39,
+// 103-124, 343-345, 376-390).  rel_k / rel_v: [2*max_rel + 1, 64] bf16, or both absent.
+Tensor attention_temporal_rel_cuda(const Tensor& qkv, const optional<Tensor>& rel_k, const optional<Tensor>& rel_v, int64_t b,
+                                   int64_t t, int64_t hw, int64_t heads, int64_t max_rel, bool causal, double scale) {
+  check_rows(qkv, "attention_temporal_rel: qkv");
+  TORCH_CHECK(qkv.is_contiguous() && qkv.size(0) == b * t * hw && qkv.size(1) == 3 * heads * 64,
+              "attention_temporal_rel: qkv must be contiguous [b*t*hw, 3*heads*64]");
+  for (const optional<Tensor>* tab : {&rel_k, &rel_v})
+    if (tab->has_value()) {
+      check_rows(**tab, "attention_temporal_rel: table");
+      TORCH_CHECK((*tab)->is_contiguous() && (*tab)->size(0) == 2 * max_rel + 1 && (*tab)->size(1) == 64,
+                  "attention_temporal_rel: a table must be contiguous [2*max_rel + 1, 64]");
+    }
+  Tensor out = at::empty({b * t * hw, heads * 64}, qkv.options());
+  TcAttnTemporalRelParams p{};
+  p.qkv = bf(qkv);
+  p.out = reinterpret_cast<tc_bf16*>(out.data_ptr());
+  p.rel_k = rel_k.has_value() ? bf(*rel_k) : nullptr;
+  p.rel_v = rel_v.has_value() ? bf(*rel_v) : nullptr;
+  p.b = (int32_t)b; p.t = (int32_t)t; p.hw = (int32_t)hw; p.heads = (int32_t)heads;
+  p.max_rel = (int32_t)max_rel; p.causal = causal ? 1 : 0;
+  p.scale = (float)scale;
+  check_rc(tc_attn_temporal_rel(&p, cur_stream()), "tc_attn_temporal_rel");
+  return out;
+}
+
+Tensor attention_temporal_rel_meta(const Tensor& qkv, const optional<Tensor>&, const optional<Tensor>&, int64_t b, int64_t t,
+                                   int64_t hw, int64_t heads, int64_t, bool, double) {
+  return at::empty({b * t * hw, heads * 64}, qkv.options());
+}
+
 void check_affine(const Tensor& g, const Tensor& b, int64_t c, const char* what) {
   TORCH_CHECK(g.is_cuda() && b.is_cuda() && g.scalar_type() == at::kFloat && b.scalar_type() == at::kFloat &&
               g.is_contiguous() && b.is_contiguous() && g.numel() == c && b.numel() == c, what, ": gamma / beta must be contiguous fp32 CUDA [C]");
@@ -457,6 +488,8 @@ TORCH_LIBRARY(tooncrafter, m) {
   m.def("attention(Tensor q, Tensor k, Tensor v, int batch, int heads, int lq, int lk, int kv_bdiv, float scale, "
         "Tensor? k2, Tensor? v2, int lk2, int kv2_bdiv) -> Tensor");
   m.def("attention_temporal(Tensor qkv, int b, int t, int hw, int heads, float scale) -> Tensor");
+  m.def("attention_temporal_rel(Tensor qkv, Tensor? rel_k, Tensor? rel_v, int b, int t, int hw, int heads, int max_rel, "
+        "bool causal, float scale) -> Tensor");
   m.def("attention_q8(Tensor q, Tensor k, Tensor v, int batch, int heads, int lq, int lk, float scale) -> Tensor");
   m.def("groupnorm(Tensor x, Tensor gamma, Tensor beta, int samples, int rows, float eps, bool silu) -> Tensor");
   m.def("ff_geglu_fused(Tensor x, Tensor w1, Tensor b1, Tensor w2, Tensor b2, float ln_eps) -> Tensor");
@@ -481,6 +514,7 @@ TORCH_LIBRARY_IMPL(tooncrafter, CUDA, m) {
   m.impl("gemm_mx", gemm_mx_cuda);
   m.impl("attention", attention_cuda);
   m.impl("attention_temporal", attention_temporal_cuda);
+  m.impl("attention_temporal_rel", attention_temporal_rel_cuda);
   m.impl("attention_q8", attention_q8_cuda);
   m.impl("groupnorm", groupnorm_cuda);
   m.impl("layernorm", layernorm_cuda);
@@ -500,6 +534,7 @@ TORCH_LIBRARY_IMPL(tooncrafter, Meta, m) {
   m.impl("gemm_mx", gemm_mx_meta);
   m.impl("attention", attention_meta);
   m.impl("attention_temporal", attention_temporal_meta);
+  m.impl("attention_temporal_rel", attention_temporal_rel_meta);
   m.impl("attention_q8", attention_q8_meta);
   m.impl("groupnorm", like_meta3);
   m.impl("layernorm", like_meta_ln);

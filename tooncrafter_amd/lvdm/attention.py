@@ -18,6 +18,8 @@ Differences in HOW (not what) is computed:
 """
 from __future__ import annotations
 
+from functools import partial
+
 import torch
 import torch.nn as nn
 
@@ -140,6 +142,20 @@ class FeedForward(PackedModule):
         return ops.gemm(g, pk["w2"], pk["b2"], residual=residual)
 
 
+class RelativePosition(nn.Module):
+    """The learned per-distance table of a relative temporal attention (reference attention.py:20-39): row
+    clamp(j - i, -max, max) + max is what key j adds for query i.  Only the parameter lives here; the lookup happens inside
+    tc_attn_temporal_rel, per distance, and the [len_q, len_k, num_units] tensor the reference's forward gathers is never
+    formed."""
+
+    def __init__(self, num_units, max_relative_position):
+        super().__init__()
+        self.num_units = num_units
+        self.max_relative_position = max_relative_position
+        self.embeddings_table = nn.Parameter(torch.empty(max_relative_position * 2 + 1, num_units))
+        nn.init.xavier_uniform_(self.embeddings_table)
+
+
 class CrossAttention(PackedModule):
     def __init__(self, query_dim, context_dim=None, heads=8, dim_head=64, dropout=0.,
                  relative_position=False, temporal_length=None, video_length=None,
@@ -148,8 +164,6 @@ class CrossAttention(PackedModule):
         super().__init__()
         if dim_head != 64:
             raise NotImplementedError("HIP attention kernels are specialised for head dim 64")
-        if relative_position:
-            raise NotImplementedError("relative position is unused by inference_512_v1.0.yaml")
         inner = dim_head * heads
         self.is_self = context_dim is None
         context_dim = query_dim if context_dim is None else context_dim
@@ -160,6 +174,14 @@ class CrossAttention(PackedModule):
         self.to_v = nn.Linear(context_dim, inner, bias=False)
         self.to_out = nn.Sequential(nn.Linear(inner, query_dim), nn.Dropout(dropout))
         self.temporal_length = temporal_length
+        self.relative_position = relative_position
+        if relative_position:
+            assert temporal_length is not None
+            if temporal_length > TC_TEMPORAL_MAX_FRAMES:
+                raise ValueError(f"temporal_length {temporal_length}: tc_attn_temporal_rel takes tables of at most "
+                                 f"TC_TEMPORAL_MAX_FRAMES = {TC_TEMPORAL_MAX_FRAMES} distances either way")
+            self.relative_position_k = RelativePosition(num_units=dim_head, max_relative_position=temporal_length)
+            self.relative_position_v = RelativePosition(num_units=dim_head, max_relative_position=temporal_length)
         self.image_cross_attention = image_cross_attention
         self.image_cross_attention_scale = image_cross_attention_scale
         self.text_context_len = text_context_len
@@ -186,6 +208,9 @@ class CrossAttention(PackedModule):
 
     def _pack(self):
         pk = {"wo": pack_linear(self.to_out[0].weight), "bo": f32(self.to_out[0].bias)}
+        if self.relative_position:                                   # the two [2 L + 1, 64] tables as the kernel reads them
+            pk["rel_k"] = self.relative_position_k.embeddings_table.detach().to(torch.bfloat16).contiguous()
+            pk["rel_v"] = self.relative_position_v.embeddings_table.detach().to(torch.bfloat16).contiguous()
         if self.is_self:
             pk["wqkv"] = pack_linear(torch.cat([self.to_q.weight, self.to_k.weight, self.to_v.weight], 0))
         else:
@@ -226,8 +251,16 @@ class CrossAttention(PackedModule):
         return ops.gemm(a, pk["wo"], pk["bo"], residual=residual)
 
     # -- self attention over the T frames at each pixel
-    def forward_temporal_self(self, x_norm, residual, act: Act, ln=None):
+    def forward_temporal_self(self, x_norm, residual, act: Act, ln=None, causal=False):
         pk = self.pk
+        if self.relative_position or causal:
+            # relative position and / or the causal mask (attention.py:103-124): the one-launch kernels have no place for
+            # either, so always the projection (a folded LayerNorm still applies) + tc_attn_temporal_rel
+            qkv = ops.gemm(x_norm, pk["wqkv"]) if ln is None else ops.gemm(x_norm, ln[0], ln[1], a_norm_eps=ln[2])
+            a = ops.attention_temporal_rel(qkv, pk.get("rel_k"), pk.get("rel_v"), b=act.b, t=act.t, hw=act.hw, heads=self.heads,
+                                           max_rel=self.temporal_length if self.relative_position else 0, causal=causal,
+                                           scale=self.scale)
+            return ops.gemm(a, pk["wo"], pk["bo"], residual=residual)
         # every level: the fused projection and the attentions over the frames as ONE launch (ABI 13) -- the [rows, 3C]
         # tensor between them never reaches HBM.  The library's own rule decides (tc_temporal_qkv_attn_eligible): 16
         # frames with hw % 8 == 0 (csrc/qkv_attn.hip); 17 .. 64 frames with hw % (128 / TT) == 0, TT = 32 | 64
@@ -375,22 +408,24 @@ class BasicTransformerBlock(PackedModule):
         out = self.ff(h, x, ln=ln)
         return out if share is None else (out, act)
 
-    def _temporal_attn(self, x, i, attn, act: Act):
+    def _temporal_attn(self, x, i, attn, act: Act, causal=False):
         """x + attn(norm<i>(x)) over the frames of every pixel: LayerNorm, then the q / k / v projection and the 16 x 16
         attentions as ONE launch (csrc/qkv_attn.hip via CrossAttention.forward_temporal_self), then the output projection
         with the residual.  Where the library offers it (TC_TB_FUSED=1, C = 320: csrc/tb_fused.hip) all of that is one launch
         -- the default of rounds 4-5 at level 0, behind the chain above since round 6 (+0.4 ... +0.6 % per forward)."""
-        fused = getattr(ops.backend(), "temporal_attn_fused_eligible", None)
+        plain = not (attn.relative_position or causal)                  # else: projection + tc_attn_temporal_rel, nothing fused
+        fused = getattr(ops.backend(), "temporal_attn_fused_eligible", None) if plain else None
         if fused is not None and fused(b=act.b, t=act.t, hw=act.hw, c=x.shape[1], heads=attn.heads, ldx=x.stride(0)):
             w, bias, eps = self._folded(i, "qkv")
             return ops.temporal_attn_fused(x, w, bias, attn.pk["wo"], attn.pk["bo"], b=act.b, t=act.t, hw=act.hw,
                                            heads=attn.heads, ln_eps=eps, scale=attn.scale)
         h, ln = self._pre(x, i, attn.pk["wqkv"], "qkv", then=attn.pk["wo"])
-        return attn.forward_temporal_self(h, x, act, ln=ln)
+        return attn.forward_temporal_self(h, x, act, ln=ln, causal=causal)
 
-    def forward_temporal(self, x, act: Act):
-        x = self._temporal_attn(x, 1, self.attn1, act)
-        x = self._temporal_attn(x, 2, self.attn2, act)                   # context=None -> self attention again
+    def forward_temporal(self, x, act: Act, causal=False):
+        """`causal`: the tril mask of a causal TemporalTransformer, on both self-attentions (attention.py:376-390)."""
+        x = self._temporal_attn(x, 1, self.attn1, act, causal)
+        x = self._temporal_attn(x, 2, self.attn2, act, causal)           # context=None -> self attention again
         h, ln = self._pre(x, 3, self.ff.pk["w1"], "ff", then=self.ff.pk["w2"])
         return self.ff(h, x, ln=ln)
 
@@ -446,8 +481,13 @@ class TemporalTransformer(PackedModule):
                  use_checkpoint=True, use_linear=False, only_self_att=True, causal_attention=False,
                  causal_block_size=1, relative_position=False, temporal_length=None):
         super().__init__()
-        if not only_self_att or causal_attention or relative_position:
-            raise NotImplementedError("only the non-causal self-attention temporal transformer of the config")
+        if not only_self_att:
+            raise NotImplementedError("only the self-attention temporal transformer (only_self_att=True)")
+        if (causal_attention or relative_position) and temporal_length is None:
+            raise ValueError("causal_attention / relative_position need temporal_length (attention.py:338-345)")
+        self.only_self_att, self.relative_position = only_self_att, relative_position
+        self.causal_attention, self.causal_block_size = causal_attention, causal_block_size
+        self.temporal_length = temporal_length
         if temporal_length is not None and temporal_length > TC_TEMPORAL_MAX_FRAMES:
             raise ValueError(f"temporal_length {temporal_length}: the temporal attention supports at most "
                              f"TC_TEMPORAL_MAX_FRAMES = {TC_TEMPORAL_MAX_FRAMES} frames")
@@ -456,17 +496,27 @@ class TemporalTransformer(PackedModule):
         self.norm = nn.GroupNorm(32, in_channels, eps=1e-6, affine=True)
         self.use_linear = use_linear
         self.proj_in = nn.Linear(in_channels, inner) if use_linear else nn.Conv1d(in_channels, inner, 1)
+        # relative position: both attentions of every block carry the two tables (attention.py:338-342)
+        attention_cls = partial(CrossAttention, relative_position=True, temporal_length=temporal_length) if relative_position else None
         self.transformer_blocks = nn.ModuleList([
-            BasicTransformerBlock(inner, n_heads, d_head, dropout=dropout, context_dim=None,
+            BasicTransformerBlock(inner, n_heads, d_head, dropout=dropout, context_dim=None, attention_cls=attention_cls,
                                   checkpoint=use_checkpoint) for _ in range(depth)])
         self.proj_out = nn.Linear(inner, in_channels) if use_linear else nn.Conv1d(inner, in_channels, 1)
 
     _pack = SpatialTransformer._pack
 
+    def check_clip(self, t: int) -> None:
+        """The reference slices its causal mask out of a [temporal_length, temporal_length] tril (attention.py:343-345,
+        379): a longer clip has no mask there.  Refused before anything is launched."""
+        if self.causal_attention and t > self.temporal_length:
+            raise ValueError(f"a clip of {t} latent frames under a causal temporal attention of temporal_length "
+                             f"{self.temporal_length}: the causal mask covers at most temporal_length frames")
+
     def forward(self, act: Act) -> Act:
+        self.check_clip(act.t)
         pk = self.pk
         h = ops.groupnorm(act.rows, pk["gn_g"], pk["gn_b"], samples=act.b, rows=act.t * act.hw, eps=1e-6, prefetch=[pk["wi"]], prefetch_linear=True)
         h = ops.gemm(h, pk["wi"], pk["bi"])
         for blk in self.transformer_blocks:
-            h = blk.forward_temporal(h, act)
+            h = blk.forward_temporal(h, act, causal=self.causal_attention)
         return act.like(ops.gemm(h, pk["wo"], pk["bo"], residual=act.rows))

@@ -284,6 +284,9 @@ class UNetModel(PackedModule):
         self.out = nn.Sequential(normalization(ch), nn.SiLU(), nn.Conv2d(model_channels, out_channels, 3, padding=1))
         # batched timestep-embedding projection: one GEMM for every ResBlock's emb_layers
         self._resblocks: List[ResBlock] = [m for m in self.modules() if isinstance(m, ResBlock)]
+        # the causal temporal transformers: forward() asks each whether its mask covers the clip before anything is launched
+        self._causal_tts: List[TemporalTransformer] = [m for m in self.modules()
+                                                       if isinstance(m, TemporalTransformer) and m.causal_attention]
         off = 0
         for m in self._resblocks:
             m.emb_slice = (off, m.out_channels)
@@ -367,6 +370,8 @@ class UNetModel(PackedModule):
         parts = x_parts if x_parts is not None else [x]
         b, _, t, hh, ww = parts[0].shape
         check_frames(t)
+        for m in self._causal_tts:                            # a causal clip longer than its mask: refused here
+            m.check_clip(t)
         if replicas > 1 and (context is None or context.shape[0] != replicas * b):
             raise ValueError(f"replicas={replicas}: context must carry {replicas * b} samples")
         cin_pad = ceil_to(self.in_channels, 64)

@@ -525,6 +525,25 @@ class HipOps:
                    "tc_attn_temporal")
         return out
 
+    def attention_temporal_rel(self, qkv, rel_k, rel_v, *, b, t, hw, heads, max_rel, causal, scale=None):
+        """attention_temporal with relative position and / or a causal mask (tc_attn_temporal_rel; reference
+        attention.py:20-39, 103-124, 343-345, 376-390).  rel_k, rel_v: contiguous bf16 [2*max_rel + 1, 64] tables
+        shared by the heads, or both None (mask only)."""
+        qkv = _rows_view(qkv)
+        cdim = heads * 64
+        if not qkv.is_contiguous() or qkv.shape != (b * t * hw, 3 * cdim):
+            raise ValueError("attention_temporal_rel: qkv must be contiguous [b*t*hw, 3*C]")
+        for tab in (rel_k, rel_v):
+            if tab is not None and (tab.dtype != BF16 or not tab.is_contiguous() or tab.device != qkv.device
+                                    or tuple(tab.shape) != (2 * max_rel + 1, 64)):
+                raise ValueError("attention_temporal_rel: a table must be contiguous bf16 [2*max_rel + 1, 64] on qkv's device")
+        out = torch.empty((b * t * hw, cdim), dtype=BF16, device=qkv.device)
+        p = _lib.TcAttnTemporalRelParams(qkv=qkv.data_ptr(), out=out.data_ptr(), rel_k=_ptr(rel_k), rel_v=_ptr(rel_v),
+                                         b=b, t=t, hw=hw, heads=heads, max_rel=int(max_rel), causal=int(bool(causal)),
+                                         scale=float(scale if scale is not None else 64 ** -0.5))
+        _lib.check(self.lib.tc_attn_temporal_rel(C.byref(p), _stream()), "tc_attn_temporal_rel")
+        return out
+
     # ------------------------------------------------------------------ norms
     def prefetch_list(self, x_rows: int, tensors, linear: bool = False):
         """Which of `tensors` (the packed weights of the GEMMs that consume a norm's output) the norm launch should

@@ -89,6 +89,10 @@ class TorchLibOps(HipOps):
     def attention_temporal(self, qkv, *, b, t, hw, heads, scale=None):
         return self.t.attention_temporal(qkv, b, t, hw, heads, float(64 ** -0.5 if scale is None else scale))
 
+    def attention_temporal_rel(self, qkv, rel_k, rel_v, *, b, t, hw, heads, max_rel, causal, scale=None):
+        return self.t.attention_temporal_rel(qkv, rel_k, rel_v, int(b), int(t), int(hw), int(heads), int(max_rel), bool(causal),
+                                             float(64 ** -0.5 if scale is None else scale))
+
     def ff_geglu_fused(self, x, w1, b1, w2, b2, *, ln_eps=None):
         return self.t.ff_geglu_fused(x, w1, b1, w2, b2, -1.0 if ln_eps is None else float(ln_eps))
 
