@@ -274,6 +274,19 @@ def run_edges():
         for heads in (1, 5):
             qkv = rnd(2 * t * 7, 3 * 64 * heads)
             same(lambda: hip.attention_temporal(qkv, b=2, t=t, hw=7, heads=heads), f"attention_temporal b=2 t={t} hw=7 heads={heads}")
+    # tc_attn_temporal_rel, every instance (TT = 32 | 64, tables or none) on the same 14 and 70 waves; t = 1 and 5 as well, its
+    # domain starts at one frame.  Tables with L = 4 (the distance clamps at every t > 5) and L = 16, without and with the
+    # causal mask, and the mask alone
+    for t in (1, 5, 16, 17, 32, 33, 64):
+        for heads in (1, 5):
+            qkv = rnd(2 * t * 7, 3 * 64 * heads)
+            for L in (4, 16):
+                rk, rv = rnd(2 * L + 1, 64, scale=0.5), rnd(2 * L + 1, 64, scale=0.5)
+                for causal in (0, 1):
+                    same(lambda: hip.attention_temporal_rel(qkv, rk, rv, b=2, t=t, hw=7, heads=heads, max_rel=L, causal=causal),
+                         f"attention_temporal_rel b=2 t={t} hw=7 heads={heads} L={L} causal={causal}")
+            same(lambda: hip.attention_temporal_rel(qkv, None, None, b=2, t=t, hw=7, heads=heads, max_rel=0, causal=1),
+                 f"attention_temporal_rel b=2 t={t} hw=7 heads={heads} no tables causal=1")
     # the level-0 fused kernels (csrc/fused_l0.h is their shared skeleton; both read their switches per call)
     c = 320
     wq, bq = rnd(3 * c, c, scale=1.4 * c ** -0.5), rnd(3 * c, scale=0.2, dtype=torch.float32)
@@ -339,6 +352,13 @@ def fused():
                 ab(lambda: hip.temporal_qkv_attn(x, wq, bq, b=2, t=t, hw=hw, heads=heads), 2.0 * m * c * c * 3, f"temporal_qkv_attn t={t} {m}x{c}")
             qkv = rnd(m, 3 * c)
             ab(lambda: hip.attention_temporal(qkv, b=2, t=t, hw=hw, heads=heads), 4.0 * m * t * c, f"attention_temporal t={t} {m}x{c}")
+    # tc_attn_temporal_rel at level 0 with tables (L = 16) and the causal mask: 16 frames too, it serves every clip length
+    rk, rv = rnd(33, 64, scale=0.5), rnd(33, 64, scale=0.5)
+    for t in (16, 32, 64):
+        m = 2 * t * 2560
+        qkv = rnd(m, 3 * 320)
+        ab(lambda: hip.attention_temporal_rel(qkv, rk, rv, b=2, t=t, hw=2560, heads=5, max_rel=16, causal=1), 4.0 * m * t * 320,
+           f"attention_temporal_rel t={t} {m}x320 L=16 causal")
 # the spatial attention kernels, the MXFP8 quantiser and the LayerNorm that carries it, at their UNet shapes (B = 2)
 def spatial():
     for batch, heads, l in ((32, 5, 2560), (32, 10, 640)):

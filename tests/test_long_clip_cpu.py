@@ -115,8 +115,9 @@ def _hipcc():
 
 
 def test_long_temporal_kernels_do_not_spill(tmp_path):
-    """csrc/attention_temporal_long.hip, both padded lengths (TT = 32, 64), with the per-source flags of build.py: no
-    scratch, and the MFMA / permlane structure the design rests on is in the code."""
+    """csrc/attention_temporal_long.hip, both padded lengths (TT = 32, 64), and csrc/attention_temporal_rel.hip, its four
+    instances, with the per-source flags of build.py: no scratch, and the MFMA / permlane structure the design rests on is
+    in the code."""
     hipcc = _hipcc()
     if hipcc is None:
         pytest.skip("hipcc not on this host")
@@ -135,3 +136,19 @@ def test_long_temporal_kernels_do_not_spill(tmp_path):
     assert len(sizes) == 2 and all(int(s) == 0 for s in sizes), sizes
     assert "v_mfma_f32_32x32x16_bf16" in asm and "v_permlane32_swap" in asm and "global_store_dwordx4" in asm
     assert "attention_temporal_long.hip" in build.SOURCES
+    # csrc/attention_temporal_rel.hip is built from the same wave (csrc/attn_temporal_wave.h): its four instances alike
+    out = tmp_path / "attention_temporal_rel.s"
+    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=on", f"-I{ROOT}/include", f"-I{CSRC}",
+           *build.EXTRA_FLAGS["attention_temporal_rel.hip"], "-S", "--cuda-device-only",
+           os.path.join(CSRC, "attention_temporal_rel.hip"), "-o", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    asm = out.read_text()
+    kernels = re.findall(r"^(_Z\w*attn_temporal_rel_kernel\w*):", asm, re.M)
+    assert len(kernels) == 4, kernels
+    for inst in ("ILi32ELi4ELb0E", "ILi32ELi4ELb1E", "ILi64ELi4ELb0E", "ILi64ELi2ELb1E"):
+        assert any(inst in k for k in kernels), (inst, kernels)
+    sizes = re.findall(r"^; ScratchSize: (\d+)", asm, re.M)
+    assert len(sizes) == 4 and all(int(s) == 0 for s in sizes), sizes
+    assert "v_mfma_f32_32x32x16_bf16" in asm and "v_permlane32_swap" in asm and "global_store_dwordx4" in asm
+    assert "attention_temporal_rel.hip" in build.SOURCES

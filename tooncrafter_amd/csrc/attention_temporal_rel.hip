@@ -8,8 +8,9 @@
 // CrossAttention.forward, 343-345 and 376-390 the tril mask of TemporalTransformer: use_relative_position /
 // use_causal_attention of the UNet.)  Rk and Rv are [2 L + 1, 64] bf16 tables shared by every head.
 //
-// The kernel is attention_temporal_long.hip with three additions; the softmax and P.V are the same text
-// (attn_frames_long.h tc_attn_frames_long, unchanged), so with no tables and no mask it computes that kernel's bits:
+// The kernel is attention_temporal_long.hip with three additions.  The wave map, V^T into LDS and the store
+// (attn_temporal_wave.h) and the softmax and P.V (attn_frames_long.h tc_attn_frames_long) are the same functions in both, the
+// K load and the Q + score block the same text (that header says why), so with no tables and no mask it computes that kernel's bits:
 //
 //  * both relative terms depend on j - i only, and of the 2 L + 1 distances a clip of t frames uses the
 //    NC = 2 Lc + 1 with Lc = min(L, t - 1): the kernel works on that compact range c = clamp(j - i, -Lc, Lc) + Lc, at most
@@ -29,9 +30,8 @@
 // with tables, Rv^T [64][NRB * 32 + 4] bf16 and one bounce buffer [32][TT + 3] fp32 per wave -- 44 KiB at TT = 32 (4 waves),
 // 50 KiB at TT = 64 (2 waves per block: four would not fit the 64 KiB of a static allocation).  Nothing here was tuned.
 // Roundings: bf16 q / k / v / tables, fp32 scores and QR, bf16 softmax weights and bucket sums, fp32 sums, bf16 output.
-// A padded frame slot is never read as data and never stored; every row address is formed in 64 bits.
-#include "gemm_common.h"
-#include "attn_frames_long.h"
+// A padded frame slot is never read as data and never stored; every row address is formed in 64 bits (attn_temporal_wave.h).
+#include "attn_temporal_wave.h"
 
 namespace {
 
@@ -43,7 +43,7 @@ __global__ __launch_bounds__(WAVES * 64) void attn_temporal_rel_kernel(const bf1
   static_assert(TT == 32 || TT == 64, "frames padded to 32 or 64");
   constexpr int NKB = TT / 32;                     // 32-key blocks (and 32-query blocks)
   constexpr int NRB = 2 * NKB;                     // 32-distance blocks: 2 Lc + 1 <= 2 TT - 1
-  constexpr int VT_LD = TT * 2 + 8;                // bytes per V^T row: 72 | 136
+  constexpr int VT_LD = tl_vt_ld(TT);
   constexpr int RV_LD = NRB * 64 + 8;              // bytes per Rv^T row and per PB row: 136 | 264
   constexpr int BQ_LD = TT + 3;                    // floats per QR row: TT key slots + the two clamped ends, odd stride
   constexpr int BOUNCE = 32 * BQ_LD * 4;           // bytes per wave: 4480 | 8576 (the PB rows, 32 * RV_LD, fit inside)
@@ -54,46 +54,18 @@ __global__ __launch_bounds__(WAVES * 64) void attn_temporal_rel_kernel(const bf1
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int l31 = lane & 31, half = lane >> 5;
-  const int64_t seq = (int64_t)blockIdx.x * WAVES + wave;     // over nb * hw * heads, head fastest
-  const int64_t total = (int64_t)nb * hw * heads;
-  const bool active = seq < total;
-  const int64_t sq = active ? seq : total - 1;                // tail waves compute a valid problem and store nothing
-  const int hd = (int)(sq % heads);
-  const int64_t bp = sq / heads;
-  const int px = (int)(bp % hw);
-  const int bb = (int)(bp / hw);
+  const TlWave w = tl_wave_map(WAVES, wave, nb, t_len, hw, heads);
+  const bool active = w.active;
+  const int hd = w.hd;
   const int C = heads * 64;
   const int64_t ld = 3 * (int64_t)C;
-  const int64_t row0 = (int64_t)bb * t_len * hw + px;         // frame f -> row row0 + f * hw
+  const int64_t row0 = w.row0;                                // frame f -> row row0 + f * hw
   const bf16_t* base = qkv + hd * 64;
   auto frame_ptr = [&](int f) { return base + (row0 + (int64_t)f * hw) * ld; };
   const int lc = max_rel < t_len - 1 ? max_rel : t_len - 1;   // distances in use: -lc .. lc -> c = 0 .. 2 lc
 
-  // ---- V^T of this pixel / head into the wave's LDS slice, as attention_temporal_long.hip: [dim][key], keys >= t zero
   char* vts = smem + wave * 64 * VT_LD;
-  {
-    uint16_t* vt = reinterpret_cast<uint16_t*>(vts);
-    constexpr int PER_LANE = TT * 8 / 64;          // 4 | 8 chunks of 16 bytes
-    u32x4 vreg[PER_LANE];
-#pragma unroll
-    for (int it = 0; it < PER_LANE; ++it) {
-      const int idx = lane + it * 64;
-      const int key = idx % TT, dch = idx / TT;
-      const int kc = key < t_len ? key : t_len - 1;
-      vreg[it] = *reinterpret_cast<const u32x4*>(frame_ptr(kc) + 2 * C + dch * 8);
-    }
-#pragma unroll
-    for (int it = 0; it < PER_LANE; ++it) {
-      const int idx = lane + it * 64;
-      const int key = idx % TT, dch = idx / TT;
-      const u32x4 v4 = key < t_len ? vreg[it] : u32x4{0u, 0u, 0u, 0u};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        vt[(dch * 8 + 2 * e) * (VT_LD / 2) + key] = (uint16_t)(v4[e] & 0xffffu);
-        vt[(dch * 8 + 2 * e + 1) * (VT_LD / 2) + key] = (uint16_t)(v4[e] >> 16);
-      }
-    }
-  }
+  tl_stage_vt<TT>(frame_ptr, C, lane, t_len, vts);
   // ---- Rv^T over the compact distance range, once per block: [dim][c] = Rv[c - lc + max_rel][dim], c > 2 lc zero (their
   // bucket sums are zero as well: 0 * garbage could still be NaN)
   char* rvt = smem + VT_BYTES;
@@ -162,7 +134,7 @@ __global__ __launch_bounds__(WAVES * 64) void attn_temporal_rel_kernel(const bf1
           qr = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8*>(rp + kk * 16), qf[kk], qr, 0, 0, 0);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int c = rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+          const int c = rb * 32 + tc_frames_key(r, half);
           const int j = c + qc - lc;
           if (c == 0) bq[TT] = qr[r];
           if (c == 2 * lc && lc > 0) bq[TT + 1] = qr[r];
@@ -174,7 +146,7 @@ __global__ __launch_bounds__(WAVES * 64) void attn_temporal_rel_kernel(const bf1
       for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int key = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+          const int key = kb * 32 + tc_frames_key(r, half);
           const int d = key - qc;                  // keys >= t read a slot nobody wrote: the mask below replaces the sum
           st[kb][r] += bq[d <= -lc ? TT : d >= lc ? TT + 1 : key];
         }
@@ -184,23 +156,16 @@ __global__ __launch_bounds__(WAVES * 64) void attn_temporal_rel_kernel(const bf1
       for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int key = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+          const int key = kb * 32 + tc_frames_key(r, half);
           st[kb][r] = key > qc ? -INFINITY : st[kb][r];
         }
     }
     // masked softmax, P^T in bf16, O^T = V^T P^T (attn_frames_long.h); st comes back as exp2(..), not yet normalised
     f32x16 oacc[2];
-    tc_attn_frames_long<NKB>(st, oacc, t_len, scale_log2e, vts, VT_LD, l31, half);
+    const float inv = tc_attn_frames_long<NKB>(st, oacc, t_len, scale_log2e, vts, VT_LD, l31, half);
 
     if constexpr (REL) {
-      // ---- the normaliser again, in the core's own order (the same bits), then PB[query][c] through the wave's buffer
-      float sum = 0.f;
-#pragma unroll
-      for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sum += st[kb][r];
-      sum = tc_half_sum(sum);
-      const float inv = __builtin_amdgcn_rcpf(sum);
+      // ---- PB[query][c] through the wave's buffer
       char* pbrow = bounce + l31 * RV_LD;
       uint16_t* pb = reinterpret_cast<uint16_t*>(pbrow);
       __syncthreads();                             // the QR rows have been read
@@ -212,7 +177,7 @@ __global__ __launch_bounds__(WAVES * 64) void attn_temporal_rel_kernel(const bf1
       for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int key = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+          const int key = kb * 32 + tc_frames_key(r, half);
           const int d = key - qc;
           const bf16_t pw = (bf16_t)(st[kb][r] * inv);             // the weight the core multiplied V by; 0 on masked keys
           if (d <= -lc) lo += (float)pw;
@@ -248,24 +213,8 @@ __global__ __launch_bounds__(WAVES * 64) void attn_temporal_rel_kernel(const bf1
       __syncthreads();                             // the PB rows have been read: the next query block writes QR over them
     }
 
-    // ---- store, as attention_temporal_long.hip: one permlane32_swap per dword pair, 16-byte row stores, padded query
-    // rows (>= t) never stored
     bf16_t* orow = out + (row0 + (int64_t)qc * hw) * C + hd * 64;
-    const bool store = active && q < t_len;
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-      for (int g = 0; g < 4; g += 2) {
-        uint32_t a0 = pack2(oacc[db][4 * g + 0], oacc[db][4 * g + 1]);
-        uint32_t a1 = pack2(oacc[db][4 * g + 2], oacc[db][4 * g + 3]);
-        uint32_t b0 = pack2(oacc[db][4 * g + 4], oacc[db][4 * g + 5]);
-        uint32_t b1 = pack2(oacc[db][4 * g + 6], oacc[db][4 * g + 7]);
-        const auto r0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
-        const auto r1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-        a0 = r0[0]; b0 = r0[1];
-        a1 = r1[0]; b1 = r1[1];
-        if (store) *reinterpret_cast<u32x4*>(orow + db * 32 + 8 * g + 8 * half) = u32x4{a0, a1, b0, b1};
-      }
+    tl_store(orow, half, active && q < t_len, oacc);   // padded query rows (>= t) are never stored
   }
 }
 

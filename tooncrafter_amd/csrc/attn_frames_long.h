@@ -1,6 +1,7 @@
 // Softmax and P.V of self-attention over 17 .. 64 frames of ONE pixel and one 64-wide head, 32 queries of one wave, on
-// v_mfma_f32_32x32x16_bf16 -- the core shared by attention_temporal_long.hip (K / Q fragments from global memory, O to
-// global memory) and qkv_attn_long.hip (K / Q from LDS, O over the q rows in LDS).  The sibling of attn_frames16.h.
+// v_mfma_f32_32x32x16_bf16 -- the core shared by attention_temporal_long.hip and attention_temporal_rel.hip (K / Q fragments
+// from global memory, O to global memory: attn_temporal_wave.h) and qkv_attn_long.hip (K / Q from LDS, O over the q rows in
+// LDS).  The sibling of attn_frames16.h.
 #pragma once
 #include "common.h"
 
@@ -12,6 +13,10 @@ namespace {
 __device__ __forceinline__ float tc_half_max(float x) { return fmaxf(x, __shfl_xor(x, 32, 64)); }
 __device__ __forceinline__ float tc_half_sum(float x) { return x + __shfl_xor(x, 32, 64); }
 
+// Accumulator register r of lane half `half` -> key within its 32-key block (the S^T / O^T layout attn_tile64.h states):
+// one set of 16 serves every block
+__device__ __forceinline__ int tc_frames_key(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
+
 // st: the raw S^T = K Q^T accumulators of the NKB = TT / 32 key blocks (frames padded to TT = 32 | 64 slots), in the layout
 // that attn_tile64.h states: a lane (l31 = lane & 31, half = lane >> 5) owns ONE query, a register is a key of its block.
 // Keys >= t are set to -inf; max and sum are in-lane plus one exchange between the lane halves; P^T is rounded to bf16 in
@@ -19,17 +24,17 @@ __device__ __forceinline__ float tc_half_sum(float x) { return x + __shfl_xor(x,
 // there; the V^T fragments are read from LDS in that same order.
 // vt: V^T of the pixel in LDS, [64 dims][keys] bf16 with rows of `vt_ld` bytes, pointing at the pixel's key 0; keys
 // t .. TT - 1 must hold finite values (their P is 0: 0 * garbage could still be NaN).
-// oacc comes out in that header's O layout: how O leaves is the caller's.
+// oacc comes out in that header's O layout: how O leaves is the caller's.  Returns 1 / sum of the lane's query: st holds
+// exp2(..) on return, and (bf16_t)(st * that) is the weight V was multiplied by.
 template <int NKB>
-__device__ __forceinline__ void tc_attn_frames_long(f32x16 (&st)[NKB], f32x16 (&oacc)[2], int t, float scale_log2e,
+__device__ __forceinline__ float tc_attn_frames_long(f32x16 (&st)[NKB], f32x16 (&oacc)[2], int t, float scale_log2e,
                                                     const char* vt, int vt_ld, int l31, int half) {
   float mx = -INFINITY;
 #pragma unroll
   for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int key = (r & 3) + 8 * (r >> 2) + 4 * half;           // within the block: one set of 16 serves every kb
-      st[kb][r] = key < t - kb * 32 ? st[kb][r] : -INFINITY;
+      st[kb][r] = tc_frames_key(r, half) < t - kb * 32 ? st[kb][r] : -INFINITY;
       mx = fmaxf(mx, st[kb][r]);
     }
   mx = tc_half_max(mx);                            // key 0 is always valid: mx is finite
@@ -70,6 +75,7 @@ __device__ __forceinline__ void tc_attn_frames_long(f32x16 (&st)[NKB], f32x16 (&
         oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vv), pf, oacc[db], 0, 0, 0);
       }
     }
+  return inv;
 }
 
 }  // namespace
