@@ -436,6 +436,83 @@ typedef struct TcDdimBlendParams {
 } TcDdimBlendParams;
 int tc_ddim_blend(const TcDdimBlendParams* p, void* stream);
 
+/* ---- Pixel front end: uint8 frames -> the model's and the CLIP image tower's inputs (additive within ABI 14: two
+ * structs, five symbols).  The reference does both steps outside its model code, on PIL images and with kornia. ---- */
+
+/* Coefficient tables of one axis of PIL's 8-bit BILINEAR resample (Pillow src/libImaging/Resample.c: precompute_coeffs
+ * + normalize_coeffs_8bpc), HOST code, double precision, no device call.  For output index xx of an axis in_size -> out_size:
+ *   scale = in / out, support = fs = max(scale, 1), kmax = ceil(support) * 2 + 1, center = (xx + 0.5) * scale,
+ *   xmin = max(int(center - support + 0.5), 0), xmax = min(int(center + support + 0.5), in),
+ *   w[x] = max(0, 1 - |(x + xmin - center + 0.5) / fs|) for x < xmax - xmin, divided by their sum,
+ *   coefs[xx * kmax + x] = int(w[x] * 2^22 + 0.5)  (0 from xmax - xmin on),  bounds[2 xx] = xmin, bounds[2 xx + 1] = xmax - xmin.
+ * Returns kmax (> 0).  bounds == NULL and coefs == NULL is the sizing query: nothing is written; otherwise bounds holds
+ * 2 * out_size and coefs coefs_len >= out_size * kmax int32 (TC_EWORKSPACE if fewer, TC_EINVAL for a size <= 0 or one
+ * table without the other). */
+int32_t tc_resize_tables(int32_t in_size, int32_t out_size, int32_t* bounds, int32_t* coefs, int64_t coefs_len);
+
+#define TC_FRAMES_U8_MAX 16   /* images per tc_frames_from_u8 call */
+
+/* n uint8 HWC images -> fp32 frames of a (b, 3, t, H, W) clip tensor: the image transform of the reference's
+ * load_data_prompts (scripts/evaluation/inference.py:64-69: Resize(min(size)), CenterCrop(size), ToTensor,
+ * Normalize(0.5, 0.5) on PIL images), bit for bit:
+ *   - resized size: the shorter source side becomes s = min(H, W), the other int(s * long / short); no resize when
+ *     the shorter side is s already;
+ *   - PIL's 8-bit BILINEAR resample with the tables of tc_resize_tables, horizontal pass (sw -> rw) into the uint8
+ *     workspace, then vertical (sh -> rh).  PIL skips a pass whose size does not change; under the rule above both
+ *     sides change or neither, so either both passes run or the source is cropped as it is (no tables needed).  A pixel
+ *     is clip(((1 << 21) + sum coefs * src) >> 22, 0, 255).  Table entries are clamped to the image, so wrong tables
+ *     give wrong pixels, never an access outside the source;
+ *   - crop: left = round_half_even((rw - W) / 2), top likewise; outside the resized image the pixel is 0 (PIL's crop);
+ *   - value: fp32 (v / 255 - 0.5) / 0.5, each operation rounded on its own (correctly rounded division).
+ * Image i goes to frame slots[i] = batch * t + frame; frames no slot names are not written.  `slots` is a HOST array
+ * (read before the launch); every other pointer is device memory.
+ * workspace: tc_frames_from_u8_workspace bytes (n * sh * rw * 3 when the images are resized, else 0).
+ * TC_EINVAL: NULL p / src / out / slots, n <= 0 or > TC_FRAMES_U8_MAX, a size <= 0, pitch < 3 * sw, image_stride < sh * pitch,
+ * a slot outside [0, b * t), tables missing for a pass that runs; TC_EWORKSPACE: workspace too small.  Nothing is
+ * launched or written on a refusal. */
+typedef struct TcFramesU8Params {
+  const uint8_t* src;        /* n images, HWC, 3 channels */
+  int64_t image_stride;      /* bytes from one image to the next */
+  int32_t pitch;             /* bytes from one row to the next, >= 3 * sw */
+  int32_t n, sh, sw;
+  const int32_t* slots;      /* HOST: n frame indices batch * t + frame */
+  float* out;                /* (b, 3, t, H, W) fp32 */
+  int32_t b, t, h, w;
+  const int32_t* h_bounds; const int32_t* h_coefs; int32_t h_kmax;   /* tables sw -> rw (NULL when nothing is resized) */
+  const int32_t* v_bounds; const int32_t* v_coefs; int32_t v_kmax;   /* tables sh -> rh */
+  void* workspace; int64_t workspace_bytes;
+} TcFramesU8Params;
+/* The resized size (rh, rw) of an (sh, sw) source for an (h, w) target by the rule above; TC_EINVAL for a size <= 0. */
+int tc_frames_from_u8_resized(int32_t sh, int32_t sw, int32_t h, int32_t w, int32_t* rh, int32_t* rw);
+int64_t tc_frames_from_u8_workspace(const TcFramesU8Params* p);
+int tc_frames_from_u8(const TcFramesU8Params* p, void* stream);
+
+/* The CLIP image tower's preprocessing up to the A operand of its patch-embedding GEMM, replaces
+ * lvdm/modules/encoders/condition.py:322-330 (kornia.geometry.resize(x, (S, S), 'bicubic', align_corners=True,
+ * antialias=True), (x + 1) / 2, (x - mean) / std) and the unfold in front of open_clip's conv1:
+ *   - antialias (only if h / S or w / S exceeds 1): separable Gaussian, per axis sigma = max((factor - 1) / 2, 0.001),
+ *     kernel size int(max(4 sigma, 3)) made odd, reflect border; rows first, then columns;
+ *   - bicubic (Keys, A = -0.75) at source coordinate dst * (in - 1) / (S - 1), tap indices clamped to the image;
+ *   - (v + 1) / 2, then (v - mean[c]) / std[c];
+ * all sums in double, rounded to bf16 once (the mean cancels the pixel value: near zero a bf16 ulp is below the rounding
+ * error of an fp32 sum).  out: rows [b * g * g, ld], g = S / patch, row = (sample, patch row, patch
+ * column), column = (c, py, px) as conv1.weight.reshape(width, -1); columns 3 * patch^2 .. ld - 1 are written as zero.
+ * workspace: tc_clip_patches_workspace bytes (two double copies of x when the blur runs, else 0), 8-byte aligned.
+ * TC_EINVAL: NULL p / x / out, a size <= 0, ld < 3 * patch^2; TC_ESHAPE: S % patch != 0, a reflect border that does
+ * not fit (kernel size / 2 >= the image's extent), a kernel of more than TC_CLIP_BLUR_TAPS taps; TC_EWORKSPACE; TC_EALIGN. */
+#define TC_CLIP_BLUR_TAPS 127
+typedef struct TcClipPatchesParams {
+  const float* x;            /* (b, 3, h, w) fp32 in [-1, 1], contiguous */
+  tc_bf16* out;              /* [b * g * g, ld] */
+  int32_t b, h, w;
+  int32_t size, patch, ld;   /* S, the patch edge, the row length of out */
+  int32_t antialias;         /* 0: never blur */
+  float mean[3], std[3];
+  void* workspace; int64_t workspace_bytes;
+} TcClipPatchesParams;
+int64_t tc_clip_patches_workspace(const TcClipPatchesParams* p);
+int tc_clip_patches(const TcClipPatchesParams* p, void* stream);
+
 /* introspection */
 int tc_abi_version(void);
 const char* tc_build_info(void);

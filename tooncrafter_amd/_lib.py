@@ -127,6 +127,31 @@ class TcAttnTemporalRelParams(C.Structure):
     ]
 
 
+class TcFramesU8Params(C.Structure):
+    """uint8 HWC images -> fp32 clip frames (tc_frames_from_u8; additive within ABI 14).  `slots` is a HOST array."""
+    _fields_ = [
+        ("src", C.c_void_p), ("image_stride", C.c_int64), ("pitch", C.c_int32),
+        ("n", C.c_int32), ("sh", C.c_int32), ("sw", C.c_int32),
+        ("slots", C.POINTER(C.c_int32)), ("out", C.c_void_p),
+        ("b", C.c_int32), ("t", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+        ("h_bounds", C.c_void_p), ("h_coefs", C.c_void_p), ("h_kmax", C.c_int32),
+        ("v_bounds", C.c_void_p), ("v_coefs", C.c_void_p), ("v_kmax", C.c_int32),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+    ]
+
+
+class TcClipPatchesParams(C.Structure):
+    """fp32 frames -> the CLIP image tower's patch rows (tc_clip_patches; additive within ABI 14)."""
+    _fields_ = [
+        ("x", C.c_void_p), ("out", C.c_void_p),
+        ("b", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+        ("size", C.c_int32), ("patch", C.c_int32), ("ld", C.c_int32), ("antialias", C.c_int32),
+        ("mean", C.c_float * 3), ("std", C.c_float * 3),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+    ]
+
+
+TC_FRAMES_U8_MAX = 16            # include/tooncrafter_hip.h: images per tc_frames_from_u8 call
 TC_PREFETCH_MAX = 4
 
 
@@ -178,6 +203,12 @@ SYMBOLS = {
     "tc_ddim_step": (C.c_int, [C.POINTER(TcDdimParams), C.c_void_p, C.c_int64, C.c_void_p]),
     "tc_ddim_step_eps": (C.c_int, [C.POINTER(TcDdimParams), C.c_void_p, C.c_int64, C.c_void_p]),
     "tc_ddim_blend": (C.c_int, [C.POINTER(TcDdimBlendParams), C.c_void_p]),
+    "tc_resize_tables": (C.c_int32, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64]),
+    "tc_frames_from_u8_resized": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "tc_frames_from_u8_workspace": (C.c_int64, [C.POINTER(TcFramesU8Params)]),
+    "tc_frames_from_u8": (C.c_int, [C.POINTER(TcFramesU8Params), C.c_void_p]),
+    "tc_clip_patches_workspace": (C.c_int64, [C.POINTER(TcClipPatchesParams)]),
+    "tc_clip_patches": (C.c_int, [C.POINTER(TcClipPatchesParams), C.c_void_p]),
     "tc_gemm_ws_eligible": (C.c_int, [C.POINTER(TcGemmParams)]),
     "tc_gemm_gn_rows": (C.c_int, [C.POINTER(TcGemmParams)]),
     "tc_groupnorm_part": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
@@ -236,7 +267,7 @@ class _TracedLib:
 
     def __getattr__(self, name):
         fn = getattr(self._lib, name)
-        if name not in SYMBOLS or name in ("tc_abi_version", "tc_build_info") or name.endswith("_workspace"):
+        if name not in SYMBOLS or name in ("tc_abi_version", "tc_build_info", "tc_resize_tables", "tc_frames_from_u8_resized") or name.endswith("_workspace"):
             return fn
         import sys
 

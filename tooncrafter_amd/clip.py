@@ -4,7 +4,9 @@
     latents = sample(model, cond, plan)                  # DDIM (two- or three-way guidance; pinned= holds extra keyframes)
     video   = decode_spliced(model, latents, cond.refs)  # 16-frame decode + 14-frame re-decode, centre frames spliced
 
-`bench.py` times the second and third stage on resident conditioning; `synthesize` chains all three.  The caller the
+`bench.py` times the second and third stage on resident conditioning; `synthesize` chains all three.  Callers that hold
+uint8 frames on the device start at `Conditions.from_uint8` / `synthesize_u8`: the script's PIL transform and the image
+tower's preprocessing run as HIP kernels there (tc_frames_from_u8, tc_clip_patches).  The caller the
 reference ships for this path is `image_guided_synthesis` (scripts/evaluation/inference.py:180-277, with its helper
 `get_latent_z_with_hidden_states`, :164-178); `image_guided_synthesis` below keeps that call signature (argument names and
 order are the interface of the reference's scripts) and is a thin adapter onto the stages.  The unmodified script's own copy
@@ -21,6 +23,7 @@ from typing import List, Optional
 
 import torch
 
+from . import ops
 from .lvdm.attention import check_frames
 from .lvdm.ddim import DDIMSampler
 from .lvdm.ddim_multiplecond import DDIMSampler as ThreeWaySampler
@@ -49,15 +52,17 @@ class Conditions:
     three_way: bool = False              # sampler family (the reference picks it by flag, not by the branch's presence)
 
     @staticmethod
-    def build(model, videos, *, prompts=None, fs=None, guided=True, three_way=False, image_branch=True, hold_endpoints=True):
+    def build(model, videos, *, prompts=None, fs=None, guided=True, three_way=False, image_branch=True, hold_endpoints=True,
+              embed=None):
         """`hold_endpoints`: frames 0 AND t-1 condition the clip (interpolation / looping); otherwise frame 0 is repeated
-        over time (plain image-to-video)."""
+        over time (plain image-to-video).  `embed`: the image tower, (b, 3, H, W) pixels -> tokens (default: `model.embedder`)."""
         b, t = videos.shape[0], videos.shape[2]
         prompts = list(prompts) if prompts is not None else [""] * b
         first = videos[:, :, 0]
+        embed = model.embedder if embed is None else embed
 
         def tokens(text_emb, image):
-            return torch.cat([text_emb, model.image_proj_model(model.embedder(image))], dim=1)
+            return torch.cat([text_emb, model.image_proj_model(embed(image))], dim=1)
 
         text = model.get_learned_conditioning(prompts)
         pos = {"c_crossattn": [tokens(text, first)]}
@@ -87,6 +92,43 @@ class Conditions:
                         branch["c_concat"] = [canvas]
         fs_t = torch.full((b,), int(fs), dtype=torch.long, device=model.device) if not torch.is_tensor(fs) else fs
         return Conditions(pos, neg, img_only, refs, fs_t, canvas, three_way)
+
+    @staticmethod
+    def from_uint8(model, first_u8, last_u8, *, size, t, **options):
+        """`build` from uint8 frames on the device: `first_u8` / `last_u8` are (b, h, w, 3) uint8 keyframes of any size (what
+        `clip_to_uint8` returns, or a decoder's output), `size` the model's (H, W).  They become frames 0 and t-1 of the clip
+        tensor by the script's transform (`frames_from_uint8`); the encoder runs as in `build` and the image tower takes its
+        patches from tc_clip_patches (`encode_on_device_front`).  `options`: the keyword options of `build` other than `embed`."""
+        for name, u8 in (("first_u8", first_u8), ("last_u8", last_u8)):
+            if not isinstance(u8, torch.Tensor) or u8.dtype != torch.uint8 or u8.dim() != 4 or u8.shape[3] != 3:
+                raise ValueError(f"from_uint8: {name} must be (b, h, w, 3) uint8, got "
+                                 f"{tuple(u8.shape) if isinstance(u8, torch.Tensor) else type(u8)} {getattr(u8, 'dtype', '')}")
+        if first_u8.shape[0] != last_u8.shape[0]:
+            raise ValueError(f"from_uint8: {first_u8.shape[0]} first frames, {last_u8.shape[0]} last frames")
+        b = first_u8.shape[0]
+        videos = frames_from_uint8(first_u8, size, [(i, 0) for i in range(b)], t)
+        frames_from_uint8(last_u8, size, [(i, t - 1) for i in range(b)], t, out=videos)
+        return Conditions.build(model, videos, embed=model.embedder.encode_on_device_front, **options)
+
+
+def frames_from_uint8(images_u8, size, slots, t, out=None):
+    """uint8 (n, h, w, 3) device images -> the (b, 3, t, H, W) fp32 clip tensor the model takes, `size` = (H, W): image i fills
+    the (batch, frame) pair slots[i] by the script's transform (inference.py:64-69: Resize(min(size)), CenterCrop(size),
+    ToTensor, Normalize(0.5, 0.5) on PIL images), bit for bit, on the device.  b = 1 + the largest batch index; frames no slot
+    names are zero.  `out`: a clip tensor to fill in place instead (the frames no slot names keep their contents)."""
+    if not isinstance(images_u8, torch.Tensor) or images_u8.dtype != torch.uint8:
+        raise ValueError(f"frames_from_uint8: expected a uint8 tensor, got {getattr(images_u8, 'dtype', type(images_u8))}")
+    if images_u8.dim() != 4 or images_u8.shape[3] != 3:
+        raise ValueError(f"frames_from_uint8: expected (n, h, w, 3) images, got {tuple(images_u8.shape)}")
+    size, slots, t = tuple(int(v) for v in size), [(int(i), int(f)) for i, f in slots], int(t)
+    if len(size) != 2 or min(size) <= 0 or t <= 0:
+        raise ValueError(f"frames_from_uint8: size {size}, t {t}")
+    if len(slots) != images_u8.shape[0] or any(i < 0 or not 0 <= f < t for i, f in slots):
+        raise ValueError(f"frames_from_uint8: {images_u8.shape[0]} images need as many (batch, frame) slots with frame < {t}, got {slots}")
+    b = out.shape[0] if out is not None else 1 + max(i for i, _ in slots)
+    if any(i >= b for i, _ in slots):
+        raise ValueError(f"frames_from_uint8: slots {slots} for a batch of {b}")
+    return ops.frames_from_u8(images_u8, size, [i * t + f for i, f in slots], b=b, t=t, out=out)
 
 
 @dataclass
@@ -158,6 +200,18 @@ def synthesize(model, videos, latent_shape, *, plan: SamplingPlan, prompts=None,
     pinned = pin_frames(model, keyframes, latent_shape[2]) if keyframes else None
     clips = [decode_spliced(model, sample(model, cond, plan, latent_shape, pinned=pinned), cond.refs) for _ in range(variants)]
     return torch.stack(clips, dim=1)
+
+
+def synthesize_u8(model, first_u8, last_u8, latent_shape, *, size, plan: SamplingPlan, prompts=None, fs=24, three_way=False,
+                  hold_endpoints=True):
+    """uint8 keyframes in, uint8 clip out, all on the device: (b, h, w, 3) first / last frames -> (b, t, H, W, 3) frames
+    (`Conditions.from_uint8`, `sample`, `decode_spliced`, `clip_to_uint8`).  The last frame of one clip can be the first
+    keyframe of the next without leaving the GPU."""
+    from .output import clip_to_uint8
+    cond = Conditions.from_uint8(model, first_u8, last_u8, size=size, t=latent_shape[2], prompts=prompts, fs=fs,
+                                 guided=plan.scale != 1.0, three_way=three_way, image_branch=plan.image_scale != 1.0,
+                                 hold_endpoints=hold_endpoints)
+    return clip_to_uint8(decode_spliced(model, sample(model, cond, plan, latent_shape), cond.refs))
 
 
 # --- the reference scripts' call signatures (scripts/evaluation/inference.py:164,180) -----------------------------------

@@ -3,6 +3,7 @@
 // The reference binds ATen / xformers operators from Python (utils/utils.py:27-42 instantiates lvdm classes whose
 // forward methods call torch ops); this registers the MI355X kernels as first-class torch operators instead:
 //   torch.ops.tooncrafter.gemm / quant_mxfp8 / gemm_mx / attention / attention_temporal(_rel) / groupnorm(_pf) / layernorm(_pf) / ddim_step(_eps) / ddim_blend /
+//   frames_from_u8 / clip_patches /
 //   ff_geglu_fused / temporal_attn_fused / temporal_qkv_attn / attention_q8
 // with (i) a CUDA(HIP)-key implementation that validates the tensors, allocates the result from the caching allocator,
 // picks up the CURRENT stream and calls the same extern "C" entry point the ctypes binding calls, and (ii) a Meta-key
@@ -477,6 +478,88 @@ Tensor ddim_blend_meta(const optional<Tensor>&, const Tensor& x0, const optional
   return at::empty_like(x0);
 }
 
+// Pixel front end (additive within ABI 14).  frames_from_u8: uint8 (n, sh, sw, 3) images -> a new (b, 3, t, h, w) fp32 clip tensor,
+// image i in frame slots[i] = batch * t + frame, zero elsewhere (reference scripts/evaluation/inference.py:64-69 on the device);
+// the tables are tc_resize_tables' for sw -> rw and sh -> rh, on the device (None when nothing is resized).
+const int32_t* i32_table(const optional<Tensor>& t, const char* what) {
+  if (!t.has_value()) return nullptr;
+  TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt && t->is_contiguous() && t->dim() == 2, what, ": contiguous int32 CUDA [out, k]");
+  return t->data_ptr<int32_t>();
+}
+
+Tensor frames_from_u8_cuda(const Tensor& images, at::IntArrayRef slots, int64_t b, int64_t t, int64_t h, int64_t w,
+                           const optional<Tensor>& h_bounds, const optional<Tensor>& h_coefs, const optional<Tensor>& v_bounds,
+                           const optional<Tensor>& v_coefs) {
+  TORCH_CHECK(images.is_cuda(), "frames_from_u8: expected a CUDA tensor (the product path is GPU-only)");
+  TORCH_CHECK(images.scalar_type() == at::kByte && images.dim() == 4 && images.size(3) == 3 && images.stride(3) == 1 &&
+              images.stride(2) == 3, "frames_from_u8: uint8 (n, h, w, 3) images with packed pixels");
+  const int64_t n = images.size(0);
+  TORCH_CHECK(n >= 1 && n <= TC_FRAMES_U8_MAX && (int64_t)slots.size() == n, "frames_from_u8: 1 .. ", TC_FRAMES_U8_MAX, " images, one slot each");
+  TORCH_CHECK(b > 0 && t > 0 && h > 0 && w > 0, "frames_from_u8: b, t, h, w must be positive");
+  Tensor out = at::zeros({b, 3, t, h, w}, images.options().dtype(at::kFloat));
+  int32_t slot[TC_FRAMES_U8_MAX];
+  for (int64_t i = 0; i < n; ++i) {
+    TORCH_CHECK(slots[i] >= 0 && slots[i] < b * t, "frames_from_u8: slot ", slots[i], " outside the clip tensor");
+    slot[i] = (int32_t)slots[i];
+  }
+  TcFramesU8Params p = {};
+  p.src = images.data_ptr<uint8_t>();
+  p.pitch = (int32_t)images.stride(1);
+  p.n = (int32_t)n; p.sh = (int32_t)images.size(1); p.sw = (int32_t)images.size(2);
+  p.image_stride = n > 1 ? images.stride(0) : (int64_t)p.sh * p.pitch;
+  p.slots = slot;
+  p.out = out.data_ptr<float>();
+  p.b = (int32_t)b; p.t = (int32_t)t; p.h = (int32_t)h; p.w = (int32_t)w;
+  p.h_bounds = i32_table(h_bounds, "frames_from_u8: h_bounds"); p.h_coefs = i32_table(h_coefs, "frames_from_u8: h_coefs");
+  p.v_bounds = i32_table(v_bounds, "frames_from_u8: v_bounds"); p.v_coefs = i32_table(v_coefs, "frames_from_u8: v_coefs");
+  int32_t rh = 0, rw = 0;
+  check_rc(tc_frames_from_u8_resized(p.sh, p.sw, p.h, p.w, &rh, &rw), "tc_frames_from_u8_resized");
+  if (rh != p.sh) {                                       // the tables must be the ones of these sizes: their rows are indexed by rw / rh
+    TORCH_CHECK(p.h_bounds && p.h_coefs && p.v_bounds && p.v_coefs && h_bounds->size(0) == rw && h_coefs->size(0) == rw &&
+                v_bounds->size(0) == rh && v_coefs->size(0) == rh && h_bounds->size(1) == 2 && v_bounds->size(1) == 2,
+                "frames_from_u8: tables of ", p.sw, " -> ", rw, " and ", p.sh, " -> ", rh, " expected");
+    p.h_kmax = (int32_t)h_coefs->size(1); p.v_kmax = (int32_t)v_coefs->size(1);
+  }
+  p.workspace_bytes = tc_frames_from_u8_workspace(&p);
+  Tensor ws = at::empty({p.workspace_bytes > 16 ? p.workspace_bytes : 16}, images.options());
+  p.workspace = ws.data_ptr();
+  check_rc(tc_frames_from_u8(&p, cur_stream()), "tc_frames_from_u8");
+  return out;
+}
+
+Tensor frames_from_u8_meta(const Tensor& images, at::IntArrayRef, int64_t b, int64_t t, int64_t h, int64_t w, const optional<Tensor>&,
+                           const optional<Tensor>&, const optional<Tensor>&, const optional<Tensor>&) {
+  return at::empty({b, 3, t, h, w}, images.options().dtype(at::kFloat));
+}
+
+// clip_patches: (B, 3, H, W) fp32 -> the bf16 A operand [B * (size / patch)^2, ld] of the CLIP image tower's patch-embedding GEMM
+// (reference condition.py:322-330: kornia resize, (x + 1) / 2, CLIP mean / std; then open_clip's conv1 unfold)
+Tensor clip_patches_cuda(const Tensor& x, int64_t size, int64_t patch, int64_t ld, at::ArrayRef<double> mean, at::ArrayRef<double> std,
+                         bool antialias) {
+  TORCH_CHECK(x.is_cuda(), "clip_patches: expected a CUDA tensor (the product path is GPU-only)");
+  TORCH_CHECK(x.scalar_type() == at::kFloat && x.is_contiguous() && x.dim() == 4 && x.size(1) == 3, "clip_patches: contiguous fp32 (B, 3, H, W)");
+  TORCH_CHECK(mean.size() == 3 && std.size() == 3, "clip_patches: mean and std have three entries");
+  TORCH_CHECK(size > 0 && patch > 0 && size % patch == 0 && ld >= 3 * patch * patch, "clip_patches: size ", size, ", patch ", patch, ", ld ", ld);
+  const int64_t g = size / patch;
+  Tensor out = at::empty({x.size(0) * g * g, ld}, x.options().dtype(at::kBFloat16));
+  TcClipPatchesParams p = {};
+  p.x = x.data_ptr<float>(); p.out = reinterpret_cast<tc_bf16*>(out.data_ptr());
+  p.b = (int32_t)x.size(0); p.h = (int32_t)x.size(2); p.w = (int32_t)x.size(3);
+  p.size = (int32_t)size; p.patch = (int32_t)patch; p.ld = (int32_t)ld; p.antialias = antialias ? 1 : 0;
+  for (int i = 0; i < 3; ++i) { p.mean[i] = (float)mean[i]; p.std[i] = (float)std[i]; }
+  p.workspace_bytes = tc_clip_patches_workspace(&p);
+  Tensor ws = at::empty({p.workspace_bytes > 16 ? p.workspace_bytes : 16}, x.options().dtype(at::kByte));
+  p.workspace = ws.data_ptr();
+  check_rc(tc_clip_patches(&p, cur_stream()), "tc_clip_patches");
+  return out;
+}
+
+Tensor clip_patches_meta(const Tensor& x, int64_t size, int64_t patch, int64_t ld, at::ArrayRef<double>, at::ArrayRef<double>, bool) {
+  TORCH_CHECK(size > 0 && patch > 0 && size % patch == 0, "clip_patches: size ", size, ", patch ", patch);
+  const int64_t g = size / patch;
+  return at::empty({x.size(0) * g * g, ld}, x.options().dtype(at::kBFloat16));
+}
+
 }  // namespace
 
 TORCH_LIBRARY(tooncrafter, m) {
@@ -505,6 +588,9 @@ TORCH_LIBRARY(tooncrafter, m) {
         "float cfg_img, float guidance_rescale, float sqrt_ac, float sqrt_1m_ac, float sqrt_a_prev, float dir_coef, "
         "float sigma, float x0_rescale) -> (Tensor, Tensor)");
   m.def("ddim_blend(Tensor? x, Tensor x0, Tensor? noise, Tensor? mask, float sqrt_ac, float sqrt_1m_ac) -> Tensor");
+  m.def("frames_from_u8(Tensor images, int[] slots, int b, int t, int h, int w, Tensor? h_bounds, Tensor? h_coefs, "
+        "Tensor? v_bounds, Tensor? v_coefs) -> Tensor");
+  m.def("clip_patches(Tensor x, int size, int patch, int ld, float[] mean, float[] std, bool antialias) -> Tensor");
   m.def("abi_version() -> int");
 }
 
@@ -523,6 +609,8 @@ TORCH_LIBRARY_IMPL(tooncrafter, CUDA, m) {
   m.impl("ddim_step", ddim_step_any<false>);
   m.impl("ddim_step_eps", ddim_step_any<true>);
   m.impl("ddim_blend", ddim_blend_cuda);
+  m.impl("frames_from_u8", frames_from_u8_cuda);
+  m.impl("clip_patches", clip_patches_cuda);
   m.impl("ff_geglu_fused", ff_geglu_fused_cuda);
   m.impl("temporal_attn_fused", temporal_attn_fused_cuda);
   m.impl("temporal_qkv_attn", temporal_qkv_attn_cuda);
@@ -543,6 +631,8 @@ TORCH_LIBRARY_IMPL(tooncrafter, Meta, m) {
   m.impl("ddim_step", ddim_step_meta);
   m.impl("ddim_step_eps", ddim_step_meta);
   m.impl("ddim_blend", ddim_blend_meta);
+  m.impl("frames_from_u8", frames_from_u8_meta);
+  m.impl("clip_patches", clip_patches_meta);
   m.impl("ff_geglu_fused", ff_geglu_fused_meta);
   m.impl("temporal_attn_fused", temporal_attn_fused_meta);
   m.impl("temporal_qkv_attn", temporal_qkv_attn_meta);

@@ -23,7 +23,10 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .. import ops
 from .openclip import _VisualHolder, build_text
+
+CLIP_MEAN, CLIP_STD = (0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711)
 
 
 def _gaussian_kernel1d(ks: int, sigma: float, device, dtype) -> torch.Tensor:
@@ -120,8 +123,8 @@ class FrozenOpenCLIPImageEmbedderV2(AbstractEncoder):
             raise NotImplementedError()
         if freeze:
             self.freeze()
-        self.register_buffer('mean', torch.Tensor([0.48145466, 0.4578275, 0.40821073]), persistent=False)
-        self.register_buffer('std', torch.Tensor([0.26862954, 0.26130258, 0.27577711]), persistent=False)
+        self.register_buffer('mean', torch.Tensor(CLIP_MEAN), persistent=False)
+        self.register_buffer('std', torch.Tensor(CLIP_STD), persistent=False)
 
     def freeze(self):
         self.model = self.model.eval()
@@ -139,3 +142,12 @@ class FrozenOpenCLIPImageEmbedderV2(AbstractEncoder):
 
     def encode_with_vision_transformer(self, x):
         return self.model.visual.tokens(self.preprocess(x))
+
+    def encode_on_device_front(self, x):
+        """`forward` with `preprocess` and the tower's unfold as the one entry point tc_clip_patches instead of ATen's pad /
+        conv2d / interpolate: the path of callers that start from uint8 frames (clip.Conditions.from_uint8).  The same
+        sums taken in double and rounded to bf16 once: close to `forward` (fp32 sums), not bit-equal to it."""
+        v = self.model.visual
+        a = ops.clip_patches(x.float().contiguous(), size=v.grid_size[0] * v.patch_size[0], patch=v.patch_size[0],
+                             ld=v.pk["wc"].shape[1], mean=CLIP_MEAN, std=CLIP_STD, antialias=self.antialias)
+        return v.tokens_from_patches(a)

@@ -143,6 +143,22 @@ class VisionTransformer(PackedModule):
         x = self.transformer.run(x, b, n + 1)
         return x.reshape(b, n + 1, self.width).float()
 
+    def tokens_from_patches(self, a):
+        """`tokens` from the patch-embedding GEMM on: `a` is its A operand, bf16 rows [B * grid^2, K padded] with K =
+        (c, py, px) and zero padding -- what `ops.clip_patches` makes of the frames in one entry point."""
+        pk = self.pk
+        n = self.grid_size[0] * self.grid_size[1]
+        if a.dim() != 2 or a.dtype != BF16 or a.shape[1] != pk["wc"].shape[1] or a.shape[0] == 0 or a.shape[0] % n:
+            raise ValueError(f"vision tower expects bf16 patch rows [B * {n}, {pk['wc'].shape[1]}], got {tuple(a.shape)} {a.dtype}")
+        b = a.shape[0] // n
+        emb = ops.gemm(a, pk["wc"], residual=pk["pos"].repeat(b, 1))                    # + positional embedding
+        x = torch.empty((b, n + 1, self.width), dtype=BF16, device=a.device)           # [class token ; patches]
+        x[:, 0] = pk["cls"]
+        x[:, 1:] = emb.reshape(b, n, self.width)
+        x = ops.layernorm(x.reshape(b * (n + 1), self.width), pk["g"], pk["b"])
+        x = self.transformer.run(x, b, n + 1)
+        return x.reshape(b, n + 1, self.width).float()
+
 
 class CLIPText(PackedModule):
     """The text half of open_clip.model.CLIP as the reference keeps it after `del model.visual`."""

@@ -88,6 +88,7 @@ class HipOps:
         import os
         self.lib = _lib.load()
         self._ws = {}
+        self._resize_tables = {}
         # BASELINE.json configs[4]: TC_FP8 routes eligible GEMMs (see _fp8_eligible) through MXFP8 operands -- weights
         # quantised once, activations by tc_quant_mxfp8 in front of each GEMM.  TC_FP8=1 = "linear": the wide-N
         # projections (qkv, GEGLU), which carry most of the time gain at 2x the bf16 error of a UNet forward;
@@ -760,6 +761,100 @@ class HipOps:
         b, _, t, h, w = video.shape
         out = torch.empty((b, t, h, w, 3), dtype=torch.uint8, device=video.device)
         _lib.check(self.lib.tc_video_to_u8(video.data_ptr(), out.data_ptr(), b, t, h * w, _stream()), "tc_video_to_u8")
+        return out
+
+    def resized_size(self, sh, sw, h, w):
+        """(rh, rw) of an (sh, sw) image under the script's Resize(min(h, w)) (tc_frames_from_u8_resized)."""
+        rh, rw = C.c_int32(), C.c_int32()
+        _lib.check(self.lib.tc_frames_from_u8_resized(int(sh), int(sw), int(h), int(w), C.byref(rh), C.byref(rw)),
+                   "tc_frames_from_u8_resized")
+        return rh.value, rw.value
+
+    def resize_tables(self, n_in, n_out, device):
+        """PIL's 8-bit BILINEAR tables of one axis on `device`: (bounds [n_out, 2], coefs [n_out, kmax]) int32, built on the host
+        by tc_resize_tables and kept per (n_in, n_out, device)."""
+        key = (int(n_in), int(n_out), torch.device(device))
+        tabs = self._resize_tables.get(key)
+        if tabs is None:
+            kmax = self.lib.tc_resize_tables(key[0], key[1], None, None, 0)
+            _lib.check(min(kmax, 0), "tc_resize_tables")
+            bounds = torch.empty((key[1], 2), dtype=torch.int32)
+            coefs = torch.empty((key[1], kmax), dtype=torch.int32)
+            i32p = C.POINTER(C.c_int32)
+            rc = self.lib.tc_resize_tables(key[0], key[1], C.cast(bounds.data_ptr(), i32p), C.cast(coefs.data_ptr(), i32p), coefs.numel())
+            _lib.check(min(rc, 0), "tc_resize_tables")
+            tabs = self._resize_tables[key] = (bounds.to(key[2]), coefs.to(key[2]))
+        return tabs
+
+    @staticmethod
+    def _check_u8_images(images, what):
+        """(n, sh, sw, 3) uint8, pixels packed (a row may be padded: stride(1) >= 3 * sw), on the device."""
+        if not isinstance(images, torch.Tensor) or images.dtype != torch.uint8:
+            raise ValueError(f"{what}: expected a uint8 tensor, got {getattr(images, 'dtype', type(images))}")
+        if images.dim() != 4 or images.shape[3] != 3 or 0 in images.shape:
+            raise ValueError(f"{what}: expected (n, h, w, 3) images, got {tuple(images.shape)}")
+        n, sh, sw, _ = images.shape
+        if images.stride(3) != 1 or images.stride(2) != 3 or images.stride(1) < 3 * sw or (n > 1 and images.stride(0) < sh * images.stride(1)):
+            raise ValueError(f"{what}: pixels must be packed HWC (strides {images.stride()})")
+        if not images.is_cuda:
+            raise _lib.TooncrafterHipError(f"{what}: expected a CUDA tensor: the product path is GPU-only")
+
+    def frames_from_u8(self, images, size, slots, *, b, t, out=None):
+        """uint8 (n, sh, sw, 3) images -> frames of a (b, 3, t, H, W) fp32 clip tensor, size = (H, W): the script's
+        Resize(min(size)) / CenterCrop(size) / ToTensor / Normalize(0.5, 0.5) on PIL images (inference.py:64-69), bit for bit
+        (tc_frames_from_u8).  Image i goes to frame slots[i] = batch * t + frame.  `out`: written in place, frames no slot names
+        keep their contents; default: a new tensor, zero there."""
+        self._check_u8_images(images, "frames_from_u8: images")
+        n, sh, sw, _ = images.shape
+        h, w = (int(v) for v in size)
+        slots = [int(s) for s in slots]
+        if len(slots) != n or any(s < 0 or s >= b * t for s in slots):
+            raise ValueError(f"frames_from_u8: {n} images need {n} slots in [0, {b * t}), got {slots}")
+        if out is None:
+            out = torch.zeros((b, 3, t, h, w), dtype=torch.float32, device=images.device)
+        else:
+            _dev(out, torch.float32, "frames_from_u8: out")
+            if tuple(out.shape) != (b, 3, t, h, w):
+                raise ValueError(f"frames_from_u8: out must be ({b}, 3, {t}, {h}, {w}), got {tuple(out.shape)}")
+        rh, rw = self.resized_size(sh, sw, h, w)
+        p = _lib.TcFramesU8Params(pitch=images.stride(1), image_stride=images.stride(0) if n > 1 else sh * images.stride(1),
+                                  sh=sh, sw=sw, out=out.data_ptr(), b=b, t=t, h=h, w=w)
+        if (rh, rw) != (sh, sw):
+            hb, hc = self.resize_tables(sw, rw, images.device)
+            vb, vc = self.resize_tables(sh, rh, images.device)
+            p.h_bounds, p.h_coefs, p.h_kmax = hb.data_ptr(), hc.data_ptr(), hc.shape[1]
+            p.v_bounds, p.v_coefs, p.v_kmax = vb.data_ptr(), vc.data_ptr(), vc.shape[1]
+        for i in range(0, n, _lib.TC_FRAMES_U8_MAX):
+            part = slots[i:i + _lib.TC_FRAMES_U8_MAX]
+            held = (C.c_int32 * len(part))(*part)
+            p.src, p.n, p.slots = images[i].data_ptr(), len(part), held
+            p.workspace_bytes = self.lib.tc_frames_from_u8_workspace(C.byref(p))
+            ws = self._workspace(p.workspace_bytes, images.device)
+            p.workspace = ws.data_ptr()
+            _lib.check(self.lib.tc_frames_from_u8(C.byref(p), _stream()), "tc_frames_from_u8")
+        return out
+
+    def clip_patches(self, x, *, size, patch, ld, mean, std, antialias=True):
+        """(B, 3, H, W) fp32 in [-1, 1] -> bf16 rows [B * (size / patch)^2, ld], the A operand of the CLIP image tower's
+        patch-embedding GEMM: kornia's antialiased bicubic resize to (size, size), (x + 1) / 2, (x - mean) / std and the
+        unfold (condition.py:322-330 of the reference and open_clip's conv1), columns from 3 * patch^2 on zero
+        (tc_clip_patches)."""
+        if _dev(x, torch.float32, "clip_patches: x") is None or x.dim() != 4 or x.shape[1] != 3 or 0 in x.shape:
+            raise ValueError(f"clip_patches: x must be (B, 3, H, W), got {None if x is None else tuple(x.shape)}")
+        if len(mean) != 3 or len(std) != 3:
+            raise ValueError("clip_patches: mean and std have three entries")
+        size, patch, ld = int(size), int(patch), int(ld)
+        if patch <= 0 or size <= 0 or size % patch or ld < 3 * patch * patch:
+            raise ValueError(f"clip_patches: size {size}, patch {patch}, ld {ld}")
+        b, _, h, w = x.shape
+        out = torch.empty((b * (size // patch) ** 2, ld), dtype=BF16, device=x.device)
+        p = _lib.TcClipPatchesParams(x=x.data_ptr(), out=out.data_ptr(), b=b, h=h, w=w, size=size, patch=patch, ld=ld,
+                                     antialias=1 if antialias else 0)
+        p.mean[:], p.std[:] = [float(v) for v in mean], [float(v) for v in std]
+        p.workspace_bytes = self.lib.tc_clip_patches_workspace(C.byref(p))
+        ws = self._workspace(p.workspace_bytes, x.device)
+        p.workspace = ws.data_ptr()
+        _lib.check(self.lib.tc_clip_patches(C.byref(p), _stream()), "tc_clip_patches")
         return out
 
     def ddim_step(self, x, e_cond, e_uncond, noise, *, cfg_scale, guidance_rescale, sqrt_ac, sqrt_1m_ac,

@@ -136,3 +136,17 @@ class TorchLibOps(HipOps):
         if out is not None:                                  # an explicit result buffer (in place): the ctypes method
             return super().ddim_blend(x, x0, noise, mask, sqrt_ac=sqrt_ac, sqrt_1m_ac=sqrt_1m_ac, out=out)
         return self.t.ddim_blend(x, x0, noise, mask, float(sqrt_ac), float(sqrt_1m_ac))
+
+    def frames_from_u8(self, images, size, slots, *, b, t, out=None):
+        self._check_u8_images(images, "frames_from_u8: images")
+        if out is not None or images.shape[0] > _lib.TC_FRAMES_U8_MAX:     # an explicit result buffer / several calls: the ctypes method
+            return super().frames_from_u8(images, size, slots, b=b, t=t, out=out)
+        (h, w), (sh, sw) = (int(v) for v in size), images.shape[1:3]
+        rh, rw = self.resized_size(sh, sw, h, w)
+        tabs = (None,) * 4
+        if (rh, rw) != (sh, sw):
+            tabs = self.resize_tables(sw, rw, images.device) + self.resize_tables(sh, rh, images.device)
+        return self.t.frames_from_u8(images, [int(s) for s in slots], int(b), int(t), h, w, *tabs)
+
+    def clip_patches(self, x, *, size, patch, ld, mean, std, antialias=True):
+        return self.t.clip_patches(x, int(size), int(patch), int(ld), [float(v) for v in mean], [float(v) for v in std], bool(antialias))
