@@ -513,6 +513,37 @@ typedef struct TcClipPatchesParams {
 int64_t tc_clip_patches_workspace(const TcClipPatchesParams* p);
 int tc_clip_patches(const TcClipPatchesParams* p, void* stream);
 
+/* ---- Per-clip Gaussian noise from a counter-based generator (additive within ABI 14: one struct, one symbol).  Replaces
+ * the sampler's torch.randn draws from the process-wide device generator (reference ddim.py:157, 266 / common.py:31-34,
+ * ddpm3d.py q_sample) when the caller names one seed per clip: element j of clip i is a pure function of
+ * (seeds[i], stream, j).  It does not depend on b, on the clip's position in the batch, on the launch chunking, on the grid
+ * or on the device; it is NOT torch's generator, so it does not reproduce a torch.manual_seed run. ----
+ *   - generator: Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11): multipliers 0xD2511F53 and 0xCD9E8D57, key increments
+ *     0x9E3779B9 and 0xBB67AE85, ten rounds;
+ *   - indexing: for clip i and the 4-element group q = j >> 2, key = (lo32(seeds[i]), hi32(seeds[i])), counter =
+ *     (q, 0, stream, 0); the four output words w0..w3 belong to elements 4q .. 4q + 3;
+ *   - size limit: n > 2^34 returns TC_ESHAPE (q then fits counter word 0 and word 1 is the constant 0);
+ *   - raw != 0: element 4q + m is the word w_m itself (the same bytes of `out` read as uint32);
+ *   - otherwise Box-Muller on word pairs, with u(w) = (2 (w >> 9) + 1) 2^-24 (exact in fp32, in [2^-24, 1 - 2^-24], so
+ *     ln u is finite) and v(w) = (w >> 9) 2^-23:  r(w) = sqrt(-2 ln u(w)),  z0 = r(w0) cos(2 pi v(w1)),
+ *     z1 = r(w0) sin(2 pi v(w1)),  z2, z3 the same from (w2, w3); the accurate logf and sincospif(2 v), not the fast
+ *     intrinsics; then one fp32 multiply by `scale` (1.0f leaves the value as it is);
+ *   - launch shape: one thread produces one Philox block and one 16-byte store; a clip's tail (n % 4) and a row that does
+ *     not start on a 16-byte boundary take scalar stores; the seeds travel as kernel arguments, TC_RANDN_CLIPS clips per
+ *     launch and as many launches as b needs.  No device allocation, no copy, no synchronisation, no workspace.
+ * `seeds` is a HOST array (read before the launches, like `slots` of tc_frames_from_u8); `out` is device memory.
+ * TC_EINVAL: NULL p / out / seeds, b <= 0, n <= 0; TC_ESHAPE: n > 2^34.  Nothing is launched or written on a refusal. */
+#define TC_RANDN_CLIPS 16   /* clips per launch of tc_randn_clips */
+typedef struct TcRandnParams {
+  float* out;             /* (b, n) fp32, or the same bytes as uint32 when raw != 0 */
+  const uint64_t* seeds;  /* HOST array, b entries, one seed per clip */
+  int32_t b; int64_t n;   /* n = elements per clip, any n >= 1 */
+  uint32_t stream;        /* which draw of the clip this is (the samplers' numbering: lvdm/ddim.py) */
+  float scale;            /* the sampler's temperature; one fp32 multiply */
+  int32_t raw;            /* != 0: store the Philox words themselves (for tests and other hosts) */
+} TcRandnParams;
+int tc_randn_clips(const TcRandnParams* p, void* stream);
+
 /* introspection */
 int tc_abi_version(void);
 const char* tc_build_info(void);

@@ -151,7 +151,16 @@ class TcClipPatchesParams(C.Structure):
     ]
 
 
+class TcRandnParams(C.Structure):
+    """Per-clip Philox noise (tc_randn_clips; additive within ABI 14).  `seeds` is a HOST array of b uint64."""
+    _fields_ = [
+        ("out", C.c_void_p), ("seeds", C.POINTER(C.c_uint64)), ("b", C.c_int32), ("n", C.c_int64),
+        ("stream", C.c_uint32), ("scale", C.c_float), ("raw", C.c_int32),
+    ]
+
+
 TC_FRAMES_U8_MAX = 16            # include/tooncrafter_hip.h: images per tc_frames_from_u8 call
+TC_RANDN_CLIPS = 16              # include/tooncrafter_hip.h: clips per launch of tc_randn_clips
 TC_PREFETCH_MAX = 4
 
 
@@ -209,6 +218,7 @@ SYMBOLS = {
     "tc_frames_from_u8": (C.c_int, [C.POINTER(TcFramesU8Params), C.c_void_p]),
     "tc_clip_patches_workspace": (C.c_int64, [C.POINTER(TcClipPatchesParams)]),
     "tc_clip_patches": (C.c_int, [C.POINTER(TcClipPatchesParams), C.c_void_p]),
+    "tc_randn_clips": (C.c_int, [C.POINTER(TcRandnParams), C.c_void_p]),
     "tc_gemm_ws_eligible": (C.c_int, [C.POINTER(TcGemmParams)]),
     "tc_gemm_gn_rows": (C.c_int, [C.POINTER(TcGemmParams)]),
     "tc_groupnorm_part": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,

@@ -19,7 +19,7 @@ hidden states; only those two frames are encoded here (8x less encoder work at T
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import List, Optional
+from typing import List, Optional, Sequence
 
 import torch
 
@@ -140,6 +140,28 @@ class SamplingPlan:
     spacing: str = "uniform_trailing"
     rescale: float = 0.7
     extra: dict = field(default_factory=dict)
+    # one integer in [0, 2^64) per clip of the batch: every Gaussian draw of clip i then comes from tc_randn_clips keyed by
+    # seeds[i] (stream numbering: lvdm/ddim.py), so the clip is the same in any batch, slot or rank and the torch generator
+    # is not touched.  Philox noise, not torch's: it does not reproduce a reference run with seed_everything -- None does.
+    seeds: Optional[Sequence[int]] = None
+
+
+_MASK64 = (1 << 64) - 1
+
+
+def variant_seed(seed: int, k: int) -> int:
+    """The seed of variant `k` of the clip seeded `seed` (`synthesize(..., variants=)`), a pure function so that variant 3
+    can be regenerated alone: k = 0 is the seed itself; k > 0 is the splitmix64 finaliser of seed + k * 0x9E3779B97F4A7C15
+    mod 2^64:  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31  (all mod 2^64)."""
+    seed, k = int(seed), int(k)
+    if not 0 <= seed <= _MASK64 or k < 0:
+        raise ValueError(f"variant_seed: seed {seed} outside [0, 2^64) or variant {k} < 0")
+    if k == 0:
+        return seed
+    z = (seed + k * 0x9E3779B97F4A7C15) & _MASK64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _MASK64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _MASK64
+    return z ^ (z >> 31)
 
 
 def pin_frames(model, frames, t):
@@ -157,21 +179,25 @@ def pin_frames(model, frames, t):
     return x0, mask
 
 
-def sample(model, cond: Conditions, plan: SamplingPlan, latent_shape, x_T=None, pinned=None):
+def sample(model, cond: Conditions, plan: SamplingPlan, latent_shape, x_T=None, pinned=None, variant=0):
     """Latents (b, 4, t, h, w) of one clip batch.  `pinned`: an (x0, mask) pair (`pin_frames`) -- where mask is one the
     latent is held at x0, noised to each step's level, while the rest is sampled (the reference's `mask` / `x0`).  As there,
-    the returned latents are not blended once more: pinned frames come out close to x0, not equal to it."""
+    the returned latents are not blended once more: pinned frames come out close to x0, not equal to it.  With `plan.seeds`
+    (or `seeds` among `plan.extra`) clip i draws from `variant_seed(seeds[i], variant)`."""
     check_frames(latent_shape[2])
     sampler = (ThreeWaySampler if cond.three_way else DDIMSampler)(model)
     extra = dict(plan.extra)
     x_T = extra.pop("x_T", x_T)                    # the reference's callers hand the start noise over among their **kwargs
     x0, mask = pinned if pinned is not None else (None, None)
     x0, mask = extra.pop("x0", x0), extra.pop("mask", mask)       # ... and `mask` / `x0` likewise
+    seeds = extra.pop("seeds", plan.seeds)
+    if seeds is not None:
+        seeds = [variant_seed(s, variant) for s in ops.clip_seeds(seeds, latent_shape[0], "sample: seeds")]
     out, _ = sampler.sample(S=plan.steps, conditioning=cond.positive, batch_size=latent_shape[0], shape=tuple(latent_shape[1:]),
                             verbose=False, unconditional_guidance_scale=plan.scale, unconditional_conditioning=cond.negative,
                             eta=plan.eta, cfg_img=plan.image_scale, mask=mask, x0=x0, fs=cond.fs,
                             timestep_spacing=plan.spacing, guidance_rescale=plan.rescale, x_T=x_T,
-                            unconditional_conditioning_img_nonetext=cond.image_only, **extra)
+                            unconditional_conditioning_img_nonetext=cond.image_only, seeds=seeds, **extra)
     return out
 
 
@@ -194,11 +220,12 @@ def synthesize(model, videos, latent_shape, *, plan: SamplingPlan, prompts=None,
                variants=1, keyframes=None):
     """(b, variants, 3, t, H, W) pixels in [-1, 1].  `keyframes`: {frame index: (b, 3, H, W) pixels} held in place between
     the endpoints while the rest is sampled (`pin_frames`; encoded once for all variants).  The concat conditioning stays
-    endpoints-only: that is what the model was trained on."""
+    endpoints-only: that is what the model was trained on.  With `plan.seeds`, variant k of clip i is the clip seeded
+    `variant_seed(plan.seeds[i], k)`: the same pixels as a `variants=1` run with that seed."""
     cond = Conditions.build(model, videos, prompts=prompts, fs=fs, guided=plan.scale != 1.0,
                             three_way=three_way, image_branch=plan.image_scale != 1.0, hold_endpoints=hold_endpoints)
     pinned = pin_frames(model, keyframes, latent_shape[2]) if keyframes else None
-    clips = [decode_spliced(model, sample(model, cond, plan, latent_shape, pinned=pinned), cond.refs) for _ in range(variants)]
+    clips = [decode_spliced(model, sample(model, cond, plan, latent_shape, pinned=pinned, variant=k), cond.refs) for k in range(variants)]
     return torch.stack(clips, dim=1)
 
 
@@ -206,7 +233,7 @@ def synthesize_u8(model, first_u8, last_u8, latent_shape, *, size, plan: Samplin
                   hold_endpoints=True):
     """uint8 keyframes in, uint8 clip out, all on the device: (b, h, w, 3) first / last frames -> (b, t, H, W, 3) frames
     (`Conditions.from_uint8`, `sample`, `decode_spliced`, `clip_to_uint8`).  The last frame of one clip can be the first
-    keyframe of the next without leaving the GPU."""
+    keyframe of the next without leaving the GPU.  `plan.seeds` as in `sample`."""
     from .output import clip_to_uint8
     cond = Conditions.from_uint8(model, first_u8, last_u8, size=size, t=latent_shape[2], prompts=prompts, fs=fs,
                                  guided=plan.scale != 1.0, three_way=three_way, image_branch=plan.image_scale != 1.0,

@@ -3,7 +3,7 @@
 // The reference binds ATen / xformers operators from Python (utils/utils.py:27-42 instantiates lvdm classes whose
 // forward methods call torch ops); this registers the MI355X kernels as first-class torch operators instead:
 //   torch.ops.tooncrafter.gemm / quant_mxfp8 / gemm_mx / attention / attention_temporal(_rel) / groupnorm(_pf) / layernorm(_pf) / ddim_step(_eps) / ddim_blend /
-//   frames_from_u8 / clip_patches /
+//   frames_from_u8 / clip_patches / randn_clips /
 //   ff_geglu_fused / temporal_attn_fused / temporal_qkv_attn / attention_q8
 // with (i) a CUDA(HIP)-key implementation that validates the tensors, allocates the result from the caching allocator,
 // picks up the CURRENT stream and calls the same extern "C" entry point the ctypes binding calls, and (ii) a Meta-key
@@ -560,6 +560,40 @@ Tensor clip_patches_meta(const Tensor& x, int64_t size, int64_t patch, int64_t l
   return at::empty({x.size(0) * g * g, ld}, x.options().dtype(at::kBFloat16));
 }
 
+// Per-clip Philox noise (tc_randn_clips, additive within ABI 14): (b, ...) fp32 on the current device, clip i from seeds[i] alone;
+// raw: the Philox words as int32 bit patterns.  A seed from 2^63 on arrives as its two's-complement int64.  The op takes no
+// tensor, so the dispatcher cannot read a backend off its arguments: the BackendSelect kernel below sends it to the CUDA key.
+void randn_check(at::IntArrayRef seeds, at::IntArrayRef shape, int64_t stream) {
+  TORCH_CHECK(!shape.empty() && (int64_t)seeds.size() == shape[0], "randn_clips: shape (b, ...) with one seed per clip");
+  for (int64_t v : shape) TORCH_CHECK(v > 0, "randn_clips: sizes must be positive");
+  TORCH_CHECK(shape[0] <= INT32_MAX, "randn_clips: b ", shape[0]);
+  TORCH_CHECK(stream >= 0 && stream <= (int64_t)UINT32_MAX, "randn_clips: stream ", stream, " outside [0, 2^32)");
+}
+
+Tensor randn_clips_cuda(at::IntArrayRef seeds, at::IntArrayRef shape, int64_t stream, double scale, bool raw) {
+  randn_check(seeds, shape, stream);
+  Tensor out = at::empty(shape, at::TensorOptions().device(at::kCUDA).dtype(raw ? at::kInt : at::kFloat));
+  std::vector<uint64_t> held(seeds.begin(), seeds.end());
+  TcRandnParams p = {};
+  p.out = reinterpret_cast<float*>(out.data_ptr());
+  p.seeds = held.data();
+  p.b = (int32_t)shape[0]; p.n = out.numel() / shape[0];
+  p.stream = (uint32_t)stream; p.scale = (float)scale; p.raw = raw ? 1 : 0;
+  check_rc(tc_randn_clips(&p, cur_stream()), "tc_randn_clips");
+  return out;
+}
+
+Tensor randn_clips_meta(at::IntArrayRef seeds, at::IntArrayRef shape, int64_t stream, double, bool raw) {
+  randn_check(seeds, shape, stream);
+  return at::empty(shape, at::TensorOptions().device(at::kMeta).dtype(raw ? at::kInt : at::kFloat));
+}
+
+Tensor randn_clips_select(at::IntArrayRef seeds, at::IntArrayRef shape, int64_t stream, double scale, bool raw) {
+  static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("tooncrafter::randn_clips", "")
+                       .typed<Tensor(at::IntArrayRef, at::IntArrayRef, int64_t, double, bool)>();
+  return op.redispatch(c10::DispatchKeySet(c10::DispatchKey::CUDA), seeds, shape, stream, scale, raw);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(tooncrafter, m) {
@@ -591,6 +625,7 @@ TORCH_LIBRARY(tooncrafter, m) {
   m.def("frames_from_u8(Tensor images, int[] slots, int b, int t, int h, int w, Tensor? h_bounds, Tensor? h_coefs, "
         "Tensor? v_bounds, Tensor? v_coefs) -> Tensor");
   m.def("clip_patches(Tensor x, int size, int patch, int ld, float[] mean, float[] std, bool antialias) -> Tensor");
+  m.def("randn_clips(int[] seeds, int[] shape, int stream, float scale, bool raw) -> Tensor");
   m.def("abi_version() -> int");
 }
 
@@ -611,6 +646,7 @@ TORCH_LIBRARY_IMPL(tooncrafter, CUDA, m) {
   m.impl("ddim_blend", ddim_blend_cuda);
   m.impl("frames_from_u8", frames_from_u8_cuda);
   m.impl("clip_patches", clip_patches_cuda);
+  m.impl("randn_clips", randn_clips_cuda);
   m.impl("ff_geglu_fused", ff_geglu_fused_cuda);
   m.impl("temporal_attn_fused", temporal_attn_fused_cuda);
   m.impl("temporal_qkv_attn", temporal_qkv_attn_cuda);
@@ -633,9 +669,14 @@ TORCH_LIBRARY_IMPL(tooncrafter, Meta, m) {
   m.impl("ddim_blend", ddim_blend_meta);
   m.impl("frames_from_u8", frames_from_u8_meta);
   m.impl("clip_patches", clip_patches_meta);
+  m.impl("randn_clips", randn_clips_meta);
   m.impl("ff_geglu_fused", ff_geglu_fused_meta);
   m.impl("temporal_attn_fused", temporal_attn_fused_meta);
   m.impl("temporal_qkv_attn", temporal_qkv_attn_meta);
+}
+
+TORCH_LIBRARY_IMPL(tooncrafter, BackendSelect, m) {
+  m.impl("randn_clips", randn_clips_select);
 }
 
 TORCH_LIBRARY_IMPL(tooncrafter, CompositeExplicitAutograd, m) {

@@ -19,6 +19,11 @@ What is different underneath:
   * pinned frames (`mask` / `x0`, ddim.py:173-180) are noised by `model.q_sample` and blended
     into the latent by tc_ddim_blend at the top of each step, with the bits of the
     reference's separate torch ops; the mask is made dense fp32 once per call.
+  * `seeds=` (one integer per clip of the batch; not in the reference): every Gaussian draw of the run comes from
+    tc_randn_clips, a pure function of (the clip's seed, the stream number below, the element index), instead of the
+    process-wide device generator.  A clip then gets the same noise in any batch, slot, process or rank, and the torch
+    generator is not touched.  This is Philox noise, not torch's: a seeded run does not reproduce a reference run with
+    seed_everything; the unseeded path (seeds=None) is the one that does, and is unchanged.
 """
 from __future__ import annotations
 
@@ -28,6 +33,15 @@ from tqdm import tqdm
 
 from .. import ops
 from .utils_diffusion import make_ddim_sampling_parameters, make_ddim_timesteps
+
+
+# Stream numbers of a seeded run: which draw of its clip a tc_randn_clips call is.  The step draws are keyed by the DDIM
+# table position `index`, not by the loop counter, so a partial run (`timesteps=`, `decode`) walks the very draws the
+# tail of the full run walks.
+STREAM_X_T = 0                 # x_T, when the caller gave none
+STREAM_STEP = 1                # + index: the step at DDIM table position `index` (drawn only when sigma != 0)
+STREAM_Q_SAMPLE = 0x10000      # + index: the q_sample draw of the pinned-frame blend at that step
+STREAM_ENCODE = 0x20000        # stochastic_encode
 
 
 def noise_like(shape, device, repeat=False):
@@ -117,7 +131,11 @@ class DDIMSampler(object):
                noise_dropout=0., score_corrector=None, corrector_kwargs=None, verbose=True,
                schedule_verbose=False, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
                unconditional_conditioning=None, precision=None, fs=None, timestep_spacing='uniform',
-               guidance_rescale=0.0, **kwargs):
+               guidance_rescale=0.0, seeds=None, **kwargs):
+        if seeds is not None:                        # host checks only, before anything is launched
+            seeds = ops.clip_seeds(seeds, batch_size, "sample: seeds")
+            if kwargs.get("repeat_noise"):
+                raise ValueError("sample: repeat_noise=True shares one draw among the clips; seeds= draws one per clip")
         if conditioning is not None:
             if isinstance(conditioning, dict):
                 first = conditioning[list(conditioning.keys())[0]]
@@ -142,19 +160,26 @@ class DDIMSampler(object):
                                   corrector_kwargs=corrector_kwargs, x_T=x_T, log_every_t=log_every_t,
                                   unconditional_guidance_scale=unconditional_guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning, verbose=verbose,
-                                  precision=precision, fs=fs, guidance_rescale=guidance_rescale, **kwargs)
+                                  precision=precision, fs=fs, guidance_rescale=guidance_rescale, seeds=seeds, **kwargs)
 
     @torch.no_grad()
     def ddim_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None,
                       timesteps=None, quantize_denoised=False, mask=None, x0=None, img_callback=None,
                       log_every_t=100, temperature=1., noise_dropout=0., score_corrector=None,
                       corrector_kwargs=None, unconditional_guidance_scale=1., unconditional_conditioning=None,
-                      verbose=True, precision=None, fs=None, guidance_rescale=0.0, **kwargs):
+                      verbose=True, precision=None, fs=None, guidance_rescale=0.0, seeds=None, **kwargs):
         if ddim_use_original_steps or quantize_denoised or score_corrector is not None:
             raise NotImplementedError("only the DDIM-subsequence sampling path the scripts use")
         device = self.model.betas.device
         b = shape[0]
-        img = torch.randn(shape, device=device) if x_T is None else x_T
+        if seeds is not None:
+            seeds = ops.clip_seeds(seeds, b, "ddim_sampling: seeds")
+        if x_T is not None:
+            img = x_T
+        elif seeds is not None:
+            img = ops.randn_clips(seeds, tuple(shape), STREAM_X_T)
+        else:
+            img = torch.randn(shape, device=device)
         img = img.to(torch.float32).contiguous()
         steps = subset_timesteps(self.ddim_timesteps, timesteps)
         total_steps = steps.shape[0]
@@ -176,13 +201,18 @@ class DDIMSampler(object):
                 # noise_like draw), replace the masked part of the latent.  The timestep goes over as a host integer:
                 # q_sample then reads its two coefficients from host tables.  Never in place: `img` may be the caller's
                 # x_T or an entry of `intermediates`.
-                img_orig = x0 if clean_cond else self.model.q_sample(x0, int(step))
+                if clean_cond:
+                    img_orig = x0
+                elif seeds is not None:
+                    img_orig = self.model.q_sample(x0, int(step), noise=ops.randn_clips(seeds, tuple(x0.shape), STREAM_Q_SAMPLE + index))
+                else:
+                    img_orig = self.model.q_sample(x0, int(step))
                 img = ops.ddim_blend(img, img_orig, None, mask)
             img, pred_x0 = self.p_sample_ddim(img, cond, ts, index=index, temperature=temperature,
                                               noise_dropout=noise_dropout,
                                               unconditional_guidance_scale=unconditional_guidance_scale,
                                               unconditional_conditioning=unconditional_conditioning,
-                                              fs=fs, guidance_rescale=guidance_rescale, _step=int(step), **kwargs)
+                                              fs=fs, guidance_rescale=guidance_rescale, _step=int(step), seeds=seeds, **kwargs)
             if callback:
                 callback(i)
             if img_callback:
@@ -197,10 +227,12 @@ class DDIMSampler(object):
                       quantize_denoised=False, temperature=1., noise_dropout=0., score_corrector=None,
                       corrector_kwargs=None, unconditional_guidance_scale=1., unconditional_conditioning=None,
                       uc_type=None, conditional_guidance_scale_temporal=None, mask=None, x0=None,
-                      guidance_rescale=0.0, _step=None, **kwargs):
+                      guidance_rescale=0.0, _step=None, seeds=None, **kwargs):
         if use_original_steps or quantize_denoised or score_corrector is not None or noise_dropout > 0.:
             raise NotImplementedError("p_sample_ddim variant unused by the inference scripts")
         self.step_kind()
+        if seeds is not None and repeat_noise:
+            raise ValueError("p_sample_ddim: repeat_noise=True shares one draw among the clips; seeds= draws one per clip")
         step = int(t[0]) if _step is None else _step
         use_cfg = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.)
         if not use_cfg:
@@ -211,27 +243,39 @@ class DDIMSampler(object):
             e_c = self.model.apply_model(x, t, c, **kwargs)
             e_u = self.model.apply_model(x, t, unconditional_conditioning, **kwargs)
         sc = self.step_scalars(index, step)
-        # the reference draws the noise every step, also when sigma == 0 (ddim.py:266): draw (and drop) it so
-        # the device generator stays in step with the reference for later draws (x_T of the next variant)
-        noise = noise_like(x.shape, x.device, repeat_noise)
-        if sc["sigma"] != 0.0:
-            if temperature != 1.:
-                noise = noise * temperature
-            noise = noise.to(torch.float32).contiguous()
-        else:
-            noise = None
+        noise = self.step_noise(x, index, sc["sigma"], temperature, repeat_noise, seeds)
         x_prev, pred_x0 = ops.ddim_step(x.contiguous(), e_c.contiguous(), None if e_u is None else e_u.contiguous(),
                                         noise, cfg_scale=unconditional_guidance_scale,
                                         guidance_rescale=guidance_rescale if use_cfg else 0.0, **sc)
         return x_prev, pred_x0
 
+    def step_noise(self, x, index, sigma, temperature, repeat_noise, seeds):
+        """The step's noise operand of tc_ddim_step (None when sigma == 0), shared by the two- and three-way samplers."""
+        if seeds is not None:
+            # one tc_randn_clips launch, the temperature applied as its `scale`; nothing is drawn for a deterministic step
+            # and the device generator is left alone
+            if sigma == 0.0:
+                return None
+            return ops.randn_clips(seeds, tuple(x.shape), STREAM_STEP + index, scale=temperature)
+        # the reference draws the noise every step, also when sigma == 0 (ddim.py:266): draw (and drop) it so
+        # the device generator stays in step with the reference for later draws (x_T of the next variant)
+        noise = noise_like(x.shape, x.device, repeat_noise)
+        if sigma == 0.0:
+            return None
+        if temperature != 1.:
+            noise = noise * temperature
+        return noise.to(torch.float32).contiguous()
+
     @torch.no_grad()
     def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
-               use_original_steps=False, callback=None):
+               use_original_steps=False, callback=None, seeds=None):
         """The last `t_start` steps of the DDIM sequence from `x_latent` (ddim.py:282-301); `make_schedule` first.  Like the
-        reference it hands p_sample_ddim neither `fs` nor a guidance rescale (the UNet falls back to its default_fs)."""
+        reference it hands p_sample_ddim neither `fs` nor a guidance rescale (the UNet falls back to its default_fs).
+        `seeds`: one per sample; the steps then draw what a seeded `sample` draws at the same table positions."""
         if use_original_steps:
             raise NotImplementedError("only the DDIM-subsequence sampling path the scripts use")
+        if seeds is not None:
+            seeds = ops.clip_seeds(seeds, x_latent.shape[0], "decode: seeds")
         timesteps = self.ddim_timesteps[:t_start]
         time_range = np.flip(timesteps)
         total_steps = timesteps.shape[0]
@@ -242,18 +286,23 @@ class DDIMSampler(object):
             ts = torch.full((x_latent.shape[0],), int(step), device=x_latent.device, dtype=torch.long)
             x_dec, _ = self.p_sample_ddim(x_dec, cond, ts, index=index,
                                           unconditional_guidance_scale=unconditional_guidance_scale,
-                                          unconditional_conditioning=unconditional_conditioning, _step=int(step))
+                                          unconditional_conditioning=unconditional_conditioning, _step=int(step), seeds=seeds)
             if callback:
                 callback(i)
         return x_dec
 
     @torch.no_grad()
-    def stochastic_encode(self, x0, t, use_original_steps=False, noise=None):
+    def stochastic_encode(self, x0, t, use_original_steps=False, noise=None, seeds=None):
         """x0 noised to the level of DDIM index `t` (ddim.py:304-317): fast, not an exact inversion.  `t` indexes the DDIM
         tables, one entry per sample; the coefficients are rounded where the reference rounds them (fp32 ddim_alphas, then
-        an fp32 sqrt; fp32 sqrt(1 - ddim_alphas))."""
+        an fp32 sqrt; fp32 sqrt(1 - ddim_alphas)).  `seeds` (one per sample, instead of `noise`): the draw is stream
+        STREAM_ENCODE of each sample's seed."""
         if use_original_steps:
             raise NotImplementedError("only the DDIM-subsequence sampling path the scripts use")
+        if seeds is not None:
+            if noise is not None:
+                raise ValueError("stochastic_encode: give `noise` or `seeds`, not both")
+            noise = ops.randn_clips(ops.clip_seeds(seeds, x0.shape[0], "stochastic_encode: seeds"), tuple(x0.shape), STREAM_ENCODE)
         if noise is None:
             noise = torch.randn_like(x0)
         idx = [int(v) for v in (t.reshape(-1).tolist() if torch.is_tensor(t) else np.atleast_1d(t).tolist())]

@@ -10,8 +10,8 @@ and "image kept, text dropped" (`kwargs['unconditional_conditioning_img_nonetext
 before the usual guidance rescale against e_cond, v-parameterisation and DDIM update.
 scripts/evaluation/funcs.py:61-76 selects it with `multiple_cond_cfg=True`.
 
-`ddim_sampling` -- pinned frames (`mask` / `x0`, :177-184), `clean_cond`, partial runs (`timesteps=`) -- `decode` and
-`stochastic_encode` are inherited from the mirror of samplers/ddim.py, as they are the same code in the reference.
+`ddim_sampling` -- pinned frames (`mask` / `x0`, :177-184), `clean_cond`, partial runs (`timesteps=`), per-clip `seeds=` --
+`decode` and `stochastic_encode` are inherited from the mirror of samplers/ddim.py, as they are the same code in the reference.
 
 Here the three passes are one batch-3B UNet call (`apply_model_multi`) and the combination is part
 of the fused tc_ddim_step kernel (TcDdimParams.e_uncond_img / cfg_img).
@@ -21,7 +21,6 @@ from __future__ import annotations
 import torch
 
 from .. import ops
-from . import ddim as _ddim
 from .ddim import DDIMSampler as _DDIMSampler
 
 
@@ -30,10 +29,13 @@ class DDIMSampler(_DDIMSampler):
     def p_sample_ddim(self, x, c, t, index, repeat_noise=False, use_original_steps=False,
                       quantize_denoised=False, temperature=1., noise_dropout=0., score_corrector=None,
                       corrector_kwargs=None, unconditional_guidance_scale=1., unconditional_conditioning=None,
-                      uc_type=None, cfg_img=None, mask=None, x0=None, guidance_rescale=0.0, _step=None, **kwargs):
+                      uc_type=None, cfg_img=None, mask=None, x0=None, guidance_rescale=0.0, _step=None, seeds=None,
+                      **kwargs):
         if use_original_steps or quantize_denoised or score_corrector is not None or noise_dropout > 0.:
             raise NotImplementedError("p_sample_ddim variant unused by the inference scripts")
         self.step_kind()
+        if seeds is not None and repeat_noise:
+            raise ValueError("p_sample_ddim: repeat_noise=True shares one draw among the clips; seeds= draws one per clip")
         if cfg_img is None:
             cfg_img = unconditional_guidance_scale                                  # :217-218
         uc_img = kwargs['unconditional_conditioning_img_nonetext']                   # :220 (KeyError like the reference)
@@ -49,13 +51,7 @@ class DDIMSampler(_DDIMSampler):
             e_u = self.model.apply_model(x, t, unconditional_conditioning, **kwargs)
             e_i = self.model.apply_model(x, t, uc_img, **kwargs)
         sc = self.step_scalars(index, step)
-        noise = _ddim.noise_like(x.shape, x.device, repeat_noise)     # always drawn, like the reference (:277)
-        if sc["sigma"] != 0.0:
-            if temperature != 1.:
-                noise = noise * temperature
-            noise = noise.to(torch.float32).contiguous()
-        else:
-            noise = None
+        noise = self.step_noise(x, index, sc["sigma"], temperature, repeat_noise, seeds)    # unseeded: always drawn, like the reference (:277)
         cont = lambda v: None if v is None else v.contiguous()
         return ops.ddim_step(x.contiguous(), e_c.contiguous(), cont(e_u), noise,
                              cfg_scale=unconditional_guidance_scale,

@@ -60,6 +60,21 @@ def _dev(t: Optional[torch.Tensor], dtype, what: str, contiguous: bool = True):
     return t.data_ptr()
 
 
+def clip_seeds(seeds, b: int, what: str = "seeds"):
+    """The per-clip seeds of a batch of `b` as a list of Python ints, or ValueError: one integer in [0, 2^64) per clip
+    (tc_randn_clips keys Philox with the two 32-bit halves).  Host-only: callers check before anything is launched."""
+    import numbers
+    if isinstance(seeds, (str, bytes)) or not hasattr(seeds, "__len__"):
+        raise ValueError(f"{what}: expected a sequence of {b} integers, got {type(seeds).__name__}")
+    seeds = list(seeds)
+    if len(seeds) != b:
+        raise ValueError(f"{what}: {len(seeds)} seeds for a batch of {b} clips")
+    for s in seeds:
+        if isinstance(s, bool) or not isinstance(s, numbers.Integral) or not 0 <= int(s) < 1 << 64:
+            raise ValueError(f"{what}: a seed is an integer in [0, 2^64), got {s!r}")
+    return [int(s) for s in seeds]
+
+
 class MxRows:
     """An activation that exists only as MXFP8 (e4m3 bytes + E8M0 block scales): what `layernorm(..., mx_for=...)`
     hands to the one GEMM that consumes it when the fp8 routing takes that GEMM."""
@@ -855,6 +870,37 @@ class HipOps:
         ws = self._workspace(p.workspace_bytes, x.device)
         p.workspace = ws.data_ptr()
         _lib.check(self.lib.tc_clip_patches(C.byref(p), _stream()), "tc_clip_patches")
+        return out
+
+    @staticmethod
+    def _randn_args(seeds, shape, stream, what="randn_clips"):
+        shape = tuple(int(v) for v in shape)
+        if len(shape) < 1 or min(shape) <= 0:
+            raise ValueError(f"{what}: shape (b, ...) with positive sizes, got {shape}")
+        stream = int(stream)
+        if not 0 <= stream < 1 << 32:
+            raise ValueError(f"{what}: stream {stream} outside [0, 2^32)")
+        return clip_seeds(seeds, shape[0], f"{what}: seeds"), shape, stream
+
+    def randn_clips(self, seeds, shape, stream, scale=1.0, out=None, raw=False):
+        """Gaussian noise of shape (b, ...), clip i drawn from seeds[i] alone (tc_randn_clips): Philox4x32-10 keyed by the
+        seed, counter (element >> 2, 0, stream, 0), Box-Muller, times `scale`.  The row of a seed is the same bits in any
+        batch, slot or process; the torch generator is not touched.  `stream` names the draw (lvdm/ddim.py numbers the
+        sampler's).  `raw`: the Philox words themselves, as int32 bit patterns.  `out`: a contiguous fp32 (raw: fp32 or
+        int32) device tensor of that shape to fill instead of a new one."""
+        seeds, shape, stream = self._randn_args(seeds, shape, stream)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int32 if raw else torch.float32, device="cuda")
+        else:
+            words_as_int = raw and getattr(out, "dtype", None) == torch.int32
+            _dev(out, torch.int32 if words_as_int else torch.float32, "randn_clips: out")
+            if tuple(out.shape) != shape:
+                raise ValueError(f"randn_clips: out must be {shape}, got {tuple(out.shape)}")
+        b = shape[0]
+        held = (C.c_uint64 * b)(*seeds)
+        p = _lib.TcRandnParams(out=out.data_ptr(), seeds=held, b=b, n=out.numel() // b, stream=stream, scale=float(scale),
+                               raw=1 if raw else 0)
+        _lib.check(self.lib.tc_randn_clips(C.byref(p), _stream()), "tc_randn_clips")
         return out
 
     def ddim_step(self, x, e_cond, e_uncond, noise, *, cfg_scale, guidance_rescale, sqrt_ac, sqrt_1m_ac,

@@ -150,3 +150,10 @@ class TorchLibOps(HipOps):
 
     def clip_patches(self, x, *, size, patch, ld, mean, std, antialias=True):
         return self.t.clip_patches(x, int(size), int(patch), int(ld), [float(v) for v in mean], [float(v) for v in std], bool(antialias))
+
+    def randn_clips(self, seeds, shape, stream, scale=1.0, out=None, raw=False):
+        if out is not None:                                  # an explicit result buffer: the ctypes method
+            return super().randn_clips(seeds, shape, stream, scale, out=out, raw=raw)
+        seeds, shape, stream = self._randn_args(seeds, shape, stream)
+        # the schema's int is an int64: a seed from 2^63 on goes over as its two's complement
+        return self.t.randn_clips([s - (1 << 64) if s >= 1 << 63 else s for s in seeds], list(shape), stream, float(scale), bool(raw))
