@@ -415,6 +415,32 @@ int tc_ddim_step(const TcDdimParams* p, void* workspace, int64_t workspace_bytes
  * branch of the reference reads (ddim.py:251-254).  TC_EINVAL also for sqrt_ac == 0 (a zero-terminal-SNR step). */
 int tc_ddim_step_eps(const TcDdimParams* p, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* The same step with a second-order multistep correction (additive within ABI 14: one struct, two symbols; the workspace
+ * and the statistics pass of tc_ddim_step).  Not in the reference, whose samplers know the first-order update only; it
+ * extends the call sites of tc_ddim_step / tc_ddim_step_eps in samplers/ddim.py:226-277 and ddim_multiplecond.py:226-288
+ * when the sampler is asked for solver_order = 2.  In exponential-integrator form this is DPM-Solver++(2M) (eta = 0) and
+ * its SDE variant (eta = 1), written as the first-order update plus ONE term:
+ *   x0u    = pred_x0 before x0_rescale   (v: sqrt_ac * x - sqrt_1m_ac * v;  eps: (x - sqrt_1m_ac * e_t) / sqrt_ac)
+ *   x_prev = sqrt_a_prev * (x0u * x0_rescale) + dir_coef * e_t + corr * (x0u - x0_hist) + sigma * noise
+ *   corr   = (sqrt_a_prev * x0_rescale - dir_coef * sqrt_ac / sqrt_1m_ac) * h / (2 * h_prev)
+ * x0_hist is the pred_x0 the PREVIOUS step returned (already rescaled, so on the scale of this step's x0u), h and h_prev
+ * this and the previous step's increments of log(sqrt(alpha) * scale / sqrt(1 - alpha)).  corr is one host scalar, computed
+ * in double and rounded once; the callers pass 0 on the first step of a run, after a step with alpha = 0 (h_prev is not
+ * finite) and on the final step.  The correction is added last before the noise term; every other operation is
+ * tc_ddim_step's in its order, and pred_x0 is tc_ddim_step's.  x0_hist is read only when it is not NULL and corr != 0;
+ * with x0_hist == NULL or corr == 0 both outputs are bit-identical to tc_ddim_step / tc_ddim_step_eps.
+ * Any n >= 2; 16-byte vectors are used when every pointer and every sample's base allow it.
+ * Aliasing: `base.pred_x0` may be EXACTLY `x0_hist` (the history updated in place; pred_x0 is then not NULL); any other
+ * overlap of x_prev or pred_x0 with x0_hist returns TC_EINVAL.  Also TC_EINVAL: a corr that is not finite, whatever
+ * tc_ddim_step / tc_ddim_step_eps refuse (sqrt_ac == 0 in the eps form included).  Nothing is launched on a refusal. */
+typedef struct TcDdimMsParams {
+  TcDdimParams base;     /* the step as tc_ddim_step takes it */
+  const float* x0_hist;  /* the previous step's pred_x0 (B, n) fp32, or NULL: no history */
+  float corr;            /* 0: first-order step */
+} TcDdimMsParams;
+int tc_ddim_step_ms(const TcDdimMsParams* p, void* workspace, int64_t workspace_bytes, void* stream);
+int tc_ddim_step_ms_eps(const TcDdimMsParams* p, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Pinned-frame blend and forward noising of the samplers, one elementwise launch (additive within ABI 14: one struct,
  * one symbol).  Replaces the mask / x0 blend at the top of a sampling step (ddim.py:173-180, ddim_multiplecond.py:177-184),
  * q_sample (ddpm3d.py:306-309) and the last line of stochastic_encode (ddim.py:316-317):

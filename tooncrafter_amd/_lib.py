@@ -80,6 +80,11 @@ class TcDdimParams(C.Structure):
     ]
 
 
+class TcDdimMsParams(C.Structure):
+    """tc_ddim_step_ms / tc_ddim_step_ms_eps: the step plus the multistep history term (additive within ABI 14)."""
+    _fields_ = [("base", TcDdimParams), ("x0_hist", C.c_void_p), ("corr", C.c_float)]
+
+
 class TcDdimBlendParams(C.Structure):
     """Pinned-frame blend / forward noising (tc_ddim_blend; additive within ABI 14)."""
     _fields_ = [
@@ -211,6 +216,8 @@ SYMBOLS = {
     "tc_ddim_workspace": (C.c_int64, [C.c_int32]),
     "tc_ddim_step": (C.c_int, [C.POINTER(TcDdimParams), C.c_void_p, C.c_int64, C.c_void_p]),
     "tc_ddim_step_eps": (C.c_int, [C.POINTER(TcDdimParams), C.c_void_p, C.c_int64, C.c_void_p]),
+    "tc_ddim_step_ms": (C.c_int, [C.POINTER(TcDdimMsParams), C.c_void_p, C.c_int64, C.c_void_p]),
+    "tc_ddim_step_ms_eps": (C.c_int, [C.POINTER(TcDdimMsParams), C.c_void_p, C.c_int64, C.c_void_p]),
     "tc_ddim_blend": (C.c_int, [C.POINTER(TcDdimBlendParams), C.c_void_p]),
     "tc_resize_tables": (C.c_int32, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64]),
     "tc_frames_from_u8_resized": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

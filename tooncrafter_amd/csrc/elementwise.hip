@@ -2,6 +2,9 @@
 // and the fused DDIM / classifier-free-guidance step.  All HBM- or latency-bound, gfx950.
 #include "common.h"
 
+#include <cmath>
+#include <initializer_list>
+
 namespace {
 
 // (B, C, T, HW) fp32 [x0 | x1 on C] -> rows [(b t hw), c_pad] bf16, zero padded.
@@ -253,6 +256,90 @@ TC_DDIM_APPLY_KERNEL(ddim_apply_kernel, false)
 TC_DDIM_APPLY_KERNEL(ddim_apply_eps_kernel, true)
 #undef TC_DDIM_APPLY_KERNEL
 
+// The apply pass with the second-order multistep term (tc_ddim_step_ms): the update above plus corr * (x0u - hist), where
+// x0u is pred_x0 BEFORE x0_rescale and hist the previous step's returned pred_x0.  Every other operation is written as
+// in TC_DDIM_APPLY_KERNEL, expression by expression, so that under -ffp-contract=on (contraction inside one expression
+// only) it rounds where that kernel rounds: with `hist_on` false the results are that kernel's bits.
+__device__ __forceinline__ float ddim_rescale_factor(const TcDdimParams& p, const double* __restrict__ part, int b) {
+  double s[4] = {0, 0, 0, 0};
+  for (int k = 0; k < DDIM_PARTS; ++k)
+    for (int j = 0; j < 4; ++j) s[j] += part[((int64_t)b * DDIM_PARTS + k) * 4 + j];
+  const double n = (double)p.n;
+  const double var_t = (s[1] - s[0] * s[0] / n) / (n - 1.0);
+  const double var_c = (s[3] - s[2] * s[2] / n) / (n - 1.0);
+  const float std_t = (float)sqrt(var_t > 0 ? var_t : 0.0);
+  const float std_c = (float)sqrt(var_c > 0 ? var_c : 0.0);
+  return std_t / std_c;
+}
+
+// One element.  eu / ei / nz / hist are read by the caller only where their operand exists.
+template <bool EPS>
+__device__ __forceinline__ void ddim_ms_one(const TcDdimParams& p, bool cfg, bool resc, float factor, bool hist_on, float corr,
+                                            float x, float v, float eu, float ei, float nz, float hist, float& xp_out,
+                                            float& x0_out) {
+  if (cfg) {
+    v = p.e_uncond_img ? cfg_combine3(v, eu, ei, p.cfg_scale, p.cfg_img) : cfg_combine(v, eu, p.cfg_scale);
+    if (resc) v = p.guidance_rescale * (v * factor) + (1.f - p.guidance_rescale) * v;
+  }
+  const float e_t = EPS ? v : p.sqrt_ac * v + p.sqrt_1m_ac * x;
+  const float x0u = EPS ? (x - p.sqrt_1m_ac * v) / p.sqrt_ac : p.sqrt_ac * x - p.sqrt_1m_ac * v;
+  float x0 = x0u;
+  x0 *= p.x0_rescale;
+  float xp = p.sqrt_a_prev * x0 + p.dir_coef * e_t;
+  if (hist_on) xp += corr * (x0u - hist);
+  if (p.noise) xp += p.sigma * nz;
+  xp_out = xp;
+  x0_out = x0;
+}
+
+// VEC: every pointer is 16-byte aligned and so is every sample's base (n % 4 == 0, or one sample) -- float4 body, then the
+// n % 4 tail as scalars.  `hist` may be exactly p.pred_x0 (the history updated in place): each element is read and then
+// written by the same thread, so it is not __restrict__.
+template <bool EPS, bool VEC>
+__global__ __launch_bounds__(256) void ddim_apply_ms_kernel(TcDdimParams p, const float* hist, float corr,
+                                                            const double* __restrict__ part) {
+  __shared__ float factor_s;
+  const int b = blockIdx.y;
+  const bool cfg = p.e_uncond != nullptr;
+  const bool resc = cfg && p.guidance_rescale > 0.f;
+  const bool three = cfg && p.e_uncond_img != nullptr;
+  const bool hist_on = hist != nullptr && corr != 0.f;
+  if (threadIdx.x == 0) factor_s = resc ? ddim_rescale_factor(p, part, b) : 1.f;
+  __syncthreads();
+  const float factor = factor_s;
+  const int64_t base = (int64_t)b * p.n;
+  const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+  int64_t done = 0;
+  if (VEC) {
+    const float4 zero = float4{0.f, 0.f, 0.f, 0.f};
+    const int64_t vecs = p.n >> 2;
+    for (int64_t i = tid; i < vecs; i += stride) {
+      const float4 x = reinterpret_cast<const float4*>(p.x + base)[i];
+      const float4 v = reinterpret_cast<const float4*>(p.e_cond + base)[i];
+      const float4 eu = cfg ? reinterpret_cast<const float4*>(p.e_uncond + base)[i] : zero;
+      const float4 ei = three ? reinterpret_cast<const float4*>(p.e_uncond_img + base)[i] : zero;
+      const float4 nz = p.noise ? reinterpret_cast<const float4*>(p.noise + base)[i] : zero;
+      const float4 h = hist_on ? reinterpret_cast<const float4*>(hist + base)[i] : zero;
+      float4 xp, x0;
+      ddim_ms_one<EPS>(p, cfg, resc, factor, hist_on, corr, x.x, v.x, eu.x, ei.x, nz.x, h.x, xp.x, x0.x);
+      ddim_ms_one<EPS>(p, cfg, resc, factor, hist_on, corr, x.y, v.y, eu.y, ei.y, nz.y, h.y, xp.y, x0.y);
+      ddim_ms_one<EPS>(p, cfg, resc, factor, hist_on, corr, x.z, v.z, eu.z, ei.z, nz.z, h.z, xp.z, x0.z);
+      ddim_ms_one<EPS>(p, cfg, resc, factor, hist_on, corr, x.w, v.w, eu.w, ei.w, nz.w, h.w, xp.w, x0.w);
+      reinterpret_cast<float4*>(p.x_prev + base)[i] = xp;
+      if (p.pred_x0) reinterpret_cast<float4*>(p.pred_x0 + base)[i] = x0;
+    }
+    done = vecs << 2;
+  }
+  for (int64_t i = done + tid; i < p.n; i += stride) {
+    float xp, x0;
+    ddim_ms_one<EPS>(p, cfg, resc, factor, hist_on, corr, p.x[base + i], p.e_cond[base + i], cfg ? p.e_uncond[base + i] : 0.f,
+                     three ? p.e_uncond_img[base + i] : 0.f, p.noise ? p.noise[base + i] : 0.f,
+                     hist_on ? hist[base + i] : 0.f, xp, x0);
+    p.x_prev[base + i] = xp;
+    if (p.pred_x0) p.pred_x0[base + i] = x0;
+  }
+}
+
 // Pinned-frame blend / forward noising (tc_ddim_blend), flat over the b * n elements.  Every product, the subtraction and every
 // sum is rounded on its own, where the reference's separate torch ops round (ddim.py:176-180, ddpm3d.py:306-309): the
 // library is built with -ffp-contract=on, which would turn `a * b + c * d` into a multiply and an FMA.
@@ -424,19 +511,31 @@ extern "C" int tc_video_to_u8(const float* x, uint8_t* out, int32_t b, int32_t t
 
 extern "C" int64_t tc_ddim_workspace(int32_t b) { return b > 0 ? (int64_t)b * DDIM_PARTS * 4 * sizeof(double) : 0; }
 
-static int ddim_step_launch(const TcDdimParams* pp, void* workspace, int64_t workspace_bytes, void* stream, bool eps) {
-  if (!pp) return TC_EINVAL;
-  const TcDdimParams& p = *pp;
+// The argument checks of a step, shared by tc_ddim_step(_eps) and tc_ddim_step_ms(_eps); nothing is launched.
+static int ddim_step_check(const TcDdimParams& p, const void* workspace, int64_t workspace_bytes) {
   if (!p.x || !p.e_cond || !p.x_prev || p.b <= 0 || p.n <= 1) return TC_EINVAL;
   if (p.e_uncond_img && !p.e_uncond) return TC_EINVAL;
   if (!workspace || workspace_bytes < tc_ddim_workspace(p.b)) return TC_EWORKSPACE;
   if (p.b > 65535) return TC_ESHAPE;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  double* part = reinterpret_cast<double*>(workspace);
+  return TC_OK;
+}
+
+// Pass 1, when the step rescales its guidance.
+static int ddim_stats_launch(const TcDdimParams& p, double* part, hipStream_t s) {
   if (p.e_uncond && p.guidance_rescale > 0.f) {
     hipLaunchKernelGGL(ddim_stats_kernel, dim3(DDIM_PARTS, p.b), dim3(256), 0, s, p, part);
     TC_LAUNCH_CHECK();
   }
+  return TC_OK;
+}
+
+static int ddim_step_launch(const TcDdimParams* pp, void* workspace, int64_t workspace_bytes, void* stream, bool eps) {
+  if (!pp) return TC_EINVAL;
+  const TcDdimParams& p = *pp;
+  if (const int rc = ddim_step_check(p, workspace, workspace_bytes)) return rc;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  double* part = reinterpret_cast<double*>(workspace);
+  if (const int rc = ddim_stats_launch(p, part, s)) return rc;
   const dim3 grid(grid_for(p.n, 256, 256), p.b);
   if (eps)
     hipLaunchKernelGGL(ddim_apply_eps_kernel, grid, dim3(256), 0, s, p, part);
@@ -453,6 +552,46 @@ extern "C" int tc_ddim_step(const TcDdimParams* pp, void* workspace, int64_t wor
 extern "C" int tc_ddim_step_eps(const TcDdimParams* pp, void* workspace, int64_t workspace_bytes, void* stream) {
   if (pp && pp->sqrt_ac == 0.f) return TC_EINVAL;          // eps divides by sqrt_ac: a zero-terminal-SNR step has no eps form
   return ddim_step_launch(pp, workspace, workspace_bytes, stream, true);
+}
+
+static int ddim_step_ms_launch(const TcDdimMsParams* mp, void* workspace, int64_t workspace_bytes, void* stream, bool eps) {
+  if (!mp) return TC_EINVAL;
+  const TcDdimParams& p = mp->base;
+  if (const int rc = ddim_step_check(p, workspace, workspace_bytes)) return rc;
+  if (eps && p.sqrt_ac == 0.f) return TC_EINVAL;
+  if (!std::isfinite(mp->corr)) return TC_EINVAL;
+  const float* hist = mp->x0_hist;
+  if (hist) {                                             // an output over the history, other than pred_x0 == x0_hist exactly
+    const uintptr_t bytes = (uintptr_t)p.b * (uintptr_t)p.n * sizeof(float), h = reinterpret_cast<uintptr_t>(hist);
+    const uintptr_t xp = reinterpret_cast<uintptr_t>(p.x_prev), x0 = reinterpret_cast<uintptr_t>(p.pred_x0);
+    if (xp < h + bytes && h < xp + bytes) return TC_EINVAL;
+    if (p.pred_x0 && x0 != h && x0 < h + bytes && h < x0 + bytes) return TC_EINVAL;
+  }
+  bool vec = (p.n & 3) == 0 || p.b == 1;
+  for (const void* q : {(const void*)p.x, (const void*)p.e_cond, (const void*)p.e_uncond, (const void*)p.e_uncond_img,
+                        (const void*)p.noise, (const void*)hist, (const void*)p.x_prev, (const void*)p.pred_x0})
+    vec = vec && tc_aligned16(q);                         // NULL counts as aligned: that operand is not touched
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  double* part = reinterpret_cast<double*>(workspace);
+  if (const int rc = ddim_stats_launch(p, part, s)) return rc;
+  const dim3 grid(grid_for(vec ? (p.n + 3) >> 2 : p.n, 256, 256), p.b);
+  if (eps) {
+    if (vec) hipLaunchKernelGGL((ddim_apply_ms_kernel<true, true>), grid, dim3(256), 0, s, p, hist, mp->corr, part);
+    else hipLaunchKernelGGL((ddim_apply_ms_kernel<true, false>), grid, dim3(256), 0, s, p, hist, mp->corr, part);
+  } else {
+    if (vec) hipLaunchKernelGGL((ddim_apply_ms_kernel<false, true>), grid, dim3(256), 0, s, p, hist, mp->corr, part);
+    else hipLaunchKernelGGL((ddim_apply_ms_kernel<false, false>), grid, dim3(256), 0, s, p, hist, mp->corr, part);
+  }
+  TC_LAUNCH_CHECK();
+  return TC_OK;
+}
+
+extern "C" int tc_ddim_step_ms(const TcDdimMsParams* p, void* workspace, int64_t workspace_bytes, void* stream) {
+  return ddim_step_ms_launch(p, workspace, workspace_bytes, stream, false);
+}
+
+extern "C" int tc_ddim_step_ms_eps(const TcDdimMsParams* p, void* workspace, int64_t workspace_bytes, void* stream) {
+  return ddim_step_ms_launch(p, workspace, workspace_bytes, stream, true);
 }
 
 extern "C" int tc_ddim_blend(const TcDdimBlendParams* pp, void* stream) {

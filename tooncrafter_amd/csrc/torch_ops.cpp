@@ -2,7 +2,7 @@
 //
 // The reference binds ATen / xformers operators from Python (utils/utils.py:27-42 instantiates lvdm classes whose
 // forward methods call torch ops); this registers the MI355X kernels as first-class torch operators instead:
-//   torch.ops.tooncrafter.gemm / quant_mxfp8 / gemm_mx / attention / attention_temporal(_rel) / groupnorm(_pf) / layernorm(_pf) / ddim_step(_eps) / ddim_blend /
+//   torch.ops.tooncrafter.gemm / quant_mxfp8 / gemm_mx / attention / attention_temporal(_rel) / groupnorm(_pf) / layernorm(_pf) / ddim_step(_eps) / ddim_step_ms(_eps) / ddim_blend /
 //   frames_from_u8 / clip_patches / randn_clips /
 //   ff_geglu_fused / temporal_attn_fused / temporal_qkv_attn / attention_q8
 // with (i) a CUDA(HIP)-key implementation that validates the tensors, allocates the result from the caching allocator,
@@ -421,15 +421,18 @@ Tensor layernorm_cuda(const Tensor& x, const Tensor& gamma, const Tensor& beta, 
 Tensor like_meta3(const Tensor& x, const Tensor&, const Tensor&, int64_t, int64_t, double, bool) { return at::empty_like(x); }
 Tensor like_meta_ln(const Tensor& x, const Tensor&, const Tensor&, double) { return at::empty_like(x); }
 
-template <bool EPS>
-std::tuple<Tensor, Tensor> ddim_step_any(const Tensor& x, const Tensor& e_cond, const optional<Tensor>& e_uncond,
-                                         const optional<Tensor>& noise, const optional<Tensor>& e_uncond_img, double cfg_scale,
-                                         double cfg_img, double guidance_rescale, double sqrt_ac, double sqrt_1m_ac,
-                                         double sqrt_a_prev, double dir_coef, double sigma, double x0_rescale) {
+// The checked TcDdimParams of a step; x_prev and x0 are its two results.
+TcDdimParams ddim_params(const char* what, const Tensor& x, const Tensor& e_cond, const optional<Tensor>& e_uncond,
+                         const optional<Tensor>& noise, const optional<Tensor>& e_uncond_img, const optional<Tensor>& x0_hist,
+                         Tensor& x_prev, Tensor& x0, double cfg_scale, double cfg_img, double guidance_rescale, double sqrt_ac,
+                         double sqrt_1m_ac, double sqrt_a_prev, double dir_coef, double sigma, double x0_rescale) {
   auto ok = [](const Tensor& t) { return t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous(); };
   TORCH_CHECK(ok(x) && ok(e_cond) && (!e_uncond.has_value() || ok(*e_uncond)) && (!noise.has_value() || ok(*noise)) &&
-              (!e_uncond_img.has_value() || ok(*e_uncond_img)), "ddim_step: contiguous fp32 CUDA tensors");
-  Tensor x_prev = at::empty_like(x), x0 = at::empty_like(x);
+              (!e_uncond_img.has_value() || ok(*e_uncond_img)) && (!x0_hist.has_value() || ok(*x0_hist)),
+              what, ": contiguous fp32 CUDA tensors");
+  TORCH_CHECK(!x0_hist.has_value() || x0_hist->sizes() == x.sizes(), what, ": x0_hist must have the shape of x");
+  x_prev = at::empty_like(x);
+  x0 = at::empty_like(x);
   TcDdimParams p = {};
   p.x = x.data_ptr<float>(); p.e_cond = e_cond.data_ptr<float>();
   p.e_uncond = e_uncond.has_value() ? e_uncond->data_ptr<float>() : nullptr;
@@ -440,6 +443,17 @@ std::tuple<Tensor, Tensor> ddim_step_any(const Tensor& x, const Tensor& e_cond, 
   p.cfg_scale = (float)cfg_scale; p.cfg_img = (float)cfg_img; p.guidance_rescale = (float)guidance_rescale;
   p.sqrt_ac = (float)sqrt_ac; p.sqrt_1m_ac = (float)sqrt_1m_ac; p.sqrt_a_prev = (float)sqrt_a_prev;
   p.dir_coef = (float)dir_coef; p.sigma = (float)sigma; p.x0_rescale = (float)x0_rescale;
+  return p;
+}
+
+template <bool EPS>
+std::tuple<Tensor, Tensor> ddim_step_any(const Tensor& x, const Tensor& e_cond, const optional<Tensor>& e_uncond,
+                                         const optional<Tensor>& noise, const optional<Tensor>& e_uncond_img, double cfg_scale,
+                                         double cfg_img, double guidance_rescale, double sqrt_ac, double sqrt_1m_ac,
+                                         double sqrt_a_prev, double dir_coef, double sigma, double x0_rescale) {
+  Tensor x_prev, x0;
+  const TcDdimParams p = ddim_params("ddim_step", x, e_cond, e_uncond, noise, e_uncond_img, c10::nullopt, x_prev, x0, cfg_scale,
+                                     cfg_img, guidance_rescale, sqrt_ac, sqrt_1m_ac, sqrt_a_prev, dir_coef, sigma, x0_rescale);
   const int64_t nbytes = tc_ddim_workspace(p.b);
   Tensor ws = at::empty({nbytes > 16 ? nbytes : 16}, x.options().dtype(at::kByte));
   if (EPS)
@@ -451,6 +465,34 @@ std::tuple<Tensor, Tensor> ddim_step_any(const Tensor& x, const Tensor& e_cond, 
 
 std::tuple<Tensor, Tensor> ddim_step_meta(const Tensor& x, const Tensor&, const optional<Tensor>&, const optional<Tensor>&,
                                           const optional<Tensor>&, double, double, double, double, double, double, double, double, double) {
+  return std::make_tuple(at::empty_like(x), at::empty_like(x));
+}
+
+// The step with the second-order multistep term (additive within ABI 14): x0_hist is the previous step's pred_x0 or None.
+template <bool EPS>
+std::tuple<Tensor, Tensor> ddim_step_ms_any(const Tensor& x, const Tensor& e_cond, const optional<Tensor>& e_uncond,
+                                            const optional<Tensor>& noise, const optional<Tensor>& e_uncond_img,
+                                            const optional<Tensor>& x0_hist, double corr, double cfg_scale, double cfg_img,
+                                            double guidance_rescale, double sqrt_ac, double sqrt_1m_ac, double sqrt_a_prev,
+                                            double dir_coef, double sigma, double x0_rescale) {
+  Tensor x_prev, x0;
+  TcDdimMsParams mp = {};
+  mp.base = ddim_params("ddim_step_ms", x, e_cond, e_uncond, noise, e_uncond_img, x0_hist, x_prev, x0, cfg_scale, cfg_img,
+                        guidance_rescale, sqrt_ac, sqrt_1m_ac, sqrt_a_prev, dir_coef, sigma, x0_rescale);
+  mp.x0_hist = x0_hist.has_value() ? x0_hist->data_ptr<float>() : nullptr;
+  mp.corr = (float)corr;
+  const int64_t nbytes = tc_ddim_workspace(mp.base.b);
+  Tensor ws = at::empty({nbytes > 16 ? nbytes : 16}, x.options().dtype(at::kByte));
+  if (EPS)
+    check_rc(tc_ddim_step_ms_eps(&mp, ws.data_ptr(), nbytes, cur_stream()), "tc_ddim_step_ms_eps");
+  else
+    check_rc(tc_ddim_step_ms(&mp, ws.data_ptr(), nbytes, cur_stream()), "tc_ddim_step_ms");
+  return std::make_tuple(x_prev, x0);
+}
+
+std::tuple<Tensor, Tensor> ddim_step_ms_meta(const Tensor& x, const Tensor&, const optional<Tensor>&, const optional<Tensor>&,
+                                             const optional<Tensor>&, const optional<Tensor>&, double, double, double, double,
+                                             double, double, double, double, double, double) {
   return std::make_tuple(at::empty_like(x), at::empty_like(x));
 }
 
@@ -621,6 +663,12 @@ TORCH_LIBRARY(tooncrafter, m) {
   m.def("ddim_step_eps(Tensor x, Tensor e_cond, Tensor? e_uncond, Tensor? noise, Tensor? e_uncond_img, float cfg_scale, "
         "float cfg_img, float guidance_rescale, float sqrt_ac, float sqrt_1m_ac, float sqrt_a_prev, float dir_coef, "
         "float sigma, float x0_rescale) -> (Tensor, Tensor)");
+  m.def("ddim_step_ms(Tensor x, Tensor e_cond, Tensor? e_uncond, Tensor? noise, Tensor? e_uncond_img, Tensor? x0_hist, float corr, "
+        "float cfg_scale, float cfg_img, float guidance_rescale, float sqrt_ac, float sqrt_1m_ac, float sqrt_a_prev, "
+        "float dir_coef, float sigma, float x0_rescale) -> (Tensor, Tensor)");
+  m.def("ddim_step_ms_eps(Tensor x, Tensor e_cond, Tensor? e_uncond, Tensor? noise, Tensor? e_uncond_img, Tensor? x0_hist, float corr, "
+        "float cfg_scale, float cfg_img, float guidance_rescale, float sqrt_ac, float sqrt_1m_ac, float sqrt_a_prev, "
+        "float dir_coef, float sigma, float x0_rescale) -> (Tensor, Tensor)");
   m.def("ddim_blend(Tensor? x, Tensor x0, Tensor? noise, Tensor? mask, float sqrt_ac, float sqrt_1m_ac) -> Tensor");
   m.def("frames_from_u8(Tensor images, int[] slots, int b, int t, int h, int w, Tensor? h_bounds, Tensor? h_coefs, "
         "Tensor? v_bounds, Tensor? v_coefs) -> Tensor");
@@ -643,6 +691,8 @@ TORCH_LIBRARY_IMPL(tooncrafter, CUDA, m) {
   m.impl("layernorm_pf", layernorm_pf_cuda);
   m.impl("ddim_step", ddim_step_any<false>);
   m.impl("ddim_step_eps", ddim_step_any<true>);
+  m.impl("ddim_step_ms", ddim_step_ms_any<false>);
+  m.impl("ddim_step_ms_eps", ddim_step_ms_any<true>);
   m.impl("ddim_blend", ddim_blend_cuda);
   m.impl("frames_from_u8", frames_from_u8_cuda);
   m.impl("clip_patches", clip_patches_cuda);
@@ -666,6 +716,8 @@ TORCH_LIBRARY_IMPL(tooncrafter, Meta, m) {
   m.impl("layernorm_pf", layernorm_pf_meta);
   m.impl("ddim_step", ddim_step_meta);
   m.impl("ddim_step_eps", ddim_step_meta);
+  m.impl("ddim_step_ms", ddim_step_ms_meta);
+  m.impl("ddim_step_ms_eps", ddim_step_ms_meta);
   m.impl("ddim_blend", ddim_blend_meta);
   m.impl("frames_from_u8", frames_from_u8_meta);
   m.impl("clip_patches", clip_patches_meta);

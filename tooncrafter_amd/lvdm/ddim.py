@@ -24,8 +24,16 @@ What is different underneath:
     process-wide device generator.  A clip then gets the same noise in any batch, slot, process or rank, and the torch
     generator is not touched.  This is Philox noise, not torch's: a seeded run does not reproduce a reference run with
     seed_everything; the unseeded path (seeds=None) is the one that does, and is unchanged.
+  * `solver_order=2` (not in the reference; the default 1 is the reference's update, untouched): a second-order multistep
+    correction from the previous step's pred_x0, with no further UNet call -- DPM-Solver++(2M) at eta = 0 and its SDE
+    variant at eta = 1, on the effective schedule of the dynamic rescale.  It is one more term of the fused kernel
+    (tc_ddim_step_ms) and one more host scalar per step (`multistep_corr`); the noise draws are those of order 1.  The
+    first step of a run, the step after an alpha = 0 step and the final step (DDIM index 0) stay first order.  Verified
+    against an analytic Gaussian model only: what it does to real frames at reduced step counts is unmeasured.
 """
 from __future__ import annotations
+
+import math
 
 import numpy as np
 import torch
@@ -61,6 +69,13 @@ def subset_timesteps(ddim_timesteps, timesteps):
     n = ddim_timesteps.shape[0]
     subset_end = int(min(timesteps / n, 1) * n) - 1
     return ddim_timesteps[:subset_end]
+
+
+def check_solver_order(solver_order, what):
+    """1 (the reference's DDIM update) or 2 (the multistep correction); a host check, before anything is launched."""
+    if isinstance(solver_order, bool) or solver_order not in (1, 2):
+        raise ValueError(f"{what}: solver_order must be 1 or 2, got {solver_order!r}")
+    return int(solver_order)
 
 
 class DDIMSampler(object):
@@ -111,7 +126,11 @@ class DDIMSampler(object):
         f32 = lambda v: torch.tensor(float(v), dtype=torch.float32)
         a_prev = f32(self.ddim_alphas_prev[index])
         sigma = f32(self.ddim_sigmas[index])
-        dir_coef = (1. - a_prev - sigma ** 2).sqrt()
+        # At eta = 1 the alpha_t = 0 start of a zero-terminal-SNR schedule has sigma^2 = 1 - a_prev in exact arithmetic, and
+        # the radicand is 0 give or take a rounding: at S = 7, 11, 14, 15, 20, 25, 33-35, 37-39 (uniform_trailing) it
+        # comes out below zero and the reference's sqrt is NaN for the whole run.  Clamped at 0: wherever the reference is
+        # finite these are its bits, and the step counts a second-order run would pick (20, 25) work.
+        dir_coef = (1. - a_prev - sigma ** 2).clamp(min=0.).sqrt()
         x0_rescale = f32(1.0)
         if self.model.use_dynamic_rescale:
             x0_rescale = self.ddim_scale_arr_prev[index] / self.ddim_scale_arr[index]
@@ -125,14 +144,49 @@ class DDIMSampler(object):
                       sqrt_1m_ac=float(f32(self.ddim_sqrt_one_minus_alphas[index])), parameterization=self.step_kind())
         return sc
 
+    def multistep_corr(self, index: int, t: int, h_prev):
+        """(corr, h) of the step at DDIM table position `index`, timestep `t`, for tc_ddim_step_ms.  h is the step's
+        increment of lambda = log(sqrt(alpha) * scale / sqrt(1 - alpha)), the log-SNR on the effective schedule of the dynamic
+        rescale, taken as the log of one ratio (infinite when alpha_t = 0); `h_prev` is the previous step's, None on the
+        first step of a run.  With A = sqrt_a_prev * rho - dir_coef * sqrt_ac / sqrt_1m_ac, the coefficient of the
+        un-rescaled prediction in the first-order update (rho = x0_rescale),
+            corr = A * h / (2 * h_prev),
+        in double from the tables `step_scalars` reads, rounded to fp32 once.  corr = 0 -- a first-order step -- without a
+        usable h_prev (first step, or the step after alpha_t = 0) and on the final step, index 0: the jump to
+        alphas_cumprod[0] is the largest log-SNR increment of the run, and extrapolating over it costs more than it gains."""
+        a_prev, sigma = float(self.ddim_alphas_prev[index]), float(self.ddim_sigmas[index])
+        if self.step_kind() == "v":
+            sqrt_ac, sqrt_1m_ac = float(self._sqrt_ac[t]), float(self._sqrt_1m_ac[t])
+        else:
+            sqrt_ac, sqrt_1m_ac = math.sqrt(float(self.ddim_alphas[index])), float(self.ddim_sqrt_one_minus_alphas[index])
+        rho = 1.0
+        if self.model.use_dynamic_rescale:
+            rho = float(self.ddim_scale_arr_prev[index]) / float(self.ddim_scale_arr[index])
+        h = math.inf
+        if sqrt_ac > 0.0 and 0.0 < a_prev < 1.0 and sqrt_1m_ac > 0.0:
+            h = math.log((math.sqrt(a_prev) * rho * sqrt_1m_ac) / (sqrt_ac * math.sqrt(1.0 - a_prev)))
+        if index == 0 or h_prev is None or not math.isfinite(h_prev) or h_prev == 0.0 or not math.isfinite(h):
+            return 0.0, h
+        dir_coef = math.sqrt(max(1.0 - a_prev - sigma * sigma, 0.0))
+        corr = (math.sqrt(a_prev) * rho - dir_coef * sqrt_ac / sqrt_1m_ac) * h / (2.0 * h_prev)
+        return float(np.float32(corr)), h
+
+    def fused_step(self, x, e_c, e_u, noise, sc, solver_order, x0_hist, ms_corr, **guidance):
+        """The fused update of the two- and the three-way sampler: tc_ddim_step at order 1 (the reference's path, the call it
+        always was), tc_ddim_step_ms at order 2 -- first order there too while there is no history."""
+        if solver_order == 1:
+            return ops.ddim_step(x, e_c, e_u, noise, **guidance, **sc)
+        return ops.ddim_step_ms(x, e_c, e_u, noise, x0_hist, corr=0.0 if x0_hist is None else ms_corr, **guidance, **sc)
+
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None,
                img_callback=None, quantize_x0=False, eta=0., mask=None, x0=None, temperature=1.,
                noise_dropout=0., score_corrector=None, corrector_kwargs=None, verbose=True,
                schedule_verbose=False, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
                unconditional_conditioning=None, precision=None, fs=None, timestep_spacing='uniform',
-               guidance_rescale=0.0, seeds=None, **kwargs):
-        if seeds is not None:                        # host checks only, before anything is launched
+               guidance_rescale=0.0, seeds=None, solver_order=1, **kwargs):
+        solver_order = check_solver_order(solver_order, "sample")      # host checks only, before anything is launched
+        if seeds is not None:
             seeds = ops.clip_seeds(seeds, batch_size, "sample: seeds")
             if kwargs.get("repeat_noise"):
                 raise ValueError("sample: repeat_noise=True shares one draw among the clips; seeds= draws one per clip")
@@ -160,14 +214,16 @@ class DDIMSampler(object):
                                   corrector_kwargs=corrector_kwargs, x_T=x_T, log_every_t=log_every_t,
                                   unconditional_guidance_scale=unconditional_guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning, verbose=verbose,
-                                  precision=precision, fs=fs, guidance_rescale=guidance_rescale, seeds=seeds, **kwargs)
+                                  precision=precision, fs=fs, guidance_rescale=guidance_rescale, seeds=seeds,
+                                  solver_order=solver_order, **kwargs)
 
     @torch.no_grad()
     def ddim_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None,
                       timesteps=None, quantize_denoised=False, mask=None, x0=None, img_callback=None,
                       log_every_t=100, temperature=1., noise_dropout=0., score_corrector=None,
                       corrector_kwargs=None, unconditional_guidance_scale=1., unconditional_conditioning=None,
-                      verbose=True, precision=None, fs=None, guidance_rescale=0.0, seeds=None, **kwargs):
+                      verbose=True, precision=None, fs=None, guidance_rescale=0.0, seeds=None, solver_order=1, **kwargs):
+        solver_order = check_solver_order(solver_order, "ddim_sampling")
         if ddim_use_original_steps or quantize_denoised or score_corrector is not None:
             raise NotImplementedError("only the DDIM-subsequence sampling path the scripts use")
         device = self.model.betas.device
@@ -193,6 +249,7 @@ class DDIMSampler(object):
             # becomes the dense fp32 operand of the blend kernel
             mask = torch.as_tensor(mask).to(device=device, dtype=torch.float32).expand(tuple(img.shape)).contiguous()
             x0 = x0.to(device=device, dtype=torch.float32).expand(tuple(img.shape)).contiguous()
+        hist, h_prev = None, None                    # order 2: the last pred_x0 and log-SNR increment; a run starts without
         for i, step in enumerate(iterator):
             index = total_steps - i - 1
             ts = torch.full((b,), int(step), device=device, dtype=torch.long)
@@ -208,11 +265,17 @@ class DDIMSampler(object):
                 else:
                     img_orig = self.model.q_sample(x0, int(step))
                 img = ops.ddim_blend(img, img_orig, None, mask)
+            ms = {}                                  # order 1: p_sample_ddim gets the keywords it always got
+            if solver_order == 2:
+                corr, h = self.multistep_corr(index, int(step), h_prev)
+                ms = dict(solver_order=2, x0_hist=hist, ms_corr=corr)
             img, pred_x0 = self.p_sample_ddim(img, cond, ts, index=index, temperature=temperature,
                                               noise_dropout=noise_dropout,
                                               unconditional_guidance_scale=unconditional_guidance_scale,
                                               unconditional_conditioning=unconditional_conditioning,
-                                              fs=fs, guidance_rescale=guidance_rescale, _step=int(step), seeds=seeds, **kwargs)
+                                              fs=fs, guidance_rescale=guidance_rescale, _step=int(step), seeds=seeds, **ms, **kwargs)
+            if solver_order == 2:
+                hist, h_prev = pred_x0, h            # a prediction of x0: the pinned-frame blend does not touch it
             if callback:
                 callback(i)
             if img_callback:
@@ -227,7 +290,10 @@ class DDIMSampler(object):
                       quantize_denoised=False, temperature=1., noise_dropout=0., score_corrector=None,
                       corrector_kwargs=None, unconditional_guidance_scale=1., unconditional_conditioning=None,
                       uc_type=None, conditional_guidance_scale_temporal=None, mask=None, x0=None,
-                      guidance_rescale=0.0, _step=None, seeds=None, **kwargs):
+                      guidance_rescale=0.0, _step=None, seeds=None, solver_order=1, x0_hist=None, ms_corr=0.0, **kwargs):
+        """`solver_order=2` with `x0_hist` (the previous step's pred_x0) and `ms_corr` (`multistep_corr`): the corrected
+        step; the caller's loop carries both, nothing is kept on the sampler."""
+        solver_order = check_solver_order(solver_order, "p_sample_ddim")
         if use_original_steps or quantize_denoised or score_corrector is not None or noise_dropout > 0.:
             raise NotImplementedError("p_sample_ddim variant unused by the inference scripts")
         self.step_kind()
@@ -244,9 +310,9 @@ class DDIMSampler(object):
             e_u = self.model.apply_model(x, t, unconditional_conditioning, **kwargs)
         sc = self.step_scalars(index, step)
         noise = self.step_noise(x, index, sc["sigma"], temperature, repeat_noise, seeds)
-        x_prev, pred_x0 = ops.ddim_step(x.contiguous(), e_c.contiguous(), None if e_u is None else e_u.contiguous(),
-                                        noise, cfg_scale=unconditional_guidance_scale,
-                                        guidance_rescale=guidance_rescale if use_cfg else 0.0, **sc)
+        x_prev, pred_x0 = self.fused_step(x.contiguous(), e_c.contiguous(), None if e_u is None else e_u.contiguous(),
+                                          noise, sc, solver_order, x0_hist, ms_corr, cfg_scale=unconditional_guidance_scale,
+                                          guidance_rescale=guidance_rescale if use_cfg else 0.0)
         return x_prev, pred_x0
 
     def step_noise(self, x, index, sigma, temperature, repeat_noise, seeds):
@@ -268,10 +334,12 @@ class DDIMSampler(object):
 
     @torch.no_grad()
     def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
-               use_original_steps=False, callback=None, seeds=None):
+               use_original_steps=False, callback=None, seeds=None, solver_order=1):
         """The last `t_start` steps of the DDIM sequence from `x_latent` (ddim.py:282-301); `make_schedule` first.  Like the
         reference it hands p_sample_ddim neither `fs` nor a guidance rescale (the UNet falls back to its default_fs).
-        `seeds`: one per sample; the steps then draw what a seeded `sample` draws at the same table positions."""
+        `seeds`: one per sample; the steps then draw what a seeded `sample` draws at the same table positions.
+        `solver_order=2`: the multistep correction, starting first order (no history) and ending first order at index 0."""
+        solver_order = check_solver_order(solver_order, "decode")
         if use_original_steps:
             raise NotImplementedError("only the DDIM-subsequence sampling path the scripts use")
         if seeds is not None:
@@ -281,12 +349,20 @@ class DDIMSampler(object):
         total_steps = timesteps.shape[0]
         print(f"Running DDIM Sampling with {total_steps} timesteps")
         x_dec = x_latent.to(torch.float32).contiguous()
+        hist, h_prev = None, None
         for i, step in enumerate(tqdm(time_range, desc='Decoding image', total=total_steps)):
             index = total_steps - i - 1
             ts = torch.full((x_latent.shape[0],), int(step), device=x_latent.device, dtype=torch.long)
-            x_dec, _ = self.p_sample_ddim(x_dec, cond, ts, index=index,
-                                          unconditional_guidance_scale=unconditional_guidance_scale,
-                                          unconditional_conditioning=unconditional_conditioning, _step=int(step), seeds=seeds)
+            ms = {}
+            if solver_order == 2:
+                corr, h = self.multistep_corr(index, int(step), h_prev)
+                ms = dict(solver_order=2, x0_hist=hist, ms_corr=corr)
+            x_dec, pred_x0 = self.p_sample_ddim(x_dec, cond, ts, index=index,
+                                                unconditional_guidance_scale=unconditional_guidance_scale,
+                                                unconditional_conditioning=unconditional_conditioning, _step=int(step), seeds=seeds,
+                                                **ms)
+            if solver_order == 2:
+                hist, h_prev = pred_x0, h
             if callback:
                 callback(i)
         return x_dec

@@ -10,8 +10,8 @@ and "image kept, text dropped" (`kwargs['unconditional_conditioning_img_nonetext
 before the usual guidance rescale against e_cond, v-parameterisation and DDIM update.
 scripts/evaluation/funcs.py:61-76 selects it with `multiple_cond_cfg=True`.
 
-`ddim_sampling` -- pinned frames (`mask` / `x0`, :177-184), `clean_cond`, partial runs (`timesteps=`), per-clip `seeds=` --
-`decode` and `stochastic_encode` are inherited from the mirror of samplers/ddim.py, as they are the same code in the reference.
+`ddim_sampling` -- pinned frames (`mask` / `x0`, :177-184), `clean_cond`, partial runs (`timesteps=`), per-clip `seeds=`,
+the opt-in `solver_order=2` with its history and `multistep_corr` -- `decode` and `stochastic_encode` are inherited from the mirror of samplers/ddim.py, as they are the same code in the reference.
 
 Here the three passes are one batch-3B UNet call (`apply_model_multi`) and the combination is part
 of the fused tc_ddim_step kernel (TcDdimParams.e_uncond_img / cfg_img).
@@ -21,7 +21,7 @@ from __future__ import annotations
 import torch
 
 from .. import ops
-from .ddim import DDIMSampler as _DDIMSampler
+from .ddim import DDIMSampler as _DDIMSampler, check_solver_order
 
 
 class DDIMSampler(_DDIMSampler):
@@ -30,7 +30,8 @@ class DDIMSampler(_DDIMSampler):
                       quantize_denoised=False, temperature=1., noise_dropout=0., score_corrector=None,
                       corrector_kwargs=None, unconditional_guidance_scale=1., unconditional_conditioning=None,
                       uc_type=None, cfg_img=None, mask=None, x0=None, guidance_rescale=0.0, _step=None, seeds=None,
-                      **kwargs):
+                      solver_order=1, x0_hist=None, ms_corr=0.0, **kwargs):
+        solver_order = check_solver_order(solver_order, "p_sample_ddim")
         if use_original_steps or quantize_denoised or score_corrector is not None or noise_dropout > 0.:
             raise NotImplementedError("p_sample_ddim variant unused by the inference scripts")
         self.step_kind()
@@ -53,7 +54,7 @@ class DDIMSampler(_DDIMSampler):
         sc = self.step_scalars(index, step)
         noise = self.step_noise(x, index, sc["sigma"], temperature, repeat_noise, seeds)    # unseeded: always drawn, like the reference (:277)
         cont = lambda v: None if v is None else v.contiguous()
-        return ops.ddim_step(x.contiguous(), e_c.contiguous(), cont(e_u), noise,
-                             cfg_scale=unconditional_guidance_scale,
-                             guidance_rescale=guidance_rescale if use_cfg else 0.0,
-                             e_uncond_img=cont(e_i), cfg_img=cfg_img, **sc)
+        return self.fused_step(x.contiguous(), e_c.contiguous(), cont(e_u), noise, sc, solver_order, x0_hist, ms_corr,
+                               cfg_scale=unconditional_guidance_scale,
+                               guidance_rescale=guidance_rescale if use_cfg else 0.0,
+                               e_uncond_img=cont(e_i), cfg_img=cfg_img)

@@ -909,15 +909,32 @@ class HipOps:
         """One fused DDIM update.  With `e_uncond_img` the guidance is the three-way form of
         ddim_multiplecond.py:236 (cfg_img defaults to cfg_scale like the reference).  `parameterization` says what the
         model predicts: "v" (tc_ddim_step) or "eps" (tc_ddim_step_eps, ddim.py:234, 258)."""
+        p, x_prev, x0 = HipOps._ddim_params("ddim_step", x, e_cond, e_uncond, noise, e_uncond_img, None, want_x0, parameterization,
+                                            cfg_scale=cfg_scale, guidance_rescale=guidance_rescale, sqrt_ac=sqrt_ac,
+                                            sqrt_1m_ac=sqrt_1m_ac, sqrt_a_prev=sqrt_a_prev, dir_coef=dir_coef, sigma=sigma,
+                                            x0_rescale=x0_rescale, cfg_img=cfg_img)
+        nbytes = self.lib.tc_ddim_workspace(p.b)
+        ws = self._workspace(nbytes, x.device)
+        if parameterization == "v":
+            _lib.check(self.lib.tc_ddim_step(C.byref(p), ws.data_ptr(), nbytes, _stream()), "tc_ddim_step")
+        else:
+            _lib.check(self.lib.tc_ddim_step_eps(C.byref(p), ws.data_ptr(), nbytes, _stream()), "tc_ddim_step_eps")
+        return x_prev, x0
+
+    @staticmethod
+    def _ddim_params(what, x, e_cond, e_uncond, noise, e_uncond_img, pred_x0, want_x0, parameterization, *, cfg_scale,
+                     guidance_rescale, sqrt_ac, sqrt_1m_ac, sqrt_a_prev, dir_coef, sigma, x0_rescale, cfg_img, also=()):
+        """The checked TcDdimParams of a step and its two results: (p, x_prev, pred_x0).  `pred_x0`: the caller's tensor for
+        that result, or None for a new one (no tensor at all when `want_x0` is false).  `also`: further operands to check."""
         if parameterization not in ("v", "eps"):
-            raise NotImplementedError(f"ddim_step: parameterization {parameterization!r} (the fused step has 'v' and 'eps')")
-        for tns in (x, e_cond, e_uncond, noise, e_uncond_img):
+            raise NotImplementedError(f"{what}: parameterization {parameterization!r} (the fused step has 'v' and 'eps')")
+        for tns in (x, e_cond, e_uncond, noise, e_uncond_img, pred_x0, *also):
             if tns is not None and (tns.dtype != torch.float32 or not tns.is_contiguous() or not tns.is_cuda):
-                raise ValueError("ddim_step: contiguous fp32 CUDA tensors")
+                raise ValueError(f"{what}: contiguous fp32 CUDA tensors")
         b = x.shape[0]
         n = x.numel() // b
         x_prev = torch.empty_like(x)
-        x0 = torch.empty_like(x) if want_x0 else None
+        x0 = pred_x0 if pred_x0 is not None else (torch.empty_like(x) if want_x0 else None)
         p = TcDdimParams()
         p.x, p.e_cond, p.e_uncond, p.noise = x.data_ptr(), e_cond.data_ptr(), _ptr(e_uncond), _ptr(noise)
         p.x_prev, p.pred_x0 = x_prev.data_ptr(), _ptr(x0)
@@ -927,12 +944,30 @@ class HipOps:
         p.dir_coef, p.sigma, p.x0_rescale = float(dir_coef), float(sigma), float(x0_rescale)
         p.e_uncond_img = _ptr(e_uncond_img)
         p.cfg_img = float(cfg_scale if cfg_img is None else cfg_img)
-        nbytes = self.lib.tc_ddim_workspace(b)
+        return p, x_prev, x0
+
+    def ddim_step_ms(self, x, e_cond, e_uncond, noise, x0_hist, *, corr, cfg_scale, guidance_rescale, sqrt_ac, sqrt_1m_ac,
+                     sqrt_a_prev, dir_coef, sigma, x0_rescale, want_x0=True, e_uncond_img=None, cfg_img=None,
+                     parameterization="v", pred_x0=None):
+        """`ddim_step` plus the second-order multistep term (tc_ddim_step_ms / tc_ddim_step_ms_eps):
+        x_prev += corr * (x0u - x0_hist), x0u the prediction before `x0_rescale`, `x0_hist` the pred_x0 the previous step
+        returned (None: no history) and `corr` the host scalar of DDIMSampler.multistep_corr.  With x0_hist None or corr 0
+        the results are `ddim_step`'s bits.  `pred_x0`: a tensor to take that result -- it may be `x0_hist` itself (the
+        history updated in place); any other overlap of it with `x0_hist` is refused (TC_EINVAL), as is a non-finite corr."""
+        for tns in (x0_hist, pred_x0):
+            if tns is not None and tns.shape != x.shape:
+                raise ValueError(f"ddim_step_ms: shape {tuple(tns.shape)} against x {tuple(x.shape)}")
+        p, x_prev, x0 = HipOps._ddim_params("ddim_step_ms", x, e_cond, e_uncond, noise, e_uncond_img, pred_x0, want_x0,
+                                            parameterization, cfg_scale=cfg_scale, guidance_rescale=guidance_rescale,
+                                            sqrt_ac=sqrt_ac, sqrt_1m_ac=sqrt_1m_ac, sqrt_a_prev=sqrt_a_prev, dir_coef=dir_coef,
+                                            sigma=sigma, x0_rescale=x0_rescale, cfg_img=cfg_img, also=(x0_hist,))
+        mp = _lib.TcDdimMsParams(base=p, x0_hist=_ptr(x0_hist), corr=float(corr))
+        nbytes = self.lib.tc_ddim_workspace(p.b)
         ws = self._workspace(nbytes, x.device)
         if parameterization == "v":
-            _lib.check(self.lib.tc_ddim_step(C.byref(p), ws.data_ptr(), nbytes, _stream()), "tc_ddim_step")
+            _lib.check(self.lib.tc_ddim_step_ms(C.byref(mp), ws.data_ptr(), nbytes, _stream()), "tc_ddim_step_ms")
         else:
-            _lib.check(self.lib.tc_ddim_step_eps(C.byref(p), ws.data_ptr(), nbytes, _stream()), "tc_ddim_step_eps")
+            _lib.check(self.lib.tc_ddim_step_ms_eps(C.byref(mp), ws.data_ptr(), nbytes, _stream()), "tc_ddim_step_ms_eps")
         return x_prev, x0
 
     def ddim_blend(self, x, x0, noise, mask, *, sqrt_ac=1.0, sqrt_1m_ac=0.0, out=None):
