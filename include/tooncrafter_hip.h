@@ -402,7 +402,8 @@ typedef struct TcDdimParams {
 
 /* CFG combine + rescale_noise_cfg (unbiased std over each sample) + v->(eps,x0) + dynamic
  * rescale + x_prev, fused.  Replaces ddim.py:226-277 / ddim_multiplecond.py:226-288 and
- * utils_diffusion.py:147-158.
+ * utils_diffusion.py:147-158.  It is tc_ddim_step_ms below without a history, {*p, NULL, 0}: one launcher and one
+ * kernel serve both, so no alignment is asked for (operands that are not 16-byte aligned take the scalar instance).
  * workspace: b * 64 * 4 doubles. */
 int64_t tc_ddim_workspace(int32_t b);
 int tc_ddim_step(const TcDdimParams* p, void* workspace, int64_t workspace_bytes, void* stream);
@@ -412,7 +413,8 @@ int tc_ddim_step(const TcDdimParams* p, void* workspace, int64_t workspace_bytes
  *   pred_x0 = (x - sqrt_1m_ac * e_t) / sqrt_ac                     (ddim.py:257-258, a true fp32 division)
  * and dynamic rescale, dir_coef * e_t, the noise term and x_prev follow as in tc_ddim_step (ddim.py:262-277).  The
  * callers pass sqrt_ac = sqrt(ddim_alphas[index]) and sqrt_1m_ac = ddim_sqrt_one_minus_alphas[index], the tables this
- * branch of the reference reads (ddim.py:251-254).  TC_EINVAL also for sqrt_ac == 0 (a zero-terminal-SNR step). */
+ * branch of the reference reads (ddim.py:251-254).  TC_EINVAL also for sqrt_ac == 0 (a zero-terminal-SNR step).  Like
+ * tc_ddim_step it is the history-free case of its _ms form, tc_ddim_step_ms_eps. */
 int tc_ddim_step_eps(const TcDdimParams* p, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* The same step with a second-order multistep correction (additive within ABI 14: one struct, two symbols; the workspace

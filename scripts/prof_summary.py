@@ -75,7 +75,7 @@ for name, (n, d) in sorted(agg.items(), key=lambda kv: -kv[1][1])[:top]:
     print(f"{name[:80]:80s} {n:7d} {d / 1e6:10.2f} {d / n / 1e3:9.1f} {100 * d / tot:6.1f}")
 
 fam = [k for k in inside if GEMM_FAMILY.search(k[0])]
-n_marks = sum(1 for k in inside if "ddim_apply_kernel" in k[0])
+n_marks = sum(1 for k in inside if "ddim_apply" in k[0])
 clips = max(1, round(n_marks / ddim_steps))                       # a warm-up clip in the trace doubles the window's work
 tflop = clips * (ddim_steps * GEMM_TFLOP_FWD_B2 + GEMM_TFLOP_DECODES)
 clip_tflop = clips * (ddim_steps * 2 * TFLOP_FWD_B1 + TFLOP_DEC16 + TFLOP_DEC14)
@@ -95,9 +95,9 @@ for k in inside:
 for (name, gx, gy, gz), (n, d) in sorted(g.items(), key=lambda kv: -kv[1][1])[:40]:
     print(f"{name[:60]:60s} grid({gx},{gy},{gz}) calls {n:6d} total {d / 1e6:9.2f} ms avg {d / n / 1e3:9.1f} us")
 
-# ---- per DDIM step (between consecutive ddim_apply_kernel launches = one guided UNet forward + the step): busy time,
+# ---- per DDIM step (between consecutive ddim_apply launches = one guided UNet forward + the step): busy time,
 # idle gaps between kernels, and the per-kernel shares averaged over the steps
-marks = [k[1] for k in inside if "ddim_apply_kernel" in k[0]]
+marks = [k[1] for k in inside if "ddim_apply" in k[0]]
 # With a warm-up clip in the trace (bench.py --warmup 1 --steps 1: the hipGraphs of the forward and of both decodes are captured
 # there) only the LAST clip is analysed: its ddim_steps marks and the decodes behind the last of them.  Without one, the first
 # interval (eager pass + capture) is skipped and the decodes carry their first-use passes (then flagged below).
@@ -118,7 +118,7 @@ if len(marks) >= 3:
             e[1] += k[2] - k[1]
     n = len(spans)
     fam_ms = sum(d for name, (_, d) in sagg.items() if GEMM_FAMILY.search(name)) / n / 1e6
-    print(f"\n# per DDIM step ({n} steps between ddim_apply_kernel launches{' of the LAST clip (graphs captured in the warm-up clip)' if warm else ''}): span {sum(s[0] for s in spans) / n / 1e6:.2f} ms, "
+    print(f"\n# per DDIM step ({n} steps between ddim_apply launches{' of the LAST clip (graphs captured in the warm-up clip)' if warm else ''}): span {sum(s[0] for s in spans) / n / 1e6:.2f} ms, "
           f"kernel-busy {sum(s[1] for s in spans) / n / 1e6:.2f} ms, gaps between kernels {sum(s[2] for s in spans) / n / 1e6:.2f} ms, "
           f"{sum(s[3] for s in spans) / n:.0f} kernels; GEMM family {fam_ms:.2f} ms = {GEMM_TFLOP_FWD_B2 / (fam_ms / 1e3):.0f} TF/s "
           f"= {GEMM_TFLOP_FWD_B2 / (fam_ms / 1e3) / PEAK_TF:.3f} of peak")

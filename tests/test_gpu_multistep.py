@@ -1,10 +1,11 @@
 """tc_ddim_step_ms / tc_ddim_step_ms_eps on the MI355X: the kernel against the float64 statement (tests/multistep_ref.py), its
-first-order case against tc_ddim_step bit for bit, the history in place, the refusals, the two bindings, and the samplers'
+first-order case against tc_ddim_step bit for bit and both against bits recorded before the two were one kernel, the history in place, the refusals, the two bindings, and the samplers'
 `solver_order=2` on the device -- the analytic Gaussian problem of tests/test_multistep_cpu.py and the tiny pipeline.
 
 Measured on the MI355X (the tests print them): kernel vs float64, worst rel-L2 over all cases 4.17e-07 (bound 1e-4);
 analytic run S = 10, RMS deviation from the float64 twin: order 1 8.17e-08, order 2 1.00e-07 (bound: 4 x order 1);
 tiny pipeline at order 2 vs the emulated contract in fp32: worst pred_x0 8.34e-02, final 7.48e-02 (bounds 0.133 / 0.108)."""
+import hashlib
 import itertools
 
 import numpy as np
@@ -32,14 +33,18 @@ def hip():
     return HipOps()
 
 
-@pytest.fixture(scope="module")
-def operands():
-    """x, e_cond, e_uncond, e_uncond_img, noise, hist per shape, on the CPU: drawn once, never written."""
+def draw_operands():
     out = {}
     for shape in SHAPES:
         g = torch.Generator().manual_seed(70 + len(shape) + shape[0])
         out[shape] = tuple(torch.randn(*shape, generator=g) for _ in range(6))
     return out
+
+
+@pytest.fixture(scope="module")
+def operands():
+    """x, e_cond, e_uncond, e_uncond_img, noise, hist per shape, on the CPU: drawn once, never written."""
+    return draw_operands()
 
 
 def _case(operands, shape, guidance, noise):
@@ -56,6 +61,22 @@ def _kw(guidance, resc, noise, par):
 
 def _dev(t):
     return None if t is None else t.to(DEV)
+
+
+# tests/golden/ddim_step_bits.npz (make_ddim_step_bits.py): what HipOps.ddim_step returned for these operands BEFORE the first-order
+# kernels were folded into the one apply kernel.  The small shapes are stored in full, the clip-sized one as a SHA-256.
+BITS_HASHED = (2, 4, 16, 40, 64)
+BITS_COMBOS = list(itertools.product((0, 2, 3), (0.0, 0.7), (False, True)))
+
+
+def bits_key(shape, par, guidance, resc, noise):
+    return f"{par}.{'x'.join(map(str, shape))}.g{guidance}.r{resc}.n{int(noise)}"
+
+
+def bits_digest(x_prev, pred_x0):
+    h = hashlib.sha256(x_prev.cpu().numpy().tobytes())
+    h.update(pred_x0.cpu().numpy().tobytes())
+    return np.frombuffer(h.digest(), dtype=np.uint8)
 
 
 @pytest.mark.parametrize("par", ["v", "eps"])
@@ -89,6 +110,39 @@ def test_first_order_case_is_tc_ddim_step_bit_for_bit(hip, operands, shape, par)
             mp, m0 = hip.ddim_step_ms(x, ec, eu, nz, h, corr=corr, e_uncond_img=ei, **kw)
             assert torch.equal(mp, xp) and torch.equal(m0, x0), (shape, par, guidance, resc, noise, h is None, corr)
         assert hip.ddim_step_ms(x, ec, eu, nz, None, corr=0.0, e_uncond_img=ei, want_x0=False, **kw)[1] is None
+
+
+@pytest.fixture(scope="module")
+def step_bits():
+    return load_golden("ddim_step_bits.npz")
+
+
+@pytest.mark.parametrize("par", ["v", "eps"])
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_first_order_step_keeps_the_recorded_bits(hip, operands, step_bits, shape, par):
+    """`ddim_step` on both bindings, and `ddim_step_ms` without a history or with corr 0, against outputs recorded from the
+    separate first-order kernels this project had: the merged kernel is anchored outside itself."""
+    from tooncrafter_amd.torch_ops import TorchLibOps
+    tlib = TorchLibOps()
+    for guidance, resc, noise in BITS_COMBOS:
+        x, ec, eu, ei, nz, hist = (_dev(t) for t in _case(operands, shape, guidance, noise))
+        kw = _kw(guidance, resc, noise, par)
+        key = bits_key(shape, par, guidance, resc, noise)
+        results = {"ctypes ddim_step": hip.ddim_step(x, ec, eu, nz, e_uncond_img=ei, **kw),
+                   "custom-op ddim_step": tlib.ddim_step(x, ec, eu, nz, e_uncond_img=ei, **kw),
+                   "ddim_step_ms(None, 0.8)": hip.ddim_step_ms(x, ec, eu, nz, None, corr=0.8, e_uncond_img=ei, **kw),
+                   "ddim_step_ms(hist, 0.0)": hip.ddim_step_ms(x, ec, eu, nz, hist, corr=0.0, e_uncond_img=ei, **kw)}
+        for what, (xp, x0) in results.items():
+            if shape == BITS_HASHED:
+                assert np.array_equal(bits_digest(xp, x0), step_bits[key + ".sha256"]), (what, key)
+            else:
+                assert torch.equal(xp.cpu(), torch.from_numpy(step_bits[key + ".x_prev"])), (what, key)
+                assert torch.equal(x0.cpu(), torch.from_numpy(step_bits[key + ".pred_x0"])), (what, key)
+        for be in (hip, tlib):
+            xp, none = be.ddim_step(x, ec, eu, nz, e_uncond_img=ei, want_x0=False, **kw)
+            assert none is None
+            if shape != BITS_HASHED:
+                assert torch.equal(xp.cpu(), torch.from_numpy(step_bits[key + ".x_prev"])), ("want_x0=False", key)
 
 
 @pytest.mark.parametrize("shape", [(2, 4, 3, 5, 7), (2, 421)], ids=lambda s: "x".join(map(str, s)))

@@ -97,6 +97,27 @@ def test_torch_ops_match_ctypes_binding_bitwise(both):
     assert torch.equal(t.temporal_qkv_attn(x0, wqkv, bqkv, **kwq), c.temporal_qkv_attn(x0, wqkv, bqkv, **kwq))
 
 
+def test_norm_ops_are_their_prefetch_forms_with_an_empty_list(both):
+    """`groupnorm` / `layernorm` are implemented by `groupnorm_pf` / `layernorm_pf` with []: the same launches, so the same bits
+    as the op with an explicit empty list and as tc_groupnorm / tc_layernorm through ctypes.  (2, 7, 320): the three-launch
+    GroupNorm; (4, 4, 64): the one-pass kernel."""
+    c, t = both
+    for k, (samples, rows, ch) in enumerate(((2, 7, 320), (4, 4, 64))):
+        x = rnd(samples * rows, ch, seed=50 + k)
+        g, be = rnd(ch, seed=52 + k, dtype=torch.float32), rnd(ch, seed=54 + k, dtype=torch.float32)
+        for silu in (False, True):
+            plain = t.t.groupnorm(x, g, be, samples, rows, 1e-5, silu)
+            assert torch.equal(plain, t.t.groupnorm_pf(x, g, be, samples, rows, 1e-5, silu, [])), (samples, rows, ch, silu)
+            assert torch.equal(plain, c.groupnorm(x, g, be, samples=samples, rows=rows, eps=1e-5, silu=silu)), (samples, rows, ch, silu)
+            assert bool(torch.isfinite(plain.float()).all()) and float(plain.float().abs().max()) > 0.5
+    x = rnd(17, 640, seed=56)
+    g, be = rnd(640, seed=57, dtype=torch.float32), rnd(640, seed=58, dtype=torch.float32)
+    plain = t.t.layernorm(x, g, be, 1e-5)
+    assert torch.equal(plain, t.t.layernorm_pf(x, g, be, 1e-5, []))
+    assert torch.equal(plain, c.layernorm(x, g, be, 1e-5))
+    assert bool(torch.isfinite(plain.float()).all()) and float(plain.float().abs().max()) > 0.5
+
+
 def test_tiny_unet_through_torch_op_layer(both, tiny_sd):
     from tooncrafter_amd.lvdm.openaimodel3d import UNetModel
     c, t = both

@@ -207,59 +207,12 @@ __global__ __launch_bounds__(256) void ddim_stats_kernel(TcDdimParams p, double*
         red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
-// EPS = false: the model output is v (ddim.py:232, 260).  EPS = true: it is e_t itself (ddim.py:234) and
-// pred_x0 = (x - sqrt_1m_ac * e_t) / sqrt_ac, a true division as on ddim.py:258.  One text, two kernels.  A macro and not
-// a template body inlined into two kernels: through the inlined form the compiler orders two scalar address adds of the
-// v kernel differently, and that kernel is to stay the instructions it was (scripts/isa_compare.py).
-#define TC_DDIM_APPLY_KERNEL(NAME, EPS)                                                                            \
-__global__ __launch_bounds__(256) void NAME(TcDdimParams p, const double* __restrict__ part) {                     \
-  __shared__ float factor_s;                                                                                       \
-  const int b = blockIdx.y;                                                                                        \
-  const bool cfg = p.e_uncond != nullptr;                                                                          \
-  const bool resc = cfg && p.guidance_rescale > 0.f;                                                               \
-  if (threadIdx.x == 0) {                                                                                          \
-    float factor = 1.f;                                                                                            \
-    if (resc) {                                                                                                    \
-      double s[4] = {0, 0, 0, 0};                                                                                  \
-      for (int k = 0; k < DDIM_PARTS; ++k)                                                                         \
-        for (int j = 0; j < 4; ++j) s[j] += part[((int64_t)b * DDIM_PARTS + k) * 4 + j];                           \
-      const double n = (double)p.n;                                                                                \
-      const double var_t = (s[1] - s[0] * s[0] / n) / (n - 1.0);                                                   \
-      const double var_c = (s[3] - s[2] * s[2] / n) / (n - 1.0);                                                   \
-      const float std_t = (float)sqrt(var_t > 0 ? var_t : 0.0);                                                    \
-      const float std_c = (float)sqrt(var_c > 0 ? var_c : 0.0);                                                    \
-      factor = std_t / std_c;                                                                                      \
-    }                                                                                                              \
-    factor_s = factor;                                                                                             \
-  }                                                                                                                \
-  __syncthreads();                                                                                                 \
-  const float factor = factor_s;                                                                                   \
-  const int64_t base = (int64_t)b * p.n;                                                                           \
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < p.n; i += (int64_t)gridDim.x * 256) {              \
-    const float x = p.x[base + i];                                                                                 \
-    float v = p.e_cond[base + i];                                                                                  \
-    if (cfg) {                                                                                                     \
-      v = p.e_uncond_img ? cfg_combine3(v, p.e_uncond[base + i], p.e_uncond_img[base + i], p.cfg_scale, p.cfg_img) \
-                         : cfg_combine(v, p.e_uncond[base + i], p.cfg_scale);                                      \
-      if (resc) v = p.guidance_rescale * (v * factor) + (1.f - p.guidance_rescale) * v;                            \
-    }                                                                                                              \
-    const float e_t = EPS ? v : p.sqrt_ac * v + p.sqrt_1m_ac * x;                                                  \
-    float x0 = EPS ? (x - p.sqrt_1m_ac * v) / p.sqrt_ac : p.sqrt_ac * x - p.sqrt_1m_ac * v;                        \
-    x0 *= p.x0_rescale;                                                                                            \
-    float xp = p.sqrt_a_prev * x0 + p.dir_coef * e_t;                                                              \
-    if (p.noise) xp += p.sigma * p.noise[base + i];                                                                \
-    p.x_prev[base + i] = xp;                                                                                       \
-    if (p.pred_x0) p.pred_x0[base + i] = x0;                                                                       \
-  }                                                                                                                \
-}
-TC_DDIM_APPLY_KERNEL(ddim_apply_kernel, false)
-TC_DDIM_APPLY_KERNEL(ddim_apply_eps_kernel, true)
-#undef TC_DDIM_APPLY_KERNEL
-
-// The apply pass with the second-order multistep term (tc_ddim_step_ms): the update above plus corr * (x0u - hist), where
-// x0u is pred_x0 BEFORE x0_rescale and hist the previous step's returned pred_x0.  Every other operation is written as
-// in TC_DDIM_APPLY_KERNEL, expression by expression, so that under -ffp-contract=on (contraction inside one expression
-// only) it rounds where that kernel rounds: with `hist_on` false the results are that kernel's bits.
+// The apply pass, one kernel text for every step: tc_ddim_step(_eps) and tc_ddim_step_ms(_eps).  EPS = false: the model output
+// is v (ddim.py:232, 260).  EPS = true: it is e_t itself (ddim.py:234) and pred_x0 = (x - sqrt_1m_ac * e_t) / sqrt_ac, a true
+// division as on ddim.py:258.  The second-order multistep term is corr * (x0u - hist), where x0u is pred_x0 BEFORE x0_rescale
+// and hist the previous step's returned pred_x0; with `hist_on` false the update is the reference's first-order one.  Each
+// operation is an expression of its own, so that under -ffp-contract=on (contraction inside one expression only) it rounds
+// where the separate first-order kernels this replaced rounded: tests/golden/ddim_step_bits.npz holds their outputs.
 __device__ __forceinline__ float ddim_rescale_factor(const TcDdimParams& p, const double* __restrict__ part, int b) {
   double s[4] = {0, 0, 0, 0};
   for (int k = 0; k < DDIM_PARTS; ++k)
@@ -511,56 +464,23 @@ extern "C" int tc_video_to_u8(const float* x, uint8_t* out, int32_t b, int32_t t
 
 extern "C" int64_t tc_ddim_workspace(int32_t b) { return b > 0 ? (int64_t)b * DDIM_PARTS * 4 * sizeof(double) : 0; }
 
-// The argument checks of a step, shared by tc_ddim_step(_eps) and tc_ddim_step_ms(_eps); nothing is launched.
-static int ddim_step_check(const TcDdimParams& p, const void* workspace, int64_t workspace_bytes) {
+// The argument checks of a step; nothing is launched.
+static int ddim_step_check(const TcDdimParams& p, const void* workspace, int64_t workspace_bytes, bool eps) {
   if (!p.x || !p.e_cond || !p.x_prev || p.b <= 0 || p.n <= 1) return TC_EINVAL;
   if (p.e_uncond_img && !p.e_uncond) return TC_EINVAL;
+  if (eps && p.sqrt_ac == 0.f) return TC_EINVAL;          // eps divides by sqrt_ac: a zero-terminal-SNR step has no eps form
   if (!workspace || workspace_bytes < tc_ddim_workspace(p.b)) return TC_EWORKSPACE;
   if (p.b > 65535) return TC_ESHAPE;
   return TC_OK;
 }
 
-// Pass 1, when the step rescales its guidance.
-static int ddim_stats_launch(const TcDdimParams& p, double* part, hipStream_t s) {
-  if (p.e_uncond && p.guidance_rescale > 0.f) {
-    hipLaunchKernelGGL(ddim_stats_kernel, dim3(DDIM_PARTS, p.b), dim3(256), 0, s, p, part);
-    TC_LAUNCH_CHECK();
-  }
-  return TC_OK;
-}
-
-static int ddim_step_launch(const TcDdimParams* pp, void* workspace, int64_t workspace_bytes, void* stream, bool eps) {
-  if (!pp) return TC_EINVAL;
-  const TcDdimParams& p = *pp;
-  if (const int rc = ddim_step_check(p, workspace, workspace_bytes)) return rc;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  double* part = reinterpret_cast<double*>(workspace);
-  if (const int rc = ddim_stats_launch(p, part, s)) return rc;
-  const dim3 grid(grid_for(p.n, 256, 256), p.b);
-  if (eps)
-    hipLaunchKernelGGL(ddim_apply_eps_kernel, grid, dim3(256), 0, s, p, part);
-  else
-    hipLaunchKernelGGL(ddim_apply_kernel, grid, dim3(256), 0, s, p, part);
-  TC_LAUNCH_CHECK();
-  return TC_OK;
-}
-
-extern "C" int tc_ddim_step(const TcDdimParams* pp, void* workspace, int64_t workspace_bytes, void* stream) {
-  return ddim_step_launch(pp, workspace, workspace_bytes, stream, false);
-}
-
-extern "C" int tc_ddim_step_eps(const TcDdimParams* pp, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (pp && pp->sqrt_ac == 0.f) return TC_EINVAL;          // eps divides by sqrt_ac: a zero-terminal-SNR step has no eps form
-  return ddim_step_launch(pp, workspace, workspace_bytes, stream, true);
-}
-
-static int ddim_step_ms_launch(const TcDdimMsParams* mp, void* workspace, int64_t workspace_bytes, void* stream, bool eps) {
-  if (!mp) return TC_EINVAL;
-  const TcDdimParams& p = mp->base;
-  if (const int rc = ddim_step_check(p, workspace, workspace_bytes)) return rc;
-  if (eps && p.sqrt_ac == 0.f) return TC_EINVAL;
-  if (!std::isfinite(mp->corr)) return TC_EINVAL;
-  const float* hist = mp->x0_hist;
+// The one launcher of a step: pass 1 when the step rescales its guidance, then the apply kernel.  The first-order entry points
+// come here without a history, which leaves the overlap check nothing to test.
+static int ddim_step_launch(const TcDdimMsParams& mp, void* workspace, int64_t workspace_bytes, void* stream, bool eps) {
+  const TcDdimParams& p = mp.base;
+  if (const int rc = ddim_step_check(p, workspace, workspace_bytes, eps)) return rc;
+  if (!std::isfinite(mp.corr)) return TC_EINVAL;
+  const float* hist = mp.x0_hist;
   if (hist) {                                             // an output over the history, other than pred_x0 == x0_hist exactly
     const uintptr_t bytes = (uintptr_t)p.b * (uintptr_t)p.n * sizeof(float), h = reinterpret_cast<uintptr_t>(hist);
     const uintptr_t xp = reinterpret_cast<uintptr_t>(p.x_prev), x0 = reinterpret_cast<uintptr_t>(p.pred_x0);
@@ -573,25 +493,36 @@ static int ddim_step_ms_launch(const TcDdimMsParams* mp, void* workspace, int64_
     vec = vec && tc_aligned16(q);                         // NULL counts as aligned: that operand is not touched
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   double* part = reinterpret_cast<double*>(workspace);
-  if (const int rc = ddim_stats_launch(p, part, s)) return rc;
+  if (p.e_uncond && p.guidance_rescale > 0.f) {
+    hipLaunchKernelGGL(ddim_stats_kernel, dim3(DDIM_PARTS, p.b), dim3(256), 0, s, p, part);
+    TC_LAUNCH_CHECK();
+  }
   const dim3 grid(grid_for(vec ? (p.n + 3) >> 2 : p.n, 256, 256), p.b);
   if (eps) {
-    if (vec) hipLaunchKernelGGL((ddim_apply_ms_kernel<true, true>), grid, dim3(256), 0, s, p, hist, mp->corr, part);
-    else hipLaunchKernelGGL((ddim_apply_ms_kernel<true, false>), grid, dim3(256), 0, s, p, hist, mp->corr, part);
+    if (vec) hipLaunchKernelGGL((ddim_apply_ms_kernel<true, true>), grid, dim3(256), 0, s, p, hist, mp.corr, part);
+    else hipLaunchKernelGGL((ddim_apply_ms_kernel<true, false>), grid, dim3(256), 0, s, p, hist, mp.corr, part);
   } else {
-    if (vec) hipLaunchKernelGGL((ddim_apply_ms_kernel<false, true>), grid, dim3(256), 0, s, p, hist, mp->corr, part);
-    else hipLaunchKernelGGL((ddim_apply_ms_kernel<false, false>), grid, dim3(256), 0, s, p, hist, mp->corr, part);
+    if (vec) hipLaunchKernelGGL((ddim_apply_ms_kernel<false, true>), grid, dim3(256), 0, s, p, hist, mp.corr, part);
+    else hipLaunchKernelGGL((ddim_apply_ms_kernel<false, false>), grid, dim3(256), 0, s, p, hist, mp.corr, part);
   }
   TC_LAUNCH_CHECK();
   return TC_OK;
 }
 
+extern "C" int tc_ddim_step(const TcDdimParams* p, void* workspace, int64_t workspace_bytes, void* stream) {
+  return p ? ddim_step_launch(TcDdimMsParams{*p, nullptr, 0.f}, workspace, workspace_bytes, stream, false) : TC_EINVAL;
+}
+
+extern "C" int tc_ddim_step_eps(const TcDdimParams* p, void* workspace, int64_t workspace_bytes, void* stream) {
+  return p ? ddim_step_launch(TcDdimMsParams{*p, nullptr, 0.f}, workspace, workspace_bytes, stream, true) : TC_EINVAL;
+}
+
 extern "C" int tc_ddim_step_ms(const TcDdimMsParams* p, void* workspace, int64_t workspace_bytes, void* stream) {
-  return ddim_step_ms_launch(p, workspace, workspace_bytes, stream, false);
+  return p ? ddim_step_launch(*p, workspace, workspace_bytes, stream, false) : TC_EINVAL;
 }
 
 extern "C" int tc_ddim_step_ms_eps(const TcDdimMsParams* p, void* workspace, int64_t workspace_bytes, void* stream) {
-  return ddim_step_ms_launch(p, workspace, workspace_bytes, stream, true);
+  return p ? ddim_step_launch(*p, workspace, workspace_bytes, stream, true) : TC_EINVAL;
 }
 
 extern "C" int tc_ddim_blend(const TcDdimBlendParams* pp, void* stream) {

@@ -272,20 +272,6 @@ void check_affine(const Tensor& g, const Tensor& b, int64_t c, const char* what)
               g.is_contiguous() && b.is_contiguous() && g.numel() == c && b.numel() == c, what, ": gamma / beta must be contiguous fp32 CUDA [C]");
 }
 
-Tensor groupnorm_cuda(const Tensor& x, const Tensor& gamma, const Tensor& beta, int64_t samples, int64_t rows, double eps, bool silu) {
-  check_rows(x, "groupnorm: x");
-  const int64_t c = x.size(1);
-  TORCH_CHECK(x.is_contiguous() && x.size(0) == samples * rows, "groupnorm: x must be contiguous [samples*rows, C]");
-  check_affine(gamma, beta, c, "groupnorm");
-  Tensor y = at::empty_like(x);
-  const int64_t nbytes = tc_groupnorm_workspace((int32_t)samples, (int32_t)rows, (int32_t)c);
-  Tensor ws = at::empty({nbytes > 16 ? nbytes : 16}, x.options().dtype(at::kByte));
-  check_rc(tc_groupnorm(bf(x), reinterpret_cast<tc_bf16*>(y.data_ptr()), gamma.data_ptr<float>(), beta.data_ptr<float>(),
-                        (int32_t)samples, (int32_t)rows, (int32_t)c, (float)eps, silu ? 1 : 0, ws.data_ptr(), nbytes, cur_stream()),
-           "tc_groupnorm");
-  return y;
-}
-
 // ABI 12: the consumer's weights (read-only CUDA tensors, contiguous) as a prefetch list for the norm's extra blocks
 TcPrefetch prefetch_of(at::TensorList ts, const char* what) {
   TORCH_CHECK((int64_t)ts.size() <= TC_PREFETCH_MAX, what, ": at most ", TC_PREFETCH_MAX, " prefetch tensors");
@@ -326,8 +312,23 @@ Tensor layernorm_pf_cuda(const Tensor& x, const Tensor& gamma, const Tensor& bet
   return y;
 }
 
-Tensor groupnorm_pf_meta(const Tensor& x, const Tensor&, const Tensor&, int64_t, int64_t, double, bool, at::TensorList) { return at::empty_like(x); }
-Tensor layernorm_pf_meta(const Tensor& x, const Tensor&, const Tensor&, double, at::TensorList) { return at::empty_like(x); }
+// groupnorm / layernorm are their _pf forms with an empty list: an empty TcPrefetch launches what a NULL one launches
+Tensor groupnorm_cuda(const Tensor& x, const Tensor& gamma, const Tensor& beta, int64_t samples, int64_t rows, double eps, bool silu) {
+  return groupnorm_pf_cuda(x, gamma, beta, samples, rows, eps, silu, {});
+}
+
+Tensor layernorm_cuda(const Tensor& x, const Tensor& gamma, const Tensor& beta, double eps) {
+  return layernorm_pf_cuda(x, gamma, beta, eps, {});
+}
+
+// Meta for every operator whose results all have the shape and dtype of its first argument: the norms (one result) and the
+// DDIM steps (two).  Boxed, so that one function serves schemas with different argument lists.
+void like_first_meta(const c10::OperatorHandle& op, torch::jit::Stack* stack) {
+  const auto& schema = op.schema();
+  const Tensor x = torch::jit::peek(*stack, 0, schema.arguments().size()).toTensor();
+  torch::jit::drop(*stack, schema.arguments().size());
+  for (size_t i = 0; i < schema.returns().size(); ++i) torch::jit::push(*stack, at::empty_like(x));
+}
 
 // ---- the level-0 one-launch operators (ABI 9): LayerNorm + GEGLU feed-forward + residual; LayerNorm + temporal self-attention +
 // residual (lvdm/modules/attention.py:81-144,225-246,415-442).  ln_eps < 0: x is taken as already normalised.
@@ -408,19 +409,6 @@ Tensor temporal_qkv_attn_meta(const Tensor& x, const Tensor&, const optional<Ten
   return at::empty({x.size(0), x.size(1)}, x.options());
 }
 
-Tensor layernorm_cuda(const Tensor& x, const Tensor& gamma, const Tensor& beta, double eps) {
-  check_rows(x, "layernorm: x");
-  TORCH_CHECK(x.is_contiguous(), "layernorm: x must be contiguous");
-  check_affine(gamma, beta, x.size(1), "layernorm");
-  Tensor y = at::empty_like(x);
-  check_rc(tc_layernorm(bf(x), reinterpret_cast<tc_bf16*>(y.data_ptr()), gamma.data_ptr<float>(), beta.data_ptr<float>(),
-                        (int32_t)x.size(0), (int32_t)x.size(1), (float)eps, cur_stream()), "tc_layernorm");
-  return y;
-}
-
-Tensor like_meta3(const Tensor& x, const Tensor&, const Tensor&, int64_t, int64_t, double, bool) { return at::empty_like(x); }
-Tensor like_meta_ln(const Tensor& x, const Tensor&, const Tensor&, double) { return at::empty_like(x); }
-
 // The checked TcDdimParams of a step; x_prev and x0 are its two results.
 TcDdimParams ddim_params(const char* what, const Tensor& x, const Tensor& e_cond, const optional<Tensor>& e_uncond,
                          const optional<Tensor>& noise, const optional<Tensor>& e_uncond_img, const optional<Tensor>& x0_hist,
@@ -446,29 +434,8 @@ TcDdimParams ddim_params(const char* what, const Tensor& x, const Tensor& e_cond
   return p;
 }
 
-template <bool EPS>
-std::tuple<Tensor, Tensor> ddim_step_any(const Tensor& x, const Tensor& e_cond, const optional<Tensor>& e_uncond,
-                                         const optional<Tensor>& noise, const optional<Tensor>& e_uncond_img, double cfg_scale,
-                                         double cfg_img, double guidance_rescale, double sqrt_ac, double sqrt_1m_ac,
-                                         double sqrt_a_prev, double dir_coef, double sigma, double x0_rescale) {
-  Tensor x_prev, x0;
-  const TcDdimParams p = ddim_params("ddim_step", x, e_cond, e_uncond, noise, e_uncond_img, c10::nullopt, x_prev, x0, cfg_scale,
-                                     cfg_img, guidance_rescale, sqrt_ac, sqrt_1m_ac, sqrt_a_prev, dir_coef, sigma, x0_rescale);
-  const int64_t nbytes = tc_ddim_workspace(p.b);
-  Tensor ws = at::empty({nbytes > 16 ? nbytes : 16}, x.options().dtype(at::kByte));
-  if (EPS)
-    check_rc(tc_ddim_step_eps(&p, ws.data_ptr(), nbytes, cur_stream()), "tc_ddim_step_eps");
-  else
-    check_rc(tc_ddim_step(&p, ws.data_ptr(), nbytes, cur_stream()), "tc_ddim_step");
-  return std::make_tuple(x_prev, x0);
-}
-
-std::tuple<Tensor, Tensor> ddim_step_meta(const Tensor& x, const Tensor&, const optional<Tensor>&, const optional<Tensor>&,
-                                          const optional<Tensor>&, double, double, double, double, double, double, double, double, double) {
-  return std::make_tuple(at::empty_like(x), at::empty_like(x));
-}
-
-// The step with the second-order multistep term (additive within ABI 14): x0_hist is the previous step's pred_x0 or None.
+// The one step implementation: x0_hist is the previous step's pred_x0 or None, and without one (or with corr 0) the step is
+// first order (the multistep term is additive within ABI 14).
 template <bool EPS>
 std::tuple<Tensor, Tensor> ddim_step_ms_any(const Tensor& x, const Tensor& e_cond, const optional<Tensor>& e_uncond,
                                             const optional<Tensor>& noise, const optional<Tensor>& e_uncond_img,
@@ -477,7 +444,7 @@ std::tuple<Tensor, Tensor> ddim_step_ms_any(const Tensor& x, const Tensor& e_con
                                             double dir_coef, double sigma, double x0_rescale) {
   Tensor x_prev, x0;
   TcDdimMsParams mp = {};
-  mp.base = ddim_params("ddim_step_ms", x, e_cond, e_uncond, noise, e_uncond_img, x0_hist, x_prev, x0, cfg_scale, cfg_img,
+  mp.base = ddim_params("ddim_step", x, e_cond, e_uncond, noise, e_uncond_img, x0_hist, x_prev, x0, cfg_scale, cfg_img,
                         guidance_rescale, sqrt_ac, sqrt_1m_ac, sqrt_a_prev, dir_coef, sigma, x0_rescale);
   mp.x0_hist = x0_hist.has_value() ? x0_hist->data_ptr<float>() : nullptr;
   mp.corr = (float)corr;
@@ -490,10 +457,14 @@ std::tuple<Tensor, Tensor> ddim_step_ms_any(const Tensor& x, const Tensor& e_con
   return std::make_tuple(x_prev, x0);
 }
 
-std::tuple<Tensor, Tensor> ddim_step_ms_meta(const Tensor& x, const Tensor&, const optional<Tensor>&, const optional<Tensor>&,
-                                             const optional<Tensor>&, const optional<Tensor>&, double, double, double, double,
-                                             double, double, double, double, double, double) {
-  return std::make_tuple(at::empty_like(x), at::empty_like(x));
+// ddim_step / ddim_step_eps: the schema without the two history operands
+template <bool EPS>
+std::tuple<Tensor, Tensor> ddim_step_any(const Tensor& x, const Tensor& e_cond, const optional<Tensor>& e_uncond,
+                                         const optional<Tensor>& noise, const optional<Tensor>& e_uncond_img, double cfg_scale,
+                                         double cfg_img, double guidance_rescale, double sqrt_ac, double sqrt_1m_ac,
+                                         double sqrt_a_prev, double dir_coef, double sigma, double x0_rescale) {
+  return ddim_step_ms_any<EPS>(x, e_cond, e_uncond, noise, e_uncond_img, c10::nullopt, 0.0, cfg_scale, cfg_img, guidance_rescale,
+                               sqrt_ac, sqrt_1m_ac, sqrt_a_prev, dir_coef, sigma, x0_rescale);
 }
 
 Tensor ddim_blend_cuda(const optional<Tensor>& x, const Tensor& x0, const optional<Tensor>& noise, const optional<Tensor>& mask,
@@ -710,14 +681,9 @@ TORCH_LIBRARY_IMPL(tooncrafter, Meta, m) {
   m.impl("attention_temporal", attention_temporal_meta);
   m.impl("attention_temporal_rel", attention_temporal_rel_meta);
   m.impl("attention_q8", attention_q8_meta);
-  m.impl("groupnorm", like_meta3);
-  m.impl("layernorm", like_meta_ln);
-  m.impl("groupnorm_pf", groupnorm_pf_meta);
-  m.impl("layernorm_pf", layernorm_pf_meta);
-  m.impl("ddim_step", ddim_step_meta);
-  m.impl("ddim_step_eps", ddim_step_meta);
-  m.impl("ddim_step_ms", ddim_step_ms_meta);
-  m.impl("ddim_step_ms_eps", ddim_step_ms_meta);
+  for (const char* name : {"groupnorm", "layernorm", "groupnorm_pf", "layernorm_pf", "ddim_step", "ddim_step_eps", "ddim_step_ms",
+                           "ddim_step_ms_eps"})
+    m.impl(name, torch::CppFunction::makeFromBoxedFunction<&like_first_meta>());
   m.impl("ddim_blend", ddim_blend_meta);
   m.impl("frames_from_u8", frames_from_u8_meta);
   m.impl("clip_patches", clip_patches_meta);

@@ -178,6 +178,18 @@ class DDIMSampler(object):
             return ops.ddim_step(x, e_c, e_u, noise, **guidance, **sc)
         return ops.ddim_step_ms(x, e_c, e_u, noise, x0_hist, corr=0.0 if x0_hist is None else ms_corr, **guidance, **sc)
 
+    def loop_step(self, order2, x, c, ts, index, step, **kw):
+        """One `p_sample_ddim` call of a sampling loop, with the order-2 bookkeeping.  `order2`: None at order 1, where
+        p_sample_ddim gets the keywords it always got; at order 2 the loop's [last pred_x0, last log-SNR increment], [None, None]
+        at the start of a run, read for this step's keywords and updated after it (a prediction of x0: the pinned-frame blend
+        does not touch it)."""
+        if order2 is None:
+            return self.p_sample_ddim(x, c, ts, index=index, _step=step, **kw)
+        corr, h = self.multistep_corr(index, step, order2[1])
+        x_prev, pred_x0 = self.p_sample_ddim(x, c, ts, index=index, _step=step, solver_order=2, x0_hist=order2[0], ms_corr=corr, **kw)
+        order2[:] = pred_x0, h
+        return x_prev, pred_x0
+
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None,
                img_callback=None, quantize_x0=False, eta=0., mask=None, x0=None, temperature=1.,
@@ -249,7 +261,7 @@ class DDIMSampler(object):
             # becomes the dense fp32 operand of the blend kernel
             mask = torch.as_tensor(mask).to(device=device, dtype=torch.float32).expand(tuple(img.shape)).contiguous()
             x0 = x0.to(device=device, dtype=torch.float32).expand(tuple(img.shape)).contiguous()
-        hist, h_prev = None, None                    # order 2: the last pred_x0 and log-SNR increment; a run starts without
+        order2 = [None, None] if solver_order == 2 else None
         for i, step in enumerate(iterator):
             index = total_steps - i - 1
             ts = torch.full((b,), int(step), device=device, dtype=torch.long)
@@ -265,17 +277,11 @@ class DDIMSampler(object):
                 else:
                     img_orig = self.model.q_sample(x0, int(step))
                 img = ops.ddim_blend(img, img_orig, None, mask)
-            ms = {}                                  # order 1: p_sample_ddim gets the keywords it always got
-            if solver_order == 2:
-                corr, h = self.multistep_corr(index, int(step), h_prev)
-                ms = dict(solver_order=2, x0_hist=hist, ms_corr=corr)
-            img, pred_x0 = self.p_sample_ddim(img, cond, ts, index=index, temperature=temperature,
-                                              noise_dropout=noise_dropout,
-                                              unconditional_guidance_scale=unconditional_guidance_scale,
-                                              unconditional_conditioning=unconditional_conditioning,
-                                              fs=fs, guidance_rescale=guidance_rescale, _step=int(step), seeds=seeds, **ms, **kwargs)
-            if solver_order == 2:
-                hist, h_prev = pred_x0, h            # a prediction of x0: the pinned-frame blend does not touch it
+            img, pred_x0 = self.loop_step(order2, img, cond, ts, index, int(step), temperature=temperature,
+                                          noise_dropout=noise_dropout,
+                                          unconditional_guidance_scale=unconditional_guidance_scale,
+                                          unconditional_conditioning=unconditional_conditioning,
+                                          fs=fs, guidance_rescale=guidance_rescale, seeds=seeds, **kwargs)
             if callback:
                 callback(i)
             if img_callback:
@@ -293,6 +299,22 @@ class DDIMSampler(object):
                       guidance_rescale=0.0, _step=None, seeds=None, solver_order=1, x0_hist=None, ms_corr=0.0, **kwargs):
         """`solver_order=2` with `x0_hist` (the previous step's pred_x0) and `ms_corr` (`multistep_corr`): the corrected
         step; the caller's loop carries both, nothing is kept on the sampler."""
+        def evaluate(use_cfg):
+            if not use_cfg:
+                return self.model.apply_model(x, t, c, **kwargs), None, {}
+            if hasattr(self.model, "apply_model_cfg"):
+                return (*self.model.apply_model_cfg(x, t, c, unconditional_conditioning, **kwargs), {})
+            return (self.model.apply_model(x, t, c, **kwargs),
+                    self.model.apply_model(x, t, unconditional_conditioning, **kwargs), {})
+        return self.guided_step(evaluate, x, t, index, repeat_noise, use_original_steps, quantize_denoised, temperature,
+                                noise_dropout, score_corrector, unconditional_guidance_scale, unconditional_conditioning,
+                                guidance_rescale, _step, seeds, solver_order, x0_hist, ms_corr)
+
+    def guided_step(self, evaluate, x, t, index, repeat_noise, use_original_steps, quantize_denoised, temperature, noise_dropout,
+                    score_corrector, unconditional_guidance_scale, unconditional_conditioning, guidance_rescale, _step, seeds,
+                    solver_order, x0_hist, ms_corr):
+        """`p_sample_ddim` of the two- and the three-way sampler, which differ in `evaluate(use_cfg)` alone: it runs the model
+        and returns (e_cond, e_uncond or None, further guidance keywords of the fused step)."""
         solver_order = check_solver_order(solver_order, "p_sample_ddim")
         if use_original_steps or quantize_denoised or score_corrector is not None or noise_dropout > 0.:
             raise NotImplementedError("p_sample_ddim variant unused by the inference scripts")
@@ -301,19 +323,13 @@ class DDIMSampler(object):
             raise ValueError("p_sample_ddim: repeat_noise=True shares one draw among the clips; seeds= draws one per clip")
         step = int(t[0]) if _step is None else _step
         use_cfg = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.)
-        if not use_cfg:
-            e_c, e_u = self.model.apply_model(x, t, c, **kwargs), None
-        elif hasattr(self.model, "apply_model_cfg"):
-            e_c, e_u = self.model.apply_model_cfg(x, t, c, unconditional_conditioning, **kwargs)
-        else:
-            e_c = self.model.apply_model(x, t, c, **kwargs)
-            e_u = self.model.apply_model(x, t, unconditional_conditioning, **kwargs)
+        e_c, e_u, guidance = evaluate(use_cfg)
         sc = self.step_scalars(index, step)
+        # unseeded: always drawn, like the reference (ddim.py:266, ddim_multiplecond.py:277)
         noise = self.step_noise(x, index, sc["sigma"], temperature, repeat_noise, seeds)
-        x_prev, pred_x0 = self.fused_step(x.contiguous(), e_c.contiguous(), None if e_u is None else e_u.contiguous(),
-                                          noise, sc, solver_order, x0_hist, ms_corr, cfg_scale=unconditional_guidance_scale,
-                                          guidance_rescale=guidance_rescale if use_cfg else 0.0)
-        return x_prev, pred_x0
+        return self.fused_step(x.contiguous(), e_c.contiguous(), None if e_u is None else e_u.contiguous(), noise, sc,
+                               solver_order, x0_hist, ms_corr, cfg_scale=unconditional_guidance_scale,
+                               guidance_rescale=guidance_rescale if use_cfg else 0.0, **guidance)
 
     def step_noise(self, x, index, sigma, temperature, repeat_noise, seeds):
         """The step's noise operand of tc_ddim_step (None when sigma == 0), shared by the two- and three-way samplers."""
@@ -349,20 +365,13 @@ class DDIMSampler(object):
         total_steps = timesteps.shape[0]
         print(f"Running DDIM Sampling with {total_steps} timesteps")
         x_dec = x_latent.to(torch.float32).contiguous()
-        hist, h_prev = None, None
+        order2 = [None, None] if solver_order == 2 else None
         for i, step in enumerate(tqdm(time_range, desc='Decoding image', total=total_steps)):
             index = total_steps - i - 1
             ts = torch.full((x_latent.shape[0],), int(step), device=x_latent.device, dtype=torch.long)
-            ms = {}
-            if solver_order == 2:
-                corr, h = self.multistep_corr(index, int(step), h_prev)
-                ms = dict(solver_order=2, x0_hist=hist, ms_corr=corr)
-            x_dec, pred_x0 = self.p_sample_ddim(x_dec, cond, ts, index=index,
-                                                unconditional_guidance_scale=unconditional_guidance_scale,
-                                                unconditional_conditioning=unconditional_conditioning, _step=int(step), seeds=seeds,
-                                                **ms)
-            if solver_order == 2:
-                hist, h_prev = pred_x0, h
+            x_dec, _ = self.loop_step(order2, x_dec, cond, ts, index, int(step),
+                                      unconditional_guidance_scale=unconditional_guidance_scale,
+                                      unconditional_conditioning=unconditional_conditioning, seeds=seeds)
             if callback:
                 callback(i)
         return x_dec

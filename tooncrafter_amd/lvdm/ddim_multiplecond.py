@@ -20,8 +20,7 @@ from __future__ import annotations
 
 import torch
 
-from .. import ops
-from .ddim import DDIMSampler as _DDIMSampler, check_solver_order
+from .ddim import DDIMSampler as _DDIMSampler
 
 
 class DDIMSampler(_DDIMSampler):
@@ -31,30 +30,19 @@ class DDIMSampler(_DDIMSampler):
                       corrector_kwargs=None, unconditional_guidance_scale=1., unconditional_conditioning=None,
                       uc_type=None, cfg_img=None, mask=None, x0=None, guidance_rescale=0.0, _step=None, seeds=None,
                       solver_order=1, x0_hist=None, ms_corr=0.0, **kwargs):
-        solver_order = check_solver_order(solver_order, "p_sample_ddim")
-        if use_original_steps or quantize_denoised or score_corrector is not None or noise_dropout > 0.:
-            raise NotImplementedError("p_sample_ddim variant unused by the inference scripts")
-        self.step_kind()
-        if seeds is not None and repeat_noise:
-            raise ValueError("p_sample_ddim: repeat_noise=True shares one draw among the clips; seeds= draws one per clip")
-        if cfg_img is None:
-            cfg_img = unconditional_guidance_scale                                  # :217-218
-        uc_img = kwargs['unconditional_conditioning_img_nonetext']                   # :220 (KeyError like the reference)
-        step = int(t[0]) if _step is None else _step
-        use_cfg = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.)
-        e_u = e_i = None
-        if not use_cfg:
-            e_c = self.model.apply_model(x, t, c, **kwargs)
-        elif hasattr(self.model, "apply_model_multi"):
-            e_c, e_u, e_i = self.model.apply_model_multi(x, t, [c, unconditional_conditioning, uc_img], **kwargs)
-        else:
-            e_c = self.model.apply_model(x, t, c, **kwargs)
-            e_u = self.model.apply_model(x, t, unconditional_conditioning, **kwargs)
-            e_i = self.model.apply_model(x, t, uc_img, **kwargs)
-        sc = self.step_scalars(index, step)
-        noise = self.step_noise(x, index, sc["sigma"], temperature, repeat_noise, seeds)    # unseeded: always drawn, like the reference (:277)
-        cont = lambda v: None if v is None else v.contiguous()
-        return self.fused_step(x.contiguous(), e_c.contiguous(), cont(e_u), noise, sc, solver_order, x0_hist, ms_corr,
-                               cfg_scale=unconditional_guidance_scale,
-                               guidance_rescale=guidance_rescale if use_cfg else 0.0,
-                               e_uncond_img=cont(e_i), cfg_img=cfg_img)
+        cfg = unconditional_guidance_scale if cfg_img is None else cfg_img             # :217-218
+
+        def evaluate(use_cfg):
+            # the lookup comes first, whatever the guidance: a KeyError like the reference's (:220), and the key stays in kwargs
+            cfgs = [c, unconditional_conditioning, kwargs['unconditional_conditioning_img_nonetext']]
+            if not use_cfg:
+                return self.model.apply_model(x, t, c, **kwargs), None, dict(e_uncond_img=None, cfg_img=cfg)
+            if hasattr(self.model, "apply_model_multi"):
+                e_c, e_u, e_i = self.model.apply_model_multi(x, t, cfgs, **kwargs)
+            else:
+                e_c, e_u, e_i = (self.model.apply_model(x, t, cond, **kwargs) for cond in cfgs)
+            return e_c, e_u, dict(e_uncond_img=e_i.contiguous(), cfg_img=cfg)
+
+        return self.guided_step(evaluate, x, t, index, repeat_noise, use_original_steps, quantize_denoised, temperature,
+                                noise_dropout, score_corrector, unconditional_guidance_scale, unconditional_conditioning,
+                                guidance_rescale, _step, seeds, solver_order, x0_hist, ms_corr)

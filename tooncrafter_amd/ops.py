@@ -913,13 +913,16 @@ class HipOps:
                                             cfg_scale=cfg_scale, guidance_rescale=guidance_rescale, sqrt_ac=sqrt_ac,
                                             sqrt_1m_ac=sqrt_1m_ac, sqrt_a_prev=sqrt_a_prev, dir_coef=dir_coef, sigma=sigma,
                                             x0_rescale=x0_rescale, cfg_img=cfg_img)
-        nbytes = self.lib.tc_ddim_workspace(p.b)
-        ws = self._workspace(nbytes, x.device)
-        if parameterization == "v":
-            _lib.check(self.lib.tc_ddim_step(C.byref(p), ws.data_ptr(), nbytes, _stream()), "tc_ddim_step")
-        else:
-            _lib.check(self.lib.tc_ddim_step_eps(C.byref(p), ws.data_ptr(), nbytes, _stream()), "tc_ddim_step_eps")
+        self._ddim_launch("tc_ddim_step", parameterization, p, p.b, x.device)
         return x_prev, x0
+
+    def _ddim_launch(self, entry, parameterization, params, b, device):
+        """The launch tail of a step after `_ddim_params`: the workspace, then `entry` or its `_eps` form on `params`."""
+        if parameterization != "v":
+            entry += "_eps"
+        nbytes = self.lib.tc_ddim_workspace(b)
+        ws = self._workspace(nbytes, device)
+        _lib.check(getattr(self.lib, entry)(C.byref(params), ws.data_ptr(), nbytes, _stream()), entry)
 
     @staticmethod
     def _ddim_params(what, x, e_cond, e_uncond, noise, e_uncond_img, pred_x0, want_x0, parameterization, *, cfg_scale,
@@ -962,12 +965,7 @@ class HipOps:
                                             sqrt_ac=sqrt_ac, sqrt_1m_ac=sqrt_1m_ac, sqrt_a_prev=sqrt_a_prev, dir_coef=dir_coef,
                                             sigma=sigma, x0_rescale=x0_rescale, cfg_img=cfg_img, also=(x0_hist,))
         mp = _lib.TcDdimMsParams(base=p, x0_hist=_ptr(x0_hist), corr=float(corr))
-        nbytes = self.lib.tc_ddim_workspace(p.b)
-        ws = self._workspace(nbytes, x.device)
-        if parameterization == "v":
-            _lib.check(self.lib.tc_ddim_step_ms(C.byref(mp), ws.data_ptr(), nbytes, _stream()), "tc_ddim_step_ms")
-        else:
-            _lib.check(self.lib.tc_ddim_step_ms_eps(C.byref(mp), ws.data_ptr(), nbytes, _stream()), "tc_ddim_step_ms_eps")
+        self._ddim_launch("tc_ddim_step_ms", parameterization, mp, p.b, x.device)
         return x_prev, x0
 
     def ddim_blend(self, x, x0, noise, mask, *, sqrt_ac=1.0, sqrt_1m_ac=0.0, out=None):

@@ -122,15 +122,18 @@ class TorchLibOps(HipOps):
             return self.t.layernorm_pf(x, gamma, beta, float(eps), pfl)
         return self.t.layernorm(x, gamma, beta, float(eps))
 
+    def _step_op(self, what, parameterization, operands, want_x0, cfg_scale, cfg_img, *scalars):
+        """`what` or its `_eps` form on `operands` and the step's nine scalars, which are marshalled here for every step."""
+        if parameterization not in ("v", "eps"):
+            raise NotImplementedError(f"{what}: parameterization {parameterization!r} (the fused step has 'v' and 'eps')")
+        op = getattr(self.t, what if parameterization == "v" else what + "_eps")
+        xp, x0 = op(*operands, float(cfg_scale), float(cfg_scale if cfg_img is None else cfg_img), *map(float, scalars))
+        return xp, (x0 if want_x0 else None)
+
     def ddim_step(self, x, e_cond, e_uncond, noise, *, cfg_scale, guidance_rescale, sqrt_ac, sqrt_1m_ac, sqrt_a_prev,
                   dir_coef, sigma, x0_rescale, want_x0=True, e_uncond_img=None, cfg_img=None, parameterization="v"):
-        if parameterization not in ("v", "eps"):
-            raise NotImplementedError(f"ddim_step: parameterization {parameterization!r} (the fused step has 'v' and 'eps')")
-        op = self.t.ddim_step if parameterization == "v" else self.t.ddim_step_eps
-        xp, x0 = op(x, e_cond, e_uncond, noise, e_uncond_img, float(cfg_scale),
-                    float(cfg_scale if cfg_img is None else cfg_img), float(guidance_rescale), float(sqrt_ac),
-                    float(sqrt_1m_ac), float(sqrt_a_prev), float(dir_coef), float(sigma), float(x0_rescale))
-        return xp, (x0 if want_x0 else None)
+        return self._step_op("ddim_step", parameterization, (x, e_cond, e_uncond, noise, e_uncond_img), want_x0, cfg_scale, cfg_img,
+                             guidance_rescale, sqrt_ac, sqrt_1m_ac, sqrt_a_prev, dir_coef, sigma, x0_rescale)
 
     def ddim_step_ms(self, x, e_cond, e_uncond, noise, x0_hist, *, corr, cfg_scale, guidance_rescale, sqrt_ac, sqrt_1m_ac,
                      sqrt_a_prev, dir_coef, sigma, x0_rescale, want_x0=True, e_uncond_img=None, cfg_img=None,
@@ -141,13 +144,9 @@ class TorchLibOps(HipOps):
                                         sqrt_a_prev=sqrt_a_prev, dir_coef=dir_coef, sigma=sigma, x0_rescale=x0_rescale,
                                         want_x0=want_x0, e_uncond_img=e_uncond_img, cfg_img=cfg_img,
                                         parameterization=parameterization, pred_x0=pred_x0)
-        if parameterization not in ("v", "eps"):
-            raise NotImplementedError(f"ddim_step_ms: parameterization {parameterization!r} (the fused step has 'v' and 'eps')")
-        op = self.t.ddim_step_ms if parameterization == "v" else self.t.ddim_step_ms_eps
-        xp, x0 = op(x, e_cond, e_uncond, noise, e_uncond_img, x0_hist, float(corr), float(cfg_scale),
-                    float(cfg_scale if cfg_img is None else cfg_img), float(guidance_rescale), float(sqrt_ac),
-                    float(sqrt_1m_ac), float(sqrt_a_prev), float(dir_coef), float(sigma), float(x0_rescale))
-        return xp, (x0 if want_x0 else None)
+        return self._step_op("ddim_step_ms", parameterization, (x, e_cond, e_uncond, noise, e_uncond_img, x0_hist, float(corr)),
+                             want_x0, cfg_scale, cfg_img, guidance_rescale, sqrt_ac, sqrt_1m_ac, sqrt_a_prev, dir_coef, sigma,
+                             x0_rescale)
 
     def ddim_blend(self, x, x0, noise, mask, *, sqrt_ac=1.0, sqrt_1m_ac=0.0, out=None):
         if out is not None:                                 # an explicit result buffer (in place): the ctypes method
