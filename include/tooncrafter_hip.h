@@ -541,6 +541,82 @@ typedef struct TcClipPatchesParams {
 int64_t tc_clip_patches_workspace(const TcClipPatchesParams* p);
 int tc_clip_patches(const TcClipPatchesParams* p, void* stream);
 
+/* ---- Pixel back end: the decoder's fp32 clips -> uint8 frames at a chosen size, in the pixel format an encoder takes,
+ * written where they belong in a longer video (additive within ABI 14: one struct, three symbols).  The reference does
+ * this step outside its own code, with torch on the host (scripts/evaluation/inference.py:146-155), PIL and torchvision.
+ * tc_video_to_u8 above stays as it is: packed RGB at the model's size. ---- */
+
+/* tc_resize_tables for PIL's other filters: the same contract (sizing query, the return value kmax, the refusals,
+ * bounds[2 xx] = xmin, bounds[2 xx + 1] = xmax - xmin; TC_EINVAL also for an unknown filter), the rule Pillow's
+ * precompute_coeffs + normalize_coeffs_8bpc in double, for a filter F of support S:
+ *   scale = in / out, fs = max(scale, 1), support = S * fs, kmax = ceil(support) * 2 + 1, center = (xx + 0.5) * scale,
+ *   xmin = max(int(center - support + 0.5), 0), xmax = min(int(center + support + 0.5), in),
+ *   w[x] = F((x + xmin - center + 0.5) * (1 / fs))  -- a MULTIPLICATION by the reciprocal, as Pillow writes it --
+ *   summed in tap order and divided by the sum when it is not zero,
+ *   coefs[xx * kmax + x] = int(0.5 + w * 2^22) for w >= 0, int(-0.5 + w * 2^22) for w < 0; the cast truncates toward zero
+ *   (bicubic and Lanczos have negative lobes: + 0.5 alone is wrong for them), 0 from xmax - xmin on.
+ * The filters, as in Resample.c, each 0 outside the stated range:
+ *   BILINEAR  S = 1    F = 1 - |x| on |x| < 1
+ *   BICUBIC   S = 2    a = -0.5:  F = ((a + 2)|x| - (a + 3)) x^2 + 1 on |x| < 1,  (((|x| - 5)|x| + 8)|x| - 4) a on 1 <= |x| < 2
+ *   LANCZOS   S = 3    F = sinc(x) sinc(x / 3) on -3 <= x < 3,  sinc(x) = sin(pi x) / (pi x),  sinc(0) = 1
+ *   BOX       S = 0.5  F = 1 on -0.5 < x <= 0.5
+ * At TC_RESIZE_BILINEAR the tables are tc_resize_tables' for every size pair 1 .. 128. */
+enum { TC_RESIZE_BILINEAR = 0, TC_RESIZE_BICUBIC = 1, TC_RESIZE_LANCZOS = 2, TC_RESIZE_BOX = 3 };
+int32_t tc_resize_tables_filter(int32_t filter, int32_t in_size, int32_t out_size, int32_t* bounds, int32_t* coefs,
+                                int64_t coefs_len);
+
+/* Frames f0 .. f0 + nf - 1 of every clip of x (b, 3, t, h, w) fp32 -> uint8 frames of (oh, ow) pixels, in this order:
+ *   1. value: clamp(x, -1, 1), (v + 1) / 2, * 255, truncation to uint8 -- tc_video_to_u8's arithmetic, operation for
+ *      operation (one __device__ function serves both);
+ *   2. resample, only for an axis whose size changes: PIL's 8-bit two-pass resample of the uint8 RGB frame with tables of
+ *      tc_resize_tables_filter, horizontal (w -> ow) first, then vertical (h -> oh), a pass skipped when its size is
+ *      unchanged.  A pixel is clip(((1 << 21) + sum coefs * src) >> 22, 0, 255) in int32 with an arithmetic shift: with
+ *      negative lobes the sum goes below zero, so shift and clip are signed.  For the four filters sum |w| < 1.6, so the
+ *      sum stays inside int32.  Table entries are clamped to the image: wrong tables give wrong pixels, never an access
+ *      outside a buffer;
+ *   3. format, from the resized uint8 RGB:
+ *        RGB24  HWC, 3 bytes per pixel, rows `pitch` apart;
+ *        I420   Y plane of oh rows `pitch` apart, Cb at pitch * oh with oh / 2 rows pitch / 2 apart, Cr at
+ *               pitch * oh + (pitch / 2) * (oh / 2);
+ *        NV12   Y as for I420, then one plane of oh / 2 rows `pitch` apart with Cb, Cr interleaved.
+ *      BT.601 limited range in integers; Rs, Gs, Bs are the sums over the 2 x 2 block:
+ *        Y  = ( 16829 R  + 33039 G  +  6416 B  + (16 << 16)  + (1 << 15)) >> 16
+ *        Cb = ( -9714 Rs - 19070 Gs + 28784 Bs + (128 << 18) + (1 << 17)) >> 18
+ *        Cr = ( 28784 Rs - 24103 Gs -  4681 Bs + (128 << 18) + (1 << 17)) >> 18
+ *      clipped to 0 .. 255; every shifted quantity is non-negative.  The chroma rows each sum to 0, the Y row to
+ *      56284 ~ 219 / 255 * 2^16: black gives Y 16, white 235, pure red 81, pure blue 41; the 2 x 2 block {black, white,
+ *      red, blue} gives Cb 147, Cr 151.  This is deliberately NOT the float32 numpy expression of mp4.rgb_to_yuv420, whose
+ *      result depends on numpy's summation order for the 2 x 2 mean (that expression stays for RGB input): the two differ
+ *      by at most 1 code value (over 40 random 64 x 96 frames and a 52^3 colour grid 0.05 % of the Y and 0.03 % of the
+ *      chroma samples differ, none by more than 1);
+ *   4. placement: frame f0 + j of clip i goes to out + i * clip_stride + j * frame_stride.  Bytes between rows (pitch
+ *      padding), between frames and between clips are not written.  `loop` is nf = t - 1; a keyframe sequence is spliced
+ *      in place by writing clips 1 .. K - 1 with f0 = 1 and clip_stride = (t - 1) * frame bytes into one video buffer.
+ * A frame's bytes: pitch * oh (RGB24), pitch * oh + 2 * (pitch / 2) * (oh / 2) (I420), pitch * oh + pitch * (oh / 2) (NV12).
+ * workspace: tc_frames_to_u8_workspace bytes -- the uint8 RGB frames at source size (b * nf * h * w * 3) plus, when
+ * ow != w, the horizontal pass's intermediate (b * nf * h * ow * 3); 0 when nothing is resampled and the format is RGB24
+ * (0 also for a request tc_frames_to_u8 refuses).  Every pointer is device memory.
+ * TC_EINVAL: NULL p / x / out, a size <= 0, f0 / nf outside the clip, an unknown format, pitch below the row's bytes
+ * (3 * ow for RGB24, ow for the Y plane), frame_stride below the frame's bytes, clip_stride < nf * frame_stride when b > 1,
+ * tables missing for a pass that runs; TC_ESHAPE: I420 / NV12 with an odd oh or ow or, for I420, an odd pitch;
+ * TC_EWORKSPACE: workspace too small.  Nothing is launched or written on a refusal. */
+enum { TC_PIXFMT_RGB24 = 0, TC_PIXFMT_I420 = 1, TC_PIXFMT_NV12 = 2 };
+typedef struct TcFramesOutParams {
+  const float* x;              /* (b, 3, t, h, w) fp32: the decoder's output */
+  uint8_t* out;
+  int32_t b, t, h, w;
+  int32_t f0, nf;              /* frames f0 .. f0+nf-1 of every clip are written, 0 <= f0, nf >= 1, f0+nf <= t */
+  int32_t oh, ow;              /* output size; (oh, ow) == (h, w): no resample, no tables, and for RGB24 no workspace */
+  int32_t format;              /* TC_PIXFMT_* */
+  int32_t pitch;               /* bytes per row of the RGB image / of the Y plane */
+  int64_t frame_stride, clip_stride;   /* bytes from one written frame / clip to the next in out */
+  const int32_t* h_bounds; const int32_t* h_coefs; int32_t h_kmax;   /* w -> ow (NULL when ow == w) */
+  const int32_t* v_bounds; const int32_t* v_coefs; int32_t v_kmax;   /* h -> oh (NULL when oh == h) */
+  void* workspace; int64_t workspace_bytes;
+} TcFramesOutParams;
+int64_t tc_frames_to_u8_workspace(const TcFramesOutParams* p);
+int tc_frames_to_u8(const TcFramesOutParams* p, void* stream);
+
 /* ---- Per-clip Gaussian noise from a counter-based generator (additive within ABI 14: one struct, one symbol).  Replaces
  * the sampler's torch.randn draws from the process-wide device generator (reference ddim.py:157, 266 / common.py:31-34,
  * ddpm3d.py q_sample) when the caller names one seed per clip: element j of clip i is a pure function of

@@ -156,6 +156,24 @@ class TcClipPatchesParams(C.Structure):
     ]
 
 
+class TcFramesOutParams(C.Structure):
+    """fp32 clips -> resized uint8 RGB / I420 / NV12 frames at named places (tc_frames_to_u8; additive within ABI 14)."""
+    _fields_ = [
+        ("x", C.c_void_p), ("out", C.c_void_p),
+        ("b", C.c_int32), ("t", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+        ("f0", C.c_int32), ("nf", C.c_int32), ("oh", C.c_int32), ("ow", C.c_int32),
+        ("format", C.c_int32), ("pitch", C.c_int32),
+        ("frame_stride", C.c_int64), ("clip_stride", C.c_int64),
+        ("h_bounds", C.c_void_p), ("h_coefs", C.c_void_p), ("h_kmax", C.c_int32),
+        ("v_bounds", C.c_void_p), ("v_coefs", C.c_void_p), ("v_kmax", C.c_int32),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+    ]
+
+
+TC_RESIZE_FILTERS = {"bilinear": 0, "bicubic": 1, "lanczos": 2, "box": 3}      # include/tooncrafter_hip.h: TC_RESIZE_*
+TC_PIXFMTS = {"rgb24": 0, "i420": 1, "nv12": 2}                                # include/tooncrafter_hip.h: TC_PIXFMT_*
+
+
 class TcRandnParams(C.Structure):
     """Per-clip Philox noise (tc_randn_clips; additive within ABI 14).  `seeds` is a HOST array of b uint64."""
     _fields_ = [
@@ -225,6 +243,9 @@ SYMBOLS = {
     "tc_frames_from_u8": (C.c_int, [C.POINTER(TcFramesU8Params), C.c_void_p]),
     "tc_clip_patches_workspace": (C.c_int64, [C.POINTER(TcClipPatchesParams)]),
     "tc_clip_patches": (C.c_int, [C.POINTER(TcClipPatchesParams), C.c_void_p]),
+    "tc_resize_tables_filter": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64]),
+    "tc_frames_to_u8_workspace": (C.c_int64, [C.POINTER(TcFramesOutParams)]),
+    "tc_frames_to_u8": (C.c_int, [C.POINTER(TcFramesOutParams), C.c_void_p]),
     "tc_randn_clips": (C.c_int, [C.POINTER(TcRandnParams), C.c_void_p]),
     "tc_gemm_ws_eligible": (C.c_int, [C.POINTER(TcGemmParams)]),
     "tc_gemm_gn_rows": (C.c_int, [C.POINTER(TcGemmParams)]),
@@ -284,7 +305,7 @@ class _TracedLib:
 
     def __getattr__(self, name):
         fn = getattr(self._lib, name)
-        if name not in SYMBOLS or name in ("tc_abi_version", "tc_build_info", "tc_resize_tables", "tc_frames_from_u8_resized") or name.endswith("_workspace"):
+        if name not in SYMBOLS or name in ("tc_abi_version", "tc_build_info", "tc_resize_tables", "tc_resize_tables_filter", "tc_frames_from_u8_resized") or name.endswith("_workspace"):
             return fn
         import sys
 

@@ -237,15 +237,19 @@ def synthesize(model, videos, latent_shape, *, plan: SamplingPlan, prompts=None,
 
 
 def synthesize_u8(model, first_u8, last_u8, latent_shape, *, size, plan: SamplingPlan, prompts=None, fs=24, three_way=False,
-                  hold_endpoints=True):
+                  hold_endpoints=True, out_size=None, out_filter="bicubic", out_fmt="rgb24"):
     """uint8 keyframes in, uint8 clip out, all on the device: (b, h, w, 3) first / last frames -> (b, t, H, W, 3) frames
     (`Conditions.from_uint8`, `sample`, `decode_spliced`, `clip_to_uint8`).  The last frame of one clip can be the first
-    keyframe of the next without leaving the GPU.  `plan.seeds` as in `sample`."""
+    keyframe of the next without leaving the GPU.  `plan.seeds` as in `sample`.
+    out_size = (oh, ow), out_filter, out_fmt: the delivery size and pixel format (`clip_to_uint8`'s size / filter / fmt, the
+    pixel back end) -- (b, t, oh, ow, 3) frames, or for "i420" / "nv12" the (b, t, oh * ow * 3 / 2) planes that
+    `mp4.write_mp4_i420` or an encoder takes."""
     from .output import clip_to_uint8
     cond = Conditions.from_uint8(model, first_u8, last_u8, size=size, t=latent_shape[2], prompts=prompts, fs=fs,
                                  guided=plan.scale != 1.0, three_way=three_way, image_branch=plan.image_scale != 1.0,
                                  hold_endpoints=hold_endpoints)
-    return clip_to_uint8(decode_spliced(model, sample(model, cond, plan, latent_shape), cond.refs))
+    return clip_to_uint8(decode_spliced(model, sample(model, cond, plan, latent_shape), cond.refs), size=out_size,
+                         filter=out_filter, fmt=out_fmt)
 
 
 # --- the reference scripts' call signatures (scripts/evaluation/inference.py:164,180) -----------------------------------

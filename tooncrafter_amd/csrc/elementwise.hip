@@ -1,6 +1,7 @@
 // Layout converters at the module boundary, embedding helpers, the AE3DConv temporal tail
 // and the fused DDIM / classifier-free-guidance step.  All HBM- or latency-bound, gfx950.
 #include "common.h"
+#include "pixel_u8.h"
 
 #include <cmath>
 #include <initializer_list>
@@ -348,12 +349,7 @@ __global__ __launch_bounds__(256) void video_to_u8_kernel(const float* __restric
     const int64_t frame = i / hw, pix = i - frame * hw;         // frame = b*t + tt
     const int64_t b = frame / t, tt = frame - b * t;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      float v = x[((b * 3 + c) * t + tt) * hw + pix];
-      v = fminf(fmaxf(v, -1.f), 1.f);
-      v = (v + 1.0f) / 2.0f;
-      out[i * 3 + c] = (uint8_t)(v * 255.f);                    // fp32 -> u8 truncates, like Tensor.to(uint8)
-    }
+    for (int c = 0; c < 3; ++c) out[i * 3 + c] = sample_to_u8(x[((b * 3 + c) * t + tt) * hw + pix]);    // pixel_u8.h
   }
 }
 

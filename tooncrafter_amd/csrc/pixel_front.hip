@@ -3,6 +3,7 @@
 // here is one thread per output element, written for the arithmetic to be read off the code: the integer resample must give
 // PIL's bytes and the blur / bicubic must stay within a bf16 ulp of kornia's, near zero too.  See include/tooncrafter_hip.h.
 #include "common.h"
+#include "pixel_u8.h"
 
 #include <math.h>
 
@@ -15,20 +16,7 @@ inline unsigned grid_for(int64_t n, unsigned cap = 8192) {
 
 // ---------------------------------------------------------------------------------------------- tc_frames_from_u8
 
-// One axis of PIL's 8-bit resample at one output index: sum coefs[k] * src[(first + k) * step] over the taps, rounded and
-// clipped as ImagingResampleHorizontal_8bpc does.  The bounds are clamped to [0, extent): a wrong table cannot reach
-// outside the image.
-__device__ __forceinline__ uint32_t resample_u8(const uint8_t* __restrict__ src, int64_t step, int extent,
-                                                const int32_t* __restrict__ bounds, const int32_t* __restrict__ coefs,
-                                                int kmax, int idx) {
-  int first = bounds[2 * idx], cnt = bounds[2 * idx + 1];
-  first = min(max(first, 0), extent - 1);
-  cnt = min(min(cnt, kmax), extent - first);
-  const int32_t* k = coefs + (int64_t)idx * kmax;
-  int32_t ss = 1 << 21;
-  for (int i = 0; i < cnt; ++i) ss += k[i] * (int32_t)src[(int64_t)(first + i) * step];
-  return (uint32_t)min(max(ss >> 22, 0), 255);
-}
+// resample_u8, one axis of PIL's 8-bit resample at one output index, is pixel_u8.h's: the back end runs it too.
 
 // horizontal pass: n images (sh, sw, 3) with a row pitch -> the packed uint8 intermediate (n, sh, rw, 3)
 __global__ __launch_bounds__(256) void frames_hpass_kernel(const uint8_t* __restrict__ src, int64_t image_stride, int pitch,

@@ -3,7 +3,7 @@
 // The reference binds ATen / xformers operators from Python (utils/utils.py:27-42 instantiates lvdm classes whose
 // forward methods call torch ops); this registers the MI355X kernels as first-class torch operators instead:
 //   torch.ops.tooncrafter.gemm / quant_mxfp8 / gemm_mx / attention / attention_temporal(_rel) / groupnorm(_pf) / layernorm(_pf) / ddim_step(_eps) / ddim_step_ms(_eps) / ddim_blend /
-//   frames_from_u8 / clip_patches / randn_clips /
+//   frames_from_u8 / frames_to_u8 / clip_patches / randn_clips /
 //   ff_geglu_fused / temporal_attn_fused / temporal_qkv_attn / attention_q8
 // with (i) a CUDA(HIP)-key implementation that validates the tensors, allocates the result from the caching allocator,
 // picks up the CURRENT stream and calls the same extern "C" entry point the ctypes binding calls, and (ii) a Meta-key
@@ -545,6 +545,55 @@ Tensor frames_from_u8_meta(const Tensor& images, at::IntArrayRef, int64_t b, int
   return at::empty({b, 3, t, h, w}, images.options().dtype(at::kFloat));
 }
 
+// Pixel back end (additive within ABI 14).  frames_to_u8: frames f0 .. f0 + nf - 1 of every clip of x (b, 3, t, h, w) fp32 -> a new
+// packed uint8 tensor, (b, nf, oh, ow, 3) for RGB24 or (b, nf, oh * ow * 3 / 2) for I420 / NV12 (tc_frames_to_u8); the tables are
+// tc_resize_tables_filter's for w -> ow and h -> oh, on the device (None for an axis that keeps its size).  Writing into a caller's
+// buffer with strides is the C ABI's (HipOps.frames_to_u8 with out=): an op returns its result.
+std::vector<int64_t> frames_to_u8_shape(const Tensor& x, int64_t oh, int64_t ow, int64_t format, int64_t f0, int64_t nf) {
+  TORCH_CHECK(x.dim() == 5 && x.size(1) == 3 && x.numel() > 0, "frames_to_u8: x must be (b, 3, t, h, w)");
+  TORCH_CHECK(oh > 0 && ow > 0 && oh <= INT32_MAX && ow <= INT32_MAX, "frames_to_u8: output size (", oh, ", ", ow, ")");
+  TORCH_CHECK(f0 >= 0 && nf >= 1 && f0 + nf <= x.size(2), "frames_to_u8: frames ", f0, " .. ", f0 + nf - 1, " outside a clip of ", x.size(2));
+  TORCH_CHECK(format == TC_PIXFMT_RGB24 || format == TC_PIXFMT_I420 || format == TC_PIXFMT_NV12, "frames_to_u8: format ", format);
+  if (format == TC_PIXFMT_RGB24) return {x.size(0), nf, oh, ow, 3};
+  TORCH_CHECK(oh % 2 == 0 && ow % 2 == 0, "frames_to_u8: I420 / NV12 need an even size, got (", oh, ", ", ow, ")");
+  return {x.size(0), nf, oh * ow * 3 / 2};
+}
+
+Tensor frames_to_u8_cuda(const Tensor& x, int64_t oh, int64_t ow, int64_t format, int64_t f0, int64_t nf,
+                         const optional<Tensor>& h_bounds, const optional<Tensor>& h_coefs, const optional<Tensor>& v_bounds,
+                         const optional<Tensor>& v_coefs) {
+  TORCH_CHECK(x.is_cuda(), "frames_to_u8: expected a CUDA tensor (the product path is GPU-only)");
+  TORCH_CHECK(x.scalar_type() == at::kFloat && x.is_contiguous(), "frames_to_u8: contiguous fp32 (b, 3, t, h, w)");
+  Tensor out = at::empty(frames_to_u8_shape(x, oh, ow, format, f0, nf), x.options().dtype(at::kByte));
+  TcFramesOutParams p = {};
+  p.x = x.data_ptr<float>(); p.out = out.data_ptr<uint8_t>();
+  p.b = (int32_t)x.size(0); p.t = (int32_t)x.size(2); p.h = (int32_t)x.size(3); p.w = (int32_t)x.size(4);
+  p.f0 = (int32_t)f0; p.nf = (int32_t)nf; p.oh = (int32_t)oh; p.ow = (int32_t)ow; p.format = (int32_t)format;
+  p.pitch = (int32_t)(format == TC_PIXFMT_RGB24 ? 3 * ow : ow);
+  p.frame_stride = out.stride(1); p.clip_stride = out.stride(0);
+  auto table = [](const optional<Tensor>& bounds, const optional<Tensor>& coefs, int64_t n_in, int64_t n_out, const int32_t** pb,
+                  const int32_t** pc, int32_t* kmax) {
+    if (n_in == n_out) return;                              // the pass does not run: its tables are not looked at
+    *pb = i32_table(bounds, "frames_to_u8: bounds"); *pc = i32_table(coefs, "frames_to_u8: coefs");
+    // the tables must be the ones of this size: their rows are indexed by the output index
+    TORCH_CHECK(*pb && *pc && bounds->size(0) == n_out && bounds->size(1) == 2 && coefs->size(0) == n_out && coefs->size(1) >= 1,
+                "frames_to_u8: tables of ", n_in, " -> ", n_out, " expected");
+    *kmax = (int32_t)coefs->size(1);
+  };
+  table(h_bounds, h_coefs, p.w, p.ow, &p.h_bounds, &p.h_coefs, &p.h_kmax);
+  table(v_bounds, v_coefs, p.h, p.oh, &p.v_bounds, &p.v_coefs, &p.v_kmax);
+  p.workspace_bytes = tc_frames_to_u8_workspace(&p);
+  Tensor ws = at::empty({p.workspace_bytes > 16 ? p.workspace_bytes : 16}, out.options());
+  p.workspace = ws.data_ptr();
+  check_rc(tc_frames_to_u8(&p, cur_stream()), "tc_frames_to_u8");
+  return out;
+}
+
+Tensor frames_to_u8_meta(const Tensor& x, int64_t oh, int64_t ow, int64_t format, int64_t f0, int64_t nf, const optional<Tensor>&,
+                         const optional<Tensor>&, const optional<Tensor>&, const optional<Tensor>&) {
+  return at::empty(frames_to_u8_shape(x, oh, ow, format, f0, nf), x.options().dtype(at::kByte));
+}
+
 // clip_patches: (B, 3, H, W) fp32 -> the bf16 A operand [B * (size / patch)^2, ld] of the CLIP image tower's patch-embedding GEMM
 // (reference condition.py:322-330: kornia resize, (x + 1) / 2, CLIP mean / std; then open_clip's conv1 unfold)
 Tensor clip_patches_cuda(const Tensor& x, int64_t size, int64_t patch, int64_t ld, at::ArrayRef<double> mean, at::ArrayRef<double> std,
@@ -643,6 +692,8 @@ TORCH_LIBRARY(tooncrafter, m) {
   m.def("ddim_blend(Tensor? x, Tensor x0, Tensor? noise, Tensor? mask, float sqrt_ac, float sqrt_1m_ac) -> Tensor");
   m.def("frames_from_u8(Tensor images, int[] slots, int b, int t, int h, int w, Tensor? h_bounds, Tensor? h_coefs, "
         "Tensor? v_bounds, Tensor? v_coefs) -> Tensor");
+  m.def("frames_to_u8(Tensor x, int oh, int ow, int format, int f0, int nf, Tensor? h_bounds, Tensor? h_coefs, Tensor? v_bounds, "
+        "Tensor? v_coefs) -> Tensor");
   m.def("clip_patches(Tensor x, int size, int patch, int ld, float[] mean, float[] std, bool antialias) -> Tensor");
   m.def("randn_clips(int[] seeds, int[] shape, int stream, float scale, bool raw) -> Tensor");
   m.def("abi_version() -> int");
@@ -666,6 +717,7 @@ TORCH_LIBRARY_IMPL(tooncrafter, CUDA, m) {
   m.impl("ddim_step_ms_eps", ddim_step_ms_any<true>);
   m.impl("ddim_blend", ddim_blend_cuda);
   m.impl("frames_from_u8", frames_from_u8_cuda);
+  m.impl("frames_to_u8", frames_to_u8_cuda);
   m.impl("clip_patches", clip_patches_cuda);
   m.impl("randn_clips", randn_clips_cuda);
   m.impl("ff_geglu_fused", ff_geglu_fused_cuda);
@@ -686,6 +738,7 @@ TORCH_LIBRARY_IMPL(tooncrafter, Meta, m) {
     m.impl(name, torch::CppFunction::makeFromBoxedFunction<&like_first_meta>());
   m.impl("ddim_blend", ddim_blend_meta);
   m.impl("frames_from_u8", frames_from_u8_meta);
+  m.impl("frames_to_u8", frames_to_u8_meta);
   m.impl("clip_patches", clip_patches_meta);
   m.impl("randn_clips", randn_clips_meta);
   m.impl("ff_geglu_fused", ff_geglu_fused_meta);

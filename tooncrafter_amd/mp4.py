@@ -157,6 +157,29 @@ def _full(kind: bytes, version: int, flags: int, payload: bytes) -> bytes:
 _MATRIX = struct.pack(">9I", 0x10000, 0, 0, 0, 0x10000, 0, 0, 0, 0x40000000)
 
 
+def encode_h264_ipcm_yuv(y: np.ndarray, cb: np.ndarray, cr: np.ndarray):
+    """y: (t, h, w), cb / cr: (t, h / 2, w / 2) uint8 planes, put into the stream as they are
+    -> (sps NAL, pps NAL, [one IDR NAL per frame])."""
+    y, cb, cr = (np.asarray(v) for v in (y, cb, cr))
+    if y.ndim != 3 or any(v.dtype != np.uint8 for v in (y, cb, cr)):
+        raise ValueError("planes must be (t, rows, columns) uint8")
+    t, h, w = y.shape
+    if h % 2 or w % 2:
+        raise ValueError("yuv420p needs even width and height")
+    if cb.shape != (t, h // 2, w // 2) or cr.shape != cb.shape:
+        raise ValueError(f"chroma planes must be {(t, h // 2, w // 2)}, got {cb.shape} and {cr.shape}")
+    ph, pw = (h + 15) // 16 * 16, (w + 15) // 16 * 16
+    slices = []
+    for i in range(t):
+        yi, cbi, cri = y[i], cb[i], cr[i]
+        if (ph, pw) != (h, w):                  # pad to whole macroblocks by edge replication (cropped away by the SPS)
+            yi = np.pad(yi, ((0, ph - h), (0, pw - w)), mode="edge")
+            cbi = np.pad(cbi, ((0, (ph - h) // 2), (0, (pw - w) // 2)), mode="edge")
+            cri = np.pad(cri, ((0, (ph - h) // 2), (0, (pw - w) // 2)), mode="edge")
+        slices.append(_idr_slice(yi, cbi, cri, i & 1))
+    return _sps(w, h), _pps(), slices
+
+
 def encode_h264_ipcm(frames: np.ndarray):
     """frames: (t, h, w, 3) uint8 -> (sps NAL, pps NAL, [one IDR NAL per frame])."""
     t, h, w, c = frames.shape
@@ -164,23 +187,38 @@ def encode_h264_ipcm(frames: np.ndarray):
         raise ValueError("frames must be (t, h, w, 3) uint8")
     if h % 2 or w % 2:
         raise ValueError("yuv420p needs even width and height")
-    ph, pw = (h + 15) // 16 * 16, (w + 15) // 16 * 16
-    slices = []
+    y, cb = np.empty((t, h, w), np.uint8), np.empty((t, h // 2, w // 2), np.uint8)
+    cr = np.empty_like(cb)
     for i in range(t):
-        y, cb, cr = rgb_to_yuv420(frames[i])
-        if (ph, pw) != (h, w):                  # pad to whole macroblocks by edge replication (cropped away by the SPS)
-            y = np.pad(y, ((0, ph - h), (0, pw - w)), mode="edge")
-            cb = np.pad(cb, ((0, (ph - h) // 2), (0, (pw - w) // 2)), mode="edge")
-            cr = np.pad(cr, ((0, (ph - h) // 2), (0, (pw - w) // 2)), mode="edge")
-        slices.append(_idr_slice(y, cb, cr, i & 1))
-    return _sps(w, h), _pps(), slices
+        y[i], cb[i], cr[i] = rgb_to_yuv420(frames[i])
+    return encode_h264_ipcm_yuv(y, cb, cr)
 
 
 def write_mp4(path: str, frames, fps: int = 8) -> str:
     """frames: (t, h, w, 3) uint8 (numpy array or torch tensor on the CPU) -> an H.264 .mp4 at `path`."""
     frames = np.ascontiguousarray(frames.numpy() if hasattr(frames, "numpy") else frames)
     t, h, w, _ = frames.shape
-    sps, pps, slices = encode_h264_ipcm(frames)
+    return _write_container(path, *encode_h264_ipcm(frames), t, h, w, fps)
+
+
+def write_mp4_i420(path: str, planes, width: int, height: int, fps: int = 8) -> str:
+    """planes: (t, height * width * 3 / 2) uint8, every frame packed I420 (Y, then Cb, then Cr: what the pixel back end's
+    fmt="i420" returns; numpy array or torch tensor on the CPU) -> an H.264 .mp4 at `path` holding exactly these samples."""
+    planes = np.ascontiguousarray(planes.numpy() if hasattr(planes, "numpy") else planes)
+    w, h = int(width), int(height)
+    if h <= 0 or w <= 0 or h % 2 or w % 2:
+        raise ValueError("yuv420p needs even, positive width and height")
+    if planes.dtype != np.uint8 or planes.ndim != 2 or planes.shape[1] != h * w * 3 // 2:
+        raise ValueError(f"planes must be (t, {h * w * 3 // 2}) uint8 for {w} x {h}, got {planes.shape} {planes.dtype}")
+    t, n = planes.shape[0], h * w
+    y = planes[:, :n].reshape(t, h, w)
+    cb = planes[:, n:n + n // 4].reshape(t, h // 2, w // 2)
+    cr = planes[:, n + n // 4:].reshape(t, h // 2, w // 2)
+    return _write_container(path, *encode_h264_ipcm_yuv(y, cb, cr), t, h, w, fps)
+
+
+def _write_container(path: str, sps: bytes, pps: bytes, slices, t: int, h: int, w: int, fps: int) -> str:
+    """One avc1 track of `t` IDR pictures of w x h in an ISO base media file."""
     samples = [struct.pack(">I", len(n)) + n for n in slices]           # AVCC: 4-byte NAL lengths
     timescale, delta = int(fps) * 1000, 1000
     duration = t * delta

@@ -849,6 +849,92 @@ class HipOps:
             _lib.check(self.lib.tc_frames_from_u8(C.byref(p), _stream()), "tc_frames_from_u8")
         return out
 
+    def resize_tables_filter(self, filter, n_in, n_out, device):
+        """PIL's 8-bit tables of one axis for `filter` ("bilinear", "bicubic", "lanczos", "box") on `device`: (bounds [n_out, 2],
+        coefs [n_out, kmax]) int32, built on the host by tc_resize_tables_filter and kept per (filter, n_in, n_out, device)."""
+        key = (str(filter), int(n_in), int(n_out), torch.device(device))
+        tabs = self._resize_tables.get(key)
+        if tabs is None:
+            if key[0] not in _lib.TC_RESIZE_FILTERS:
+                raise ValueError(f"resize filter {filter!r}: one of {sorted(_lib.TC_RESIZE_FILTERS)}")
+            code = _lib.TC_RESIZE_FILTERS[key[0]]
+            kmax = self.lib.tc_resize_tables_filter(code, key[1], key[2], None, None, 0)
+            _lib.check(min(kmax, 0), "tc_resize_tables_filter")
+            bounds = torch.empty((key[2], 2), dtype=torch.int32)
+            coefs = torch.empty((key[2], kmax), dtype=torch.int32)
+            i32p = C.POINTER(C.c_int32)
+            rc = self.lib.tc_resize_tables_filter(code, key[1], key[2], C.cast(bounds.data_ptr(), i32p), C.cast(coefs.data_ptr(), i32p),
+                                                  coefs.numel())
+            _lib.check(min(rc, 0), "tc_resize_tables_filter")
+            tabs = self._resize_tables[key] = (bounds.to(key[3]), coefs.to(key[3]))
+        return tabs
+
+    @staticmethod
+    def _frames_out_args(x, size, filter, fmt, frames):
+        """The checked request of frames_to_u8: (oh, ow, format code, f0, nf, bytes of a packed row, bytes of a packed frame)."""
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
+            raise ValueError(f"frames_to_u8: x: expected an fp32 tensor, got {getattr(x, 'dtype', type(x))}")
+        if x.dim() != 5 or x.shape[1] != 3 or 0 in x.shape:
+            raise ValueError(f"frames_to_u8: x must be (b, 3, t, h, w), got {tuple(x.shape)}")
+        if fmt not in _lib.TC_PIXFMTS:
+            raise ValueError(f"frames_to_u8: fmt {fmt!r}: one of {sorted(_lib.TC_PIXFMTS)}")
+        if filter not in _lib.TC_RESIZE_FILTERS:
+            raise ValueError(f"frames_to_u8: filter {filter!r}: one of {sorted(_lib.TC_RESIZE_FILTERS)}")
+        t, h, w = x.shape[2:]
+        oh, ow = (h, w) if size is None else (int(v) for v in size)
+        if oh <= 0 or ow <= 0:
+            raise ValueError(f"frames_to_u8: size {(oh, ow)}")
+        f0, nf = (0, t) if frames is None else (int(v) for v in frames)
+        if f0 < 0 or nf < 1 or f0 + nf > t:
+            raise ValueError(f"frames_to_u8: frames (first, count) = {(f0, nf)} outside a clip of {t}")
+        if fmt != "rgb24" and (oh % 2 or ow % 2):
+            raise ValueError(f"frames_to_u8: {fmt} needs an even size, got {(oh, ow)}")
+        if not x.is_cuda:
+            raise _lib.TooncrafterHipError("frames_to_u8: x: expected a CUDA tensor: the product path is GPU-only")
+        row = 3 * ow if fmt == "rgb24" else ow
+        return oh, ow, _lib.TC_PIXFMTS[fmt], f0, nf, row, row * oh if fmt == "rgb24" else oh * ow * 3 // 2
+
+    def frames_to_u8(self, x, size=None, filter="bicubic", fmt="rgb24", frames=None, out=None, strides=None):
+        """Frames of the decoder's (b, 3, t, h, w) fp32 clips -> uint8 frames on the device (tc_frames_to_u8): tc_video_to_u8's
+        value arithmetic, PIL's 8-bit two-pass resample to size = (oh, ow) with `filter` ("bilinear", "bicubic", "lanczos",
+        "box"; None: the clip's own size, nothing resampled), then fmt "rgb24" (HWC), "i420" or "nv12" (BT.601 limited range, in
+        integers).  frames = (first, count): which frames of every clip (None: all).
+        Returns a new (b, nf, oh, ow, 3) tensor for rgb24, (b, nf, oh * ow * 3 / 2) for the planar formats.
+        out: a contiguous uint8 device buffer written in place instead, frame first + j of clip i at byte
+        i * clip_stride + j * frame_stride, rows `pitch` bytes apart, strides = (pitch, frame_stride, clip_stride) (None: packed);
+        the bytes between rows, frames and clips keep their contents.  Returns `out`."""
+        oh, ow, code, f0, nf, row, frame = self._frames_out_args(x, size, filter, fmt, frames)
+        x = x.contiguous()
+        b, _, t, h, w = x.shape
+        pitch, frame_stride, clip_stride = (row, frame, nf * frame) if strides is None else (int(v) for v in strides)
+        if out is None:
+            if strides is not None:
+                raise ValueError("frames_to_u8: strides describe an `out` buffer")
+            out = torch.empty((b, nf, oh, ow, 3) if fmt == "rgb24" else (b, nf, frame), dtype=torch.uint8, device=x.device)
+        else:
+            _dev(out, torch.uint8, "frames_to_u8: out")
+            if out.device != x.device:
+                raise ValueError(f"frames_to_u8: out is on {out.device}, x on {x.device}")
+        p = _lib.TcFramesOutParams(x=x.data_ptr(), out=out.data_ptr(), b=b, t=t, h=h, w=w, f0=f0, nf=nf, oh=oh, ow=ow, format=code,
+                                   pitch=pitch, frame_stride=frame_stride, clip_stride=clip_stride)
+        if ow != w:
+            hb, hc = self.resize_tables_filter(filter, w, ow, x.device)
+            p.h_bounds, p.h_coefs, p.h_kmax = hb.data_ptr(), hc.data_ptr(), hc.shape[1]
+        if oh != h:
+            vb, vc = self.resize_tables_filter(filter, h, oh, x.device)
+            p.v_bounds, p.v_coefs, p.v_kmax = vb.data_ptr(), vc.data_ptr(), vc.shape[1]
+        # the last byte the kernels may write: a frame's bytes by the header's rule, at the last place
+        used = pitch * oh if fmt == "rgb24" else pitch * oh + (2 * (pitch // 2) * (oh // 2) if fmt == "i420" else pitch * (oh // 2))
+        if pitch < row or frame_stride < used or (b > 1 and clip_stride < nf * frame_stride) or \
+                (b - 1) * clip_stride + (nf - 1) * frame_stride + used > out.numel():
+            raise ValueError(f"frames_to_u8: strides (pitch, frame, clip) = {(pitch, frame_stride, clip_stride)} do not fit {b} x {nf} "
+                             f"frames of {used} bytes into an out of {out.numel()} bytes")
+        p.workspace_bytes = self.lib.tc_frames_to_u8_workspace(C.byref(p))
+        ws = self._workspace(p.workspace_bytes, x.device)
+        p.workspace = ws.data_ptr()
+        _lib.check(self.lib.tc_frames_to_u8(C.byref(p), _stream()), "tc_frames_to_u8")
+        return out
+
     def clip_patches(self, x, *, size, patch, ld, mean, std, antialias=True):
         """(B, 3, H, W) fp32 in [-1, 1] -> bf16 rows [B * (size / patch)^2, ld], the A operand of the CLIP image tower's
         patch-embedding GEMM: kornia's antialiased bicubic resize to (size, size), (x + 1) / 2, (x - mean) / std and the

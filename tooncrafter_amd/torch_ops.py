@@ -164,6 +164,15 @@ class TorchLibOps(HipOps):
             tabs = self.resize_tables(sw, rw, images.device) + self.resize_tables(sh, rh, images.device)
         return self.t.frames_from_u8(images, [int(s) for s in slots], int(b), int(t), h, w, *tabs)
 
+    def frames_to_u8(self, x, size=None, filter="bicubic", fmt="rgb24", frames=None, out=None, strides=None):
+        if out is not None or strides is not None:          # an explicit result buffer with its strides: the ctypes method
+            return super().frames_to_u8(x, size, filter, fmt, frames, out=out, strides=strides)
+        oh, ow, code, f0, nf, _, _ = self._frames_out_args(x, size, filter, fmt, frames)
+        h, w = x.shape[3:]
+        tabs = (self.resize_tables_filter(filter, w, ow, x.device) if ow != w else (None, None)) + \
+               (self.resize_tables_filter(filter, h, oh, x.device) if oh != h else (None, None))
+        return self.t.frames_to_u8(x.contiguous(), oh, ow, code, f0, nf, *tabs)
+
     def clip_patches(self, x, *, size, patch, ld, mean, std, antialias=True):
         return self.t.clip_patches(x, int(size), int(patch), int(ld), [float(v) for v in mean], [float(v) for v in std], bool(antialias))
 
