@@ -56,7 +56,7 @@ def test_meta_kernels_infer_shapes(t):
     y = t.temporal_attn_fused(x0r, torch.empty(960, 320, **bf), torch.empty(960, **f32), torch.empty(320, 320, **bf), torch.empty(320, **f32),
                               2, 16, 2560, 5, 1e-5, 0.125)
     assert y.shape == (81920, 320)
-    # ABI 13: qkv projection + temporal attention as one launch (levels 1-3): rows in, rows out, the bias optional
+    # ABI 13: qkv projection + temporal attention as one launch (the default at every level with c = heads * 64): rows in, rows out, the bias optional
     x1r = torch.empty(20480, 640, **bf)
     y = t.temporal_qkv_attn(x1r, torch.empty(1920, 640, **bf), None, 2, 16, 640, 10, 0.125)
     assert y.shape == (20480, 640) and y.dtype == torch.bfloat16

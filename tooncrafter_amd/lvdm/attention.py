@@ -19,6 +19,7 @@ Differences in HOW (not what) is computed:
 from __future__ import annotations
 
 from functools import partial
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -102,6 +103,23 @@ class CtxBranch:
         return kv[self.k * self.b * per:(self.k + 1) * self.b * per]
 
 
+class Normed(NamedTuple):
+    """Input of the GEMM behind one LayerNorm of a block (BasicTransformerBlock._pre alone makes it): the LayerNorm's output,
+    or -- when that GEMM normalises its A rows itself -- the RAW rows and `fold` = (folded consumer weight, folded bias, eps)."""
+    rows: object
+    fold: tuple = None
+
+    @property
+    def plain(self) -> bool:  # normalised bf16 rows, which a one-launch kernel may read: no fold, no ops.MxRows (fp8 route's LayerNorm)
+        return self.fold is None and torch.is_tensor(self.rows)
+
+    def project(self, w, bias=None, **kw):
+        if self.fold is None:
+            return ops.gemm(self.rows, w, bias, **kw)
+        w, bias, eps = self.fold
+        return ops.gemm(self.rows, w, bias, a_norm_eps=eps, **kw)
+
+
 class GEGLU(nn.Module):
     def __init__(self, dim_in, dim_out):
         super().__init__()
@@ -121,25 +139,10 @@ class FeedForward(PackedModule):
         w1, b1 = pack_geglu(self.net[0].proj.weight, self.net[0].proj.bias)
         return {"w1": w1, "b1": b1, "w2": pack_linear(self.net[2].weight), "b2": f32(self.net[2].bias)}
 
-    def ln_consumer(self):
-        """(packed weight, gated) of the GEMM that reads the LayerNorm in front of this block."""
-        return self.pk["w1"], True
-
-    def forward(self, x_norm, residual, ln=None):
-        """`ln` = (folded packed weight, folded bias, eps): `x_norm` is then the RAW rows and the LayerNorm runs as the
-        prologue of the first GEMM (BasicTransformerBlock._pre)."""
+    def forward(self, h: Normed, residual):
+        """The two-launch route (BasicTransformerBlock._ff chose it)."""
         pk = self.pk
-        if ln is not None and x_norm is residual:
-            # level 0 (C = 320, hidden 1280): LayerNorm, both products, GEGLU and the residual as ONE launch -- the
-            # [rows, 1280] hidden tensor (210 MB per block at the BASELINE shape) never reaches HBM (csrc/ff_fused.hip)
-            probe = getattr(ops.backend(), "ff_fused_eligible", None)
-            if probe is not None and probe(x_norm.shape[0], x_norm.shape[1], pk["w2"].shape[1], ldx=x_norm.stride(0)):
-                return ops.ff_geglu_fused(x_norm, ln[0], ln[1], pk["w2"], pk["b2"], ln_eps=ln[2])
-        if ln is not None:
-            g = ops.gemm(x_norm, ln[0], ln[1], act=ACT_GEGLU, a_norm_eps=ln[2])
-        else:
-            g = ops.gemm(x_norm, pk["w1"], pk["b1"], act=ACT_GEGLU)
-        return ops.gemm(g, pk["w2"], pk["b2"], residual=residual)
+        return ops.gemm(h.project(pk["w1"], pk["b1"], act=ACT_GEGLU), pk["w2"], pk["b2"], residual=residual)
 
 
 class RelativePosition(nn.Module):
@@ -236,44 +239,28 @@ class CrossAttention(PackedModule):
         return pk
 
     # -- self attention over the H*W tokens of each frame
-    def forward_spatial_self(self, x_norm, residual, act: Act, ln=None):
+    def forward_spatial_self(self, h: Normed, residual, act: Act):
         pk = self.pk
         c = self.heads * 64
-        qkv = ops.gemm(x_norm, pk["wqkv"]) if ln is None else ops.gemm(x_norm, ln[0], ln[1], a_norm_eps=ln[2])
+        qkv = h.project(pk["wqkv"])
         # the 8-bit route (ABI 14, TC_FP8_ATTN=1): the backend's own rule decides; backends without it keep bf16
-        q8 = getattr(ops.backend(), "spatial_attn_q8_eligible", None)
-        if q8 is not None and q8(lk=act.hw):
-            a = ops.attention_q8(qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:], batch=act.frames, heads=self.heads,
-                                 lq=act.hw, lk=act.hw, scale=self.scale)
-        else:
-            a = ops.attention(qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:], batch=act.frames, heads=self.heads,
-                              lq=act.hw, lk=act.hw, scale=self.scale)
+        attention = ops.attention_q8 if ops.eligible("spatial_attn_q8", lk=act.hw) else ops.attention
+        a = attention(qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:], batch=act.frames, heads=self.heads, lq=act.hw, lk=act.hw, scale=self.scale)
         return ops.gemm(a, pk["wo"], pk["bo"], residual=residual)
 
     # -- self attention over the T frames at each pixel
-    def forward_temporal_self(self, x_norm, residual, act: Act, ln=None, causal=False):
+    def forward_temporal_self(self, h: Normed, residual, act: Act, rel=False, causal=False, one_launch=False):
+        """The route BasicTransformerBlock._temporal_attn chose.  `one_launch`: projection and attentions as one launch (ABI 13) --
+        the [rows, 3C] tensor between them never reaches HBM; `rel`: relative position and / or the causal mask (attention.py:103-124)."""
         pk = self.pk
-        if self.relative_position or causal:
-            # relative position and / or the causal mask (attention.py:103-124): the one-launch kernels have no place for
-            # either, so always the projection (a folded LayerNorm still applies) + tc_attn_temporal_rel
-            qkv = ops.gemm(x_norm, pk["wqkv"]) if ln is None else ops.gemm(x_norm, ln[0], ln[1], a_norm_eps=ln[2])
-            a = ops.attention_temporal_rel(qkv, pk.get("rel_k"), pk.get("rel_v"), b=act.b, t=act.t, hw=act.hw, heads=self.heads,
-                                           max_rel=self.temporal_length if self.relative_position else 0, causal=causal,
-                                           scale=self.scale)
-            return ops.gemm(a, pk["wo"], pk["bo"], residual=residual)
-        # every level: the fused projection and the attentions over the frames as ONE launch (ABI 13) -- the [rows, 3C]
-        # tensor between them never reaches HBM.  The library's own rule decides (tc_temporal_qkv_attn_eligible): 16
-        # frames with hw % 8 == 0 (csrc/qkv_attn.hip); 17 .. 64 frames with hw % (128 / TT) == 0, TT = 32 | 64
-        # (csrc/qkv_attn_long.hip) where TC_QKV_ATTN admits the shape -- mode 1, the default, what measured ahead;
-        # mode 2 every shape the kernel takes.  Everything else takes the projection + tc_attn_temporal (17 .. 64 frames:
-        # csrc/attention_temporal_long.hip), and so does a LayerNorm folded into the projection (ln is not None: the
-        # one-launch kernels read normalised rows).
-        fused = getattr(ops.backend(), "temporal_qkv_attn_eligible", None) if ln is None and torch.is_tensor(x_norm) else None
-        if fused is not None and fused(b=act.b, t=act.t, hw=act.hw, c=x_norm.shape[1], heads=self.heads, ldx=x_norm.stride(0)):
-            a = ops.temporal_qkv_attn(x_norm, pk["wqkv"], None, b=act.b, t=act.t, hw=act.hw, heads=self.heads, scale=self.scale)
-            return ops.gemm(a, pk["wo"], pk["bo"], residual=residual)
-        qkv = ops.gemm(x_norm, pk["wqkv"]) if ln is None else ops.gemm(x_norm, ln[0], ln[1], a_norm_eps=ln[2])
-        a = ops.attention_temporal(qkv, b=act.b, t=act.t, hw=act.hw, heads=self.heads, scale=self.scale)
+        if one_launch:
+            a = ops.temporal_qkv_attn(h.rows, pk["wqkv"], None, b=act.b, t=act.t, hw=act.hw, heads=self.heads, scale=self.scale)
+        elif rel:
+            a = ops.attention_temporal_rel(h.project(pk["wqkv"]), pk.get("rel_k"), pk.get("rel_v"), b=act.b, t=act.t, hw=act.hw,
+                                           heads=self.heads, max_rel=self.temporal_length if self.relative_position else 0,
+                                           causal=causal, scale=self.scale)
+        else:
+            a = ops.attention_temporal(h.project(pk["wqkv"]), b=act.b, t=act.t, hw=act.hw, heads=self.heads, scale=self.scale)
         return ops.gemm(a, pk["wo"], pk["bo"], residual=residual)
 
     # -- text + image cross attention: two softmaxes, summed
@@ -299,21 +286,16 @@ class CrossAttention(PackedModule):
             return hit[1], hit[2]
         return ctx.rows_of(hit[1]), None if hit[2] is None else ctx.rows_of(hit[2])
 
-    def forward_cross(self, x_norm, residual, act: Act, ctx: ContextCache, ln=None):
+    def forward_cross(self, h: Normed, residual, act: Act, ctx: ContextCache):
         pk = self.pk
         c = self.heads * 64
         kv_text, kv_img = self.context_kv(ctx)
-        q = ops.gemm(x_norm, pk["wq"]) if ln is None else ops.gemm(x_norm, ln[0], ln[1], a_norm_eps=ln[2])
-        if kv_img is not None:
-            # text and image softmaxes in ONE launch (attention.py:153-207 runs two attentions and adds them): Q is read
-            # once and the sum is formed in fp32 registers -- no bf16 round trip of the first result through HBM
-            a = ops.attention(q, kv_text[:, :c], kv_text[:, c:], batch=act.frames, heads=self.heads, lq=act.hw,
-                              lk=ctx.text_len, kv_bdiv=act.t, scale=self.scale,
-                              k2=kv_img[:, :c], v2=kv_img[:, c:], lk2=ctx.img_len,
-                              kv2_bdiv=1 if ctx.img_per_frame else act.t)
-        else:
-            a = ops.attention(q, kv_text[:, :c], kv_text[:, c:], batch=act.frames, heads=self.heads, lq=act.hw,
-                              lk=ctx.text_len, kv_bdiv=act.t, scale=self.scale)
+        q = h.project(pk["wq"])
+        # text and image softmaxes in ONE launch (attention.py:153-207 runs two attentions and adds them): Q is read
+        # once and the sum is formed in fp32 registers -- no bf16 round trip of the first result through HBM
+        img = {} if kv_img is None else dict(k2=kv_img[:, :c], v2=kv_img[:, c:], lk2=ctx.img_len, kv2_bdiv=1 if ctx.img_per_frame else act.t)
+        a = ops.attention(q, kv_text[:, :c], kv_text[:, c:], batch=act.frames, heads=self.heads, lq=act.hw,
+                          lk=ctx.text_len, kv_bdiv=act.t, scale=self.scale, **img)
         return ops.gemm(a, pk["wo"], pk["bo"], residual=residual)
 
 
@@ -374,60 +356,63 @@ class BasicTransformerBlock(PackedModule):
             ent = cpk[key] = (stamp, folded)
         return (*ent[1], self.LN_EPS)
 
-    def _pre(self, x, i, consumer, kind, then=None):
-        """Input of the GEMM behind norm<i>: (LayerNorm(x), None), or -- when that GEMM can normalise its A rows itself
-        (K = 320 at level 0: ops.gemm_ln_eligible, the library's own rule) -- (x, folded consumer weights): the
-        LayerNorm launch and its HBM round trip (reference attention.py:242-246 runs it as its own kernel) disappear.
-        `then`: the packed weight of the GEMM that follows the consumer (output projection, second feed-forward layer):
-        prefetched with the consumer's by the norm's launch (ABI 12)."""
+    def _pre(self, x, i, consumer, kind, then=None) -> Normed:
+        """Input of the GEMM behind norm<i>: LayerNorm(x), or -- when that GEMM can normalise its A rows itself (K = 320 at level 0:
+        ops.gemm_ln_eligible, the library's own rule) -- x with the folded consumer weights: the LayerNorm launch and its HBM
+        round trip (reference attention.py:242-246 runs it as its own kernel) disappear.  `then`: the packed weight of the GEMM
+        that follows the consumer (output projection, second feed-forward layer): prefetched with it by the norm's launch (ABI 12)."""
         gated = kind == "ff"
-        if gated:   # the one-launch feed-forward (csrc/ff_fused.hip) normalises its rows itself: raw rows + folded weights
-            fused = getattr(ops.backend(), "ff_fused_eligible", None)
-            if fused is not None and fused(x.shape[0], x.shape[1], self.ff.pk["w2"].shape[1], ldx=x.stride(0)):
-                return x, self._folded(i, kind)
-        probe = getattr(ops.backend(), "gemm_ln_eligible", None)
-        if probe is not None and probe(x.shape[0], consumer.shape[0], consumer.shape[1], geglu=gated, lda=x.stride(0)):
-            return x, self._folded(i, kind)
-        return self._ln(x, i, consumer if kind != "q" else None, gated, prefetch=[consumer, then]), None
+        if ops.eligible("gemm_ln", x.shape[0], consumer.shape[0], consumer.shape[1], geglu=gated, lda=x.stride(0)):
+            return Normed(x, self._folded(i, kind))
+        return Normed(self._ln(x, i, consumer if kind != "q" else None, gated, prefetch=[consumer, then]))
 
     def forward_spatial(self, x, act: Act, ctx: ContextCache, share: CfgShare = None):
         """`share` (first block of the UNet's first spatial transformer under batched guidance): x / act arrive at the
         single-copy batch; the guided passes part ways at the cross-attention, so the rows are repeated in front of it
         and (x, expanded act) is returned."""
         def self_attn(x=x):
-            h, ln = self._pre(x, 1, self.attn1.pk["wqkv"], "qkv", then=self.attn1.pk["wo"])
-            return self.attn1.forward_spatial_self(h, x, act, ln=ln)
+            return self.attn1.forward_spatial_self(self._pre(x, 1, self.attn1.pk["wqkv"], "qkv", then=self.attn1.pk["wo"]), x, act)
         x = self_attn() if share is None else share.cached(("attn1", id(self)), self_attn)
         if share is not None:
             if not share.branches:
                 x, act = ops.repeat_rows(x, share.n), share.expand(act)
             share.split(x)                                               # branches: every pass goes on alone, at batch b
-        h, ln = self._pre(x, 2, self.attn2.pk["wq"], "q", then=self.attn2.pk["wo"])
-        x = self.attn2.forward_cross(h, x, act, ctx, ln=ln)
-        h, ln = self._pre(x, 3, self.ff.pk["w1"], "ff", then=self.ff.pk["w2"])
-        out = self.ff(h, x, ln=ln)
+        x = self.attn2.forward_cross(self._pre(x, 2, self.attn2.pk["wq"], "q", then=self.attn2.pk["wo"]), x, act, ctx)
+        out = self._ff(x)
         return out if share is None else (out, act)
 
     def _temporal_attn(self, x, i, attn, act: Act, causal=False):
-        """x + attn(norm<i>(x)) over the frames of every pixel: LayerNorm, then the q / k / v projection and the 16 x 16
-        attentions as ONE launch (csrc/qkv_attn.hip via CrossAttention.forward_temporal_self), then the output projection
-        with the residual.  Where the library offers it (TC_TB_FUSED=1, C = 320: csrc/tb_fused.hip) all of that is one launch
-        -- the default of rounds 4-5 at level 0, behind the chain above since round 6 (+0.4 ... +0.6 % per forward)."""
-        plain = not (attn.relative_position or causal)                  # else: projection + tc_attn_temporal_rel, nothing fused
-        fused = getattr(ops.backend(), "temporal_attn_fused_eligible", None) if plain else None
-        if fused is not None and fused(b=act.b, t=act.t, hw=act.hw, c=x.shape[1], heads=attn.heads, ldx=x.stride(0)):
+        """x + attn(norm<i>(x)) over the frames of every pixel; the route is chosen here, in priority order.  The default at every
+        level with c = heads * 64 is the last: LayerNorm, then projection and attentions as ONE launch (the library's own rule:
+        16 frames with hw % 8 == 0; 17 .. 64 frames where TC_QKV_ATTN=1, the default, admits them: DESIGN 5.11), then to_out."""
+        shape = dict(b=act.b, t=act.t, hw=act.hw, c=x.shape[1], heads=attn.heads)
+        if attn.relative_position or causal:    # no one-launch kernel takes a table or a mask; a folded LayerNorm still applies
+            h = self._pre(x, i, attn.pk["wqkv"], "qkv", then=attn.pk["wo"])
+            return attn.forward_temporal_self(h, x, act, rel=True, causal=causal)
+        if ops.eligible("temporal_attn_fused", **shape, ldx=x.stride(0)):
+            # all of it as one launch (csrc/tb_fused.hip: C = 320, TC_TB_FUSED=1) -- the default of rounds 4-5 at level 0, one
+            # switch away since round 6 (the chain below measured +0.4 ... +0.6 % per forward ahead)
             w, bias, eps = self._folded(i, "qkv")
             return ops.temporal_attn_fused(x, w, bias, attn.pk["wo"], attn.pk["bo"], b=act.b, t=act.t, hw=act.hw,
                                            heads=attn.heads, ln_eps=eps, scale=attn.scale)
-        h, ln = self._pre(x, i, attn.pk["wqkv"], "qkv", then=attn.pk["wo"])
-        return attn.forward_temporal_self(h, x, act, ln=ln, causal=causal)
+        h = self._pre(x, i, attn.pk["wqkv"], "qkv", then=attn.pk["wo"])  # a fold keeps two launches: one_launch reads normalised rows
+        one_launch = h.plain and ops.eligible("temporal_qkv_attn", **shape, ldx=h.rows.stride(0))
+        return attn.forward_temporal_self(h, x, act, one_launch=one_launch)
+
+    def _ff(self, x):
+        pk = self.ff.pk                                                  # x + ff(norm3(x)): the route is chosen here
+        if ops.eligible("ff_fused", x.shape[0], x.shape[1], pk["w2"].shape[1], ldx=x.stride(0)):
+            # level 0 (C = 320, hidden 1280): LayerNorm, both products, GEGLU and the residual as ONE launch -- the
+            # [rows, 1280] hidden tensor (210 MB per block at the BASELINE shape) never reaches HBM (csrc/ff_fused.hip)
+            w1, b1, eps = self._folded(3, "ff")
+            return ops.ff_geglu_fused(x, w1, b1, pk["w2"], pk["b2"], ln_eps=eps)
+        return self.ff(self._pre(x, 3, pk["w1"], "ff", then=pk["w2"]), x)
 
     def forward_temporal(self, x, act: Act, causal=False):
         """`causal`: the tril mask of a causal TemporalTransformer, on both self-attentions (attention.py:376-390)."""
         x = self._temporal_attn(x, 1, self.attn1, act, causal)
         x = self._temporal_attn(x, 2, self.attn2, act, causal)           # context=None -> self attention again
-        h, ln = self._pre(x, 3, self.ff.pk["w1"], "ff", then=self.ff.pk["w2"])
-        return self.ff(h, x, ln=ln)
+        return self._ff(x)
 
 
 class SpatialTransformer(PackedModule):

@@ -273,9 +273,7 @@ class HipOps:
         p.act = ACT_GEGLU if geglu else ACT_NONE
         p.ldc = p.ldr = n // 2 if geglu else n
         p.alpha, p.out_scale, p.batch = 1.0, 1.0, 1
-        if not self.lib.tc_gemm_ws_eligible(C.byref(p)):
-            return False
-        return not (self.fp8 is not None and self._fp8_eligible(p, False, p.ldc, 1))
+        return bool(self.lib.tc_gemm_ws_eligible(C.byref(p))) and not self._fp8_takes_linear(m, n, k, p.ldc)
 
     # ------------------------------------------------------------------ fused level-0 feed-forward (ABI 9)
     def _ff_params(self, m, c, hidden, ldx, ldo, ln_eps):
@@ -442,6 +440,11 @@ class HipOps:
         return self.fp8 in ("all", "linear") and p.k >= self.fp8_min_k and p.n >= self.fp8_min_n \
             and p.n >= self.fp8_n_over_k * p.k
 
+    def _fp8_takes_linear(self, m, n, k, n_out) -> bool:
+        """Would the MXFP8 route take the plain linear GEMM a[m, k] . w[n, k]^T (n_out = n // 2 behind a GEGLU)?"""
+        p = TcGemmParams(m=int(m), n=int(n), k=int(k), gather=GATHER_LINEAR)
+        return self.fp8 is not None and self._fp8_eligible(p, False, n_out, 1)
+
     def _gemm_mx(self, p, a, w, mx_a=None):
         kc = p.cin if p.gather != GATHER_LINEAR else p.k
         rows = p.frames * p.h_in * p.w_in if p.gather == GATHER_CONV3x3 else p.m
@@ -577,11 +580,8 @@ class HipOps:
         for t in tensors:
             if t is None or not isinstance(t, torch.Tensor) or not t.is_contiguous() or t.data_ptr() % 16:
                 continue                                              # (a hint: what the ABI would refuse is simply not streamed)
-            if self.fp8 is not None and linear and t.dim() == 2:
-                probe = TcGemmParams()
-                probe.m, probe.n, probe.k, probe.gather = x_rows, t.shape[0], t.shape[1], GATHER_LINEAR
-                if self._fp8_eligible(probe, False, t.shape[0], 1) or self._fp8_eligible(probe, False, t.shape[0] // 2, 1):
-                    continue                                          # (a GEGLU weight's N_out is N / 2: either answer means "taken")
+            if linear and t.dim() == 2 and any(self._fp8_takes_linear(x_rows, *t.shape, n_out) for n_out in (t.shape[0], t.shape[0] // 2)):
+                continue                                            # (a GEGLU weight's N_out is N / 2: either answer means "taken")
             nbytes = t.numel() * t.element_size()
             if nbytes < self.prefetch_min_bytes or total + nbytes > self.prefetch_max_bytes:
                 continue
@@ -653,17 +653,14 @@ class HipOps:
         if gamma.numel() != x.shape[1] or beta.numel() != x.shape[1]:
             raise ValueError("layernorm: gamma/beta must have C elements")
         gp, bp = _dev(gamma, torch.float32, "layernorm: gamma"), _dev(beta, torch.float32, "layernorm: beta")
-        if mx_for is not None and self.fp8 is not None and self.fp8_fuse_ln:
-            probe = TcGemmParams()
-            probe.m, probe.n, probe.k, probe.gather = x.shape[0], mx_for[0], x.shape[1], GATHER_LINEAR
-            if self._fp8_eligible(probe, False, mx_for[1], 1):
-                rows, k = x.shape
-                lds = (k + 127) // 128 * 4
-                q = torch.empty((rows, k), dtype=torch.uint8, device=x.device)
-                sc = torch.empty((rows, lds), dtype=torch.uint8, device=x.device)
-                _lib.check(self.lib.tc_layernorm_mxfp8(x.data_ptr(), q.data_ptr(), k, sc.data_ptr(), lds, gp, bp, rows, k,
-                                                       float(eps), _stream()), "tc_layernorm_mxfp8")
-                return MxRows(q, sc, k)
+        if mx_for is not None and self.fp8_fuse_ln and self._fp8_takes_linear(x.shape[0], mx_for[0], x.shape[1], mx_for[1]):
+            rows, k = x.shape
+            lds = (k + 127) // 128 * 4
+            q = torch.empty((rows, k), dtype=torch.uint8, device=x.device)
+            sc = torch.empty((rows, lds), dtype=torch.uint8, device=x.device)
+            _lib.check(self.lib.tc_layernorm_mxfp8(x.data_ptr(), q.data_ptr(), k, sc.data_ptr(), lds, gp, bp, rows, k,
+                                                   float(eps), _stream()), "tc_layernorm_mxfp8")
+            return MxRows(q, sc, k)
         y = torch.empty_like(x)
         pfl = self.prefetch_list(x.shape[0], prefetch, linear=True)
         if pfl:
@@ -1142,6 +1139,11 @@ def set_backend(b):
     global _backend
     prev, _backend = _backend, b
     return prev
+
+
+def eligible(rule: str, *args, **kw) -> bool:
+    """The backend's `<rule>_eligible(...)`: would it take that launch now?  A backend without the method does not offer the route."""
+    return bool(getattr(backend(), rule + "_eligible", lambda *a, **k: False)(*args, **kw))
 
 
 def __getattr__(name):   # ops.gemm(...) -> backend().gemm(...)
