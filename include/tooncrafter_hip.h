@@ -648,6 +648,76 @@ typedef struct TcRandnParams {
 } TcRandnParams;
 int tc_randn_clips(const TcRandnParams* p, void* stream);
 
+/* ---- Planar YUV keyframes: what a hardware decoder leaves in device memory -> the model's fp32 frames (additive within
+ * ABI 14: one struct, three symbols, one pixel format).  tc_frames_from_u8 for 4:2:0 sources: NV12 surfaces of an 8-bit
+ * stream, P010 / P016 surfaces of a 10-bit one, or the I420 / NV12 frames tc_frames_to_u8 writes. ---- */
+
+/* The integer YCbCr -> RGB matrix of a standard, HOST code, double precision, no device call:
+ *   m = {cy, crv, cgu, cgv, cbu, yoff, coff}.
+ * (Kr, Kb) = (0.299, 0.114) for BT.601, (0.2126, 0.0722) for BT.709; Kg = 1 - Kr - Kb; q = 2^(bits - 8).
+ *   limited range: Y gain 255 / (219 q), chroma gain s = 255 / (224 q), yoff = 16 q;
+ *   full range:    Y gain = s = 255 / (2^bits - 1), yoff = 0;           coff = 128 q in both.
+ * The five coefficients are floor(v * 65536 + 0.5) of the Y gain, 2 (1 - Kr) s, 2 Kb (1 - Kb) / Kg s, 2 Kr (1 - Kr) / Kg s,
+ * 2 (1 - Kb) s -- e.g. BT.601 limited 8 bit: 76309, 104597, 25675, 53279, 132201, yoff 16, coff 128.
+ * TC_EINVAL: an unknown standard or range, bits other than 8 or 10, NULL m. */
+enum { TC_YUV_BT601 = 0, TC_YUV_BT709 = 1 };
+enum { TC_YUV_LIMITED = 0, TC_YUV_FULL = 1 };
+int tc_yuv_matrix(int32_t standard, int32_t range, int32_t bits, int32_t m[7]);
+
+/* n planar 4:2:0 images -> fp32 frames of a (b, 3, t, H, W) clip tensor.  The result is DEFINED as tc_frames_from_u8 applied
+ * to the packed RGB image (n, sh, sw, 3) that the per-pixel rule below gives: resize, crop and value steps and their bits
+ * are that entry point's.  All arithmetic is int32, shifts are arithmetic, sums may be negative.
+ *   - format: TC_PIXFMT_I420  y, c0 = Cb, c1 = Cr: three planes of 8-bit samples;
+ *             TC_PIXFMT_NV12  y and c0 = one plane of interleaved Cb, Cr; c1 NULL;
+ *             TC_PIXFMT_P010  NV12's layout in 16-bit little-endian words, sample = word >> 6 (the low six bits are
+ *                             ignored): a decoder's P016 surface of a 10-bit stream; c1 NULL;
+ *     luma rows are pitch_y bytes apart, chroma rows pitch_c; the chroma planes hold ch = (sh + 1) / 2 rows of
+ *     cw = (sw + 1) / 2 samples (odd pictures are legal: decoders crop); image i starts image_stride_y / image_stride_c
+ *     bytes after image i - 1, so with n = 1 the pointers describe any one surface, whatever its chroma offset;
+ *   - chroma at luma pixel (y, x), j = y >> 1, i = x >> 1, every index clamped to the plane, at the source bit depth:
+ *       TC_CHROMA_NEAREST  C[j][i];
+ *       TC_CHROMA_CENTER   (the siting of a 2 x 2 mean: the inverse of tc_frames_to_u8)  i' = i - 1 for even x, i + 1 for
+ *                          odd x, j' likewise from y:  (9 C[j][i] + 3 C[j][i'] + 3 C[j'][i] + C[j'][i'] + 8) >> 4;
+ *       TC_CHROMA_LEFT     (H.264 / HEVC chroma_sample_loc_type 0: co-sited with even columns, centred between rows)
+ *                          x even: (3 C[j][i] + C[j'][i] + 2) >> 2;
+ *                          x odd, i+ = min(i + 1, cw - 1): (3 C[j][i] + 3 C[j][i+] + C[j'][i] + C[j'][i+] + 4) >> 3;
+ *   - colour, with c = Y - yoff, d = Cb - coff, e = Cr - coff and the matrix m of the STRUCT (tc_yuv_matrix's or any other:
+ *     the kernel has no built-in standard):
+ *       R = clip((cy c + crv e + 32768) >> 16, 0, 255)
+ *       G = clip((cy c - cgu d - cgv e + 32768) >> 16, 0, 255)
+ *       B = clip((cy c + cbu d + 32768) >> 16, 0, 255)
+ *     with 10-bit samples and tc_yuv_matrix's tables every sum stays below 2^27.
+ * 10-bit code values map linearly to 8-bit RGB: no transfer function, no tone mapping.
+ * `slots` is a HOST array; every other pointer is device memory.
+ * workspace: tc_frames_from_yuv_workspace bytes = n * sh * sw * 3 (the RGB image) + tc_frames_from_u8_workspace of the same
+ * sizes (0 for a request tc_frames_from_yuv refuses for its sizes).
+ * TC_EINVAL: NULL p / y / c0 / out / slots, c1 missing for I420 or present otherwise, an unknown format or siting, n <= 0 or
+ * > TC_FRAMES_U8_MAX, a size <= 0, pitch_y below the row's bytes (sw; 2 sw for P010), pitch_c below cw (I420), 2 cw (NV12),
+ * 4 cw (P010), image_stride_y < sh * pitch_y, image_stride_c < ch * pitch_c, a slot outside [0, b * t), tables missing for a
+ * pass that runs, cy <= 0; TC_EALIGN: a P010 pointer, pitch or image stride that is not 2-byte aligned; TC_EWORKSPACE:
+ * workspace too small.  Nothing is launched or written on a refusal. */
+enum { TC_PIXFMT_P010 = 3 };   /* an input format: tc_frames_to_u8 does not write it */
+enum { TC_CHROMA_NEAREST = 0, TC_CHROMA_CENTER = 1, TC_CHROMA_LEFT = 2 };
+typedef struct TcFramesYuvParams {
+  const void* y;             /* n luma planes */
+  const void* c0;            /* Cb (I420) or interleaved Cb, Cr (NV12, P010) */
+  const void* c1;            /* Cr (I420), else NULL */
+  int64_t image_stride_y, image_stride_c;   /* bytes from one image to the next */
+  int32_t pitch_y, pitch_c;  /* bytes from one row to the next */
+  int32_t format;            /* TC_PIXFMT_I420 / NV12 / P010 */
+  int32_t siting;            /* TC_CHROMA_* */
+  int32_t m[7];              /* cy, crv, cgu, cgv, cbu, yoff, coff */
+  int32_t n, sh, sw;
+  const int32_t* slots;      /* HOST: n frame indices batch * t + frame */
+  float* out;                /* (b, 3, t, H, W) fp32 */
+  int32_t b, t, h, w;
+  const int32_t* h_bounds; const int32_t* h_coefs; int32_t h_kmax;   /* tables sw -> rw (NULL when nothing is resized) */
+  const int32_t* v_bounds; const int32_t* v_coefs; int32_t v_kmax;   /* tables sh -> rh */
+  void* workspace; int64_t workspace_bytes;
+} TcFramesYuvParams;
+int64_t tc_frames_from_yuv_workspace(const TcFramesYuvParams* p);
+int tc_frames_from_yuv(const TcFramesYuvParams* p, void* stream);
+
 /* introspection */
 int tc_abi_version(void);
 const char* tc_build_info(void);

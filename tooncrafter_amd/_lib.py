@@ -170,6 +170,26 @@ class TcFramesOutParams(C.Structure):
     ]
 
 
+class TcFramesYuvParams(C.Structure):
+    """Planar 4:2:0 images -> fp32 clip frames (tc_frames_from_yuv; additive within ABI 14).  `slots` is a HOST array."""
+    _fields_ = [
+        ("y", C.c_void_p), ("c0", C.c_void_p), ("c1", C.c_void_p),
+        ("image_stride_y", C.c_int64), ("image_stride_c", C.c_int64),
+        ("pitch_y", C.c_int32), ("pitch_c", C.c_int32), ("format", C.c_int32), ("siting", C.c_int32),
+        ("m", C.c_int32 * 7),
+        ("n", C.c_int32), ("sh", C.c_int32), ("sw", C.c_int32),
+        ("slots", C.POINTER(C.c_int32)), ("out", C.c_void_p),
+        ("b", C.c_int32), ("t", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+        ("h_bounds", C.c_void_p), ("h_coefs", C.c_void_p), ("h_kmax", C.c_int32),
+        ("v_bounds", C.c_void_p), ("v_coefs", C.c_void_p), ("v_kmax", C.c_int32),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+    ]
+
+
+TC_YUV_FORMATS = {"i420": 1, "nv12": 2, "p010": 3}       # include/tooncrafter_hip.h: the TC_PIXFMT_* tc_frames_from_yuv reads
+TC_YUV_STANDARDS = {"bt601": 0, "bt709": 1}              # TC_YUV_BT*
+TC_YUV_RANGES = {"limited": 0, "full": 1}                # TC_YUV_LIMITED / TC_YUV_FULL
+TC_CHROMA_SITINGS = {"nearest": 0, "center": 1, "left": 2}                     # TC_CHROMA_*
 TC_RESIZE_FILTERS = {"bilinear": 0, "bicubic": 1, "lanczos": 2, "box": 3}      # include/tooncrafter_hip.h: TC_RESIZE_*
 TC_PIXFMTS = {"rgb24": 0, "i420": 1, "nv12": 2}                                # include/tooncrafter_hip.h: TC_PIXFMT_*
 
@@ -247,6 +267,9 @@ SYMBOLS = {
     "tc_frames_to_u8_workspace": (C.c_int64, [C.POINTER(TcFramesOutParams)]),
     "tc_frames_to_u8": (C.c_int, [C.POINTER(TcFramesOutParams), C.c_void_p]),
     "tc_randn_clips": (C.c_int, [C.POINTER(TcRandnParams), C.c_void_p]),
+    "tc_yuv_matrix": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "tc_frames_from_yuv_workspace": (C.c_int64, [C.POINTER(TcFramesYuvParams)]),
+    "tc_frames_from_yuv": (C.c_int, [C.POINTER(TcFramesYuvParams), C.c_void_p]),
     "tc_gemm_ws_eligible": (C.c_int, [C.POINTER(TcGemmParams)]),
     "tc_gemm_gn_rows": (C.c_int, [C.POINTER(TcGemmParams)]),
     "tc_groupnorm_part": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
@@ -305,7 +328,7 @@ class _TracedLib:
 
     def __getattr__(self, name):
         fn = getattr(self._lib, name)
-        if name not in SYMBOLS or name in ("tc_abi_version", "tc_build_info", "tc_resize_tables", "tc_resize_tables_filter", "tc_frames_from_u8_resized") or name.endswith("_workspace"):
+        if name not in SYMBOLS or name in ("tc_abi_version", "tc_build_info", "tc_resize_tables", "tc_resize_tables_filter", "tc_frames_from_u8_resized", "tc_yuv_matrix") or name.endswith("_workspace"):
             return fn
         import sys
 

@@ -110,6 +110,95 @@ class Conditions:
         frames_from_uint8(last_u8, size, [(i, t - 1) for i in range(b)], t, out=videos)
         return Conditions.build(model, videos, embed=model.embedder.encode_on_device_front, **options)
 
+    @staticmethod
+    def from_planes(model, first, last, *, size, t, **options):
+        """`from_uint8` for planar 4:2:0 keyframes on the device: `first` / `last` are `Planes` of b images each (a decoder's
+        NV12 / P010 surfaces, or `planes_from_packed` of a planar clip).  They become frames 0 and t-1 by `frames_from_planes`;
+        the encoder and the image tower run as in `from_uint8`."""
+        for name, planes in (("first", first), ("last", last)):
+            if not isinstance(planes, Planes):
+                raise ValueError(f"from_planes: {name} must be a Planes, got {type(planes).__name__}")
+        if len(first) != len(last):
+            raise ValueError(f"from_planes: {len(first)} first frames, {len(last)} last frames")
+        b = len(first)
+        videos = frames_from_planes(first, size, [(i, 0) for i in range(b)], t)
+        frames_from_planes(last, size, [(i, t - 1) for i in range(b)], t, out=videos)
+        return Conditions.build(model, videos, embed=model.embedder.encode_on_device_front, **options)
+
+
+@dataclass(eq=False)
+class Planes:
+    """n planar 4:2:0 images as a hardware decoder (or `clip_to_uint8(fmt="i420" | "nv12")`) leaves them:
+      fmt "i420": y (n, h, w) uint8, chroma = (Cb, Cr), each (n, ch, cw) uint8, one pitch for both;
+      fmt "nv12": y (n, h, w) uint8, chroma = (CbCr,), (n, ch, cw, 2) uint8;
+      fmt "p010": the nv12 shapes with 2-byte elements (torch.uint16 or torch.int16: the bits are what is read), the sample
+                  in the upper ten bits of each little-endian word -- a P016 surface of a 10-bit stream;
+    ch = (h + 1) // 2, cw = (w + 1) // 2.  Row-strided views are taken as they are (the pitch is the stride); inside a row the
+    stride is one.  `standard` "bt601" | "bt709" and `range` "limited" | "full" pick the integer matrix (tc_yuv_matrix), or
+    `matrix` gives its seven integers; `siting` "nearest" | "center" | "left" where the chroma samples sit.
+    Wrong dtypes, shapes or strides raise ValueError here, before anything is launched."""
+    y: torch.Tensor
+    chroma: tuple
+    fmt: str
+    standard: str = "bt601"
+    range: str = "limited"
+    siting: str = "center"
+    matrix: Optional[Sequence[int]] = None
+
+    def __post_init__(self):
+        self.chroma = tuple(self.chroma) if isinstance(self.chroma, (tuple, list)) else (self.chroma,)
+        ops.planes_layout(self, "Planes")
+
+    def __len__(self):
+        return self.y.shape[0]
+
+    def __getitem__(self, index):
+        """images `index` (a slice) as a Planes over the same memory"""
+        if not isinstance(index, slice):
+            raise TypeError("Planes: index with a slice (planes[i:i + 1] for one image)")
+        return Planes(self.y[index], tuple(c[index] for c in self.chroma), self.fmt, self.standard, self.range, self.siting, self.matrix)
+
+
+def planes_from_packed(buf, h, w, fmt, **options):
+    """Views (no copy) of the (..., h * w * 3 / 2) uint8 buffers `clip_to_uint8(fmt="i420" | "nv12")` returns as a `Planes` of
+    all their frames, in order: a planar clip's last frame is `planes_from_packed(clip[:, -1], h, w, fmt)`.  The back end writes
+    BT.601 limited range from 2 x 2 means, which the defaults (`options`: standard, range, siting) undo."""
+    h, w = int(h), int(w)
+    if fmt not in ("i420", "nv12"):
+        raise ValueError(f"planes_from_packed: fmt {fmt!r}: 'i420' or 'nv12'")
+    if h <= 0 or w <= 0 or h % 2 or w % 2:
+        raise ValueError(f"planes_from_packed: the packed planar formats have an even size, got {(h, w)}")
+    if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8 or buf.dim() < 1 or buf.shape[-1] != h * w * 3 // 2 or buf.stride(-1) != 1:
+        raise ValueError(f"planes_from_packed: expected uint8 (..., {h * w * 3 // 2}) frames with unit stride, got "
+                         f"{tuple(buf.shape) if isinstance(buf, torch.Tensor) else type(buf)} {getattr(buf, 'dtype', '')}")
+    try:
+        flat = buf.view(-1, buf.shape[-1])
+    except RuntimeError as e:
+        raise ValueError(f"planes_from_packed: the leading dimensions do not flatten without a copy (strides {buf.stride()})") from e
+    n, q = h * w, (h // 2) * (w // 2)
+    y = flat[:, :n].unflatten(1, (h, w))
+    if fmt == "i420":
+        chroma = (flat[:, n:n + q].unflatten(1, (h // 2, w // 2)), flat[:, n + q:].unflatten(1, (h // 2, w // 2)))
+    else:
+        chroma = (flat[:, n:].unflatten(1, (h // 2, w // 2, 2)),)
+    return Planes(y, chroma, fmt, **options)
+
+
+def frames_from_planes(planes, size, slots, t, out=None):
+    """`frames_from_uint8` for a `Planes` of n images: chroma upsample and YCbCr -> RGB in integers, then the script's
+    transform of that RGB image, bit for bit, on the device (tc_frames_from_yuv)."""
+    if not isinstance(planes, Planes):
+        raise ValueError(f"frames_from_planes: expected a Planes, got {type(planes).__name__}")
+    size, slots, t = tuple(int(v) for v in size), [(int(i), int(f)) for i, f in slots], int(t)
+    if len(size) != 2 or min(size) <= 0 or t <= 0:
+        raise ValueError(f"frames_from_planes: size {size}, t {t}")
+    if len(slots) != len(planes) or any(i < 0 or not 0 <= f < t for i, f in slots):
+        raise ValueError(f"frames_from_planes: {len(planes)} images need as many (batch, frame) slots with frame < {t}, got {slots}")
+    b = out.shape[0] if out is not None else 1 + max(i for i, _ in slots)
+    if any(i >= b for i, _ in slots):
+        raise ValueError(f"frames_from_planes: slots {slots} for a batch of {b}")
+    return ops.frames_from_yuv(planes, size, [i * t + f for i, f in slots], b=b, t=t, out=out)
+
 
 def frames_from_uint8(images_u8, size, slots, t, out=None):
     """uint8 (n, h, w, 3) device images -> the (b, 3, t, H, W) fp32 clip tensor the model takes, `size` = (H, W): image i fills
@@ -250,6 +339,63 @@ def synthesize_u8(model, first_u8, last_u8, latent_shape, *, size, plan: Samplin
                                  hold_endpoints=hold_endpoints)
     return clip_to_uint8(decode_spliced(model, sample(model, cond, plan, latent_shape), cond.refs), size=out_size,
                          filter=out_filter, fmt=out_fmt)
+
+
+def timeline_layout(keyframes: int, t: int, batch: int, out_hw, fmt: str):
+    """Where a timeline of `keyframes` keyframes puts its frames (the splice rule of tc_frames_to_u8, include/tooncrafter_hip.h):
+    segment i runs from keyframe i to i + 1; segment 0 gives frames 0 .. t-1 of the video, every later one its frames 1 .. t-1,
+    F = (K - 1)(t - 1) + 1 frames in all.  Returns (F, bytes per frame, batches); a batch is (first segment, segments) and its
+    frames 1 .. t-1 start at video frame first * (t - 1) + 1, clips (t - 1) frames apart."""
+    keyframes, t, batch = int(keyframes), int(t), int(batch)
+    oh, ow = (int(v) for v in out_hw)
+    if keyframes < 2 or t < 2 or batch < 1:
+        raise ValueError(f"timeline: {keyframes} keyframes (at least 2), clips of {t} frames (at least 2), batches of {batch}")
+    if fmt not in ("rgb24", "i420", "nv12"):
+        raise ValueError(f"timeline: out_fmt {fmt!r}: 'rgb24', 'i420' or 'nv12'")
+    if oh <= 0 or ow <= 0 or (fmt != "rgb24" and (oh % 2 or ow % 2)):
+        raise ValueError(f"timeline: output size {(oh, ow)} for {fmt}")
+    segments = keyframes - 1
+    frame = oh * ow * 3 if fmt == "rgb24" else oh * ow * 3 // 2
+    return segments * (t - 1) + 1, frame, [(i, min(batch, segments - i)) for i in range(0, segments, batch)]
+
+
+def synthesize_timeline_u8(model, keyframes, latent_shape, *, size, plan: SamplingPlan, prompts=None, fs=24, three_way=False,
+                           out_size=None, out_filter="bicubic", out_fmt="rgb24"):
+    """K keyframes in, one video out, all on the device.  `keyframes`: (K, h, w, 3) uint8 or a `Planes` of K images, K >= 2.
+    Segment i interpolates keyframe i -> i + 1 (endpoints held); segments run in order, latent_shape[0] per batch (the last
+    batch may be smaller), each batch exactly `Conditions.from_uint8` / `from_planes` with first = kf[i : i + n] and
+    last = kf[i + 1 : i + n + 1], `sample`, `decode_spliced` and tc_frames_to_u8 writing into ONE buffer by `timeline_layout`'s
+    rule: (F, oh, ow, 3) for "rgb24", (F, oh * ow * 3 / 2) for "i420" / "nv12" (what `mp4.write_mp4_i420` / `planar_writer`
+    take), F = (K - 1)(t - 1) + 1.  `plan.seeds`: one seed per SEGMENT (sliced per batch); `prompts`: one per segment or None.
+    Without seeds the device generator is drawn as the same sequence of `synthesize_u8` calls draws it.  Every inner keyframe is
+    encoded twice, as one segment's last frame and the next one's first."""
+    from dataclasses import replace
+    planar = isinstance(keyframes, Planes)
+    if not planar and not (isinstance(keyframes, torch.Tensor) and keyframes.dtype == torch.uint8 and keyframes.dim() == 4 and keyframes.shape[3] == 3):
+        raise ValueError("synthesize_timeline_u8: keyframes must be (K, h, w, 3) uint8 or a Planes")
+    k, t = len(keyframes), int(latent_shape[2])
+    size = tuple(int(v) for v in size)
+    oh, ow = size if out_size is None else (int(v) for v in out_size)
+    total, frame, batches = timeline_layout(k, t, latent_shape[0], (oh, ow), out_fmt)
+    seeds = None if plan.seeds is None else ops.clip_seeds(plan.seeds, k - 1, "synthesize_timeline_u8: plan.seeds (one per segment)")
+    if prompts is not None and len(prompts) != k - 1:
+        raise ValueError(f"synthesize_timeline_u8: {len(prompts)} prompts for {k - 1} segments")
+    device = keyframes.y.device if planar else keyframes.device
+    video = torch.empty((total, oh, ow, 3) if out_fmt == "rgb24" else (total, frame), dtype=torch.uint8, device=device)
+    flat, row = video.view(-1), 3 * ow if out_fmt == "rgb24" else ow
+    build = Conditions.from_planes if planar else Conditions.from_uint8
+    for i, n in batches:
+        cond = build(model, keyframes[i:i + n], keyframes[i + 1:i + n + 1], size=size, t=t,
+                     prompts=None if prompts is None else list(prompts[i:i + n]), fs=fs, guided=plan.scale != 1.0,
+                     three_way=three_way, image_branch=plan.image_scale != 1.0, hold_endpoints=True)
+        part = plan if seeds is None else replace(plan, seeds=seeds[i:i + n])
+        clips = decode_spliced(model, sample(model, cond, part, [n, *latent_shape[1:]]), cond.refs).to(torch.float32)
+        if i == 0:                                    # the video's first frame: segment 0 alone writes its frame 0
+            ops.frames_to_u8(clips[:1], size=out_size, filter=out_filter, fmt=out_fmt, frames=(0, 1), out=flat,
+                             strides=(row, frame, frame))
+        ops.frames_to_u8(clips, size=out_size, filter=out_filter, fmt=out_fmt, frames=(1, t - 1),
+                         out=flat[(i * (t - 1) + 1) * frame:], strides=(row, frame, (t - 1) * frame))
+    return video
 
 
 # --- the reference scripts' call signatures (scripts/evaluation/inference.py:164,180) -----------------------------------

@@ -1,5 +1,6 @@
-// Pixel front end, gfx950: uint8 frames -> the model's fp32 frames (tc_frames_from_u8) and fp32 frames -> the CLIP image
-// tower's patch rows (tc_clip_patches).  Both run a handful of times per clip on at most a few megabytes, so every kernel
+// Pixel front end, gfx950: uint8 frames -> the model's fp32 frames (tc_frames_from_u8; tc_frames_from_yuv for a decoder's
+// planar 4:2:0 surfaces, which converts to packed RGB and runs the same plan) and fp32 frames -> the CLIP image
+// tower's patch rows (tc_clip_patches).  All run a handful of times per clip on at most a few megabytes, so every kernel
 // here is one thread per output element, written for the arithmetic to be read off the code: the integer resample must give
 // PIL's bytes and the blur / bicubic must stay within a bf16 ulp of kornia's, near zero too.  See include/tooncrafter_hip.h.
 #include "common.h"
@@ -241,42 +242,187 @@ extern "C" int64_t tc_frames_from_u8_workspace(const TcFramesU8Params* p) {
   return rh != p->sh ? (int64_t)p->n * p->sh * rw * 3 : 0;            // both passes run, or neither
 }
 
-extern "C" int tc_frames_from_u8(const TcFramesU8Params* pp, void* stream) {
-  if (!pp) return TC_EINVAL;
-  const TcFramesU8Params& p = *pp;
-  if (!p.src || !p.out || !p.slots || p.n <= 0 || p.n > TC_FRAMES_U8_MAX || p.b <= 0 || p.t <= 0) return TC_EINVAL;
-  int32_t rh, rw;
-  if (tc_frames_from_u8_resized(p.sh, p.sw, p.h, p.w, &rh, &rw) != TC_OK) return TC_EINVAL;
-  if ((int64_t)p.pitch < 3 * (int64_t)p.sw || p.image_stride < (int64_t)p.sh * p.pitch) return TC_EINVAL;
-  FrameSlots slots = {};
+namespace {
+
+// What a request for n (sh, sw) images into a (b, 3, t, h, w) tensor runs, or TC_EINVAL: everything of TcFramesU8Params
+// that does not describe the source's memory or the workspace.  Both front ends ask it.
+struct FramesPlan { FrameSlots slots; int32_t rh, rw; bool resized; int64_t mid_bytes; };
+int frames_plan(const TcFramesU8Params& p, FramesPlan* plan) {
+  if (!p.out || !p.slots || p.n <= 0 || p.n > TC_FRAMES_U8_MAX || p.b <= 0 || p.t <= 0) return TC_EINVAL;
+  if (tc_frames_from_u8_resized(p.sh, p.sw, p.h, p.w, &plan->rh, &plan->rw) != TC_OK) return TC_EINVAL;
+  plan->slots = {};
   for (int i = 0; i < p.n; ++i) {
     if (p.slots[i] < 0 || (int64_t)p.slots[i] >= (int64_t)p.b * p.t) return TC_EINVAL;
-    slots.v[i] = p.slots[i];
+    plan->slots.v[i] = p.slots[i];
   }
   // the rule resizes both sides or neither: the shorter side changes whenever anything does, and the longer one then moves by
   // at least a pixel (s * long / short is below long for s < short and at least long + 1 for s > short)
-  const bool resized = rh != p.sh;
-  if (resized && (!p.h_bounds || !p.h_coefs || p.h_kmax <= 0 || !p.v_bounds || !p.v_coefs || p.v_kmax <= 0)) return TC_EINVAL;
-  const int64_t mid_bytes = tc_frames_from_u8_workspace(pp);
-  if (mid_bytes > 0 && (!p.workspace || p.workspace_bytes < mid_bytes)) return TC_EWORKSPACE;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  plan->resized = plan->rh != p.sh;
+  if (plan->resized && (!p.h_bounds || !p.h_coefs || p.h_kmax <= 0 || !p.v_bounds || !p.v_coefs || p.v_kmax <= 0)) return TC_EINVAL;
+  plan->mid_bytes = plan->resized ? (int64_t)p.n * p.sh * plan->rw * 3 : 0;
+  return TC_OK;
+}
+
+// the launches of a planned request: packed uint8 images at p.src, the intermediate of the horizontal pass at `mid`
+int frames_launch(const TcFramesU8Params& p, const FramesPlan& plan, uint8_t* mid, hipStream_t s) {
+  const int32_t rh = plan.rh, rw = plan.rw;
   const int32_t top = half_even(rh - p.h), left = half_even(rw - p.w);
   const int64_t total = (int64_t)p.n * p.h * p.w;
   const dim3 grid(grid_for(total)), block(256);
-  if (resized) {
-    uint8_t* mid = reinterpret_cast<uint8_t*>(p.workspace);
+  if (plan.resized) {
     const int64_t mid_total = (int64_t)p.n * p.sh * rw;
     hipLaunchKernelGGL(frames_hpass_kernel, dim3(grid_for(mid_total)), block, 0, s, p.src, p.image_stride, p.pitch, p.sh, p.sw, rw,
                        p.h_bounds, p.h_coefs, p.h_kmax, mid, mid_total);
     TC_LAUNCH_CHECK();
     hipLaunchKernelGGL(frames_final_kernel<true>, grid, block, 0, s, (const uint8_t*)mid, (int64_t)p.sh * rw * 3, rw * 3, p.sh, rh,
-                       rw, p.v_bounds, p.v_coefs, p.v_kmax, top, left, slots, p.out, p.t, p.h, p.w, total);
+                       rw, p.v_bounds, p.v_coefs, p.v_kmax, top, left, plan.slots, p.out, p.t, p.h, p.w, total);
   } else {
     hipLaunchKernelGGL(frames_final_kernel<false>, grid, block, 0, s, p.src, p.image_stride, p.pitch, p.sh, rh, rw,
-                       (const int32_t*)nullptr, (const int32_t*)nullptr, 0, top, left, slots, p.out, p.t, p.h, p.w, total);
+                       (const int32_t*)nullptr, (const int32_t*)nullptr, 0, top, left, plan.slots, p.out, p.t, p.h, p.w, total);
   }
   TC_LAUNCH_CHECK();
   return TC_OK;
+}
+
+}  // namespace
+
+extern "C" int tc_frames_from_u8(const TcFramesU8Params* pp, void* stream) {
+  if (!pp) return TC_EINVAL;
+  const TcFramesU8Params& p = *pp;
+  FramesPlan plan;
+  if (!p.src || frames_plan(p, &plan) != TC_OK) return TC_EINVAL;
+  if ((int64_t)p.pitch < 3 * (int64_t)p.sw || p.image_stride < (int64_t)p.sh * p.pitch) return TC_EINVAL;
+  if (plan.mid_bytes > 0 && (!p.workspace || p.workspace_bytes < plan.mid_bytes)) return TC_EWORKSPACE;
+  return frames_launch(p, plan, reinterpret_cast<uint8_t*>(p.workspace), reinterpret_cast<hipStream_t>(stream));
+}
+
+// ---------------------------------------------------------------------------------------------- tc_frames_from_yuv
+
+namespace {
+
+// n planar 4:2:0 images as the kernel addresses them: Cb and Cr are planes of their own (I420) or one plane read at element
+// 2 i and 2 i + 1 (NV12, P010), which `cstep` and the Cr pointer say; `wide`: 16-bit words whose sample is word >> 6
+struct YuvPlanes {
+  const uint8_t* y; const uint8_t* cb; const uint8_t* cr;
+  int64_t image_stride_y, image_stride_c;
+  int pitch_y, pitch_c, cstep, wide;
+};
+struct YuvMatrix { int32_t cy, crv, cgu, cgv, cbu, yoff, coff; };
+
+__device__ __forceinline__ int sample_at(const uint8_t* row, int idx, int wide) {
+  return wide ? (int)(reinterpret_cast<const uint16_t*>(row)[idx] >> 6) : (int)row[idx];
+}
+
+// chroma sample (j, i) of one image's Cb or Cr plane of (ch, cw) samples, both indices clamped to the plane
+__device__ __forceinline__ int chroma_at(const uint8_t* plane, const YuvPlanes& s, int ch, int cw, int j, int i) {
+  j = min(max(j, 0), ch - 1);
+  i = min(max(i, 0), cw - 1);
+  return sample_at(plane + (int64_t)j * s.pitch_c, i * s.cstep, s.wide);
+}
+
+// the chroma value under luma pixel (y, x), at the source bit depth
+__device__ __forceinline__ int chroma_up(const uint8_t* plane, const YuvPlanes& s, int ch, int cw, int siting, int y, int x) {
+  const int j = y >> 1, i = x >> 1;
+  if (siting == TC_CHROMA_NEAREST) return chroma_at(plane, s, ch, cw, j, i);
+  const int jn = (y & 1) ? j + 1 : j - 1;                        // the other row the pixel lies between
+  if (siting == TC_CHROMA_CENTER) {
+    const int in = (x & 1) ? i + 1 : i - 1;
+    return (9 * chroma_at(plane, s, ch, cw, j, i) + 3 * chroma_at(plane, s, ch, cw, j, in) + 3 * chroma_at(plane, s, ch, cw, jn, i) +
+            chroma_at(plane, s, ch, cw, jn, in) + 8) >> 4;
+  }
+  // TC_CHROMA_LEFT: an even column sits on its sample, an odd one halfway to the next
+  if (!(x & 1)) return (3 * chroma_at(plane, s, ch, cw, j, i) + chroma_at(plane, s, ch, cw, jn, i) + 2) >> 2;
+  return (3 * chroma_at(plane, s, ch, cw, j, i) + 3 * chroma_at(plane, s, ch, cw, j, i + 1) + chroma_at(plane, s, ch, cw, jn, i) +
+          chroma_at(plane, s, ch, cw, jn, i + 1) + 4) >> 3;
+}
+
+__device__ __forceinline__ uint8_t clip_u8(int32_t v) { return (uint8_t)min(max(v, 0), 255); }
+
+// one thread per source pixel: n planar images (sh, sw) -> the packed RGB image (n, sh, sw, 3)
+__global__ __launch_bounds__(256) void yuv_to_rgb_kernel(YuvPlanes s, int sh, int sw, int siting, YuvMatrix m,
+                                                         uint8_t* __restrict__ rgb, int64_t total) {
+  const int ch = (sh + 1) / 2, cw = (sw + 1) / 2;
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < total; p += (int64_t)gridDim.x * 256) {
+    const int x = (int)(p % sw);
+    const int64_t r = p / sw;
+    const int y = (int)(r % sh);
+    const int64_t img = r / sh;
+    const int32_t c = sample_at(s.y + img * s.image_stride_y + (int64_t)y * s.pitch_y, x, s.wide) - m.yoff;
+    const int32_t d = chroma_up(s.cb + img * s.image_stride_c, s, ch, cw, siting, y, x) - m.coff;
+    const int32_t e = chroma_up(s.cr + img * s.image_stride_c, s, ch, cw, siting, y, x) - m.coff;
+    rgb[p * 3 + 0] = clip_u8((m.cy * c + m.crv * e + 32768) >> 16);
+    rgb[p * 3 + 1] = clip_u8((m.cy * c - m.cgu * d - m.cgv * e + 32768) >> 16);
+    rgb[p * 3 + 2] = clip_u8((m.cy * c + m.cbu * d + 32768) >> 16);
+  }
+}
+
+// the request as tc_frames_from_u8 sees it once the RGB image stands at `rgb`
+TcFramesU8Params yuv_as_u8(const TcFramesYuvParams& p, const uint8_t* rgb) {
+  TcFramesU8Params u = {};
+  u.src = rgb; u.pitch = 3 * p.sw; u.image_stride = (int64_t)p.sh * p.sw * 3;
+  u.n = p.n; u.sh = p.sh; u.sw = p.sw; u.slots = p.slots; u.out = p.out; u.b = p.b; u.t = p.t; u.h = p.h; u.w = p.w;
+  u.h_bounds = p.h_bounds; u.h_coefs = p.h_coefs; u.h_kmax = p.h_kmax;
+  u.v_bounds = p.v_bounds; u.v_coefs = p.v_coefs; u.v_kmax = p.v_kmax;
+  return u;
+}
+
+}  // namespace
+
+extern "C" int tc_yuv_matrix(int32_t standard, int32_t range, int32_t bits, int32_t m[7]) {
+  if (!m || (standard != TC_YUV_BT601 && standard != TC_YUV_BT709) || (range != TC_YUV_LIMITED && range != TC_YUV_FULL) ||
+      (bits != 8 && bits != 10))
+    return TC_EINVAL;
+  const double kr = standard == TC_YUV_BT601 ? 0.299 : 0.2126, kb = standard == TC_YUV_BT601 ? 0.114 : 0.0722;
+  const double kg = 1.0 - kr - kb, q = (double)(1 << (bits - 8)), top = (double)((1 << bits) - 1);
+  const double gy = range == TC_YUV_LIMITED ? 255.0 / (219.0 * q) : 255.0 / top;
+  const double s = range == TC_YUV_LIMITED ? 255.0 / (224.0 * q) : 255.0 / top;
+  const double v[5] = {gy, 2.0 * (1.0 - kr) * s, 2.0 * kb * (1.0 - kb) / kg * s, 2.0 * kr * (1.0 - kr) / kg * s, 2.0 * (1.0 - kb) * s};
+  for (int i = 0; i < 5; ++i) m[i] = (int32_t)floor(v[i] * 65536.0 + 0.5);
+  m[5] = range == TC_YUV_LIMITED ? 16 << (bits - 8) : 0;
+  m[6] = 128 << (bits - 8);
+  return TC_OK;
+}
+
+extern "C" int64_t tc_frames_from_yuv_workspace(const TcFramesYuvParams* p) {
+  if (!p || p->n <= 0 || p->sh <= 0 || p->sw <= 0 || p->h <= 0 || p->w <= 0) return 0;
+  const TcFramesU8Params u = yuv_as_u8(*p, nullptr);
+  return (int64_t)p->n * p->sh * p->sw * 3 + tc_frames_from_u8_workspace(&u);
+}
+
+extern "C" int tc_frames_from_yuv(const TcFramesYuvParams* pp, void* stream) {
+  if (!pp) return TC_EINVAL;
+  const TcFramesYuvParams& p = *pp;
+  if (!p.y || !p.c0) return TC_EINVAL;
+  if (p.format != TC_PIXFMT_I420 && p.format != TC_PIXFMT_NV12 && p.format != TC_PIXFMT_P010) return TC_EINVAL;
+  if (p.siting != TC_CHROMA_NEAREST && p.siting != TC_CHROMA_CENTER && p.siting != TC_CHROMA_LEFT) return TC_EINVAL;
+  const bool planar = p.format == TC_PIXFMT_I420, wide = p.format == TC_PIXFMT_P010;
+  if (planar != (p.c1 != nullptr)) return TC_EINVAL;
+  TcFramesU8Params u = yuv_as_u8(p, nullptr);
+  FramesPlan plan;
+  if (frames_plan(u, &plan) != TC_OK) return TC_EINVAL;              // n, sizes, slots, tables
+  const int64_t ch = (p.sh + 1) / 2, cw = (p.sw + 1) / 2, bytes = wide ? 2 : 1;
+  if ((int64_t)p.pitch_y < bytes * p.sw || (int64_t)p.pitch_c < (planar ? 1 : 2) * bytes * cw) return TC_EINVAL;
+  if (p.image_stride_y < (int64_t)p.sh * p.pitch_y || p.image_stride_c < ch * p.pitch_c) return TC_EINVAL;
+  if (p.m[0] <= 0) return TC_EINVAL;
+  if (wide && (((reinterpret_cast<uintptr_t>(p.y) | reinterpret_cast<uintptr_t>(p.c0)) & 1u) || ((p.pitch_y | p.pitch_c) & 1) ||
+               ((p.image_stride_y | p.image_stride_c) & 1)))
+    return TC_EALIGN;
+  const int64_t rgb_bytes = (int64_t)p.n * p.sh * p.sw * 3;
+  if (!p.workspace || p.workspace_bytes < rgb_bytes + plan.mid_bytes) return TC_EWORKSPACE;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  uint8_t* rgb = reinterpret_cast<uint8_t*>(p.workspace);
+  YuvPlanes src;
+  src.y = reinterpret_cast<const uint8_t*>(p.y);
+  src.cb = reinterpret_cast<const uint8_t*>(p.c0);
+  src.cr = planar ? reinterpret_cast<const uint8_t*>(p.c1) : src.cb + bytes;      // the second sample of each pair
+  src.image_stride_y = p.image_stride_y; src.image_stride_c = p.image_stride_c;
+  src.pitch_y = p.pitch_y; src.pitch_c = p.pitch_c; src.cstep = planar ? 1 : 2; src.wide = wide ? 1 : 0;
+  const YuvMatrix m = {p.m[0], p.m[1], p.m[2], p.m[3], p.m[4], p.m[5], p.m[6]};
+  const int64_t total = (int64_t)p.n * p.sh * p.sw;
+  hipLaunchKernelGGL(yuv_to_rgb_kernel, dim3(grid_for(total)), dim3(256), 0, s, src, p.sh, p.sw, p.siting, m, rgb, total);
+  TC_LAUNCH_CHECK();
+  u.src = rgb;
+  return frames_launch(u, plan, rgb + rgb_bytes, s);
 }
 
 extern "C" int64_t tc_clip_patches_workspace(const TcClipPatchesParams* p) {

@@ -3,7 +3,7 @@
 // The reference binds ATen / xformers operators from Python (utils/utils.py:27-42 instantiates lvdm classes whose
 // forward methods call torch ops); this registers the MI355X kernels as first-class torch operators instead:
 //   torch.ops.tooncrafter.gemm / quant_mxfp8 / gemm_mx / attention / attention_temporal(_rel) / groupnorm(_pf) / layernorm(_pf) / ddim_step(_eps) / ddim_step_ms(_eps) / ddim_blend /
-//   frames_from_u8 / frames_to_u8 / clip_patches / randn_clips /
+//   frames_from_u8 / frames_from_yuv / frames_to_u8 / clip_patches / randn_clips /
 //   ff_geglu_fused / temporal_attn_fused / temporal_qkv_attn / attention_q8
 // with (i) a CUDA(HIP)-key implementation that validates the tensors, allocates the result from the caching allocator,
 // picks up the CURRENT stream and calls the same extern "C" entry point the ctypes binding calls, and (ii) a Meta-key
@@ -545,6 +545,80 @@ Tensor frames_from_u8_meta(const Tensor& images, at::IntArrayRef, int64_t b, int
   return at::empty({b, 3, t, h, w}, images.options().dtype(at::kFloat));
 }
 
+// frames_from_yuv: n planar 4:2:0 images -> a new (b, 3, t, h, w) fp32 clip tensor (tc_frames_from_yuv).  y (n, sh, sw), c0 / c1
+// (n, ch, cw) for I420, c0 (n, ch, cw, 2) for NV12 and P010 (2-byte elements); pitches and image strides are the tensors' strides.
+std::pair<int64_t, int64_t> plane_rows(const Tensor& p, int64_t row_elems, const char* what) {   // (pitch, image stride) in bytes
+  const int64_t es = p.element_size(), n = p.size(0);
+  TORCH_CHECK(p.stride(p.dim() - 1) == 1 && (p.dim() == 3 || p.stride(2) == 2) && p.stride(1) >= row_elems &&
+              (n == 1 || p.stride(0) >= p.size(1) * p.stride(1)), what, ": rows with unit stride inside that do not overlap");
+  return {p.stride(1) * es, (n > 1 ? p.stride(0) : p.size(1) * p.stride(1)) * es};
+}
+
+Tensor frames_from_yuv_cuda(const Tensor& y, const Tensor& c0, const optional<Tensor>& c1, int64_t format, at::IntArrayRef m,
+                            int64_t siting, at::IntArrayRef slots, int64_t b, int64_t t, int64_t h, int64_t w,
+                            const optional<Tensor>& h_bounds, const optional<Tensor>& h_coefs, const optional<Tensor>& v_bounds,
+                            const optional<Tensor>& v_coefs) {
+  TORCH_CHECK(y.is_cuda() && c0.is_cuda() && (!c1.has_value() || c1->is_cuda()),
+              "frames_from_yuv: expected CUDA tensors (the product path is GPU-only)");
+  TORCH_CHECK(format == TC_PIXFMT_I420 || format == TC_PIXFMT_NV12 || format == TC_PIXFMT_P010, "frames_from_yuv: format ", format);
+  const bool planar = format == TC_PIXFMT_I420, wide = format == TC_PIXFMT_P010;
+  auto sample_type = [&](const Tensor& p) {
+    return wide ? p.scalar_type() == at::kShort || p.scalar_type() == at::kUInt16 : p.scalar_type() == at::kByte;
+  };
+  TORCH_CHECK(y.dim() == 3 && y.numel() > 0 && sample_type(y) && sample_type(c0), "frames_from_yuv: y (n, h, w) of ",
+              wide ? "2-byte" : "uint8", " samples");
+  const int64_t n = y.size(0), sh = y.size(1), sw = y.size(2), ch = (sh + 1) / 2, cw = (sw + 1) / 2;
+  TORCH_CHECK(planar == c1.has_value(), "frames_from_yuv: a Cr plane for I420 only");
+  if (planar) {
+    TORCH_CHECK(c0.sizes() == at::IntArrayRef({n, ch, cw}) && c1->sizes() == c0.sizes() && c1->strides() == c0.strides() &&
+                sample_type(*c1), "frames_from_yuv: I420 chroma planes (n, (h + 1) / 2, (w + 1) / 2) with one pitch");
+  } else {
+    TORCH_CHECK(c0.sizes() == at::IntArrayRef({n, ch, cw, 2}), "frames_from_yuv: an interleaved chroma plane (n, (h + 1) / 2, (w + 1) / 2, 2)");
+  }
+  TORCH_CHECK(n >= 1 && n <= TC_FRAMES_U8_MAX && (int64_t)slots.size() == n, "frames_from_yuv: 1 .. ", TC_FRAMES_U8_MAX, " images, one slot each");
+  TORCH_CHECK(b > 0 && t > 0 && h > 0 && w > 0, "frames_from_yuv: b, t, h, w must be positive");
+  TORCH_CHECK(m.size() == 7, "frames_from_yuv: the matrix has seven entries");
+  TORCH_CHECK(siting == TC_CHROMA_NEAREST || siting == TC_CHROMA_CENTER || siting == TC_CHROMA_LEFT, "frames_from_yuv: siting ", siting);
+  Tensor out = at::zeros({b, 3, t, h, w}, y.options().dtype(at::kFloat));
+  int32_t slot[TC_FRAMES_U8_MAX];
+  for (int64_t i = 0; i < n; ++i) {
+    TORCH_CHECK(slots[i] >= 0 && slots[i] < b * t, "frames_from_yuv: slot ", slots[i], " outside the clip tensor");
+    slot[i] = (int32_t)slots[i];
+  }
+  TcFramesYuvParams p = {};
+  p.y = y.data_ptr(); p.c0 = c0.data_ptr(); p.c1 = planar ? c1->data_ptr() : nullptr;
+  const auto ry = plane_rows(y, sw, "frames_from_yuv: y"), rc = plane_rows(c0, planar ? cw : 2 * cw, "frames_from_yuv: chroma");
+  p.pitch_y = (int32_t)ry.first; p.image_stride_y = ry.second;
+  p.pitch_c = (int32_t)rc.first; p.image_stride_c = rc.second;
+  p.format = (int32_t)format; p.siting = (int32_t)siting;
+  for (int i = 0; i < 7; ++i) p.m[i] = (int32_t)m[i];
+  p.n = (int32_t)n; p.sh = (int32_t)sh; p.sw = (int32_t)sw;
+  p.slots = slot;
+  p.out = out.data_ptr<float>();
+  p.b = (int32_t)b; p.t = (int32_t)t; p.h = (int32_t)h; p.w = (int32_t)w;
+  p.h_bounds = i32_table(h_bounds, "frames_from_yuv: h_bounds"); p.h_coefs = i32_table(h_coefs, "frames_from_yuv: h_coefs");
+  p.v_bounds = i32_table(v_bounds, "frames_from_yuv: v_bounds"); p.v_coefs = i32_table(v_coefs, "frames_from_yuv: v_coefs");
+  int32_t rh = 0, rw = 0;
+  check_rc(tc_frames_from_u8_resized(p.sh, p.sw, p.h, p.w, &rh, &rw), "tc_frames_from_u8_resized");
+  if (rh != p.sh) {                                       // the tables must be the ones of these sizes: their rows are indexed by rw / rh
+    TORCH_CHECK(p.h_bounds && p.h_coefs && p.v_bounds && p.v_coefs && h_bounds->size(0) == rw && h_coefs->size(0) == rw &&
+                v_bounds->size(0) == rh && v_coefs->size(0) == rh && h_bounds->size(1) == 2 && v_bounds->size(1) == 2,
+                "frames_from_yuv: tables of ", p.sw, " -> ", rw, " and ", p.sh, " -> ", rh, " expected");
+    p.h_kmax = (int32_t)h_coefs->size(1); p.v_kmax = (int32_t)v_coefs->size(1);
+  }
+  p.workspace_bytes = tc_frames_from_yuv_workspace(&p);
+  Tensor ws = at::empty({p.workspace_bytes > 16 ? p.workspace_bytes : 16}, y.options().dtype(at::kByte));
+  p.workspace = ws.data_ptr();
+  check_rc(tc_frames_from_yuv(&p, cur_stream()), "tc_frames_from_yuv");
+  return out;
+}
+
+Tensor frames_from_yuv_meta(const Tensor& y, const Tensor&, const optional<Tensor>&, int64_t, at::IntArrayRef, int64_t, at::IntArrayRef,
+                            int64_t b, int64_t t, int64_t h, int64_t w, const optional<Tensor>&, const optional<Tensor>&,
+                            const optional<Tensor>&, const optional<Tensor>&) {
+  return at::empty({b, 3, t, h, w}, y.options().dtype(at::kFloat));
+}
+
 // Pixel back end (additive within ABI 14).  frames_to_u8: frames f0 .. f0 + nf - 1 of every clip of x (b, 3, t, h, w) fp32 -> a new
 // packed uint8 tensor, (b, nf, oh, ow, 3) for RGB24 or (b, nf, oh * ow * 3 / 2) for I420 / NV12 (tc_frames_to_u8); the tables are
 // tc_resize_tables_filter's for w -> ow and h -> oh, on the device (None for an axis that keeps its size).  Writing into a caller's
@@ -692,6 +766,8 @@ TORCH_LIBRARY(tooncrafter, m) {
   m.def("ddim_blend(Tensor? x, Tensor x0, Tensor? noise, Tensor? mask, float sqrt_ac, float sqrt_1m_ac) -> Tensor");
   m.def("frames_from_u8(Tensor images, int[] slots, int b, int t, int h, int w, Tensor? h_bounds, Tensor? h_coefs, "
         "Tensor? v_bounds, Tensor? v_coefs) -> Tensor");
+  m.def("frames_from_yuv(Tensor y, Tensor c0, Tensor? c1, int format, int[] m, int siting, int[] slots, int b, int t, int h, int w, "
+        "Tensor? h_bounds, Tensor? h_coefs, Tensor? v_bounds, Tensor? v_coefs) -> Tensor");
   m.def("frames_to_u8(Tensor x, int oh, int ow, int format, int f0, int nf, Tensor? h_bounds, Tensor? h_coefs, Tensor? v_bounds, "
         "Tensor? v_coefs) -> Tensor");
   m.def("clip_patches(Tensor x, int size, int patch, int ld, float[] mean, float[] std, bool antialias) -> Tensor");
@@ -717,6 +793,7 @@ TORCH_LIBRARY_IMPL(tooncrafter, CUDA, m) {
   m.impl("ddim_step_ms_eps", ddim_step_ms_any<true>);
   m.impl("ddim_blend", ddim_blend_cuda);
   m.impl("frames_from_u8", frames_from_u8_cuda);
+  m.impl("frames_from_yuv", frames_from_yuv_cuda);
   m.impl("frames_to_u8", frames_to_u8_cuda);
   m.impl("clip_patches", clip_patches_cuda);
   m.impl("randn_clips", randn_clips_cuda);
@@ -738,6 +815,7 @@ TORCH_LIBRARY_IMPL(tooncrafter, Meta, m) {
     m.impl(name, torch::CppFunction::makeFromBoxedFunction<&like_first_meta>());
   m.impl("ddim_blend", ddim_blend_meta);
   m.impl("frames_from_u8", frames_from_u8_meta);
+  m.impl("frames_from_yuv", frames_from_yuv_meta);
   m.impl("frames_to_u8", frames_to_u8_meta);
   m.impl("clip_patches", clip_patches_meta);
   m.impl("randn_clips", randn_clips_meta);

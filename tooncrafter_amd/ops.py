@@ -75,6 +75,51 @@ def clip_seeds(seeds, b: int, what: str = "seeds"):
     return [int(s) for s in seeds]
 
 
+def planes_layout(planes, what: str = "planes"):
+    """The memory layout of n planar 4:2:0 images (`clip.Planes`) as tc_frames_from_yuv takes it, or ValueError: format code,
+    n, sh, sw, the two pitches and image strides in bytes, and `wide` (2-byte samples).  Host-only: nothing is launched."""
+    fmt = getattr(planes, "fmt", None)
+    if fmt not in _lib.TC_YUV_FORMATS:
+        raise ValueError(f"{what}: fmt {fmt!r}: one of {sorted(_lib.TC_YUV_FORMATS)}")
+    if planes.standard not in _lib.TC_YUV_STANDARDS or planes.range not in _lib.TC_YUV_RANGES or planes.siting not in _lib.TC_CHROMA_SITINGS:
+        raise ValueError(f"{what}: standard {planes.standard!r}, range {planes.range!r}, siting {planes.siting!r}: one of "
+                         f"{sorted(_lib.TC_YUV_STANDARDS)}, {sorted(_lib.TC_YUV_RANGES)}, {sorted(_lib.TC_CHROMA_SITINGS)}")
+    if planes.matrix is not None and (len(planes.matrix) != 7 or int(planes.matrix[0]) <= 0):
+        raise ValueError(f"{what}: matrix {list(planes.matrix)}: seven integers (cy, crv, cgu, cgv, cbu, yoff, coff), cy > 0")
+    wide = fmt == "p010"
+    dtypes = (torch.uint16, torch.int16) if wide else (torch.uint8,)
+    y, chroma = planes.y, tuple(planes.chroma) if isinstance(planes.chroma, (tuple, list)) else (planes.chroma,)
+    if len(chroma) != (2 if fmt == "i420" else 1):
+        raise ValueError(f"{what}: {fmt} has {2 if fmt == 'i420' else 1} chroma plane(s), got {len(chroma)}")
+    for name, p in (("y", y),) + tuple((f"chroma[{i}]", c) for i, c in enumerate(chroma)):
+        if not isinstance(p, torch.Tensor) or p.dtype not in dtypes:
+            raise ValueError(f"{what}: {name}: expected a tensor of {' or '.join(str(d) for d in dtypes)} for {fmt}, got "
+                             f"{getattr(p, 'dtype', type(p))}")
+        if p.device != y.device:
+            raise ValueError(f"{what}: {name} is on {p.device}, y on {y.device}")
+    if y.dim() != 3 or 0 in y.shape:
+        raise ValueError(f"{what}: y must be (n, h, w), got {tuple(y.shape)}")
+    n, sh, sw = y.shape
+    ch, cw = (sh + 1) // 2, (sw + 1) // 2
+    cshape = (n, ch, cw) if fmt == "i420" else (n, ch, cw, 2)
+    for i, c in enumerate(chroma):
+        if tuple(c.shape) != cshape:
+            raise ValueError(f"{what}: chroma[{i}] must be {cshape} for {fmt} with a {(sh, sw)} picture, got {tuple(c.shape)}")
+    if fmt == "i420" and chroma[0].stride() != chroma[1].stride():
+        raise ValueError(f"{what}: the Cb and Cr planes must share one pitch (strides {chroma[0].stride()}, {chroma[1].stride()})")
+
+    def rows(p, row_elems, inner):
+        """(pitch, image stride) in elements of a plane whose rows hold row_elems unit-stride elements"""
+        if p.stride()[2:] != inner or p.stride(1) < row_elems or (n > 1 and p.stride(0) < p.shape[1] * p.stride(1)):
+            raise ValueError(f"{what}: rows must have unit stride inside and may not overlap (shape {tuple(p.shape)}, strides {p.stride()})")
+        return p.stride(1), p.stride(0) if n > 1 else p.shape[1] * p.stride(1)
+    es = 2 if wide else 1
+    pitch_y, stride_y = rows(y, sw, (1,))
+    pitch_c, stride_c = rows(chroma[0], cw if fmt == "i420" else 2 * cw, (1,) if fmt == "i420" else (2, 1))
+    return dict(format=_lib.TC_YUV_FORMATS[fmt], wide=wide, n=n, sh=sh, sw=sw, pitch_y=pitch_y * es, pitch_c=pitch_c * es,
+                image_stride_y=stride_y * es, image_stride_c=stride_c * es)
+
+
 class MxRows:
     """An activation that exists only as MXFP8 (e4m3 bytes + E8M0 block scales): what `layernorm(..., mx_for=...)`
     hands to the one GEMM that consumes it when the fp8 routing takes that GEMM."""
@@ -844,6 +889,62 @@ class HipOps:
             ws = self._workspace(p.workspace_bytes, images.device)
             p.workspace = ws.data_ptr()
             _lib.check(self.lib.tc_frames_from_u8(C.byref(p), _stream()), "tc_frames_from_u8")
+        return out
+
+    def yuv_matrix(self, standard="bt601", range="limited", bits=8):
+        """The seven integers {cy, crv, cgu, cgv, cbu, yoff, coff} of a YCbCr -> RGB conversion (tc_yuv_matrix; host only):
+        standard "bt601" | "bt709", range "limited" | "full", bits 8 | 10."""
+        if standard not in _lib.TC_YUV_STANDARDS or range not in _lib.TC_YUV_RANGES:
+            raise ValueError(f"yuv_matrix: standard {standard!r} (one of {sorted(_lib.TC_YUV_STANDARDS)}), "
+                             f"range {range!r} (one of {sorted(_lib.TC_YUV_RANGES)})")
+        m = (C.c_int32 * 7)()
+        _lib.check(self.lib.tc_yuv_matrix(_lib.TC_YUV_STANDARDS[standard], _lib.TC_YUV_RANGES[range], int(bits), m), "tc_yuv_matrix")
+        return list(m)
+
+    def _frames_yuv_args(self, planes, size, slots, b, t, out):
+        """The checked request of frames_from_yuv: (layout, matrix, (h, w), slots, out)."""
+        lay = planes_layout(planes, "frames_from_yuv: planes")
+        if not planes.y.is_cuda:
+            raise _lib.TooncrafterHipError("frames_from_yuv: planes: expected CUDA tensors: the product path is GPU-only")
+        h, w = (int(v) for v in size)
+        slots = [int(s) for s in slots]
+        if len(slots) != lay["n"] or any(s < 0 or s >= b * t for s in slots):
+            raise ValueError(f"frames_from_yuv: {lay['n']} images need {lay['n']} slots in [0, {b * t}), got {slots}")
+        if out is not None:
+            _dev(out, torch.float32, "frames_from_yuv: out")
+            if tuple(out.shape) != (b, 3, t, h, w):
+                raise ValueError(f"frames_from_yuv: out must be ({b}, 3, {t}, {h}, {w}), got {tuple(out.shape)}")
+        m = self.yuv_matrix(planes.standard, planes.range, 10 if lay["wide"] else 8) if planes.matrix is None else [int(v) for v in planes.matrix]
+        return lay, m, (h, w), slots, out
+
+    def frames_from_yuv(self, planes, size, slots, *, b, t, out=None):
+        """Planar 4:2:0 images (`clip.Planes`: I420, NV12 or P010, rows pitched as their strides say) -> frames of a
+        (b, 3, t, H, W) fp32 clip tensor: chroma upsampled by `planes.siting`, YCbCr -> RGB in integers by the matrix of
+        `planes.standard` / `planes.range` (or `planes.matrix`), then frames_from_u8's transform of that RGB image, bit for bit
+        (tc_frames_from_yuv).  slots / out as in frames_from_u8."""
+        lay, m, (h, w), slots, out = self._frames_yuv_args(planes, size, slots, b, t, out)
+        n, sh, sw, dev = lay["n"], lay["sh"], lay["sw"], planes.y.device
+        if out is None:
+            out = torch.zeros((b, 3, t, h, w), dtype=torch.float32, device=dev)
+        rh, rw = self.resized_size(sh, sw, h, w)
+        p = _lib.TcFramesYuvParams(image_stride_y=lay["image_stride_y"], image_stride_c=lay["image_stride_c"], pitch_y=lay["pitch_y"],
+                                   pitch_c=lay["pitch_c"], format=lay["format"], siting=_lib.TC_CHROMA_SITINGS[planes.siting],
+                                   m=(C.c_int32 * 7)(*m), sh=sh, sw=sw, out=out.data_ptr(), b=b, t=t, h=h, w=w)
+        if (rh, rw) != (sh, sw):
+            hb, hc = self.resize_tables(sw, rw, dev)
+            vb, vc = self.resize_tables(sh, rh, dev)
+            p.h_bounds, p.h_coefs, p.h_kmax = hb.data_ptr(), hc.data_ptr(), hc.shape[1]
+            p.v_bounds, p.v_coefs, p.v_kmax = vb.data_ptr(), vc.data_ptr(), vc.shape[1]
+        for i in range(0, n, _lib.TC_FRAMES_U8_MAX):
+            part = slots[i:i + _lib.TC_FRAMES_U8_MAX]
+            held = (C.c_int32 * len(part))(*part)
+            p.y, p.c0 = planes.y[i].data_ptr(), planes.chroma[0][i].data_ptr()
+            p.c1 = planes.chroma[1][i].data_ptr() if len(planes.chroma) > 1 else None
+            p.n, p.slots = len(part), held
+            p.workspace_bytes = self.lib.tc_frames_from_yuv_workspace(C.byref(p))
+            ws = self._workspace(p.workspace_bytes, dev)
+            p.workspace = ws.data_ptr()
+            _lib.check(self.lib.tc_frames_from_yuv(C.byref(p), _stream()), "tc_frames_from_yuv")
         return out
 
     def resize_tables_filter(self, filter, n_in, n_out, device):

@@ -164,6 +164,19 @@ class TorchLibOps(HipOps):
             tabs = self.resize_tables(sw, rw, images.device) + self.resize_tables(sh, rh, images.device)
         return self.t.frames_from_u8(images, [int(s) for s in slots], int(b), int(t), h, w, *tabs)
 
+    def frames_from_yuv(self, planes, size, slots, *, b, t, out=None):
+        lay, m, (h, w), slots, out = self._frames_yuv_args(planes, size, slots, b, t, out)
+        if out is not None or lay["n"] > _lib.TC_FRAMES_U8_MAX:            # an explicit result buffer / several calls: the ctypes method
+            return super().frames_from_yuv(planes, size, slots, b=b, t=t, out=out)
+        sh, sw, dev = lay["sh"], lay["sw"], planes.y.device
+        rh, rw = self.resized_size(sh, sw, h, w)
+        tabs = (None,) * 4
+        if (rh, rw) != (sh, sw):
+            tabs = self.resize_tables(sw, rw, dev) + self.resize_tables(sh, rh, dev)
+        c1 = planes.chroma[1] if len(planes.chroma) > 1 else None
+        return self.t.frames_from_yuv(planes.y, planes.chroma[0], c1, lay["format"], m, _lib.TC_CHROMA_SITINGS[planes.siting], slots,
+                                      int(b), int(t), h, w, *tabs)
+
     def frames_to_u8(self, x, size=None, filter="bicubic", fmt="rgb24", frames=None, out=None, strides=None):
         if out is not None or strides is not None:          # an explicit result buffer with its strides: the ctypes method
             return super().frames_to_u8(x, size, filter, fmt, frames, out=out, strides=strides)
