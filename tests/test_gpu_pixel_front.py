@@ -110,6 +110,21 @@ def test_torch_op_binding_equals_ctypes(hip, g, name):
         tl.t.frames_from_u8(img, [3], 1, 3, h, w, None, None, None, None)
 
 
+def test_more_images_than_one_call_takes(hip):
+    """17 images of 5 x 7 (resized to 4 x 5: both passes run) into slots 0 .. 16 of a (2, 3, 9, 4, 6) clip tensor, which takes
+    two calls of the entry point: the same images sent one to a call into a zeroed `out`, and slot 17 stays zero."""
+    from tooncrafter_amd import _lib
+    n, b, t, size = _lib.TC_FRAMES_U8_MAX + 1, 2, 9, (4, 6)
+    assert n == 17 and hip.resized_size(5, 7, *size) == (4, 5)
+    imgs = torch.randint(0, 256, (n, 5, 7, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(17)).to(DEV)
+    got = hip.frames_from_u8(imgs, size, list(range(n)), b=b, t=t)
+    want = torch.zeros(b, 3, t, *size, dtype=torch.float32, device=DEV)
+    for i in range(n):
+        hip.frames_from_u8(imgs[i:i + 1], size, [i], b=b, t=t, out=want)
+    assert got.shape == want.shape and torch.equal(got, want)
+    assert want[1, :, 7].any() and not got[1, :, 8].any()                         # slot 16 is written, slot 17 = (1, 8) is not
+
+
 # ------------------------------------------------------------------------------------------------ tc_clip_patches
 
 def blur_rule(factor):

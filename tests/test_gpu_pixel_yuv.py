@@ -162,6 +162,21 @@ def test_p010_low_six_bits_are_ignored(hip):
     assert torch.equal(a, c)
 
 
+def test_more_images_than_one_call_takes(hip):
+    """17 NV12 images of 5 x 7 (resized to 4 x 5: both passes run) into slots 0 .. 16 of a (2, 3, 9, 4, 6) clip tensor, which
+    takes two calls of the entry point: the same images sent one to a call into a zeroed `out`, and slot 17 stays zero."""
+    from tooncrafter_amd import _lib
+    n, b, t, size = _lib.TC_FRAMES_U8_MAX + 1, 2, 9, (4, 6)
+    assert n == 17 and hip.resized_size(5, 7, *size) == (4, 5)
+    planes = device_planes(ref.random_planes(np.random.default_rng(8450), n, 5, 7, "nv12"), "nv12")
+    got = hip.frames_from_yuv(planes, size, list(range(n)), b=b, t=t)
+    want = torch.zeros(b, 3, t, *size, dtype=torch.float32, device=DEV)
+    for i in range(n):
+        hip.frames_from_yuv(planes[i:i + 1], size, [i], b=b, t=t, out=want)
+    assert got.shape == want.shape and torch.equal(got, want)
+    assert want[1, :, 7].any() and not got[1, :, 8].any()                         # slot 16 is written, slot 17 = (1, 8) is not
+
+
 # ------------------------------------------------------------------------------------------------ bindings
 
 @pytest.mark.parametrize("case,fmt,siting", [("5x7_odd", "i420", "center"), ("64x96_crop", "nv12", "left"), ("300x290_both", "p010", "nearest")])

@@ -143,11 +143,13 @@ def test_library_exports_and_binds_the_symbols():
 # ---------------------------------------------------------------- the table builder and its statement
 
 def test_resize_tables_equal_the_numpy_statement():
-    """Bounds and every coefficient, over in, out in 1 .. 64 and the full-HD frame widths both ways; the columns of a row past
-    its tap count are zero."""
+    """Bounds and every coefficient, over in, out in 1 .. 64, the full-HD frame widths both ways and the usual frame sides down
+    to the model's; the columns of a row past its tap count are zero.  The statement divides by the filter scale where the
+    library, like Pillow, multiplies by its reciprocal."""
     from tooncrafter_amd import _lib
     lib = _lib.load()
     pairs = [(i, o) for i in range(1, 65) for o in range(1, 65)] + [(1920, 569), (569, 1920)]
+    pairs += [(i, o) for i in (240, 360, 480, 720, 1080, 1440, 2160) for o in (320, 512, 576)]
     for n_in, n_out in pairs:
         bounds, coefs = c_tables(lib, n_in, n_out)
         want_b, want_c = pil_tables(n_in, n_out)

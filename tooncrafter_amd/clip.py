@@ -103,12 +103,7 @@ class Conditions:
             if not isinstance(u8, torch.Tensor) or u8.dtype != torch.uint8 or u8.dim() != 4 or u8.shape[3] != 3:
                 raise ValueError(f"from_uint8: {name} must be (b, h, w, 3) uint8, got "
                                  f"{tuple(u8.shape) if isinstance(u8, torch.Tensor) else type(u8)} {getattr(u8, 'dtype', '')}")
-        if first_u8.shape[0] != last_u8.shape[0]:
-            raise ValueError(f"from_uint8: {first_u8.shape[0]} first frames, {last_u8.shape[0]} last frames")
-        b = first_u8.shape[0]
-        videos = frames_from_uint8(first_u8, size, [(i, 0) for i in range(b)], t)
-        frames_from_uint8(last_u8, size, [(i, t - 1) for i in range(b)], t, out=videos)
-        return Conditions.build(model, videos, embed=model.embedder.encode_on_device_front, **options)
+        return Conditions._from_keyframes("from_uint8", frames_from_uint8, model, first_u8, last_u8, size, t, options)
 
     @staticmethod
     def from_planes(model, first, last, *, size, t, **options):
@@ -118,11 +113,17 @@ class Conditions:
         for name, planes in (("first", first), ("last", last)):
             if not isinstance(planes, Planes):
                 raise ValueError(f"from_planes: {name} must be a Planes, got {type(planes).__name__}")
-        if len(first) != len(last):
-            raise ValueError(f"from_planes: {len(first)} first frames, {len(last)} last frames")
+        return Conditions._from_keyframes("from_planes", frames_from_planes, model, first, last, size, t, options)
+
+    @staticmethod
+    def _from_keyframes(what, frames, model, first, last, size, t, options):
+        """The shared tail of from_uint8 / from_planes: b first and b last keyframes become frames 0 and t-1 of the clip tensor
+        by `frames` (frames_from_uint8 or frames_from_planes), then `build` with the image tower on the device front."""
         b = len(first)
-        videos = frames_from_planes(first, size, [(i, 0) for i in range(b)], t)
-        frames_from_planes(last, size, [(i, t - 1) for i in range(b)], t, out=videos)
+        if b != len(last):
+            raise ValueError(f"{what}: {b} first frames, {len(last)} last frames")
+        videos = frames(first, size, [(i, 0) for i in range(b)], t)
+        frames(last, size, [(i, t - 1) for i in range(b)], t, out=videos)
         return Conditions.build(model, videos, embed=model.embedder.encode_on_device_front, **options)
 
 
@@ -189,15 +190,22 @@ def frames_from_planes(planes, size, slots, t, out=None):
     transform of that RGB image, bit for bit, on the device (tc_frames_from_yuv)."""
     if not isinstance(planes, Planes):
         raise ValueError(f"frames_from_planes: expected a Planes, got {type(planes).__name__}")
+    size, flat, b, t = _clip_slots("frames_from_planes", len(planes), size, slots, t, out)
+    return ops.frames_from_yuv(planes, size, flat, b=b, t=t, out=out)
+
+
+def _clip_slots(what, n, size, slots, t, out):
+    """The checked request of `what` (frames_from_uint8 / frames_from_planes) for n images: (size, the slots as batch * t + frame,
+    b, t), b from `out` or 1 + the largest batch index."""
     size, slots, t = tuple(int(v) for v in size), [(int(i), int(f)) for i, f in slots], int(t)
     if len(size) != 2 or min(size) <= 0 or t <= 0:
-        raise ValueError(f"frames_from_planes: size {size}, t {t}")
-    if len(slots) != len(planes) or any(i < 0 or not 0 <= f < t for i, f in slots):
-        raise ValueError(f"frames_from_planes: {len(planes)} images need as many (batch, frame) slots with frame < {t}, got {slots}")
+        raise ValueError(f"{what}: size {size}, t {t}")
+    if len(slots) != n or any(i < 0 or not 0 <= f < t for i, f in slots):
+        raise ValueError(f"{what}: {n} images need as many (batch, frame) slots with frame < {t}, got {slots}")
     b = out.shape[0] if out is not None else 1 + max(i for i, _ in slots)
     if any(i >= b for i, _ in slots):
-        raise ValueError(f"frames_from_planes: slots {slots} for a batch of {b}")
-    return ops.frames_from_yuv(planes, size, [i * t + f for i, f in slots], b=b, t=t, out=out)
+        raise ValueError(f"{what}: slots {slots} for a batch of {b}")
+    return size, [i * t + f for i, f in slots], b, t
 
 
 def frames_from_uint8(images_u8, size, slots, t, out=None):
@@ -209,15 +217,8 @@ def frames_from_uint8(images_u8, size, slots, t, out=None):
         raise ValueError(f"frames_from_uint8: expected a uint8 tensor, got {getattr(images_u8, 'dtype', type(images_u8))}")
     if images_u8.dim() != 4 or images_u8.shape[3] != 3:
         raise ValueError(f"frames_from_uint8: expected (n, h, w, 3) images, got {tuple(images_u8.shape)}")
-    size, slots, t = tuple(int(v) for v in size), [(int(i), int(f)) for i, f in slots], int(t)
-    if len(size) != 2 or min(size) <= 0 or t <= 0:
-        raise ValueError(f"frames_from_uint8: size {size}, t {t}")
-    if len(slots) != images_u8.shape[0] or any(i < 0 or not 0 <= f < t for i, f in slots):
-        raise ValueError(f"frames_from_uint8: {images_u8.shape[0]} images need as many (batch, frame) slots with frame < {t}, got {slots}")
-    b = out.shape[0] if out is not None else 1 + max(i for i, _ in slots)
-    if any(i >= b for i, _ in slots):
-        raise ValueError(f"frames_from_uint8: slots {slots} for a batch of {b}")
-    return ops.frames_from_u8(images_u8, size, [i * t + f for i, f in slots], b=b, t=t, out=out)
+    size, flat, b, t = _clip_slots("frames_from_uint8", images_u8.shape[0], size, slots, t, out)
+    return ops.frames_from_u8(images_u8, size, flat, b=b, t=t, out=out)
 
 
 @dataclass

@@ -8,11 +8,6 @@
 
 namespace {
 
-inline unsigned grid_for(int64_t n, unsigned cap = 8192) {
-  const int64_t g = (n + 255) / 256;
-  return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);
-}
-
 // Where image m = clip * nf + j (frame f0 + j of its clip) starts in a destination: the caller's `out`, or a packed staging
 // buffer (frame_stride = one image, clip_stride = nf images).
 struct Place { int nf; int64_t frame_stride, clip_stride; };
@@ -36,30 +31,9 @@ __global__ __launch_bounds__(256) void frames_value_kernel(const float* __restri
   }
 }
 
-// horizontal pass: n packed images (h, w, 3) -> n packed images (h, ow, 3)
-__global__ __launch_bounds__(256) void frames_out_hpass_kernel(const uint8_t* __restrict__ src, int h, int w, int ow,
-                                                               const int32_t* __restrict__ bounds,
-                                                               const int32_t* __restrict__ coefs, int kmax,
-                                                               uint8_t* __restrict__ mid, int64_t total) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int col = (int)(i % ow);
-    const uint8_t* line = src + (i / ow) * ((int64_t)w * 3);     // i / ow = image * h + row
-#pragma unroll
-    for (int c = 0; c < 3; ++c) mid[i * 3 + c] = (uint8_t)resample_u8(line + c, 3, w, bounds, coefs, kmax, col);
-  }
-}
-
-// One pixel of the (oh, ow) frame from a packed image of ih rows and ow columns: resampled over rows (VRES), or the image
-// is that frame already.
-template <bool VRES>
-__device__ __forceinline__ void frame_pixel(const uint8_t* __restrict__ img, int ih, int ow, const int32_t* __restrict__ bounds,
-                                            const int32_t* __restrict__ coefs, int kmax, int row, int col, int32_t* rgb) {
-  const uint8_t* base = img + (int64_t)col * 3;
-  const int64_t rowb = (int64_t)ow * 3;
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-    rgb[c] = VRES ? (int32_t)resample_u8(base + c, rowb, ih, bounds, coefs, kmax, row) : (int32_t)base[row * rowb + c];
-}
+// The horizontal pass (resample_hpass_kernel) and the pixel under (row, col) of the (oh, ow) frame (resized_pixel<VRES>:
+// resampled over the ih rows of a packed image of ow columns, or that image is the frame already) are pixel_u8.h's: the
+// front end runs them too.
 
 // vertical pass (or none) + RGB24 write, one thread per output pixel
 template <bool VRES>
@@ -73,7 +47,7 @@ __global__ __launch_bounds__(256) void frames_out_rgb_kernel(const uint8_t* __re
     const int row = (int)(r % oh);
     const int64_t m = r / oh;
     int32_t rgb[3];
-    frame_pixel<VRES>(img + m * ((int64_t)ih * ow * 3), ih, ow, bounds, coefs, kmax, row, col, rgb);
+    resized_pixel<VRES>(img + m * ((int64_t)ih * ow * 3), (int64_t)ow * 3, ih, bounds, coefs, kmax, row, col, rgb);
     uint8_t* px = out + place_of(pl, m) + (int64_t)row * pitch + (int64_t)col * 3;
 #pragma unroll
     for (int c = 0; c < 3; ++c) px[c] = (uint8_t)rgb[c];
@@ -109,7 +83,7 @@ __global__ __launch_bounds__(256) void frames_out_yuv_kernel(const uint8_t* __re
 #pragma unroll
       for (int dx = 0; dx < 2; ++dx) {
         int32_t rgb[3];
-        frame_pixel<VRES>(image, ih, ow, bounds, coefs, kmax, 2 * by + dy, 2 * bx + dx, rgb);
+        resized_pixel<VRES>(image, (int64_t)ow * 3, ih, bounds, coefs, kmax, 2 * by + dy, 2 * bx + dx, rgb);
         frame[(int64_t)(2 * by + dy) * pitch + 2 * bx + dx] = luma_601(rgb);
 #pragma unroll
         for (int c = 0; c < 3; ++c) sum[c] += rgb[c];
@@ -174,7 +148,7 @@ extern "C" int tc_frames_to_u8(const TcFramesOutParams* pp, void* stream) {
   const Place to_out = {p.nf, p.frame_stride, p.clip_stride};
   const int64_t src_total = n * p.h * p.w;
   if (!plan.staged) {                                            // packed RGB at the source size: the value pass writes `out`
-    hipLaunchKernelGGL(frames_value_kernel, dim3(grid_for(src_total)), block, 0, s, p.x, p.t, p.f0, p.h, p.w, p.out, to_out,
+    hipLaunchKernelGGL(frames_value_kernel, dim3(pixel_grid(src_total)), block, 0, s, p.x, p.t, p.f0, p.h, p.w, p.out, to_out,
                        (int64_t)p.pitch, src_total);
     TC_LAUNCH_CHECK();
     return TC_OK;
@@ -182,20 +156,20 @@ extern "C" int tc_frames_to_u8(const TcFramesOutParams* pp, void* stream) {
   uint8_t* stage = reinterpret_cast<uint8_t*>(p.workspace);
   const int64_t image = (int64_t)p.h * p.w * 3;
   const Place packed = {p.nf, image, (int64_t)p.nf * image};
-  hipLaunchKernelGGL(frames_value_kernel, dim3(grid_for(src_total)), block, 0, s, p.x, p.t, p.f0, p.h, p.w, stage, packed,
+  hipLaunchKernelGGL(frames_value_kernel, dim3(pixel_grid(src_total)), block, 0, s, p.x, p.t, p.f0, p.h, p.w, stage, packed,
                      (int64_t)p.w * 3, src_total);
   TC_LAUNCH_CHECK();
   const uint8_t* img = stage;                                    // n packed images of p.h rows and p.ow columns from here on
   if (plan.hres) {
     uint8_t* mid = stage + plan.stage_bytes;
     const int64_t mid_total = n * p.h * p.ow;
-    hipLaunchKernelGGL(frames_out_hpass_kernel, dim3(grid_for(mid_total)), block, 0, s, (const uint8_t*)stage, p.h, p.w, p.ow, p.h_bounds,
-                       p.h_coefs, p.h_kmax, mid, mid_total);
+    hipLaunchKernelGGL(resample_hpass_kernel, dim3(pixel_grid(mid_total)), block, 0, s, (const uint8_t*)stage, image, p.w * 3, p.h, p.w,
+                       p.ow, p.h_bounds, p.h_coefs, p.h_kmax, mid, mid_total);
     TC_LAUNCH_CHECK();
     img = mid;
   }
   const int64_t total = p.format == TC_PIXFMT_RGB24 ? n * p.oh * p.ow : n * (p.oh / 2) * (p.ow / 2);
-  const dim3 grid(grid_for(total));
+  const dim3 grid(pixel_grid(total));
 #define TC_FRAMES_OUT_LAUNCH(kernel) \
   hipLaunchKernelGGL(kernel, grid, block, 0, s, img, p.h, p.oh, p.ow, p.v_bounds, p.v_coefs, p.v_kmax, p.out, to_out, p.pitch, total)
   if (p.format == TC_PIXFMT_RGB24) {

@@ -10,29 +10,10 @@
 
 namespace {
 
-inline unsigned grid_for(int64_t n, unsigned cap = 8192) {
-  const int64_t g = (n + 255) / 256;
-  return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);
-}
-
 // ---------------------------------------------------------------------------------------------- tc_frames_from_u8
 
-// resample_u8, one axis of PIL's 8-bit resample at one output index, is pixel_u8.h's: the back end runs it too.
-
-// horizontal pass: n images (sh, sw, 3) with a row pitch -> the packed uint8 intermediate (n, sh, rw, 3)
-__global__ __launch_bounds__(256) void frames_hpass_kernel(const uint8_t* __restrict__ src, int64_t image_stride, int pitch,
-                                                           int sh, int sw, int rw, const int32_t* __restrict__ bounds,
-                                                           const int32_t* __restrict__ coefs, int kmax,
-                                                           uint8_t* __restrict__ mid, int64_t total) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int x = (int)(i % rw);
-    const int64_t row = i / rw;                                  // image * sh + y
-    const int64_t img = row / sh, y = row - img * sh;
-    const uint8_t* line = src + img * image_stride + y * pitch;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) mid[i * 3 + c] = (uint8_t)resample_u8(line + c, 3, sw, bounds, coefs, kmax, x);
-  }
-}
+// The grid rule, one axis of PIL's 8-bit resample, the horizontal pass and the pixel under (row, col) of the resized image are
+// pixel_u8.h's: the back end runs them too.
 
 struct FrameSlots { int32_t v[TC_FRAMES_U8_MAX]; };
 
@@ -62,13 +43,9 @@ __global__ __launch_bounds__(256) void frames_final_kernel(const uint8_t* __rest
     const int y = (int)(r % h);
     const int64_t n = r / h;
     const int ry = y + top, rx = x + left;
-    uint32_t px[3] = {0u, 0u, 0u};
-    if (ry >= 0 && ry < rh && rx >= 0 && rx < rw) {
-      const uint8_t* base = img + n * image_stride + rx * 3;
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-        px[c] = RESAMPLE ? resample_u8(base + c, pitch, ih, bounds, coefs, kmax, ry) : base[(int64_t)ry * pitch + c];
-    }
+    int32_t px[3] = {0, 0, 0};
+    if (ry >= 0 && ry < rh && rx >= 0 && rx < rw)
+      resized_pixel<RESAMPLE>(img + n * image_stride, pitch, ih, bounds, coefs, kmax, ry, rx, px);
     const int64_t frame = slots.v[n];                            // batch * t + frame index
     const int64_t bb = frame / t, ff = frame - bb * t;
 #pragma unroll
@@ -236,30 +213,30 @@ extern "C" int tc_frames_from_u8_resized(int32_t sh, int32_t sw, int32_t h, int3
   return TC_OK;
 }
 
-extern "C" int64_t tc_frames_from_u8_workspace(const TcFramesU8Params* p) {
-  int32_t rh, rw;
-  if (!p || p->n <= 0 || tc_frames_from_u8_resized(p->sh, p->sw, p->h, p->w, &rh, &rw) != TC_OK) return 0;
-  return rh != p->sh ? (int64_t)p->n * p->sh * rw * 3 : 0;            // both passes run, or neither
-}
-
 namespace {
 
 // What a request for n (sh, sw) images into a (b, 3, t, h, w) tensor runs, or TC_EINVAL: everything of TcFramesU8Params
 // that does not describe the source's memory or the workspace.  Both front ends ask it.
 struct FramesPlan { FrameSlots slots; int32_t rh, rw; bool resized; int64_t mid_bytes; };
+
+// the sizing part, which the workspace query asks on its own: it reads n and the four sizes, nothing else
+int frames_sizes(const TcFramesU8Params& p, FramesPlan* plan) {
+  if (p.n <= 0 || tc_frames_from_u8_resized(p.sh, p.sw, p.h, p.w, &plan->rh, &plan->rw) != TC_OK) return TC_EINVAL;
+  // the rule resizes both sides or neither: the shorter side changes whenever anything does, and the longer one then moves by
+  // at least a pixel (s * long / short is below long for s < short and at least long + 1 for s > short)
+  plan->resized = plan->rh != p.sh;
+  plan->mid_bytes = plan->resized ? (int64_t)p.n * p.sh * plan->rw * 3 : 0;
+  return TC_OK;
+}
+
 int frames_plan(const TcFramesU8Params& p, FramesPlan* plan) {
-  if (!p.out || !p.slots || p.n <= 0 || p.n > TC_FRAMES_U8_MAX || p.b <= 0 || p.t <= 0) return TC_EINVAL;
-  if (tc_frames_from_u8_resized(p.sh, p.sw, p.h, p.w, &plan->rh, &plan->rw) != TC_OK) return TC_EINVAL;
+  if (!p.out || !p.slots || p.n > TC_FRAMES_U8_MAX || p.b <= 0 || p.t <= 0 || frames_sizes(p, plan) != TC_OK) return TC_EINVAL;
   plan->slots = {};
   for (int i = 0; i < p.n; ++i) {
     if (p.slots[i] < 0 || (int64_t)p.slots[i] >= (int64_t)p.b * p.t) return TC_EINVAL;
     plan->slots.v[i] = p.slots[i];
   }
-  // the rule resizes both sides or neither: the shorter side changes whenever anything does, and the longer one then moves by
-  // at least a pixel (s * long / short is below long for s < short and at least long + 1 for s > short)
-  plan->resized = plan->rh != p.sh;
   if (plan->resized && (!p.h_bounds || !p.h_coefs || p.h_kmax <= 0 || !p.v_bounds || !p.v_coefs || p.v_kmax <= 0)) return TC_EINVAL;
-  plan->mid_bytes = plan->resized ? (int64_t)p.n * p.sh * plan->rw * 3 : 0;
   return TC_OK;
 }
 
@@ -268,10 +245,10 @@ int frames_launch(const TcFramesU8Params& p, const FramesPlan& plan, uint8_t* mi
   const int32_t rh = plan.rh, rw = plan.rw;
   const int32_t top = half_even(rh - p.h), left = half_even(rw - p.w);
   const int64_t total = (int64_t)p.n * p.h * p.w;
-  const dim3 grid(grid_for(total)), block(256);
+  const dim3 grid(pixel_grid(total)), block(256);
   if (plan.resized) {
     const int64_t mid_total = (int64_t)p.n * p.sh * rw;
-    hipLaunchKernelGGL(frames_hpass_kernel, dim3(grid_for(mid_total)), block, 0, s, p.src, p.image_stride, p.pitch, p.sh, p.sw, rw,
+    hipLaunchKernelGGL(resample_hpass_kernel, dim3(pixel_grid(mid_total)), block, 0, s, p.src, p.image_stride, p.pitch, p.sh, p.sw, rw,
                        p.h_bounds, p.h_coefs, p.h_kmax, mid, mid_total);
     TC_LAUNCH_CHECK();
     hipLaunchKernelGGL(frames_final_kernel<true>, grid, block, 0, s, (const uint8_t*)mid, (int64_t)p.sh * rw * 3, rw * 3, p.sh, rh,
@@ -285,6 +262,11 @@ int frames_launch(const TcFramesU8Params& p, const FramesPlan& plan, uint8_t* mi
 }
 
 }  // namespace
+
+extern "C" int64_t tc_frames_from_u8_workspace(const TcFramesU8Params* p) {
+  FramesPlan plan;
+  return p && frames_sizes(*p, &plan) == TC_OK ? plan.mid_bytes : 0;
+}
 
 extern "C" int tc_frames_from_u8(const TcFramesU8Params* pp, void* stream) {
   if (!pp) return TC_EINVAL;
@@ -419,7 +401,7 @@ extern "C" int tc_frames_from_yuv(const TcFramesYuvParams* pp, void* stream) {
   src.pitch_y = p.pitch_y; src.pitch_c = p.pitch_c; src.cstep = planar ? 1 : 2; src.wide = wide ? 1 : 0;
   const YuvMatrix m = {p.m[0], p.m[1], p.m[2], p.m[3], p.m[4], p.m[5], p.m[6]};
   const int64_t total = (int64_t)p.n * p.sh * p.sw;
-  hipLaunchKernelGGL(yuv_to_rgb_kernel, dim3(grid_for(total)), dim3(256), 0, s, src, p.sh, p.sw, p.siting, m, rgb, total);
+  hipLaunchKernelGGL(yuv_to_rgb_kernel, dim3(pixel_grid(total)), dim3(256), 0, s, src, p.sh, p.sw, p.siting, m, rgb, total);
   TC_LAUNCH_CHECK();
   u.src = rgb;
   return frames_launch(u, plan, rgb + rgb_bytes, s);
@@ -448,16 +430,16 @@ extern "C" int tc_clip_patches(const TcClipPatchesParams* pp, void* stream) {
     const int64_t total = (int64_t)p.b * 3 * p.h * p.w;
     BlurTaps taps;
     blur_taps(plan.rx, &taps);
-    hipLaunchKernelGGL((blur_kernel<true, float>), dim3(grid_for(total)), dim3(256), 0, s, p.x, rows, p.h, p.w, plan.rx.ks, taps, total);
+    hipLaunchKernelGGL((blur_kernel<true, float>), dim3(pixel_grid(total)), dim3(256), 0, s, p.x, rows, p.h, p.w, plan.rx.ks, taps, total);
     TC_LAUNCH_CHECK();
     blur_taps(plan.ry, &taps);
-    hipLaunchKernelGGL((blur_kernel<false, double>), dim3(grid_for(total)), dim3(256), 0, s, (const double*)rows, cols, p.h, p.w,
+    hipLaunchKernelGGL((blur_kernel<false, double>), dim3(pixel_grid(total)), dim3(256), 0, s, (const double*)rows, cols, p.h, p.w,
                        plan.ry.ks, taps, total);
     TC_LAUNCH_CHECK();
-    hipLaunchKernelGGL(clip_rows_kernel<double>, dim3(grid_for(rows_total)), dim3(256), 0, s, (const double*)cols, out, p.h, p.w, p.size,
+    hipLaunchKernelGGL(clip_rows_kernel<double>, dim3(pixel_grid(rows_total)), dim3(256), 0, s, (const double*)cols, out, p.h, p.w, p.size,
                        p.patch, p.ld, p.mean[0], p.mean[1], p.mean[2], p.std[0], p.std[1], p.std[2], rows_total);
   } else {
-    hipLaunchKernelGGL(clip_rows_kernel<float>, dim3(grid_for(rows_total)), dim3(256), 0, s, p.x, out, p.h, p.w, p.size, p.patch, p.ld,
+    hipLaunchKernelGGL(clip_rows_kernel<float>, dim3(pixel_grid(rows_total)), dim3(256), 0, s, p.x, out, p.h, p.w, p.size, p.patch, p.ld,
                        p.mean[0], p.mean[1], p.mean[2], p.std[0], p.std[1], p.std[2], rows_total);
   }
   TC_LAUNCH_CHECK();

@@ -1,52 +1,10 @@
 // tc_resize_tables / tc_resize_tables_filter: the coefficient tables of PIL's 8-bit resample for one axis, host code in
 // double precision (Pillow src/libImaging/Resample.c: precompute_coeffs, normalize_coeffs_8bpc).  The device side
-// (csrc/pixel_front.hip, csrc/pixel_back.hip) only multiplies and adds these integers.  See include/tooncrafter_hip.h
-// for the rule.
+// (csrc/pixel_u8.h, run by csrc/pixel_front.hip and csrc/pixel_back.hip) only multiplies and adds these integers.  See
+// include/tooncrafter_hip.h for the rule.
 #include <math.h>
 
 #include "tooncrafter_hip.h"
-
-extern "C" int32_t tc_resize_tables(int32_t in_size, int32_t out_size, int32_t* bounds, int32_t* coefs, int64_t coefs_len) {
-  if (in_size <= 0 || out_size <= 0 || (bounds == nullptr) != (coefs == nullptr)) return TC_EINVAL;
-  const double scale = (double)in_size / (double)out_size;
-  const double fs = scale < 1.0 ? 1.0 : scale;                  // bilinear: support 1, stretched when downscaling
-  const double support = fs;
-  const double kd = ceil(support) * 2.0 + 1.0;
-  if (kd > 1e9) return TC_EINVAL;
-  const int32_t kmax = (int32_t)kd;
-  if (!bounds) return kmax;                                     // sizing query
-  if (coefs_len < (int64_t)out_size * kmax) return TC_EWORKSPACE;
-  for (int32_t xx = 0; xx < out_size; ++xx) {
-    const double center = (xx + 0.5) * scale;
-    int32_t xmin = (int32_t)(center - support + 0.5);
-    if (xmin < 0) xmin = 0;
-    int32_t xmax = (int32_t)(center + support + 0.5);
-    if (xmax > in_size) xmax = in_size;
-    const int32_t cnt = xmax - xmin;
-    int32_t* k = coefs + (int64_t)xx * kmax;
-    // the weights are summed in tap order, as PIL does (Pillow multiplies by 1 / fs where this divides; the integer tables
-    // of the two forms are equal for every size pair 1 .. 128 and the frame sizes of tests/test_pixel_front_cpu.py)
-    double ww = 0.0;
-    for (int32_t x = 0; x < cnt; ++x) {
-      double a = (x + xmin - center + 0.5) / fs;
-      if (a < 0.0) a = -a;
-      ww += a < 1.0 ? 1.0 - a : 0.0;
-    }
-    for (int32_t x = 0; x < kmax; ++x) {
-      double w = 0.0;
-      if (x < cnt) {
-        double a = (x + xmin - center + 0.5) / fs;
-        if (a < 0.0) a = -a;
-        w = a < 1.0 ? 1.0 - a : 0.0;
-        if (ww != 0.0) w /= ww;
-      }
-      k[x] = (int32_t)(w * (double)(1 << 22) + 0.5);           // bilinear weights are never negative
-    }
-    bounds[2 * xx] = xmin;
-    bounds[2 * xx + 1] = cnt;
-  }
-  return kmax;
-}
 
 namespace {
 
@@ -70,20 +28,14 @@ double sinc(double x) {
 double filter_lanczos(double x) { return -3.0 <= x && x < 3.0 ? sinc(x) * sinc(x / 3) : 0.0; }
 double filter_box(double x) { return x > -0.5 && x <= 0.5 ? 1.0 : 0.0; }
 
-}  // namespace
-
-extern "C" int32_t tc_resize_tables_filter(int32_t filter, int32_t in_size, int32_t out_size, int32_t* bounds, int32_t* coefs,
-                                           int64_t coefs_len) {
+// The tables of one axis in_size -> out_size for the filter F of support S, or kmax alone when bounds is NULL.  The tap
+// argument is multiplied by 1 / fs, as Pillow does.  Dividing by fs instead, as the numpy statement of
+// tests/test_pixel_front_cpu.py does, gives the bilinear filter the same bounds, kmax and integer coefficients for every
+// pair in, out in 1 .. 768 and for in in 1 .. 4320 with out in {224, 256, 320, 384, 512, 576, 640, 720, 1024, 1080} (checked
+// on the host), so the one form serves both entry points.
+int32_t resize_tables(double (*F)(double), double S, int32_t in_size, int32_t out_size, int32_t* bounds, int32_t* coefs,
+                      int64_t coefs_len) {
   if (in_size <= 0 || out_size <= 0 || (bounds == nullptr) != (coefs == nullptr)) return TC_EINVAL;
-  double (*F)(double);
-  double S;
-  switch (filter) {
-    case TC_RESIZE_BILINEAR: F = filter_bilinear; S = 1.0; break;
-    case TC_RESIZE_BICUBIC: F = filter_bicubic; S = 2.0; break;
-    case TC_RESIZE_LANCZOS: F = filter_lanczos; S = 3.0; break;
-    case TC_RESIZE_BOX: F = filter_box; S = 0.5; break;
-    default: return TC_EINVAL;
-  }
   const double scale = (double)in_size / (double)out_size;
   const double fs = scale < 1.0 ? 1.0 : scale;                  // the filter is stretched when downscaling
   const double support = S * fs;
@@ -92,7 +44,7 @@ extern "C" int32_t tc_resize_tables_filter(int32_t filter, int32_t in_size, int3
   const int32_t kmax = (int32_t)kd;
   if (!bounds) return kmax;                                     // sizing query
   if (coefs_len < (int64_t)out_size * kmax) return TC_EWORKSPACE;
-  const double ss = 1.0 / fs;                                   // Pillow multiplies by the reciprocal
+  const double ss = 1.0 / fs;
   for (int32_t xx = 0; xx < out_size; ++xx) {
     const double center = (xx + 0.5) * scale;
     int32_t xmin = (int32_t)(center - support + 0.5);
@@ -116,4 +68,21 @@ extern "C" int32_t tc_resize_tables_filter(int32_t filter, int32_t in_size, int3
     bounds[2 * xx + 1] = cnt;
   }
   return kmax;
+}
+
+}  // namespace
+
+extern "C" int32_t tc_resize_tables(int32_t in_size, int32_t out_size, int32_t* bounds, int32_t* coefs, int64_t coefs_len) {
+  return resize_tables(filter_bilinear, 1.0, in_size, out_size, bounds, coefs, coefs_len);
+}
+
+extern "C" int32_t tc_resize_tables_filter(int32_t filter, int32_t in_size, int32_t out_size, int32_t* bounds, int32_t* coefs,
+                                           int64_t coefs_len) {
+  switch (filter) {
+    case TC_RESIZE_BILINEAR: return resize_tables(filter_bilinear, 1.0, in_size, out_size, bounds, coefs, coefs_len);
+    case TC_RESIZE_BICUBIC: return resize_tables(filter_bicubic, 2.0, in_size, out_size, bounds, coefs, coefs_len);
+    case TC_RESIZE_LANCZOS: return resize_tables(filter_lanczos, 3.0, in_size, out_size, bounds, coefs, coefs_len);
+    case TC_RESIZE_BOX: return resize_tables(filter_box, 0.5, in_size, out_size, bounds, coefs, coefs_len);
+    default: return TC_EINVAL;
+  }
 }

@@ -35,6 +35,11 @@ void check_rc(int rc, const char* what) {
 
 const tc_bf16* bf(const Tensor& t) { return reinterpret_cast<const tc_bf16*>(t.data_ptr()); }
 
+// stream-ordered scratch of nbytes on the device of `like`: never empty, so that its pointer is one
+Tensor workspace(int64_t nbytes, const Tensor& like) {
+  return at::empty({nbytes > 16 ? nbytes : 16}, like.options().dtype(at::kByte));
+}
+
 void check_rows(const Tensor& t, const char* name, at::ScalarType dt = at::kBFloat16) {
   TORCH_CHECK(t.is_cuda(), name, ": expected a CUDA tensor (the product path is GPU-only)");
   TORCH_CHECK(t.dim() == 2 && t.stride(1) == 1 && t.scalar_type() == dt, name,
@@ -211,7 +216,7 @@ Tensor attention_q8_cuda(const Tensor& q, const Tensor& k, const Tensor& v, int6
   p.q_sb = lq * q.stride(0); p.k_sb = lk * k.stride(0); p.v_sb = lk * v.stride(0); p.o_sb = lq * out.stride(0);
   p.scale = (float)scale;
   const int64_t nbytes = tc_attn_q8_workspace(&p);
-  Tensor ws = at::empty({nbytes > 16 ? nbytes : 16}, q.options().dtype(at::kByte));
+  Tensor ws = workspace(nbytes, q);
   p.workspace = ws.data_ptr(); p.workspace_bytes = ws.numel();
   check_rc(tc_attn_q8_quant_kv(&p, cur_stream()), "tc_attn_q8_quant_kv");
   check_rc(tc_attn_d64_q8(&p, cur_stream()), "tc_attn_d64_q8");
@@ -294,7 +299,7 @@ Tensor groupnorm_pf_cuda(const Tensor& x, const Tensor& gamma, const Tensor& bet
   const TcPrefetch pf = prefetch_of(prefetch, "groupnorm_pf");
   Tensor y = at::empty_like(x);
   const int64_t nbytes = tc_groupnorm_workspace((int32_t)samples, (int32_t)rows, (int32_t)c);
-  Tensor ws = at::empty({nbytes > 16 ? nbytes : 16}, x.options().dtype(at::kByte));
+  Tensor ws = workspace(nbytes, x);
   check_rc(tc_groupnorm_pf(bf(x), reinterpret_cast<tc_bf16*>(y.data_ptr()), gamma.data_ptr<float>(), beta.data_ptr<float>(),
                            (int32_t)samples, (int32_t)rows, (int32_t)c, (float)eps, silu ? 1 : 0, ws.data_ptr(), nbytes, &pf, cur_stream()),
            "tc_groupnorm_pf");
@@ -449,7 +454,7 @@ std::tuple<Tensor, Tensor> ddim_step_ms_any(const Tensor& x, const Tensor& e_con
   mp.x0_hist = x0_hist.has_value() ? x0_hist->data_ptr<float>() : nullptr;
   mp.corr = (float)corr;
   const int64_t nbytes = tc_ddim_workspace(mp.base.b);
-  Tensor ws = at::empty({nbytes > 16 ? nbytes : 16}, x.options().dtype(at::kByte));
+  Tensor ws = workspace(nbytes, x);
   if (EPS)
     check_rc(tc_ddim_step_ms_eps(&mp, ws.data_ptr(), nbytes, cur_stream()), "tc_ddim_step_ms_eps");
   else
@@ -491,13 +496,49 @@ Tensor ddim_blend_meta(const optional<Tensor>&, const Tensor& x0, const optional
   return at::empty_like(x0);
 }
 
-// Pixel front end (additive within ABI 14).  frames_from_u8: uint8 (n, sh, sw, 3) images -> a new (b, 3, t, h, w) fp32 clip tensor,
-// image i in frame slots[i] = batch * t + frame, zero elsewhere (reference scripts/evaluation/inference.py:64-69 on the device);
-// the tables are tc_resize_tables' for sw -> rw and sh -> rh, on the device (None when nothing is resized).
-const int32_t* i32_table(const optional<Tensor>& t, const char* what) {
-  if (!t.has_value()) return nullptr;
-  TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt && t->is_contiguous() && t->dim() == 2, what, ": contiguous int32 CUDA [out, k]");
-  return t->data_ptr<int32_t>();
+// Pixel path (additive within ABI 14).  One axis of a resample request: the tables of n_in -> n_out (tc_resize_tables /
+// tc_resize_tables_filter), on the device, as the C ABI takes them.  n_in == n_out: the pass does not run, its tables are not looked at.
+struct ResizeAxis { const int32_t* bounds = nullptr; const int32_t* coefs = nullptr; int32_t kmax = 0; };
+ResizeAxis resize_axis(const optional<Tensor>& bounds, const optional<Tensor>& coefs, int64_t n_in, int64_t n_out, const char* name,
+                       const char* axis) {
+  ResizeAxis a;
+  if (n_in == n_out) return a;
+  for (const auto* t : {&bounds, &coefs})
+    TORCH_CHECK(!t->has_value() || ((*t)->is_cuda() && (*t)->scalar_type() == at::kInt && (*t)->is_contiguous() && (*t)->dim() == 2),
+                name, ": ", axis, " tables: contiguous int32 CUDA [out, k]");
+  // the tables must be the ones of this size: their rows are indexed by the output index
+  TORCH_CHECK(bounds.has_value() && coefs.has_value() && bounds->size(0) == n_out && bounds->size(1) == 2 && coefs->size(0) == n_out &&
+              coefs->size(1) >= 1, name, ": ", axis, " tables of ", n_in, " -> ", n_out, " expected");
+  a.bounds = bounds->data_ptr<int32_t>(); a.coefs = coefs->data_ptr<int32_t>(); a.kmax = (int32_t)coefs->size(1);
+  return a;
+}
+
+// What the two front ends ask besides their source: n images of (sh, sw), image i into frame slots[i] = batch * t + frame of a new
+// (b, 3, t, h, w) fp32 clip tensor on the device of `src`, zero elsewhere (reference scripts/evaluation/inference.py:64-69 on the
+// device); the tables are tc_resize_tables' for sw -> rw and sh -> rh (None when nothing is resized).  Fills those fields of p, which
+// points at the caller's `slot`, and returns the clip tensor.
+template <typename Params>
+Tensor front_request(Params& p, int32_t (&slot)[TC_FRAMES_U8_MAX], const char* name, const Tensor& src, int64_t n, int64_t sh, int64_t sw,
+                     at::IntArrayRef slots, int64_t b, int64_t t, int64_t h, int64_t w, const optional<Tensor>& h_bounds,
+                     const optional<Tensor>& h_coefs, const optional<Tensor>& v_bounds, const optional<Tensor>& v_coefs) {
+  TORCH_CHECK(n >= 1 && n <= TC_FRAMES_U8_MAX && (int64_t)slots.size() == n, name, ": 1 .. ", TC_FRAMES_U8_MAX, " images, one slot each");
+  TORCH_CHECK(b > 0 && t > 0 && h > 0 && w > 0, name, ": b, t, h, w must be positive");
+  Tensor out = at::zeros({b, 3, t, h, w}, src.options().dtype(at::kFloat));
+  for (int64_t i = 0; i < n; ++i) {
+    TORCH_CHECK(slots[i] >= 0 && slots[i] < b * t, name, ": slot ", slots[i], " outside the clip tensor");
+    slot[i] = (int32_t)slots[i];
+  }
+  p.n = (int32_t)n; p.sh = (int32_t)sh; p.sw = (int32_t)sw;
+  p.slots = slot;
+  p.out = out.data_ptr<float>();
+  p.b = (int32_t)b; p.t = (int32_t)t; p.h = (int32_t)h; p.w = (int32_t)w;
+  int32_t rh = 0, rw = 0;
+  check_rc(tc_frames_from_u8_resized(p.sh, p.sw, p.h, p.w, &rh, &rw), "tc_frames_from_u8_resized");
+  const ResizeAxis ah = resize_axis(h_bounds, h_coefs, sw, rw, name, "horizontal");
+  const ResizeAxis av = resize_axis(v_bounds, v_coefs, sh, rh, name, "vertical");
+  p.h_bounds = ah.bounds; p.h_coefs = ah.coefs; p.h_kmax = ah.kmax;
+  p.v_bounds = av.bounds; p.v_coefs = av.coefs; p.v_kmax = av.kmax;
+  return out;
 }
 
 Tensor frames_from_u8_cuda(const Tensor& images, at::IntArrayRef slots, int64_t b, int64_t t, int64_t h, int64_t w,
@@ -506,35 +547,15 @@ Tensor frames_from_u8_cuda(const Tensor& images, at::IntArrayRef slots, int64_t 
   TORCH_CHECK(images.is_cuda(), "frames_from_u8: expected a CUDA tensor (the product path is GPU-only)");
   TORCH_CHECK(images.scalar_type() == at::kByte && images.dim() == 4 && images.size(3) == 3 && images.stride(3) == 1 &&
               images.stride(2) == 3, "frames_from_u8: uint8 (n, h, w, 3) images with packed pixels");
-  const int64_t n = images.size(0);
-  TORCH_CHECK(n >= 1 && n <= TC_FRAMES_U8_MAX && (int64_t)slots.size() == n, "frames_from_u8: 1 .. ", TC_FRAMES_U8_MAX, " images, one slot each");
-  TORCH_CHECK(b > 0 && t > 0 && h > 0 && w > 0, "frames_from_u8: b, t, h, w must be positive");
-  Tensor out = at::zeros({b, 3, t, h, w}, images.options().dtype(at::kFloat));
-  int32_t slot[TC_FRAMES_U8_MAX];
-  for (int64_t i = 0; i < n; ++i) {
-    TORCH_CHECK(slots[i] >= 0 && slots[i] < b * t, "frames_from_u8: slot ", slots[i], " outside the clip tensor");
-    slot[i] = (int32_t)slots[i];
-  }
   TcFramesU8Params p = {};
+  int32_t slot[TC_FRAMES_U8_MAX];
+  Tensor out = front_request(p, slot, "frames_from_u8", images, images.size(0), images.size(1), images.size(2), slots, b, t, h, w,
+                             h_bounds, h_coefs, v_bounds, v_coefs);
   p.src = images.data_ptr<uint8_t>();
   p.pitch = (int32_t)images.stride(1);
-  p.n = (int32_t)n; p.sh = (int32_t)images.size(1); p.sw = (int32_t)images.size(2);
-  p.image_stride = n > 1 ? images.stride(0) : (int64_t)p.sh * p.pitch;
-  p.slots = slot;
-  p.out = out.data_ptr<float>();
-  p.b = (int32_t)b; p.t = (int32_t)t; p.h = (int32_t)h; p.w = (int32_t)w;
-  p.h_bounds = i32_table(h_bounds, "frames_from_u8: h_bounds"); p.h_coefs = i32_table(h_coefs, "frames_from_u8: h_coefs");
-  p.v_bounds = i32_table(v_bounds, "frames_from_u8: v_bounds"); p.v_coefs = i32_table(v_coefs, "frames_from_u8: v_coefs");
-  int32_t rh = 0, rw = 0;
-  check_rc(tc_frames_from_u8_resized(p.sh, p.sw, p.h, p.w, &rh, &rw), "tc_frames_from_u8_resized");
-  if (rh != p.sh) {                                       // the tables must be the ones of these sizes: their rows are indexed by rw / rh
-    TORCH_CHECK(p.h_bounds && p.h_coefs && p.v_bounds && p.v_coefs && h_bounds->size(0) == rw && h_coefs->size(0) == rw &&
-                v_bounds->size(0) == rh && v_coefs->size(0) == rh && h_bounds->size(1) == 2 && v_bounds->size(1) == 2,
-                "frames_from_u8: tables of ", p.sw, " -> ", rw, " and ", p.sh, " -> ", rh, " expected");
-    p.h_kmax = (int32_t)h_coefs->size(1); p.v_kmax = (int32_t)v_coefs->size(1);
-  }
+  p.image_stride = p.n > 1 ? images.stride(0) : (int64_t)p.sh * p.pitch;
   p.workspace_bytes = tc_frames_from_u8_workspace(&p);
-  Tensor ws = at::empty({p.workspace_bytes > 16 ? p.workspace_bytes : 16}, images.options());
+  Tensor ws = workspace(p.workspace_bytes, images);
   p.workspace = ws.data_ptr();
   check_rc(tc_frames_from_u8(&p, cur_stream()), "tc_frames_from_u8");
   return out;
@@ -575,39 +596,19 @@ Tensor frames_from_yuv_cuda(const Tensor& y, const Tensor& c0, const optional<Te
   } else {
     TORCH_CHECK(c0.sizes() == at::IntArrayRef({n, ch, cw, 2}), "frames_from_yuv: an interleaved chroma plane (n, (h + 1) / 2, (w + 1) / 2, 2)");
   }
-  TORCH_CHECK(n >= 1 && n <= TC_FRAMES_U8_MAX && (int64_t)slots.size() == n, "frames_from_yuv: 1 .. ", TC_FRAMES_U8_MAX, " images, one slot each");
-  TORCH_CHECK(b > 0 && t > 0 && h > 0 && w > 0, "frames_from_yuv: b, t, h, w must be positive");
   TORCH_CHECK(m.size() == 7, "frames_from_yuv: the matrix has seven entries");
   TORCH_CHECK(siting == TC_CHROMA_NEAREST || siting == TC_CHROMA_CENTER || siting == TC_CHROMA_LEFT, "frames_from_yuv: siting ", siting);
-  Tensor out = at::zeros({b, 3, t, h, w}, y.options().dtype(at::kFloat));
-  int32_t slot[TC_FRAMES_U8_MAX];
-  for (int64_t i = 0; i < n; ++i) {
-    TORCH_CHECK(slots[i] >= 0 && slots[i] < b * t, "frames_from_yuv: slot ", slots[i], " outside the clip tensor");
-    slot[i] = (int32_t)slots[i];
-  }
   TcFramesYuvParams p = {};
+  int32_t slot[TC_FRAMES_U8_MAX];
+  Tensor out = front_request(p, slot, "frames_from_yuv", y, n, sh, sw, slots, b, t, h, w, h_bounds, h_coefs, v_bounds, v_coefs);
   p.y = y.data_ptr(); p.c0 = c0.data_ptr(); p.c1 = planar ? c1->data_ptr() : nullptr;
   const auto ry = plane_rows(y, sw, "frames_from_yuv: y"), rc = plane_rows(c0, planar ? cw : 2 * cw, "frames_from_yuv: chroma");
   p.pitch_y = (int32_t)ry.first; p.image_stride_y = ry.second;
   p.pitch_c = (int32_t)rc.first; p.image_stride_c = rc.second;
   p.format = (int32_t)format; p.siting = (int32_t)siting;
   for (int i = 0; i < 7; ++i) p.m[i] = (int32_t)m[i];
-  p.n = (int32_t)n; p.sh = (int32_t)sh; p.sw = (int32_t)sw;
-  p.slots = slot;
-  p.out = out.data_ptr<float>();
-  p.b = (int32_t)b; p.t = (int32_t)t; p.h = (int32_t)h; p.w = (int32_t)w;
-  p.h_bounds = i32_table(h_bounds, "frames_from_yuv: h_bounds"); p.h_coefs = i32_table(h_coefs, "frames_from_yuv: h_coefs");
-  p.v_bounds = i32_table(v_bounds, "frames_from_yuv: v_bounds"); p.v_coefs = i32_table(v_coefs, "frames_from_yuv: v_coefs");
-  int32_t rh = 0, rw = 0;
-  check_rc(tc_frames_from_u8_resized(p.sh, p.sw, p.h, p.w, &rh, &rw), "tc_frames_from_u8_resized");
-  if (rh != p.sh) {                                       // the tables must be the ones of these sizes: their rows are indexed by rw / rh
-    TORCH_CHECK(p.h_bounds && p.h_coefs && p.v_bounds && p.v_coefs && h_bounds->size(0) == rw && h_coefs->size(0) == rw &&
-                v_bounds->size(0) == rh && v_coefs->size(0) == rh && h_bounds->size(1) == 2 && v_bounds->size(1) == 2,
-                "frames_from_yuv: tables of ", p.sw, " -> ", rw, " and ", p.sh, " -> ", rh, " expected");
-    p.h_kmax = (int32_t)h_coefs->size(1); p.v_kmax = (int32_t)v_coefs->size(1);
-  }
   p.workspace_bytes = tc_frames_from_yuv_workspace(&p);
-  Tensor ws = at::empty({p.workspace_bytes > 16 ? p.workspace_bytes : 16}, y.options().dtype(at::kByte));
+  Tensor ws = workspace(p.workspace_bytes, y);
   p.workspace = ws.data_ptr();
   check_rc(tc_frames_from_yuv(&p, cur_stream()), "tc_frames_from_yuv");
   return out;
@@ -645,19 +646,12 @@ Tensor frames_to_u8_cuda(const Tensor& x, int64_t oh, int64_t ow, int64_t format
   p.f0 = (int32_t)f0; p.nf = (int32_t)nf; p.oh = (int32_t)oh; p.ow = (int32_t)ow; p.format = (int32_t)format;
   p.pitch = (int32_t)(format == TC_PIXFMT_RGB24 ? 3 * ow : ow);
   p.frame_stride = out.stride(1); p.clip_stride = out.stride(0);
-  auto table = [](const optional<Tensor>& bounds, const optional<Tensor>& coefs, int64_t n_in, int64_t n_out, const int32_t** pb,
-                  const int32_t** pc, int32_t* kmax) {
-    if (n_in == n_out) return;                              // the pass does not run: its tables are not looked at
-    *pb = i32_table(bounds, "frames_to_u8: bounds"); *pc = i32_table(coefs, "frames_to_u8: coefs");
-    // the tables must be the ones of this size: their rows are indexed by the output index
-    TORCH_CHECK(*pb && *pc && bounds->size(0) == n_out && bounds->size(1) == 2 && coefs->size(0) == n_out && coefs->size(1) >= 1,
-                "frames_to_u8: tables of ", n_in, " -> ", n_out, " expected");
-    *kmax = (int32_t)coefs->size(1);
-  };
-  table(h_bounds, h_coefs, p.w, p.ow, &p.h_bounds, &p.h_coefs, &p.h_kmax);
-  table(v_bounds, v_coefs, p.h, p.oh, &p.v_bounds, &p.v_coefs, &p.v_kmax);
+  const ResizeAxis ah = resize_axis(h_bounds, h_coefs, p.w, p.ow, "frames_to_u8", "horizontal");
+  const ResizeAxis av = resize_axis(v_bounds, v_coefs, p.h, p.oh, "frames_to_u8", "vertical");
+  p.h_bounds = ah.bounds; p.h_coefs = ah.coefs; p.h_kmax = ah.kmax;
+  p.v_bounds = av.bounds; p.v_coefs = av.coefs; p.v_kmax = av.kmax;
   p.workspace_bytes = tc_frames_to_u8_workspace(&p);
-  Tensor ws = at::empty({p.workspace_bytes > 16 ? p.workspace_bytes : 16}, out.options());
+  Tensor ws = workspace(p.workspace_bytes, out);
   p.workspace = ws.data_ptr();
   check_rc(tc_frames_to_u8(&p, cur_stream()), "tc_frames_to_u8");
   return out;
@@ -684,7 +678,7 @@ Tensor clip_patches_cuda(const Tensor& x, int64_t size, int64_t patch, int64_t l
   p.size = (int32_t)size; p.patch = (int32_t)patch; p.ld = (int32_t)ld; p.antialias = antialias ? 1 : 0;
   for (int i = 0; i < 3; ++i) { p.mean[i] = (float)mean[i]; p.std[i] = (float)std[i]; }
   p.workspace_bytes = tc_clip_patches_workspace(&p);
-  Tensor ws = at::empty({p.workspace_bytes > 16 ? p.workspace_bytes : 16}, x.options().dtype(at::kByte));
+  Tensor ws = workspace(p.workspace_bytes, x);
   p.workspace = ws.data_ptr();
   check_rc(tc_clip_patches(&p, cur_stream()), "tc_clip_patches");
   return out;

@@ -828,20 +828,81 @@ class HipOps:
         return rh.value, rw.value
 
     def resize_tables(self, n_in, n_out, device):
-        """PIL's 8-bit BILINEAR tables of one axis on `device`: (bounds [n_out, 2], coefs [n_out, kmax]) int32, built on the host
-        by tc_resize_tables and kept per (n_in, n_out, device)."""
-        key = (int(n_in), int(n_out), torch.device(device))
+        """PIL's 8-bit BILINEAR tables of one axis on `device`: resize_tables_filter's bilinear case, as tc_resize_tables is
+        tc_resize_tables_filter's."""
+        return self.resize_tables_filter("bilinear", n_in, n_out, device)
+
+    def resize_tables_filter(self, filter, n_in, n_out, device):
+        """PIL's 8-bit tables of one axis for `filter` ("bilinear", "bicubic", "lanczos", "box") on `device`: (bounds [n_out, 2],
+        coefs [n_out, kmax]) int32, built on the host by tc_resize_tables_filter and kept per (filter, n_in, n_out, device)."""
+        key = (str(filter), int(n_in), int(n_out), torch.device(device))
         tabs = self._resize_tables.get(key)
         if tabs is None:
-            kmax = self.lib.tc_resize_tables(key[0], key[1], None, None, 0)
-            _lib.check(min(kmax, 0), "tc_resize_tables")
-            bounds = torch.empty((key[1], 2), dtype=torch.int32)
-            coefs = torch.empty((key[1], kmax), dtype=torch.int32)
+            if key[0] not in _lib.TC_RESIZE_FILTERS:
+                raise ValueError(f"resize filter {filter!r}: one of {sorted(_lib.TC_RESIZE_FILTERS)}")
+            code = _lib.TC_RESIZE_FILTERS[key[0]]
+            kmax = self.lib.tc_resize_tables_filter(code, key[1], key[2], None, None, 0)
+            _lib.check(min(kmax, 0), "tc_resize_tables_filter")
+            bounds = torch.empty((key[2], 2), dtype=torch.int32)
+            coefs = torch.empty((key[2], kmax), dtype=torch.int32)
             i32p = C.POINTER(C.c_int32)
-            rc = self.lib.tc_resize_tables(key[0], key[1], C.cast(bounds.data_ptr(), i32p), C.cast(coefs.data_ptr(), i32p), coefs.numel())
-            _lib.check(min(rc, 0), "tc_resize_tables")
-            tabs = self._resize_tables[key] = (bounds.to(key[2]), coefs.to(key[2]))
+            rc = self.lib.tc_resize_tables_filter(code, key[1], key[2], C.cast(bounds.data_ptr(), i32p), C.cast(coefs.data_ptr(), i32p),
+                                                  coefs.numel())
+            _lib.check(min(rc, 0), "tc_resize_tables_filter")
+            tabs = self._resize_tables[key] = (bounds.to(key[3]), coefs.to(key[3]))
         return tabs
+
+    def _axis_tables(self, filter, n_in, n_out, device):
+        """(bounds, coefs) of one axis of a request, (None, None) where it keeps its size: that pass does not run."""
+        return self.resize_tables_filter(filter, n_in, n_out, device) if n_out != n_in else (None, None)
+
+    def _front_tables(self, sh, sw, h, w, device):
+        """(h_bounds, h_coefs, v_bounds, v_coefs) of a front-end request for (sh, sw) images into (h, w) frames: both axes are
+        resized or neither (tc_frames_from_u8_resized), then all four are None."""
+        rh, rw = self.resized_size(sh, sw, h, w)
+        return self._axis_tables("bilinear", sw, rw, device) + self._axis_tables("bilinear", sh, rh, device)
+
+    @staticmethod
+    def _set_tables(p, tabs):
+        """A pair of axes (h_bounds, h_coefs, v_bounds, v_coefs, None for an axis that keeps its size) into any of the pixel
+        path's params structs."""
+        for axis, bounds, coefs in (("h", *tabs[:2]), ("v", *tabs[2:])):
+            if bounds is not None:
+                setattr(p, axis + "_bounds", bounds.data_ptr())
+                setattr(p, axis + "_coefs", coefs.data_ptr())
+                setattr(p, axis + "_kmax", coefs.shape[1])
+
+    def _launch(self, entry, p, device):
+        """The tail of an entry point whose params carry their workspace: query it, allocate, set, call, check."""
+        p.workspace_bytes = getattr(self.lib, entry + "_workspace")(C.byref(p))
+        ws = self._workspace(p.workspace_bytes, device)
+        p.workspace = ws.data_ptr()
+        _lib.check(getattr(self.lib, entry)(C.byref(p), _stream()), entry)
+
+    def _front_launch(self, entry, p, slots, tabs, device, sources):
+        """A front-end request, at most TC_FRAMES_U8_MAX images to a call: sources(i) gives the fields of `p` that point at
+        image i, the first of a call's."""
+        self._set_tables(p, tabs)
+        for i in range(0, len(slots), _lib.TC_FRAMES_U8_MAX):
+            part = slots[i:i + _lib.TC_FRAMES_U8_MAX]
+            held = (C.c_int32 * len(part))(*part)
+            p.n, p.slots = len(part), held
+            for field, pointer in sources(i).items():
+                setattr(p, field, pointer)
+            self._launch(entry, p, device)
+
+    @staticmethod
+    def _front_args(what, n, size, slots, b, t, out):
+        """The checked (h, w) and slots of a front-end request for n images; `out`, where given, is the clip tensor they name."""
+        h, w = (int(v) for v in size)
+        slots = [int(s) for s in slots]
+        if len(slots) != n or any(s < 0 or s >= b * t for s in slots):
+            raise ValueError(f"{what}: {n} images need {n} slots in [0, {b * t}), got {slots}")
+        if out is not None:
+            _dev(out, torch.float32, f"{what}: out")
+            if tuple(out.shape) != (b, 3, t, h, w):
+                raise ValueError(f"{what}: out must be ({b}, 3, {t}, {h}, {w}), got {tuple(out.shape)}")
+        return (h, w), slots
 
     @staticmethod
     def _check_u8_images(images, what):
@@ -863,32 +924,13 @@ class HipOps:
         keep their contents; default: a new tensor, zero there."""
         self._check_u8_images(images, "frames_from_u8: images")
         n, sh, sw, _ = images.shape
-        h, w = (int(v) for v in size)
-        slots = [int(s) for s in slots]
-        if len(slots) != n or any(s < 0 or s >= b * t for s in slots):
-            raise ValueError(f"frames_from_u8: {n} images need {n} slots in [0, {b * t}), got {slots}")
+        (h, w), slots = self._front_args("frames_from_u8", n, size, slots, b, t, out)
         if out is None:
             out = torch.zeros((b, 3, t, h, w), dtype=torch.float32, device=images.device)
-        else:
-            _dev(out, torch.float32, "frames_from_u8: out")
-            if tuple(out.shape) != (b, 3, t, h, w):
-                raise ValueError(f"frames_from_u8: out must be ({b}, 3, {t}, {h}, {w}), got {tuple(out.shape)}")
-        rh, rw = self.resized_size(sh, sw, h, w)
         p = _lib.TcFramesU8Params(pitch=images.stride(1), image_stride=images.stride(0) if n > 1 else sh * images.stride(1),
                                   sh=sh, sw=sw, out=out.data_ptr(), b=b, t=t, h=h, w=w)
-        if (rh, rw) != (sh, sw):
-            hb, hc = self.resize_tables(sw, rw, images.device)
-            vb, vc = self.resize_tables(sh, rh, images.device)
-            p.h_bounds, p.h_coefs, p.h_kmax = hb.data_ptr(), hc.data_ptr(), hc.shape[1]
-            p.v_bounds, p.v_coefs, p.v_kmax = vb.data_ptr(), vc.data_ptr(), vc.shape[1]
-        for i in range(0, n, _lib.TC_FRAMES_U8_MAX):
-            part = slots[i:i + _lib.TC_FRAMES_U8_MAX]
-            held = (C.c_int32 * len(part))(*part)
-            p.src, p.n, p.slots = images[i].data_ptr(), len(part), held
-            p.workspace_bytes = self.lib.tc_frames_from_u8_workspace(C.byref(p))
-            ws = self._workspace(p.workspace_bytes, images.device)
-            p.workspace = ws.data_ptr()
-            _lib.check(self.lib.tc_frames_from_u8(C.byref(p), _stream()), "tc_frames_from_u8")
+        self._front_launch("tc_frames_from_u8", p, slots, self._front_tables(sh, sw, h, w, images.device), images.device,
+                           lambda i: {"src": images[i].data_ptr()})
         return out
 
     def yuv_matrix(self, standard="bt601", range="limited", bits=8):
@@ -906,14 +948,7 @@ class HipOps:
         lay = planes_layout(planes, "frames_from_yuv: planes")
         if not planes.y.is_cuda:
             raise _lib.TooncrafterHipError("frames_from_yuv: planes: expected CUDA tensors: the product path is GPU-only")
-        h, w = (int(v) for v in size)
-        slots = [int(s) for s in slots]
-        if len(slots) != lay["n"] or any(s < 0 or s >= b * t for s in slots):
-            raise ValueError(f"frames_from_yuv: {lay['n']} images need {lay['n']} slots in [0, {b * t}), got {slots}")
-        if out is not None:
-            _dev(out, torch.float32, "frames_from_yuv: out")
-            if tuple(out.shape) != (b, 3, t, h, w):
-                raise ValueError(f"frames_from_yuv: out must be ({b}, 3, {t}, {h}, {w}), got {tuple(out.shape)}")
+        (h, w), slots = self._front_args("frames_from_yuv", lay["n"], size, slots, b, t, out)
         m = self.yuv_matrix(planes.standard, planes.range, 10 if lay["wide"] else 8) if planes.matrix is None else [int(v) for v in planes.matrix]
         return lay, m, (h, w), slots, out
 
@@ -923,49 +958,15 @@ class HipOps:
         `planes.standard` / `planes.range` (or `planes.matrix`), then frames_from_u8's transform of that RGB image, bit for bit
         (tc_frames_from_yuv).  slots / out as in frames_from_u8."""
         lay, m, (h, w), slots, out = self._frames_yuv_args(planes, size, slots, b, t, out)
-        n, sh, sw, dev = lay["n"], lay["sh"], lay["sw"], planes.y.device
+        sh, sw, dev = lay["sh"], lay["sw"], planes.y.device
         if out is None:
             out = torch.zeros((b, 3, t, h, w), dtype=torch.float32, device=dev)
-        rh, rw = self.resized_size(sh, sw, h, w)
         p = _lib.TcFramesYuvParams(image_stride_y=lay["image_stride_y"], image_stride_c=lay["image_stride_c"], pitch_y=lay["pitch_y"],
                                    pitch_c=lay["pitch_c"], format=lay["format"], siting=_lib.TC_CHROMA_SITINGS[planes.siting],
                                    m=(C.c_int32 * 7)(*m), sh=sh, sw=sw, out=out.data_ptr(), b=b, t=t, h=h, w=w)
-        if (rh, rw) != (sh, sw):
-            hb, hc = self.resize_tables(sw, rw, dev)
-            vb, vc = self.resize_tables(sh, rh, dev)
-            p.h_bounds, p.h_coefs, p.h_kmax = hb.data_ptr(), hc.data_ptr(), hc.shape[1]
-            p.v_bounds, p.v_coefs, p.v_kmax = vb.data_ptr(), vc.data_ptr(), vc.shape[1]
-        for i in range(0, n, _lib.TC_FRAMES_U8_MAX):
-            part = slots[i:i + _lib.TC_FRAMES_U8_MAX]
-            held = (C.c_int32 * len(part))(*part)
-            p.y, p.c0 = planes.y[i].data_ptr(), planes.chroma[0][i].data_ptr()
-            p.c1 = planes.chroma[1][i].data_ptr() if len(planes.chroma) > 1 else None
-            p.n, p.slots = len(part), held
-            p.workspace_bytes = self.lib.tc_frames_from_yuv_workspace(C.byref(p))
-            ws = self._workspace(p.workspace_bytes, dev)
-            p.workspace = ws.data_ptr()
-            _lib.check(self.lib.tc_frames_from_yuv(C.byref(p), _stream()), "tc_frames_from_yuv")
+        self._front_launch("tc_frames_from_yuv", p, slots, self._front_tables(sh, sw, h, w, dev), dev,
+                           lambda i: dict(zip(("y", "c0", "c1"), (plane[i].data_ptr() for plane in (planes.y,) + planes.chroma))))
         return out
-
-    def resize_tables_filter(self, filter, n_in, n_out, device):
-        """PIL's 8-bit tables of one axis for `filter` ("bilinear", "bicubic", "lanczos", "box") on `device`: (bounds [n_out, 2],
-        coefs [n_out, kmax]) int32, built on the host by tc_resize_tables_filter and kept per (filter, n_in, n_out, device)."""
-        key = (str(filter), int(n_in), int(n_out), torch.device(device))
-        tabs = self._resize_tables.get(key)
-        if tabs is None:
-            if key[0] not in _lib.TC_RESIZE_FILTERS:
-                raise ValueError(f"resize filter {filter!r}: one of {sorted(_lib.TC_RESIZE_FILTERS)}")
-            code = _lib.TC_RESIZE_FILTERS[key[0]]
-            kmax = self.lib.tc_resize_tables_filter(code, key[1], key[2], None, None, 0)
-            _lib.check(min(kmax, 0), "tc_resize_tables_filter")
-            bounds = torch.empty((key[2], 2), dtype=torch.int32)
-            coefs = torch.empty((key[2], kmax), dtype=torch.int32)
-            i32p = C.POINTER(C.c_int32)
-            rc = self.lib.tc_resize_tables_filter(code, key[1], key[2], C.cast(bounds.data_ptr(), i32p), C.cast(coefs.data_ptr(), i32p),
-                                                  coefs.numel())
-            _lib.check(min(rc, 0), "tc_resize_tables_filter")
-            tabs = self._resize_tables[key] = (bounds.to(key[3]), coefs.to(key[3]))
-        return tabs
 
     @staticmethod
     def _frames_out_args(x, size, filter, fmt, frames):
@@ -1015,22 +1016,14 @@ class HipOps:
                 raise ValueError(f"frames_to_u8: out is on {out.device}, x on {x.device}")
         p = _lib.TcFramesOutParams(x=x.data_ptr(), out=out.data_ptr(), b=b, t=t, h=h, w=w, f0=f0, nf=nf, oh=oh, ow=ow, format=code,
                                    pitch=pitch, frame_stride=frame_stride, clip_stride=clip_stride)
-        if ow != w:
-            hb, hc = self.resize_tables_filter(filter, w, ow, x.device)
-            p.h_bounds, p.h_coefs, p.h_kmax = hb.data_ptr(), hc.data_ptr(), hc.shape[1]
-        if oh != h:
-            vb, vc = self.resize_tables_filter(filter, h, oh, x.device)
-            p.v_bounds, p.v_coefs, p.v_kmax = vb.data_ptr(), vc.data_ptr(), vc.shape[1]
+        self._set_tables(p, self._axis_tables(filter, w, ow, x.device) + self._axis_tables(filter, h, oh, x.device))
         # the last byte the kernels may write: a frame's bytes by the header's rule, at the last place
         used = pitch * oh if fmt == "rgb24" else pitch * oh + (2 * (pitch // 2) * (oh // 2) if fmt == "i420" else pitch * (oh // 2))
         if pitch < row or frame_stride < used or (b > 1 and clip_stride < nf * frame_stride) or \
                 (b - 1) * clip_stride + (nf - 1) * frame_stride + used > out.numel():
             raise ValueError(f"frames_to_u8: strides (pitch, frame, clip) = {(pitch, frame_stride, clip_stride)} do not fit {b} x {nf} "
                              f"frames of {used} bytes into an out of {out.numel()} bytes")
-        p.workspace_bytes = self.lib.tc_frames_to_u8_workspace(C.byref(p))
-        ws = self._workspace(p.workspace_bytes, x.device)
-        p.workspace = ws.data_ptr()
-        _lib.check(self.lib.tc_frames_to_u8(C.byref(p), _stream()), "tc_frames_to_u8")
+        self._launch("tc_frames_to_u8", p, x.device)
         return out
 
     def clip_patches(self, x, *, size, patch, ld, mean, std, antialias=True):
@@ -1050,10 +1043,7 @@ class HipOps:
         p = _lib.TcClipPatchesParams(x=x.data_ptr(), out=out.data_ptr(), b=b, h=h, w=w, size=size, patch=patch, ld=ld,
                                      antialias=1 if antialias else 0)
         p.mean[:], p.std[:] = [float(v) for v in mean], [float(v) for v in std]
-        p.workspace_bytes = self.lib.tc_clip_patches_workspace(C.byref(p))
-        ws = self._workspace(p.workspace_bytes, x.device)
-        p.workspace = ws.data_ptr()
-        _lib.check(self.lib.tc_clip_patches(C.byref(p), _stream()), "tc_clip_patches")
+        self._launch("tc_clip_patches", p, x.device)
         return out
 
     @staticmethod

@@ -158,33 +158,24 @@ class TorchLibOps(HipOps):
         if out is not None or images.shape[0] > _lib.TC_FRAMES_U8_MAX:     # an explicit result buffer / several calls: the ctypes method
             return super().frames_from_u8(images, size, slots, b=b, t=t, out=out)
         (h, w), (sh, sw) = (int(v) for v in size), images.shape[1:3]
-        rh, rw = self.resized_size(sh, sw, h, w)
-        tabs = (None,) * 4
-        if (rh, rw) != (sh, sw):
-            tabs = self.resize_tables(sw, rw, images.device) + self.resize_tables(sh, rh, images.device)
-        return self.t.frames_from_u8(images, [int(s) for s in slots], int(b), int(t), h, w, *tabs)
+        return self.t.frames_from_u8(images, [int(s) for s in slots], int(b), int(t), h, w,
+                                     *self._front_tables(sh, sw, h, w, images.device))
 
     def frames_from_yuv(self, planes, size, slots, *, b, t, out=None):
         lay, m, (h, w), slots, out = self._frames_yuv_args(planes, size, slots, b, t, out)
         if out is not None or lay["n"] > _lib.TC_FRAMES_U8_MAX:            # an explicit result buffer / several calls: the ctypes method
             return super().frames_from_yuv(planes, size, slots, b=b, t=t, out=out)
-        sh, sw, dev = lay["sh"], lay["sw"], planes.y.device
-        rh, rw = self.resized_size(sh, sw, h, w)
-        tabs = (None,) * 4
-        if (rh, rw) != (sh, sw):
-            tabs = self.resize_tables(sw, rw, dev) + self.resize_tables(sh, rh, dev)
         c1 = planes.chroma[1] if len(planes.chroma) > 1 else None
         return self.t.frames_from_yuv(planes.y, planes.chroma[0], c1, lay["format"], m, _lib.TC_CHROMA_SITINGS[planes.siting], slots,
-                                      int(b), int(t), h, w, *tabs)
+                                      int(b), int(t), h, w, *self._front_tables(lay["sh"], lay["sw"], h, w, planes.y.device))
 
     def frames_to_u8(self, x, size=None, filter="bicubic", fmt="rgb24", frames=None, out=None, strides=None):
         if out is not None or strides is not None:          # an explicit result buffer with its strides: the ctypes method
             return super().frames_to_u8(x, size, filter, fmt, frames, out=out, strides=strides)
         oh, ow, code, f0, nf, _, _ = self._frames_out_args(x, size, filter, fmt, frames)
         h, w = x.shape[3:]
-        tabs = (self.resize_tables_filter(filter, w, ow, x.device) if ow != w else (None, None)) + \
-               (self.resize_tables_filter(filter, h, oh, x.device) if oh != h else (None, None))
-        return self.t.frames_to_u8(x.contiguous(), oh, ow, code, f0, nf, *tabs)
+        return self.t.frames_to_u8(x.contiguous(), oh, ow, code, f0, nf, *self._axis_tables(filter, w, ow, x.device),
+                                   *self._axis_tables(filter, h, oh, x.device))
 
     def clip_patches(self, x, *, size, patch, ld, mean, std, antialias=True):
         return self.t.clip_patches(x, int(size), int(patch), int(ld), [float(v) for v in mean], [float(v) for v in std], bool(antialias))
