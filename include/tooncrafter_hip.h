@@ -718,6 +718,76 @@ typedef struct TcFramesYuvParams {
 int64_t tc_frames_from_yuv_workspace(const TcFramesYuvParams* p);
 int tc_frames_from_yuv(const TcFramesYuvParams* p, void* stream);
 
+/* ---- Planar frames out in a named colour: the decoder's fp32 clips -> I420 / NV12 frames of any standard and range with
+ * centre or left chroma siting, or 10-bit P010 (additive within ABI 14: one struct, three symbols).  tc_frames_to_u8 above
+ * stays as it is (8-bit BT.601 limited range, centre siting); tc_frames_to_yuv contains it: with tc_yuv_out_matrix's
+ * BT.601 limited 8-bit row and TC_CHROMA_CENTER it writes the same bytes. ---- */
+
+/* The integer RGB -> YCbCr matrix of a standard, the forward counterpart of tc_yuv_matrix: HOST code, double precision, no
+ * device call.   m = {yr, yg, yb, ur, ug, ub, vr, vg, vb, yoff, coff}.
+ * bits 8: the RGB samples are 8-bit; bits 10: they are the 16-bit intermediate of tc_frames_to_yuv's P010 path.  With
+ * bits_in = 8 | 16:  F = 8 + bits_in (16 | 24), inmax = 2^bits_in - 1, q = 2^(bits - 8), (Kr, Kb) as for tc_yuv_matrix.
+ *   limited range: gy = 219 q / inmax, gc = 224 q / inmax, yoff = 16 q;
+ *   full range:    gy = gc = (2^bits - 1) / inmax, yoff = 0;                 coff = 128 q in both.
+ * With r(v) = floor(v * 2^F + 0.5):
+ *   yr = r(Kr gy), yb = r(Kb gy), yg = r(gy) - yr - yb                      (white lands exactly on r(gy));
+ *   ub = vr = r(gc / 2), ur = r(-Kr / (2 (1 - Kb)) gc), ug = -(ub + ur),
+ *   vb = r(-Kb / (2 (1 - Kr)) gc), vg = -(vr + vb)                          (each chroma row sums to 0: grey is neutral).
+ * E.g. BT.601 limited 8 bit: 16829, 33039, 6416, -9714, -19070, 28784, 28784, -24103, -4681, yoff 16, coff 128 -- the
+ * constants of tc_frames_to_u8; BT.709 limited 10 bit: 47678, 160389, 16192, -26280, -88410, 114690, 114690, -104174,
+ * -10516, yoff 64, coff 512 (red gives Y, Cb, Cr = 250, 409, 960; white Y 940; black Y 64).
+ * TC_EINVAL: an unknown standard or range, bits other than 8 or 10, NULL m. */
+int tc_yuv_out_matrix(int32_t standard, int32_t range, int32_t bits, int32_t m[11]);
+
+/* Frames f0 .. f0 + nf - 1 of every clip of x (b, 3, t, h, w) fp32 -> planar 4:2:0 frames of (oh, ow) pixels by the matrix
+ * m of the STRUCT (tc_yuv_out_matrix's or any other: the kernel has no built-in standard), in this order:
+ *   I420 / NV12 (8 bit):
+ *   1. value and 2. resample: steps 1 and 2 of tc_frames_to_u8, on uint8 RGB in int32 (the same device functions);
+ *   P010 (10 bit) -- the path never passes through 8 bits:
+ *   1. value: c = clamp(x, -1, 1), h = (c + 1) / 2, s = h * 65535.0f, q = (uint16_t)floorf(s + 0.5f), every fp32 operation
+ *      rounded on its own (nothing contracted);
+ *   2. resample of the uint16 RGB with the SAME tables (tc_resize_tables_filter, 2^22 coefficients), summed in int64:
+ *      clip(((1 << 21) + sum coefs * src) >> 22, 0, 65535), passes and their order as for tc_frames_to_u8;
+ *   3. colour, with F = 16 (8 bit) or 24 (P010), max = 255 or 1023, in int32 (8 bit) or int64 (P010):
+ *        Y = clip((yr R + yg G + yb B + (yoff << F) + (1 << (F - 1))) >> F, 0, max)       for every pixel,
+ *        C = clip((cr Rs + cg Gs + cb Bs + (coff << (F + s)) + (1 << (F + s - 1))) >> (F + s), 0, max)
+ *      for every chroma sample (bx, by), with the row (ur, ug, ub) for Cb and (vr, vg, vb) for Cr:
+ *        TC_CHROMA_CENTER  Rs, Gs, Bs = the sums over the 2 x 2 block, s = 2 (the siting of tc_frames_to_u8);
+ *        TC_CHROMA_LEFT    (H.264 / HEVC chroma_sample_loc_type 0) the sample is co-sited with column x0 = 2 bx and centred
+ *                          between rows 2 by and 2 by + 1: Rs, Gs, Bs = the sum over both rows of P[x0 - 1] + 2 P[x0] +
+ *                          P[x0 + 1], x0 - 1 clamped to 0 (x0 + 1 exists: ow is even), s = 3.
+ *      All shifts are arithmetic, sums may be negative, the clip is two-sided (full-range blue reaches 256 before it).  With
+ *      tc_yuv_out_matrix's rows no 8-bit sum exceeds 2^27 (full-range blue reaches exactly that); a caller's own matrix
+ *      must keep them inside int32.
+ *   4. format: I420 and NV12 as tc_frames_to_u8 lays them out; P010 is NV12's layout in 16-bit little-endian words, the
+ *      stored word = code << 6 (the low six bits are zero): `pitch` is in bytes and >= 2 ow;
+ *   5. placement, f0 / nf, frame_stride, clip_stride (bytes): exactly tc_frames_to_u8's.
+ * A frame's bytes: I420 / NV12 as there; P010 pitch * oh + pitch * (oh / 2).
+ * workspace: tc_frames_to_yuv_workspace bytes -- 8 bit: b * nf * h * w * 3 plus, when ow != w, b * nf * h * ow * 3; P010: two
+ * bytes per sample, b * nf * h * w * 6 plus b * nf * h * ow * 6 (0 for a request tc_frames_to_yuv refuses for anything but
+ * its workspace).  Every pointer is device memory.
+ * TC_EINVAL: what tc_frames_to_u8 refuses with it (pitch below ow bytes, 2 ow for P010), a format other than I420 / NV12 /
+ * P010 (RGB24 too), a siting other than CENTER / LEFT (NEAREST is not a way to produce chroma), yr, yg, yb not all
+ * positive; TC_ESHAPE: an odd oh or ow or, for I420, an odd pitch; TC_EALIGN: P010 with an odd out, pitch, frame_stride,
+ * clip_stride or workspace; TC_EWORKSPACE: workspace too small.  Nothing is launched or written on a refusal. */
+typedef struct TcFramesYuvOutParams {
+  const float* x;              /* (b, 3, t, h, w) fp32: the decoder's output */
+  void* out;
+  int32_t b, t, h, w;
+  int32_t f0, nf;              /* frames f0 .. f0+nf-1 of every clip are written, 0 <= f0, nf >= 1, f0+nf <= t */
+  int32_t oh, ow;              /* output size, both even; (oh, ow) == (h, w): no resample, no tables */
+  int32_t format;              /* TC_PIXFMT_I420 / NV12 / P010 */
+  int32_t pitch;               /* bytes per row of the Y plane */
+  int64_t frame_stride, clip_stride;   /* bytes from one written frame / clip to the next in out */
+  const int32_t* h_bounds; const int32_t* h_coefs; int32_t h_kmax;   /* w -> ow (NULL when ow == w) */
+  const int32_t* v_bounds; const int32_t* v_coefs; int32_t v_kmax;   /* h -> oh (NULL when oh == h) */
+  void* workspace; int64_t workspace_bytes;
+  int32_t siting;              /* TC_CHROMA_CENTER / TC_CHROMA_LEFT */
+  int32_t m[11];               /* yr, yg, yb, ur, ug, ub, vr, vg, vb, yoff, coff */
+} TcFramesYuvOutParams;
+int64_t tc_frames_to_yuv_workspace(const TcFramesYuvOutParams* p);
+int tc_frames_to_yuv(const TcFramesYuvOutParams* p, void* stream);
+
 /* introspection */
 int tc_abi_version(void);
 const char* tc_build_info(void);

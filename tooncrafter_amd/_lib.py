@@ -186,6 +186,12 @@ class TcFramesYuvParams(C.Structure):
     ]
 
 
+class TcFramesYuvOutParams(C.Structure):
+    """fp32 clips -> I420 / NV12 / P010 frames by a caller's RGB -> YCbCr matrix and chroma siting, at named places
+    (tc_frames_to_yuv; additive within ABI 14): TcFramesOutParams' fields, then the siting and the matrix."""
+    _fields_ = TcFramesOutParams._fields_ + [("siting", C.c_int32), ("m", C.c_int32 * 11)]
+
+
 TC_YUV_FORMATS = {"i420": 1, "nv12": 2, "p010": 3}       # include/tooncrafter_hip.h: the TC_PIXFMT_* tc_frames_from_yuv reads
 TC_YUV_STANDARDS = {"bt601": 0, "bt709": 1}              # TC_YUV_BT*
 TC_YUV_RANGES = {"limited": 0, "full": 1}                # TC_YUV_LIMITED / TC_YUV_FULL
@@ -270,6 +276,9 @@ SYMBOLS = {
     "tc_yuv_matrix": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "tc_frames_from_yuv_workspace": (C.c_int64, [C.POINTER(TcFramesYuvParams)]),
     "tc_frames_from_yuv": (C.c_int, [C.POINTER(TcFramesYuvParams), C.c_void_p]),
+    "tc_yuv_out_matrix": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "tc_frames_to_yuv_workspace": (C.c_int64, [C.POINTER(TcFramesYuvOutParams)]),
+    "tc_frames_to_yuv": (C.c_int, [C.POINTER(TcFramesYuvOutParams), C.c_void_p]),
     "tc_gemm_ws_eligible": (C.c_int, [C.POINTER(TcGemmParams)]),
     "tc_gemm_gn_rows": (C.c_int, [C.POINTER(TcGemmParams)]),
     "tc_groupnorm_part": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
@@ -328,7 +337,7 @@ class _TracedLib:
 
     def __getattr__(self, name):
         fn = getattr(self._lib, name)
-        if name not in SYMBOLS or name in ("tc_abi_version", "tc_build_info", "tc_resize_tables", "tc_resize_tables_filter", "tc_frames_from_u8_resized", "tc_yuv_matrix") or name.endswith("_workspace"):
+        if name not in SYMBOLS or name in ("tc_abi_version", "tc_build_info", "tc_resize_tables", "tc_resize_tables_filter", "tc_frames_from_u8_resized", "tc_yuv_matrix", "tc_yuv_out_matrix") or name.endswith("_workspace"):
             return fn
         import sys
 

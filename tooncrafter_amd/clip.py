@@ -185,6 +185,34 @@ def planes_from_packed(buf, h, w, fmt, **options):
     return Planes(y, chroma, fmt, **options)
 
 
+def planes_from_frames(buf, h, w, fmt, colour):
+    """`planes_from_packed` for the frames `clip_to_uint8(..., colour=)` / `synthesize_u8(..., out_colour=)` return: views (no
+    copy) of the uint8 (..., bytes per frame) buffers as a `Planes` carrying the colour's standard / range / siting, so that a
+    clip's last frame is the next clip's keyframe in the same description.  colour.bits == 10: the (..., h * w * 3) bytes of
+    P010 frames, viewed as fmt "p010" with 2-byte elements (`fmt` is then "nv12", as it was for the call that wrote them)."""
+    from .output import Colour
+    if not isinstance(colour, Colour):
+        raise ValueError(f"planes_from_frames: colour: expected a Colour, got {type(colour).__name__}")
+    options = dict(standard=colour.standard, range=colour.range, siting=colour.siting)
+    if colour.bits == 8:
+        return planes_from_packed(buf, h, w, fmt, **options)
+    h, w = int(h), int(w)
+    if fmt != "nv12":
+        raise ValueError(f"planes_from_frames: fmt {fmt!r}: 10-bit frames are 'nv12' in 2-byte words (P010)")
+    if h <= 0 or w <= 0 or h % 2 or w % 2:
+        raise ValueError(f"planes_from_frames: the packed planar formats have an even size, got {(h, w)}")
+    if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8 or buf.dim() < 1 or buf.shape[-1] != h * w * 3 or buf.stride(-1) != 1:
+        raise ValueError(f"planes_from_frames: expected uint8 (..., {h * w * 3}) P010 frames with unit stride, got "
+                         f"{tuple(buf.shape) if isinstance(buf, torch.Tensor) else type(buf)} {getattr(buf, 'dtype', '')}")
+    try:
+        words = buf.view(-1, buf.shape[-1]).view(torch.uint16)
+    except RuntimeError as e:
+        raise ValueError(f"planes_from_frames: the frames do not flatten into 2-byte words without a copy (strides {buf.stride()}, "
+                         f"offset {buf.storage_offset()})") from e
+    n = h * w
+    return Planes(words[:, :n].unflatten(1, (h, w)), (words[:, n:].unflatten(1, (h // 2, w // 2, 2)),), "p010", **options)
+
+
 def frames_from_planes(planes, size, slots, t, out=None):
     """`frames_from_uint8` for a `Planes` of n images: chroma upsample and YCbCr -> RGB in integers, then the script's
     transform of that RGB image, bit for bit, on the device (tc_frames_from_yuv)."""
@@ -327,26 +355,29 @@ def synthesize(model, videos, latent_shape, *, plan: SamplingPlan, prompts=None,
 
 
 def synthesize_u8(model, first_u8, last_u8, latent_shape, *, size, plan: SamplingPlan, prompts=None, fs=24, three_way=False,
-                  hold_endpoints=True, out_size=None, out_filter="bicubic", out_fmt="rgb24"):
+                  hold_endpoints=True, out_size=None, out_filter="bicubic", out_fmt="rgb24", out_colour=None):
     """uint8 keyframes in, uint8 clip out, all on the device: (b, h, w, 3) first / last frames -> (b, t, H, W, 3) frames
     (`Conditions.from_uint8`, `sample`, `decode_spliced`, `clip_to_uint8`).  The last frame of one clip can be the first
     keyframe of the next without leaving the GPU.  `plan.seeds` as in `sample`.
     out_size = (oh, ow), out_filter, out_fmt: the delivery size and pixel format (`clip_to_uint8`'s size / filter / fmt, the
     pixel back end) -- (b, t, oh, ow, 3) frames, or for "i420" / "nv12" the (b, t, oh * ow * 3 / 2) planes that
-    `mp4.write_mp4_i420` or an encoder takes."""
+    `mp4.write_mp4_i420` or an encoder takes.  out_colour: an `output.Colour` for those planes (`clip_to_uint8`'s colour)."""
     from .output import clip_to_uint8
     cond = Conditions.from_uint8(model, first_u8, last_u8, size=size, t=latent_shape[2], prompts=prompts, fs=fs,
                                  guided=plan.scale != 1.0, three_way=three_way, image_branch=plan.image_scale != 1.0,
                                  hold_endpoints=hold_endpoints)
-    return clip_to_uint8(decode_spliced(model, sample(model, cond, plan, latent_shape), cond.refs), size=out_size,
-                         filter=out_filter, fmt=out_fmt)
+    video = decode_spliced(model, sample(model, cond, plan, latent_shape), cond.refs)
+    if out_colour is None:
+        return clip_to_uint8(video, size=out_size, filter=out_filter, fmt=out_fmt)
+    return clip_to_uint8(video, size=out_size, filter=out_filter, fmt=out_fmt, colour=out_colour)
 
 
-def timeline_layout(keyframes: int, t: int, batch: int, out_hw, fmt: str):
+def timeline_layout(keyframes: int, t: int, batch: int, out_hw, fmt: str, colour=None):
     """Where a timeline of `keyframes` keyframes puts its frames (the splice rule of tc_frames_to_u8, include/tooncrafter_hip.h):
     segment i runs from keyframe i to i + 1; segment 0 gives frames 0 .. t-1 of the video, every later one its frames 1 .. t-1,
     F = (K - 1)(t - 1) + 1 frames in all.  Returns (F, bytes per frame, batches); a batch is (first segment, segments) and its
-    frames 1 .. t-1 start at video frame first * (t - 1) + 1, clips (t - 1) frames apart."""
+    frames 1 .. t-1 start at video frame first * (t - 1) + 1, clips (t - 1) frames apart.  colour: the `output.Colour` of planar
+    frames (fmt "i420" / "nv12"); its bits = 10 ("nv12" only: P010) doubles the bytes per frame."""
     keyframes, t, batch = int(keyframes), int(t), int(batch)
     oh, ow = (int(v) for v in out_hw)
     if keyframes < 2 or t < 2 or batch < 1:
@@ -355,13 +386,17 @@ def timeline_layout(keyframes: int, t: int, batch: int, out_hw, fmt: str):
         raise ValueError(f"timeline: out_fmt {fmt!r}: 'rgb24', 'i420' or 'nv12'")
     if oh <= 0 or ow <= 0 or (fmt != "rgb24" and (oh % 2 or ow % 2)):
         raise ValueError(f"timeline: output size {(oh, ow)} for {fmt}")
+    if colour is not None and (fmt == "rgb24" or (colour.bits == 10 and fmt != "nv12")):
+        raise ValueError(f"timeline: out_fmt {fmt!r} with a {colour.bits}-bit colour: 'i420' or 'nv12', 10 bits 'nv12' only")
     segments = keyframes - 1
     frame = oh * ow * 3 if fmt == "rgb24" else oh * ow * 3 // 2
+    if colour is not None and colour.bits == 10:
+        frame *= 2
     return segments * (t - 1) + 1, frame, [(i, min(batch, segments - i)) for i in range(0, segments, batch)]
 
 
 def synthesize_timeline_u8(model, keyframes, latent_shape, *, size, plan: SamplingPlan, prompts=None, fs=24, three_way=False,
-                           out_size=None, out_filter="bicubic", out_fmt="rgb24"):
+                           out_size=None, out_filter="bicubic", out_fmt="rgb24", out_colour=None):
     """K keyframes in, one video out, all on the device.  `keyframes`: (K, h, w, 3) uint8 or a `Planes` of K images, K >= 2.
     Segment i interpolates keyframe i -> i + 1 (endpoints held); segments run in order, latent_shape[0] per batch (the last
     batch may be smaller), each batch exactly `Conditions.from_uint8` / `from_planes` with first = kf[i : i + n] and
@@ -369,7 +404,9 @@ def synthesize_timeline_u8(model, keyframes, latent_shape, *, size, plan: Sampli
     rule: (F, oh, ow, 3) for "rgb24", (F, oh * ow * 3 / 2) for "i420" / "nv12" (what `mp4.write_mp4_i420` / `planar_writer`
     take), F = (K - 1)(t - 1) + 1.  `plan.seeds`: one seed per SEGMENT (sliced per batch); `prompts`: one per segment or None.
     Without seeds the device generator is drawn as the same sequence of `synthesize_u8` calls draws it.  Every inner keyframe is
-    encoded twice, as one segment's last frame and the next one's first."""
+    encoded twice, as one segment's last frame and the next one's first.
+    out_colour: an `output.Colour` for planar frames (tc_frames_to_yuv instead; 10 bits: (F, oh * ow * 3) bytes of P010), or
+    "source": the colour the `Planes` keyframes came in (`Colour.of`), so the video leaves in the description it arrived with."""
     from dataclasses import replace
     planar = isinstance(keyframes, Planes)
     if not planar and not (isinstance(keyframes, torch.Tensor) and keyframes.dtype == torch.uint8 and keyframes.dim() == 4 and keyframes.shape[3] == 3):
@@ -377,13 +414,24 @@ def synthesize_timeline_u8(model, keyframes, latent_shape, *, size, plan: Sampli
     k, t = len(keyframes), int(latent_shape[2])
     size = tuple(int(v) for v in size)
     oh, ow = size if out_size is None else (int(v) for v in out_size)
-    total, frame, batches = timeline_layout(k, t, latent_shape[0], (oh, ow), out_fmt)
+    from .output import Colour
+    if out_colour is not None and not isinstance(out_colour, (str, Colour)):
+        raise ValueError(f"synthesize_timeline_u8: out_colour: expected a Colour or 'source', got {type(out_colour).__name__}")
+    if isinstance(out_colour, str):
+        if out_colour != "source" or not planar:
+            raise ValueError(f"synthesize_timeline_u8: out_colour {out_colour!r}: a Colour, or 'source' with Planes keyframes "
+                             "(RGB keyframes carry no colour description)")
+        out_colour = Colour.of(keyframes)
+    total, frame, batches = timeline_layout(k, t, latent_shape[0], (oh, ow), out_fmt) if out_colour is None else \
+        timeline_layout(k, t, latent_shape[0], (oh, ow), out_fmt, out_colour)
     seeds = None if plan.seeds is None else ops.clip_seeds(plan.seeds, k - 1, "synthesize_timeline_u8: plan.seeds (one per segment)")
     if prompts is not None and len(prompts) != k - 1:
         raise ValueError(f"synthesize_timeline_u8: {len(prompts)} prompts for {k - 1} segments")
     device = keyframes.y.device if planar else keyframes.device
     video = torch.empty((total, oh, ow, 3) if out_fmt == "rgb24" else (total, frame), dtype=torch.uint8, device=device)
-    flat, row = video.view(-1), 3 * ow if out_fmt == "rgb24" else ow
+    wide = out_colour is not None and out_colour.bits == 10                                       # P010: 2-byte samples
+    flat, row = video.view(-1), 3 * ow if out_fmt == "rgb24" else 2 * ow if wide else ow
+    write = ops.frames_to_u8 if out_colour is None else (lambda x, **kw: ops.frames_to_yuv(x, colour=out_colour, **kw))
     build = Conditions.from_planes if planar else Conditions.from_uint8
     for i, n in batches:
         cond = build(model, keyframes[i:i + n], keyframes[i + 1:i + n + 1], size=size, t=t,
@@ -392,10 +440,9 @@ def synthesize_timeline_u8(model, keyframes, latent_shape, *, size, plan: Sampli
         part = plan if seeds is None else replace(plan, seeds=seeds[i:i + n])
         clips = decode_spliced(model, sample(model, cond, part, [n, *latent_shape[1:]]), cond.refs).to(torch.float32)
         if i == 0:                                    # the video's first frame: segment 0 alone writes its frame 0
-            ops.frames_to_u8(clips[:1], size=out_size, filter=out_filter, fmt=out_fmt, frames=(0, 1), out=flat,
-                             strides=(row, frame, frame))
-        ops.frames_to_u8(clips, size=out_size, filter=out_filter, fmt=out_fmt, frames=(1, t - 1),
-                         out=flat[(i * (t - 1) + 1) * frame:], strides=(row, frame, (t - 1) * frame))
+            write(clips[:1], size=out_size, filter=out_filter, fmt=out_fmt, frames=(0, 1), out=flat, strides=(row, frame, frame))
+        write(clips, size=out_size, filter=out_filter, fmt=out_fmt, frames=(1, t - 1), out=flat[(i * (t - 1) + 1) * frame:],
+              strides=(row, frame, (t - 1) * frame))
     return video
 
 

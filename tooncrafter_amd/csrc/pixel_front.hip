@@ -248,7 +248,7 @@ int frames_launch(const TcFramesU8Params& p, const FramesPlan& plan, uint8_t* mi
   const dim3 grid(pixel_grid(total)), block(256);
   if (plan.resized) {
     const int64_t mid_total = (int64_t)p.n * p.sh * rw;
-    hipLaunchKernelGGL(resample_hpass_kernel, dim3(pixel_grid(mid_total)), block, 0, s, p.src, p.image_stride, p.pitch, p.sh, p.sw, rw,
+    hipLaunchKernelGGL(resample_hpass_kernel<uint8_t>, dim3(pixel_grid(mid_total)), block, 0, s, p.src, p.image_stride, p.pitch, p.sh, p.sw, rw,
                        p.h_bounds, p.h_coefs, p.h_kmax, mid, mid_total);
     TC_LAUNCH_CHECK();
     hipLaunchKernelGGL(frames_final_kernel<true>, grid, block, 0, s, (const uint8_t*)mid, (int64_t)p.sh * rw * 3, rw * 3, p.sh, rh,

@@ -3,7 +3,7 @@
 // The reference binds ATen / xformers operators from Python (utils/utils.py:27-42 instantiates lvdm classes whose
 // forward methods call torch ops); this registers the MI355X kernels as first-class torch operators instead:
 //   torch.ops.tooncrafter.gemm / quant_mxfp8 / gemm_mx / attention / attention_temporal(_rel) / groupnorm(_pf) / layernorm(_pf) / ddim_step(_eps) / ddim_step_ms(_eps) / ddim_blend /
-//   frames_from_u8 / frames_from_yuv / frames_to_u8 / clip_patches / randn_clips /
+//   frames_from_u8 / frames_from_yuv / frames_to_u8 / frames_to_yuv / clip_patches / randn_clips /
 //   ff_geglu_fused / temporal_attn_fused / temporal_qkv_attn / attention_q8
 // with (i) a CUDA(HIP)-key implementation that validates the tensors, allocates the result from the caching allocator,
 // picks up the CURRENT stream and calls the same extern "C" entry point the ctypes binding calls, and (ii) a Meta-key
@@ -662,6 +662,51 @@ Tensor frames_to_u8_meta(const Tensor& x, int64_t oh, int64_t ow, int64_t format
   return at::empty(frames_to_u8_shape(x, oh, ow, format, f0, nf), x.options().dtype(at::kByte));
 }
 
+// frames_to_yuv: frames_to_u8 for planar frames in a caller's colour (tc_frames_to_yuv): format I420 / NV12 / P010, the siting code
+// and the eleven integers of the RGB -> YCbCr matrix -> a new packed uint8 tensor (b, nf, oh * ow * 3 / 2), twice the bytes for P010.
+std::vector<int64_t> frames_to_yuv_shape(const Tensor& x, int64_t oh, int64_t ow, int64_t format, int64_t f0, int64_t nf, int64_t siting,
+                                         at::IntArrayRef m) {
+  TORCH_CHECK(x.dim() == 5 && x.size(1) == 3 && x.numel() > 0, "frames_to_yuv: x must be (b, 3, t, h, w)");
+  TORCH_CHECK(oh > 0 && ow > 0 && oh <= INT32_MAX && ow <= INT32_MAX, "frames_to_yuv: output size (", oh, ", ", ow, ")");
+  TORCH_CHECK(f0 >= 0 && nf >= 1 && f0 + nf <= x.size(2), "frames_to_yuv: frames ", f0, " .. ", f0 + nf - 1, " outside a clip of ", x.size(2));
+  TORCH_CHECK(format == TC_PIXFMT_I420 || format == TC_PIXFMT_NV12 || format == TC_PIXFMT_P010, "frames_to_yuv: format ", format);
+  TORCH_CHECK(siting == TC_CHROMA_CENTER || siting == TC_CHROMA_LEFT, "frames_to_yuv: siting ", siting);
+  TORCH_CHECK(m.size() == 11, "frames_to_yuv: the matrix has eleven entries");
+  TORCH_CHECK(oh % 2 == 0 && ow % 2 == 0, "frames_to_yuv: planar frames need an even size, got (", oh, ", ", ow, ")");
+  return {x.size(0), nf, oh * ow * 3 / 2 * (format == TC_PIXFMT_P010 ? 2 : 1)};
+}
+
+Tensor frames_to_yuv_cuda(const Tensor& x, int64_t oh, int64_t ow, int64_t format, int64_t f0, int64_t nf, int64_t siting,
+                          at::IntArrayRef m, const optional<Tensor>& h_bounds, const optional<Tensor>& h_coefs,
+                          const optional<Tensor>& v_bounds, const optional<Tensor>& v_coefs) {
+  TORCH_CHECK(x.is_cuda(), "frames_to_yuv: expected a CUDA tensor (the product path is GPU-only)");
+  TORCH_CHECK(x.scalar_type() == at::kFloat && x.is_contiguous(), "frames_to_yuv: contiguous fp32 (b, 3, t, h, w)");
+  Tensor out = at::empty(frames_to_yuv_shape(x, oh, ow, format, f0, nf, siting, m), x.options().dtype(at::kByte));
+  TcFramesYuvOutParams p = {};
+  p.x = x.data_ptr<float>(); p.out = out.data_ptr();
+  p.b = (int32_t)x.size(0); p.t = (int32_t)x.size(2); p.h = (int32_t)x.size(3); p.w = (int32_t)x.size(4);
+  p.f0 = (int32_t)f0; p.nf = (int32_t)nf; p.oh = (int32_t)oh; p.ow = (int32_t)ow; p.format = (int32_t)format;
+  p.pitch = (int32_t)(format == TC_PIXFMT_P010 ? 2 * ow : ow);
+  p.frame_stride = out.stride(1); p.clip_stride = out.stride(0);
+  p.siting = (int32_t)siting;
+  for (int i = 0; i < 11; ++i) p.m[i] = (int32_t)m[i];
+  const ResizeAxis ah = resize_axis(h_bounds, h_coefs, p.w, p.ow, "frames_to_yuv", "horizontal");
+  const ResizeAxis av = resize_axis(v_bounds, v_coefs, p.h, p.oh, "frames_to_yuv", "vertical");
+  p.h_bounds = ah.bounds; p.h_coefs = ah.coefs; p.h_kmax = ah.kmax;
+  p.v_bounds = av.bounds; p.v_coefs = av.coefs; p.v_kmax = av.kmax;
+  p.workspace_bytes = tc_frames_to_yuv_workspace(&p);
+  Tensor ws = workspace(p.workspace_bytes, out);
+  p.workspace = ws.data_ptr();
+  check_rc(tc_frames_to_yuv(&p, cur_stream()), "tc_frames_to_yuv");
+  return out;
+}
+
+Tensor frames_to_yuv_meta(const Tensor& x, int64_t oh, int64_t ow, int64_t format, int64_t f0, int64_t nf, int64_t siting,
+                          at::IntArrayRef m, const optional<Tensor>&, const optional<Tensor>&, const optional<Tensor>&,
+                          const optional<Tensor>&) {
+  return at::empty(frames_to_yuv_shape(x, oh, ow, format, f0, nf, siting, m), x.options().dtype(at::kByte));
+}
+
 // clip_patches: (B, 3, H, W) fp32 -> the bf16 A operand [B * (size / patch)^2, ld] of the CLIP image tower's patch-embedding GEMM
 // (reference condition.py:322-330: kornia resize, (x + 1) / 2, CLIP mean / std; then open_clip's conv1 unfold)
 Tensor clip_patches_cuda(const Tensor& x, int64_t size, int64_t patch, int64_t ld, at::ArrayRef<double> mean, at::ArrayRef<double> std,
@@ -764,6 +809,8 @@ TORCH_LIBRARY(tooncrafter, m) {
         "Tensor? h_bounds, Tensor? h_coefs, Tensor? v_bounds, Tensor? v_coefs) -> Tensor");
   m.def("frames_to_u8(Tensor x, int oh, int ow, int format, int f0, int nf, Tensor? h_bounds, Tensor? h_coefs, Tensor? v_bounds, "
         "Tensor? v_coefs) -> Tensor");
+  m.def("frames_to_yuv(Tensor x, int oh, int ow, int format, int f0, int nf, int siting, int[] m, Tensor? h_bounds, Tensor? h_coefs, "
+        "Tensor? v_bounds, Tensor? v_coefs) -> Tensor");
   m.def("clip_patches(Tensor x, int size, int patch, int ld, float[] mean, float[] std, bool antialias) -> Tensor");
   m.def("randn_clips(int[] seeds, int[] shape, int stream, float scale, bool raw) -> Tensor");
   m.def("abi_version() -> int");
@@ -789,6 +836,7 @@ TORCH_LIBRARY_IMPL(tooncrafter, CUDA, m) {
   m.impl("frames_from_u8", frames_from_u8_cuda);
   m.impl("frames_from_yuv", frames_from_yuv_cuda);
   m.impl("frames_to_u8", frames_to_u8_cuda);
+  m.impl("frames_to_yuv", frames_to_yuv_cuda);
   m.impl("clip_patches", clip_patches_cuda);
   m.impl("randn_clips", randn_clips_cuda);
   m.impl("ff_geglu_fused", ff_geglu_fused_cuda);
@@ -811,6 +859,7 @@ TORCH_LIBRARY_IMPL(tooncrafter, Meta, m) {
   m.impl("frames_from_u8", frames_from_u8_meta);
   m.impl("frames_from_yuv", frames_from_yuv_meta);
   m.impl("frames_to_u8", frames_to_u8_meta);
+  m.impl("frames_to_yuv", frames_to_yuv_meta);
   m.impl("clip_patches", clip_patches_meta);
   m.impl("randn_clips", randn_clips_meta);
   m.impl("ff_geglu_fused", ff_geglu_fused_meta);

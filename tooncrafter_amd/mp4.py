@@ -9,13 +9,14 @@ is an IDR picture.  The stream is lossless with respect to the yuv420p conversio
 
 Bitstream (all numbers refer to H.264 clauses):
   SPS 7.3.2.1.1: profile_idc 66, level 5.1, pic_order_cnt_type 2, max_num_ref_frames 1, frame_mbs_only, cropping to the
-                 true size when width / height are not multiples of 16.
+                 true size when width / height are not multiples of 16; with a `colour`, VUI (E.1.1) carrying the video
+                 signal type (range, primaries / transfer / matrix) and the chroma sample location, nothing else.
   PPS 7.3.2.2:   CAVLC, one slice group, deblocking_filter_control_present (the slices switch the loop filter off).
   IDR slice 7.3.3 + 7.3.4: slice_type 7 (I), per macroblock `mb_type` = ue(25) (I_PCM, table 7-11), zero bits up to the
                  byte boundary, 256 luma + 64 Cb + 64 Cr bytes; rbsp_slice_trailing_bits.
   NAL 7.3.1 / 7.4.1: emulation prevention (00 00 0x -> 00 00 03 0x).
 Container (ISO/IEC 14496-12 / -15): ftyp, moov (mvhd, trak: tkhd, mdia: mdhd, hdlr, minf: vmhd, dinf, stbl: stsd with
-avc1 + avcC, stts, stsc, stsz, stco), mdat with 4-byte length-prefixed NAL units, one sample per chunk.
+avc1 + avcC (+ colr / nclx with a `colour`), stts, stsc, stsz, stco), mdat with 4-byte length-prefixed NAL units, one sample per chunk.
 """
 from __future__ import annotations
 
@@ -62,7 +63,19 @@ def _nal(ref_idc: int, unit_type: int, rbsp: bytes) -> bytes:
     return bytes([(ref_idc << 5) | unit_type]) + body
 
 
-def _sps(width: int, height: int) -> bytes:
+def _colour_codes(colour):
+    """(primaries, transfer, matrix, full range flag, chroma_sample_loc_type) of an `output.Colour` (H.264 tables E-3 .. E-5,
+    figure E-1): BT.709 is 1 / 1 / 1, BT.601 6 / 6 / 6 (SMPTE 170M); loc type 0 is left siting, 1 centre.  8 bit only: the
+    I_PCM samples here are bytes."""
+    if any(not hasattr(colour, a) for a in ("standard", "range", "siting", "bits")):
+        raise ValueError(f"colour: expected an output.Colour, got {type(colour).__name__}")
+    if colour.bits != 8:
+        raise ValueError(f"colour: {colour.bits}-bit planes do not fit this stream (8-bit I_PCM samples)")
+    code = {"bt709": 1, "bt601": 6}[colour.standard]
+    return code, code, code, {"limited": 0, "full": 1}[colour.range], {"left": 0, "center": 1}[colour.siting]
+
+
+def _sps(width: int, height: int, colour=None) -> bytes:
     mbw, mbh = (width + 15) // 16, (height + 15) // 16
     b = _Bits()
     b.u(8, 66)                                  # profile_idc: Baseline
@@ -85,7 +98,21 @@ def _sps(width: int, height: int) -> bytes:
         b.ue(0); b.ue(crop_r // 2); b.ue(0); b.ue(crop_b // 2)      # in chroma sample units (CropUnit = 2)
     else:
         b.u(1, 0)
-    b.u(1, 0)                                   # vui_parameters_present_flag
+    if colour is None:
+        b.u(1, 0)                               # vui_parameters_present_flag
+    else:
+        primaries, transfer, matrix, full, loc = _colour_codes(colour)
+        b.u(1, 1)                               # vui_parameters_present_flag; vui_parameters() E.1.1:
+        b.u(1, 0); b.u(1, 0)                    # aspect_ratio_info_present_flag, overscan_info_present_flag
+        b.u(1, 1)                               # video_signal_type_present_flag
+        b.u(3, 5); b.u(1, full)                 # video_format 5 (unspecified), video_full_range_flag
+        b.u(1, 1)                               # colour_description_present_flag
+        b.u(8, primaries); b.u(8, transfer); b.u(8, matrix)
+        b.u(1, 1)                               # chroma_loc_info_present_flag
+        b.ue(loc); b.ue(loc)                    # chroma_sample_loc_type_top_field / _bottom_field
+        b.u(1, 0)                               # timing_info_present_flag
+        b.u(1, 0); b.u(1, 0)                    # nal_hrd_parameters_present_flag, vcl_hrd_parameters_present_flag
+        b.u(1, 0); b.u(1, 0)                    # pic_struct_present_flag, bitstream_restriction_flag
     b.trailing()
     return _nal(3, 7, b.bytes())
 
@@ -157,9 +184,9 @@ def _full(kind: bytes, version: int, flags: int, payload: bytes) -> bytes:
 _MATRIX = struct.pack(">9I", 0x10000, 0, 0, 0, 0x10000, 0, 0, 0, 0x40000000)
 
 
-def encode_h264_ipcm_yuv(y: np.ndarray, cb: np.ndarray, cr: np.ndarray):
+def encode_h264_ipcm_yuv(y: np.ndarray, cb: np.ndarray, cr: np.ndarray, colour=None):
     """y: (t, h, w), cb / cr: (t, h / 2, w / 2) uint8 planes, put into the stream as they are
-    -> (sps NAL, pps NAL, [one IDR NAL per frame])."""
+    -> (sps NAL, pps NAL, [one IDR NAL per frame]).  colour: what the planes are, for the SPS's VUI."""
     y, cb, cr = (np.asarray(v) for v in (y, cb, cr))
     if y.ndim != 3 or any(v.dtype != np.uint8 for v in (y, cb, cr)):
         raise ValueError("planes must be (t, rows, columns) uint8")
@@ -177,7 +204,7 @@ def encode_h264_ipcm_yuv(y: np.ndarray, cb: np.ndarray, cr: np.ndarray):
             cbi = np.pad(cbi, ((0, (ph - h) // 2), (0, (pw - w) // 2)), mode="edge")
             cri = np.pad(cri, ((0, (ph - h) // 2), (0, (pw - w) // 2)), mode="edge")
         slices.append(_idr_slice(yi, cbi, cri, i & 1))
-    return _sps(w, h), _pps(), slices
+    return _sps(w, h, colour), _pps(), slices
 
 
 def encode_h264_ipcm(frames: np.ndarray):
@@ -201,9 +228,13 @@ def write_mp4(path: str, frames, fps: int = 8) -> str:
     return _write_container(path, *encode_h264_ipcm(frames), t, h, w, fps)
 
 
-def write_mp4_i420(path: str, planes, width: int, height: int, fps: int = 8) -> str:
+def write_mp4_i420(path: str, planes, width: int, height: int, fps: int = 8, colour=None) -> str:
     """planes: (t, height * width * 3 / 2) uint8, every frame packed I420 (Y, then Cb, then Cr: what the pixel back end's
-    fmt="i420" returns; numpy array or torch tensor on the CPU) -> an H.264 .mp4 at `path` holding exactly these samples."""
+    fmt="i420" returns; numpy array or torch tensor on the CPU) -> an H.264 .mp4 at `path` holding exactly these samples.
+    colour: the `output.Colour` the planes were written in (8 bit); the stream then says so -- range, primaries / transfer /
+    matrix and chroma sample location in the SPS's VUI, the same codes in a `colr` box.  None: neither, as before (a player
+    then assumes its defaults: left siting, and a matrix guessed from the size)."""
+    codes = None if colour is None else _colour_codes(colour)
     planes = np.ascontiguousarray(planes.numpy() if hasattr(planes, "numpy") else planes)
     w, h = int(width), int(height)
     if h <= 0 or w <= 0 or h % 2 or w % 2:
@@ -214,11 +245,12 @@ def write_mp4_i420(path: str, planes, width: int, height: int, fps: int = 8) -> 
     y = planes[:, :n].reshape(t, h, w)
     cb = planes[:, n:n + n // 4].reshape(t, h // 2, w // 2)
     cr = planes[:, n + n // 4:].reshape(t, h // 2, w // 2)
-    return _write_container(path, *encode_h264_ipcm_yuv(y, cb, cr), t, h, w, fps)
+    return _write_container(path, *encode_h264_ipcm_yuv(y, cb, cr, colour), t, h, w, fps, codes)
 
 
-def _write_container(path: str, sps: bytes, pps: bytes, slices, t: int, h: int, w: int, fps: int) -> str:
-    """One avc1 track of `t` IDR pictures of w x h in an ISO base media file."""
+def _write_container(path: str, sps: bytes, pps: bytes, slices, t: int, h: int, w: int, fps: int, colour_codes=None) -> str:
+    """One avc1 track of `t` IDR pictures of w x h in an ISO base media file.  colour_codes: `_colour_codes` for a `colr` box
+    of type nclx in the sample entry (ISO/IEC 14496-12 12.1.5)."""
     samples = [struct.pack(">I", len(n)) + n for n in slices]           # AVCC: 4-byte NAL lengths
     timescale, delta = int(fps) * 1000, 1000
     duration = t * delta
@@ -227,7 +259,8 @@ def _write_container(path: str, sps: bytes, pps: bytes, slices, t: int, h: int, 
         bytes([1]) + struct.pack(">H", len(pps)) + pps
     avc1 = _box(b"avc1", b"\x00" * 6 + struct.pack(">H", 1) + b"\x00" * 16 + struct.pack(">HH", w, h) +
                 struct.pack(">II", 0x00480000, 0x00480000) + b"\x00" * 4 + struct.pack(">H", 1) + b"\x00" * 32 +
-                struct.pack(">Hh", 0x0018, -1) + _box(b"avcC", avcc))
+                struct.pack(">Hh", 0x0018, -1) + _box(b"avcC", avcc) +
+                (b"" if colour_codes is None else _box(b"colr", b"nclx" + struct.pack(">HHHB", *colour_codes[:3], colour_codes[3] << 7))))
     ftyp = _box(b"ftyp", b"isom" + struct.pack(">I", 0x200) + b"isomiso2avc1mp41")
     sizes = [len(s) for s in samples]
 

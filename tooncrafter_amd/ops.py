@@ -969,27 +969,28 @@ class HipOps:
         return out
 
     @staticmethod
-    def _frames_out_args(x, size, filter, fmt, frames):
-        """The checked request of frames_to_u8: (oh, ow, format code, f0, nf, bytes of a packed row, bytes of a packed frame)."""
+    def _frames_out_args(x, size, filter, fmt, frames, what="frames_to_u8"):
+        """The checked request of frames_to_u8 (or of `what`, which shares its rules): (oh, ow, format code, f0, nf, bytes of a
+        packed row, bytes of a packed frame)."""
         if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
-            raise ValueError(f"frames_to_u8: x: expected an fp32 tensor, got {getattr(x, 'dtype', type(x))}")
+            raise ValueError(f"{what}: x: expected an fp32 tensor, got {getattr(x, 'dtype', type(x))}")
         if x.dim() != 5 or x.shape[1] != 3 or 0 in x.shape:
-            raise ValueError(f"frames_to_u8: x must be (b, 3, t, h, w), got {tuple(x.shape)}")
+            raise ValueError(f"{what}: x must be (b, 3, t, h, w), got {tuple(x.shape)}")
         if fmt not in _lib.TC_PIXFMTS:
-            raise ValueError(f"frames_to_u8: fmt {fmt!r}: one of {sorted(_lib.TC_PIXFMTS)}")
+            raise ValueError(f"{what}: fmt {fmt!r}: one of {sorted(_lib.TC_PIXFMTS)}")
         if filter not in _lib.TC_RESIZE_FILTERS:
-            raise ValueError(f"frames_to_u8: filter {filter!r}: one of {sorted(_lib.TC_RESIZE_FILTERS)}")
+            raise ValueError(f"{what}: filter {filter!r}: one of {sorted(_lib.TC_RESIZE_FILTERS)}")
         t, h, w = x.shape[2:]
         oh, ow = (h, w) if size is None else (int(v) for v in size)
         if oh <= 0 or ow <= 0:
-            raise ValueError(f"frames_to_u8: size {(oh, ow)}")
+            raise ValueError(f"{what}: size {(oh, ow)}")
         f0, nf = (0, t) if frames is None else (int(v) for v in frames)
         if f0 < 0 or nf < 1 or f0 + nf > t:
-            raise ValueError(f"frames_to_u8: frames (first, count) = {(f0, nf)} outside a clip of {t}")
+            raise ValueError(f"{what}: frames (first, count) = {(f0, nf)} outside a clip of {t}")
         if fmt != "rgb24" and (oh % 2 or ow % 2):
-            raise ValueError(f"frames_to_u8: {fmt} needs an even size, got {(oh, ow)}")
+            raise ValueError(f"{what}: {fmt} needs an even size, got {(oh, ow)}")
         if not x.is_cuda:
-            raise _lib.TooncrafterHipError("frames_to_u8: x: expected a CUDA tensor: the product path is GPU-only")
+            raise _lib.TooncrafterHipError(f"{what}: x: expected a CUDA tensor: the product path is GPU-only")
         row = 3 * ow if fmt == "rgb24" else ow
         return oh, ow, _lib.TC_PIXFMTS[fmt], f0, nf, row, row * oh if fmt == "rgb24" else oh * ow * 3 // 2
 
@@ -1024,6 +1025,66 @@ class HipOps:
             raise ValueError(f"frames_to_u8: strides (pitch, frame, clip) = {(pitch, frame_stride, clip_stride)} do not fit {b} x {nf} "
                              f"frames of {used} bytes into an out of {out.numel()} bytes")
         self._launch("tc_frames_to_u8", p, x.device)
+        return out
+
+    def yuv_out_matrix(self, standard="bt601", range="limited", bits=8):
+        """The eleven integers {yr, yg, yb, ur, ug, ub, vr, vg, vb, yoff, coff} of an RGB -> YCbCr conversion
+        (tc_yuv_out_matrix; host only): standard "bt601" | "bt709", range "limited" | "full", bits 8 | 10 (10: for the 16-bit
+        RGB of the P010 path)."""
+        if standard not in _lib.TC_YUV_STANDARDS or range not in _lib.TC_YUV_RANGES:
+            raise ValueError(f"yuv_out_matrix: standard {standard!r} (one of {sorted(_lib.TC_YUV_STANDARDS)}), "
+                             f"range {range!r} (one of {sorted(_lib.TC_YUV_RANGES)})")
+        m = (C.c_int32 * 11)()
+        _lib.check(self.lib.tc_yuv_out_matrix(_lib.TC_YUV_STANDARDS[standard], _lib.TC_YUV_RANGES[range], int(bits), m),
+                   "tc_yuv_out_matrix")
+        return list(m)
+
+    def _frames_yuv_out_args(self, x, size, filter, fmt, colour, frames):
+        """The checked request of frames_to_yuv: _frames_out_args' tuple with P010's format code and doubled bytes for a 10-bit
+        colour, then the matrix and the siting code."""
+        what = "frames_to_yuv"
+        if any(not hasattr(colour, a) for a in ("standard", "range", "siting", "bits")):
+            raise ValueError(f"{what}: colour: expected an output.Colour, got {type(colour).__name__}")
+        if fmt not in ("i420", "nv12"):
+            raise ValueError(f"{what}: fmt {fmt!r}: a colour describes planar frames, 'i420' or 'nv12'")
+        if colour.siting not in ("center", "left"):
+            raise ValueError(f"{what}: siting {colour.siting!r}: chroma is produced 'center' or 'left'")
+        if colour.bits not in (8, 10) or (colour.bits == 10 and fmt != "nv12"):
+            raise ValueError(f"{what}: bits {colour.bits!r} with {fmt}: 8, or 10 with 'nv12' (P010)")
+        oh, ow, code, f0, nf, row, frame = self._frames_out_args(x, size, filter, fmt, frames, what)
+        m = self.yuv_out_matrix(colour.standard, colour.range, colour.bits)
+        if colour.bits == 10:
+            code, row, frame = _lib.TC_YUV_FORMATS["p010"], 2 * row, 2 * frame
+        return oh, ow, code, f0, nf, row, frame, m, _lib.TC_CHROMA_SITINGS[colour.siting]
+
+    def frames_to_yuv(self, x, size=None, filter="bicubic", fmt="nv12", colour=None, frames=None, out=None, strides=None):
+        """frames_to_u8 for planar frames in a named colour (tc_frames_to_yuv): `colour` (an `output.Colour`) picks the integer
+        RGB -> YCbCr matrix (standard, range), where the chroma samples sit ("center": 2 x 2 means; "left": H.264's default) and
+        the depth -- bits 8 writes fmt "i420" / "nv12", bits 10 (fmt "nv12" only) P010: 16-bit words, code << 6, from a 16-bit
+        RGB intermediate.  size / filter / frames / out / strides (bytes) as in frames_to_u8.
+        Returns a new uint8 (b, nf, oh * ow * 3 / 2) tensor, (b, nf, oh * ow * 3) bytes for P010, or `out`."""
+        oh, ow, code, f0, nf, row, frame, m, siting = self._frames_yuv_out_args(x, size, filter, fmt, colour, frames)
+        x = x.contiguous()
+        b, _, t, h, w = x.shape
+        pitch, frame_stride, clip_stride = (row, frame, nf * frame) if strides is None else (int(v) for v in strides)
+        if out is None:
+            if strides is not None:
+                raise ValueError("frames_to_yuv: strides describe an `out` buffer")
+            out = torch.empty((b, nf, frame), dtype=torch.uint8, device=x.device)
+        else:
+            _dev(out, torch.uint8, "frames_to_yuv: out")
+            if out.device != x.device:
+                raise ValueError(f"frames_to_yuv: out is on {out.device}, x on {x.device}")
+        p = _lib.TcFramesYuvOutParams(x=x.data_ptr(), out=out.data_ptr(), b=b, t=t, h=h, w=w, f0=f0, nf=nf, oh=oh, ow=ow, format=code,
+                                      pitch=pitch, frame_stride=frame_stride, clip_stride=clip_stride, siting=siting,
+                                      m=(C.c_int32 * 11)(*m))
+        self._set_tables(p, self._axis_tables(filter, w, ow, x.device) + self._axis_tables(filter, h, oh, x.device))
+        used = pitch * oh + (2 * (pitch // 2) * (oh // 2) if fmt == "i420" else pitch * (oh // 2))     # the header's frame bytes
+        if pitch < row or frame_stride < used or (b > 1 and clip_stride < nf * frame_stride) or \
+                (b - 1) * clip_stride + (nf - 1) * frame_stride + used > out.numel():
+            raise ValueError(f"frames_to_yuv: strides (pitch, frame, clip) = {(pitch, frame_stride, clip_stride)} do not fit {b} x {nf} "
+                             f"frames of {used} bytes into an out of {out.numel()} bytes")
+        self._launch("tc_frames_to_yuv", p, x.device)
         return out
 
     def clip_patches(self, x, *, size, patch, ld, mean, std, antialias=True):

@@ -14,6 +14,7 @@ after the yuv420p conversion where libx264 at crf 10 is not.
 from __future__ import annotations
 
 import os
+from dataclasses import dataclass
 from typing import Callable, List, Optional
 
 import numpy as np
@@ -23,12 +24,50 @@ from . import dist as tdist
 from . import ops
 
 
-def clip_to_uint8(samples: torch.Tensor, loop: bool = False, size=None, filter: str = "bicubic", fmt: str = "rgb24") -> torch.Tensor:
+@dataclass(frozen=True)
+class Colour:
+    """How planar frames describe their colour: `standard` "bt601" | "bt709" (the RGB <-> YCbCr matrix), `range` "limited" |
+    "full", `siting` "center" (chroma = 2 x 2 means) | "left" (H.264 / HEVC chroma_sample_loc_type 0, what a stream without
+    VUI means), `bits` 8 | 10 (10: P010 words).  The `colour=` / `out_colour=` keywords of the output path take one
+    (tc_frames_to_yuv); `mp4.write_mp4_i420` writes it into the stream.  Anything else raises ValueError here."""
+    standard: str = "bt601"
+    range: str = "limited"
+    siting: str = "center"
+    bits: int = 8
+
+    def __post_init__(self):
+        for name, value, allowed in (("standard", self.standard, ("bt601", "bt709")), ("range", self.range, ("limited", "full")),
+                                     ("siting", self.siting, ("center", "left")), ("bits", self.bits, (8, 10))):
+            if isinstance(value, bool) or value not in allowed:
+                raise ValueError(f"Colour: {name} {value!r}: one of {allowed}")
+
+    @staticmethod
+    def of(planes) -> "Colour":
+        """The colour a `clip.Planes` carries: its standard / range / siting, 10 bits when its fmt is "p010".  A custom `matrix`
+        names no standard and "nearest" is no way to produce chroma: both raise ValueError."""
+        if any(not hasattr(planes, a) for a in ("standard", "range", "siting", "fmt", "matrix")):
+            raise ValueError(f"Colour.of: expected a Planes, got {type(planes).__name__}")
+        if planes.matrix is not None:
+            raise ValueError("Colour.of: the planes carry a custom matrix, which names no standard to write")
+        return Colour(planes.standard, planes.range, planes.siting, 10 if planes.fmt == "p010" else 8)
+
+
+def clip_to_uint8(samples: torch.Tensor, loop: bool = False, size=None, filter: str = "bicubic", fmt: str = "rgb24",
+                  colour: Optional[Colour] = None) -> torch.Tensor:
     """(b, 3, t, h, w) fp32 -> (b, t, h, w, 3) uint8 on the device of `samples`
     (inference.py:146-153; `loop` drops the last frame, :146-147).
     size = (oh, ow) and / or fmt "i420" | "nv12": the pixel back end (tc_frames_to_u8) instead -- PIL's 8-bit resample with
     `filter` to the delivery size, then packed RGB (b, t, oh, ow, 3) or the planes an encoder takes, (b, t, oh * ow * 3 / 2);
-    `loop` is then a frame count, not a slice."""
+    `loop` is then a frame count, not a slice.
+    colour: a `Colour` for the planes instead of the default BT.601 limited range with centre siting (tc_frames_to_yuv); fmt
+    must then be "i420" or "nv12", and bits=10 ("nv12" only) gives P010, (b, t, oh * ow * 3) bytes
+    (`clip.planes_from_frames` views them)."""
+    if colour is not None:
+        if not isinstance(colour, Colour):
+            raise ValueError(f"clip_to_uint8: colour: expected a Colour, got {type(colour).__name__}")
+        t = samples.shape[2]
+        return ops.frames_to_yuv(samples.to(torch.float32), size=size, filter=filter, fmt=fmt, colour=colour,
+                                 frames=(0, t - 1 if loop else t))
     if size is None and fmt == "rgb24":
         if loop:
             samples = samples[:, :, :-1]
@@ -37,9 +76,10 @@ def clip_to_uint8(samples: torch.Tensor, loop: bool = False, size=None, filter: 
     return ops.frames_to_u8(samples.to(torch.float32), size=size, filter=filter, fmt=fmt, frames=(0, t - 1 if loop else t))
 
 
-def planar_writer(width: int, height: int, fmt: str = "i420") -> Callable[[str, torch.Tensor, int], str]:
+def planar_writer(width: int, height: int, fmt: str = "i420", colour: Optional[Colour] = None) -> Callable[[str, torch.Tensor, int], str]:
     """A writer for the planar frames (t, height * width * 3 / 2) of clip_to_uint8(fmt="i420" | "nv12"): the planes go into the
-    I_PCM stream of mp4.py as they are (no colour conversion on the host)."""
+    I_PCM stream of mp4.py as they are (no colour conversion on the host).  `colour`: what the planes are, written into the
+    stream (8 bit only: `write_mp4_i420`)."""
     from .mp4 import write_mp4_i420
 
     def write(path: str, planes: torch.Tensor, fps: int) -> str:
@@ -48,7 +88,8 @@ def planar_writer(width: int, height: int, fmt: str = "i420") -> Callable[[str, 
             n = width * height
             uv = planes[:, n:].reshape(len(planes), -1, 2)
             planes = np.concatenate([planes[:, :n], uv[:, :, 0], uv[:, :, 1]], axis=1)
-        return write_mp4_i420(path, planes, width, height, fps)
+        return write_mp4_i420(path, planes, width, height, fps) if colour is None else \
+            write_mp4_i420(path, planes, width, height, fps, colour=colour)
     return write
 
 
@@ -72,17 +113,19 @@ def default_writer(path: str, frames: torch.Tensor, fps: int) -> str:
 
 def save_results_seperate(prompt, samples, filename, fakedir, fps=10, loop=False,
                           writer: Optional[Callable[[str, torch.Tensor, int], str]] = None,
-                          size=None, filter: str = "bicubic", fmt: str = "rgb24") -> List[str]:
+                          size=None, filter: str = "bicubic", fmt: str = "rgb24", colour: Optional[Colour] = None) -> List[str]:
     """Reference signature (inference.py:135) plus an optional `writer(path, frames_thwc_u8, fps)` and the pixel back end's
-    keywords (clip_to_uint8): with a planar `fmt` the writer gets (t, oh * ow * 3 / 2) planes, by default planar_writer's."""
+    keywords (clip_to_uint8): with a planar `fmt` the writer gets (t, oh * ow * 3 / 2) planes, by default planar_writer's,
+    which writes `colour` into the stream (a 10-bit colour needs a `writer` of the caller's: the .mp4 here is 8 bit)."""
     prompt = prompt[0] if isinstance(prompt, list) else prompt
     if samples is None:
         return []
     if fmt != "rgb24":
         oh, ow = samples.shape[3:] if size is None else size
-        writer = writer or planar_writer(int(ow), int(oh), fmt)
+        writer = writer or (planar_writer(int(ow), int(oh), fmt) if colour is None else planar_writer(int(ow), int(oh), fmt, colour))
     writer = writer or default_writer
-    frames = clip_to_uint8(samples.detach(), loop=loop, size=size, filter=filter, fmt=fmt).cpu()
+    frames = (clip_to_uint8(samples.detach(), loop=loop, size=size, filter=filter, fmt=fmt) if colour is None else
+              clip_to_uint8(samples.detach(), loop=loop, size=size, filter=filter, fmt=fmt, colour=colour)).cpu()
     outdir = fakedir.replace('samples', 'samples_separate')
     os.makedirs(outdir, exist_ok=True)
     written = []
@@ -92,8 +135,11 @@ def save_results_seperate(prompt, samples, filename, fakedir, fps=10, loop=False
     return written
 
 
-def gather_frames(samples: torch.Tensor, dst: int = 0, loop: bool = False, size=None, filter: str = "bicubic", fmt: str = "rgb24"):
+def gather_frames(samples: torch.Tensor, dst: int = 0, loop: bool = False, size=None, filter: str = "bicubic", fmt: str = "rgb24",
+                  colour: Optional[Colour] = None):
     """Multi-GPU writer side: convert on every rank, gather the uint8 frames to `dst` (one RCCL gather,
     7.9 MB per 16-frame clip instead of 31.5 MB fp32; half of that, 1.5 bytes per pixel, with fmt "i420" / "nv12").
-    Returns the per-rank list on `dst`, None elsewhere."""
-    return tdist.gather_clips(clip_to_uint8(samples, loop=loop, size=size, filter=filter, fmt=fmt), dst=dst)
+    `colour` as in clip_to_uint8.  Returns the per-rank list on `dst`, None elsewhere."""
+    if colour is None:
+        return tdist.gather_clips(clip_to_uint8(samples, loop=loop, size=size, filter=filter, fmt=fmt), dst=dst)
+    return tdist.gather_clips(clip_to_uint8(samples, loop=loop, size=size, filter=filter, fmt=fmt, colour=colour), dst=dst)

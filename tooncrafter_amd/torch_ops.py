@@ -177,6 +177,14 @@ class TorchLibOps(HipOps):
         return self.t.frames_to_u8(x.contiguous(), oh, ow, code, f0, nf, *self._axis_tables(filter, w, ow, x.device),
                                    *self._axis_tables(filter, h, oh, x.device))
 
+    def frames_to_yuv(self, x, size=None, filter="bicubic", fmt="nv12", colour=None, frames=None, out=None, strides=None):
+        if out is not None or strides is not None:          # an explicit result buffer with its strides: the ctypes method
+            return super().frames_to_yuv(x, size, filter, fmt, colour, frames, out=out, strides=strides)
+        oh, ow, code, f0, nf, _, _, m, siting = self._frames_yuv_out_args(x, size, filter, fmt, colour, frames)
+        h, w = x.shape[3:]
+        return self.t.frames_to_yuv(x.contiguous(), oh, ow, code, f0, nf, siting, m, *self._axis_tables(filter, w, ow, x.device),
+                                    *self._axis_tables(filter, h, oh, x.device))
+
     def clip_patches(self, x, *, size, patch, ld, mean, std, antialias=True):
         return self.t.clip_patches(x, int(size), int(patch), int(ld), [float(v) for v in mean], [float(v) for v in std], bool(antialias))
 
