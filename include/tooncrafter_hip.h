@@ -788,6 +788,82 @@ typedef struct TcFramesYuvOutParams {
 int64_t tc_frames_to_yuv_workspace(const TcFramesYuvOutParams* p);
 int tc_frames_to_yuv(const TcFramesYuvOutParams* p, void* stream);
 
+/* ---- Colour match: decoded frames to their keyframes, on the device (additive within ABI 14: two structs, three symbols).
+ * The decoder's frames drift in colour and contrast away from the keyframes they interpolate; this is the linear colour
+ * transfer that workflows around the model run on the host (mean / std transfer, or the Monge-Kantorovich linear map), as
+ * one reduction, one 3 x 3 solve per frame and one affine pass, without a synchronisation.  THE RULE, stated once (its
+ * float64 restatement for the tests: tests/colour_match_ref.py):
+ *
+ * All statistics are taken of c = clamp(x, -1, 1): what the output path shows (tc_video_to_u8 clamps to it).
+ *
+ * Frame statistics: TC_COLOUR_STATS = 9 doubles per frame over its n = h * w pixels, in this order:
+ *   sum r, sum g, sum b, sum rr, sum rg, sum rb, sum gg, sum gb, sum bb.
+ * Products are formed in double (exact: both factors are fp32); sums are in double in an order fixed by h * w alone: the
+ * frame is cut into P = min(64, ceil(h * w / 2048)) parts of 256 threads, thread j of part p adds pixels 4 q .. 4 q + 3 for
+ * q = p * 256 + j, then q + 256 P, ..., in that order; the 64 lanes of a wave are added by an xor tree (32, 16, .. 1), the four
+ * waves in index order, and the P per-part sums (in the workspace) in index order.  No atomics.  A frame's nine numbers
+ * therefore do not depend on b, on the batch slot, on the alignment of x or on which other frames are requested.
+ * From the sums: m = S1 / n, C = S2 / n - m m^T (symmetric 3 x 3).
+ *
+ * Target of frame f of a t-frame clip.  Every clip has two reference images with statistics (m0, C0), (m1, C1) over
+ * ref_pixels pixels each:  w = f / (t - 1) (0 when t = 1),  m_t = (1 - w) m0 + w m1,  C_t = (1 - w) C0 + w C1.  Frame 0 is
+ * matched to the first keyframe and frame t - 1 to the last, with a linear course between (a convex combination of
+ * covariances is a covariance).
+ *
+ * Regularisation: eps = 2^-16 in value^2 units (about half an 8-bit code value squared), added to every diagonal that is
+ * inverted or rooted, on the source and on the target side.
+ *
+ * Map of frame f, with (m_s, C_s) the frame's own statistics; every step in double:
+ *   TC_COLOUR_MEAN_STD  A = diag(sqrt((C_t[k][k] + eps) / (C_s[k][k] + eps)));
+ *   TC_COLOUR_MKL       S = C_s + eps I, T = C_t + eps I,  A = S^(-1/2) (S^(1/2) T S^(1/2))^(1/2) S^(-1/2), the symmetric
+ *                       roots from an eigendecomposition of the 3 x 3 matrix: cyclic Jacobi, pairs (0,1), (0,2), (1,2), a
+ *                       fixed eight sweeps; eigenvalues of S are clamped below at eps / 2, those of the middle matrix at 0,
+ *                       and the middle matrix is symmetrised, (M + M^T) / 2, before it is decomposed;
+ *   o = m_t - A m_s;   with strength s in [0, 1]:  A' = I + s (A - I),  o' = s o.
+ * Each of the twelve numbers is rounded to fp32 once and written to coefs[frame][12]: A' row-major, then o'.
+ *
+ * Apply, in fp32, per pixel and output channel k, with r, g, b the CLAMPED inputs:
+ *   y_k = ((o'_k + A'_k0 r) + A'_k1 g) + A'_k2 b,
+ * every product and every sum rounded on its own (nothing contracted into an FMA), so that separate float32 operations on
+ * any host give the same bits.  y is NOT clamped: the back end clamps.  Exact consequences: strength 0 returns clamp(x);
+ * MEAN_STD of a frame against its own statistics returns clamp(x).
+ *
+ * Not offered: targets at inner frames, a colour space other than the model's RGB values, histogram matching, a gain limit
+ * (a frame that is flat where its keyframes are not gets a large gain by the rule above; strength is the only control). */
+#define TC_COLOUR_STATS 9
+typedef struct TcColourStatsParams {
+  const float* x;            /* (b, 3, t, h, w) fp32 */
+  int32_t b, t, h, w;
+  int32_t f0, nf, fstep;     /* frames f0, f0 + fstep, ... (nf of them) of every clip; nf = 1: fstep is ignored */
+  double* stats;             /* [b * nf][TC_COLOUR_STATS], 8-byte aligned */
+  void* workspace; int64_t workspace_bytes;
+} TcColourStatsParams;
+/* Statistics of the named frames: two launches (per-part sums, then their sum in index order).  h * w need not be a
+ * multiple of anything: 16-byte loads where every plane base allows them, 4-byte loads otherwise, the same order either way.
+ * workspace: b * nf * P * 9 doubles (0 for a request that is refused for anything but its workspace).
+ * TC_EINVAL: NULL p / x / stats, a size <= 0, nf <= 0, f0 outside [0, t), fstep < 1 with nf > 1, a frame past t - 1;
+ * TC_EALIGN: stats or workspace not 8-byte aligned; TC_EWORKSPACE: workspace NULL or too small; TC_ESHAPE: more than 2^31 - 1
+ * parts in all.  Nothing is launched or written on a refusal. */
+int64_t tc_colour_stats_workspace(const TcColourStatsParams* p);
+int tc_colour_stats(const TcColourStatsParams* p, void* stream);
+
+enum { TC_COLOUR_MEAN_STD = 0, TC_COLOUR_MKL = 1 };
+typedef struct TcColourMatchParams {
+  const float* x; float* out;   /* (b, 3, t, h, w); out may be EXACTLY x, any other overlap is TC_EINVAL */
+  int32_t b, t, h, w;
+  const double* src;            /* [b * t][9]: the statistics of x with f0 = 0, nf = t, fstep = 1 */
+  const double* ref;            /* [b * 2][9]: statistics of the two reference images of every clip */
+  int64_t ref_pixels;           /* pixels per reference image (need not be h * w) */
+  int32_t method; float strength;
+  float* coefs;                 /* [b * t][12] fp32, written by the call (required) */
+} TcColourMatchParams;
+/* The match: two launches (the coefficients, one thread per frame in double; then the apply pass).  No allocation, no
+ * synchronisation, no host read of device memory.
+ * TC_EINVAL: NULL p / x / out / src / ref / coefs, a size <= 0, an unknown method, a strength outside [0, 1] or not finite,
+ * ref_pixels <= 0, out overlapping x other than out == x; TC_EALIGN: src or ref not 8-byte aligned; TC_ESHAPE: more than
+ * 2^31 - 1 blocks in all.  Nothing is launched or written on a refusal. */
+int tc_colour_match(const TcColourMatchParams* p, void* stream);
+
 /* introspection */
 int tc_abi_version(void);
 const char* tc_build_info(void);

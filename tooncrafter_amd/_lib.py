@@ -192,6 +192,31 @@ class TcFramesYuvOutParams(C.Structure):
     _fields_ = TcFramesOutParams._fields_ + [("siting", C.c_int32), ("m", C.c_int32 * 11)]
 
 
+class TcColourStatsParams(C.Structure):
+    """Nine double sums per named frame of fp32 clips (tc_colour_stats; additive within ABI 14)."""
+    _fields_ = [
+        ("x", C.c_void_p),
+        ("b", C.c_int32), ("t", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+        ("f0", C.c_int32), ("nf", C.c_int32), ("fstep", C.c_int32),
+        ("stats", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+    ]
+
+
+class TcColourMatchParams(C.Structure):
+    """Frames matched in colour to two reference images per clip (tc_colour_match; additive within ABI 14)."""
+    _fields_ = [
+        ("x", C.c_void_p), ("out", C.c_void_p),
+        ("b", C.c_int32), ("t", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+        ("src", C.c_void_p), ("ref", C.c_void_p),
+        ("ref_pixels", C.c_int64),
+        ("method", C.c_int32), ("strength", C.c_float),
+        ("coefs", C.c_void_p),
+    ]
+
+
+TC_COLOUR_STATS = 9                                      # include/tooncrafter_hip.h: doubles per frame of tc_colour_stats
+TC_COLOUR_METHODS = {"mean_std": 0, "mkl": 1}            # TC_COLOUR_MEAN_STD / TC_COLOUR_MKL
 TC_YUV_FORMATS = {"i420": 1, "nv12": 2, "p010": 3}       # include/tooncrafter_hip.h: the TC_PIXFMT_* tc_frames_from_yuv reads
 TC_YUV_STANDARDS = {"bt601": 0, "bt709": 1}              # TC_YUV_BT*
 TC_YUV_RANGES = {"limited": 0, "full": 1}                # TC_YUV_LIMITED / TC_YUV_FULL
@@ -279,6 +304,9 @@ SYMBOLS = {
     "tc_yuv_out_matrix": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "tc_frames_to_yuv_workspace": (C.c_int64, [C.POINTER(TcFramesYuvOutParams)]),
     "tc_frames_to_yuv": (C.c_int, [C.POINTER(TcFramesYuvOutParams), C.c_void_p]),
+    "tc_colour_stats_workspace": (C.c_int64, [C.POINTER(TcColourStatsParams)]),
+    "tc_colour_stats": (C.c_int, [C.POINTER(TcColourStatsParams), C.c_void_p]),
+    "tc_colour_match": (C.c_int, [C.POINTER(TcColourMatchParams), C.c_void_p]),
     "tc_gemm_ws_eligible": (C.c_int, [C.POINTER(TcGemmParams)]),
     "tc_gemm_gn_rows": (C.c_int, [C.POINTER(TcGemmParams)]),
     "tc_groupnorm_part": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,

@@ -50,6 +50,9 @@ class Conditions:
     fs: torch.Tensor
     endpoints: Optional[torch.Tensor] = field(default=None, repr=False)    # (b, 4, t, h, w), frames 0 / t-1 filled
     three_way: bool = False              # sampler family (the reference picks it by flag, not by the branch's presence)
+    # (b, 3, 2, H, W): the pixels of the two keyframes at model size, what `match=` matches the decoded clip to (a small copy of
+    # frames 0 and t-1 of `videos`; without hold_endpoints both slots hold frame 0)
+    ends_px: Optional[torch.Tensor] = field(default=None, repr=False)
 
     @staticmethod
     def build(model, videos, *, prompts=None, fs=None, guided=True, three_way=False, image_branch=True, hold_endpoints=True,
@@ -91,7 +94,8 @@ class Conditions:
                     if branch is not None:
                         branch["c_concat"] = [canvas]
         fs_t = torch.full((b,), int(fs), dtype=torch.long, device=model.device) if not torch.is_tensor(fs) else fs
-        return Conditions(pos, neg, img_only, refs, fs_t, canvas, three_way)
+        ends_px = torch.stack([first, videos[:, :, t - 1] if hold_endpoints else first], dim=2)
+        return Conditions(pos, neg, img_only, refs, fs_t, canvas, three_way, ends_px)
 
     @staticmethod
     def from_uint8(model, first_u8, last_u8, *, size, t, **options):
@@ -341,32 +345,47 @@ def decode_spliced(model, latents, refs, marks=None):
     return video
 
 
+def _matched(video, cond, match):
+    """The decoded clip as it is (match None: nothing is called), or matched in colour to the keyframes of its conditions
+    (`output.match_colour`: tc_colour_stats twice, tc_colour_match)."""
+    if match is None:
+        return video
+    from .output import match_colour
+    return match_colour(video, cond.ends_px, match)
+
+
 def synthesize(model, videos, latent_shape, *, plan: SamplingPlan, prompts=None, fs=24, three_way=False, hold_endpoints=True,
-               variants=1, keyframes=None):
+               variants=1, keyframes=None, match=None):
     """(b, variants, 3, t, H, W) pixels in [-1, 1].  `keyframes`: {frame index: (b, 3, H, W) pixels} held in place between
     the endpoints while the rest is sampled (`pin_frames`; encoded once for all variants).  The concat conditioning stays
     endpoints-only: that is what the model was trained on.  With `plan.seeds`, variant k of clip i is the clip seeded
-    `variant_seed(plan.seeds[i], k)`: the same pixels as a `variants=1` run with that seed."""
+    `variant_seed(plan.seeds[i], k)`: the same pixels as a `variants=1` run with that seed.
+    match: an `output.ColourMatch` -- every decoded clip is matched in colour to frames 0 and t-1 of `videos` (frame 0 alone
+    without hold_endpoints) before it is returned; None: no colour op is called.  The targets are the two endpoints only:
+    `keyframes=` pins latents, it does not add targets."""
     cond = Conditions.build(model, videos, prompts=prompts, fs=fs, guided=plan.scale != 1.0,
                             three_way=three_way, image_branch=plan.image_scale != 1.0, hold_endpoints=hold_endpoints)
     pinned = pin_frames(model, keyframes, latent_shape[2]) if keyframes else None
-    clips = [decode_spliced(model, sample(model, cond, plan, latent_shape, pinned=pinned, variant=k), cond.refs) for k in range(variants)]
+    clips = [_matched(decode_spliced(model, sample(model, cond, plan, latent_shape, pinned=pinned, variant=k), cond.refs), cond, match)
+             for k in range(variants)]
     return torch.stack(clips, dim=1)
 
 
 def synthesize_u8(model, first_u8, last_u8, latent_shape, *, size, plan: SamplingPlan, prompts=None, fs=24, three_way=False,
-                  hold_endpoints=True, out_size=None, out_filter="bicubic", out_fmt="rgb24", out_colour=None):
+                  hold_endpoints=True, out_size=None, out_filter="bicubic", out_fmt="rgb24", out_colour=None, match=None):
     """uint8 keyframes in, uint8 clip out, all on the device: (b, h, w, 3) first / last frames -> (b, t, H, W, 3) frames
     (`Conditions.from_uint8`, `sample`, `decode_spliced`, `clip_to_uint8`).  The last frame of one clip can be the first
     keyframe of the next without leaving the GPU.  `plan.seeds` as in `sample`.
     out_size = (oh, ow), out_filter, out_fmt: the delivery size and pixel format (`clip_to_uint8`'s size / filter / fmt, the
     pixel back end) -- (b, t, oh, ow, 3) frames, or for "i420" / "nv12" the (b, t, oh * ow * 3 / 2) planes that
-    `mp4.write_mp4_i420` or an encoder takes.  out_colour: an `output.Colour` for those planes (`clip_to_uint8`'s colour)."""
+    `mp4.write_mp4_i420` or an encoder takes.  out_colour: an `output.Colour` for those planes (`clip_to_uint8`'s colour).
+    match: an `output.ColourMatch` -- the decoded clip is matched in colour to the two keyframes at model size
+    (`output.match_colour`) before it goes to the writer; None: no colour op is called."""
     from .output import clip_to_uint8
     cond = Conditions.from_uint8(model, first_u8, last_u8, size=size, t=latent_shape[2], prompts=prompts, fs=fs,
                                  guided=plan.scale != 1.0, three_way=three_way, image_branch=plan.image_scale != 1.0,
                                  hold_endpoints=hold_endpoints)
-    video = decode_spliced(model, sample(model, cond, plan, latent_shape), cond.refs)
+    video = _matched(decode_spliced(model, sample(model, cond, plan, latent_shape), cond.refs), cond, match)
     if out_colour is None:
         return clip_to_uint8(video, size=out_size, filter=out_filter, fmt=out_fmt)
     return clip_to_uint8(video, size=out_size, filter=out_filter, fmt=out_fmt, colour=out_colour)
@@ -396,7 +415,7 @@ def timeline_layout(keyframes: int, t: int, batch: int, out_hw, fmt: str, colour
 
 
 def synthesize_timeline_u8(model, keyframes, latent_shape, *, size, plan: SamplingPlan, prompts=None, fs=24, three_way=False,
-                           out_size=None, out_filter="bicubic", out_fmt="rgb24", out_colour=None):
+                           out_size=None, out_filter="bicubic", out_fmt="rgb24", out_colour=None, match=None):
     """K keyframes in, one video out, all on the device.  `keyframes`: (K, h, w, 3) uint8 or a `Planes` of K images, K >= 2.
     Segment i interpolates keyframe i -> i + 1 (endpoints held); segments run in order, latent_shape[0] per batch (the last
     batch may be smaller), each batch exactly `Conditions.from_uint8` / `from_planes` with first = kf[i : i + n] and
@@ -406,7 +425,10 @@ def synthesize_timeline_u8(model, keyframes, latent_shape, *, size, plan: Sampli
     Without seeds the device generator is drawn as the same sequence of `synthesize_u8` calls draws it.  Every inner keyframe is
     encoded twice, as one segment's last frame and the next one's first.
     out_colour: an `output.Colour` for planar frames (tc_frames_to_yuv instead; 10 bits: (F, oh * ow * 3) bytes of P010), or
-    "source": the colour the `Planes` keyframes came in (`Colour.of`), so the video leaves in the description it arrived with."""
+    "source": the colour the `Planes` keyframes came in (`Colour.of`), so the video leaves in the description it arrived with.
+    match: an `output.ColourMatch` -- every batch of segments is matched in colour to its own keyframes (`output.match_colour`)
+    before it is written: the last frame of segment i and frame 0 of segment i + 1 then have the same target, the inner
+    keyframe's statistics, so the video does not step in colour there.  None: no colour op is called."""
     from dataclasses import replace
     planar = isinstance(keyframes, Planes)
     if not planar and not (isinstance(keyframes, torch.Tensor) and keyframes.dtype == torch.uint8 and keyframes.dim() == 4 and keyframes.shape[3] == 3):
@@ -438,7 +460,7 @@ def synthesize_timeline_u8(model, keyframes, latent_shape, *, size, plan: Sampli
                      prompts=None if prompts is None else list(prompts[i:i + n]), fs=fs, guided=plan.scale != 1.0,
                      three_way=three_way, image_branch=plan.image_scale != 1.0, hold_endpoints=True)
         part = plan if seeds is None else replace(plan, seeds=seeds[i:i + n])
-        clips = decode_spliced(model, sample(model, cond, part, [n, *latent_shape[1:]]), cond.refs).to(torch.float32)
+        clips = _matched(decode_spliced(model, sample(model, cond, part, [n, *latent_shape[1:]]), cond.refs), cond, match).to(torch.float32)
         if i == 0:                                    # the video's first frame: segment 0 alone writes its frame 0
             write(clips[:1], size=out_size, filter=out_filter, fmt=out_fmt, frames=(0, 1), out=flat, strides=(row, frame, frame))
         write(clips, size=out_size, filter=out_filter, fmt=out_fmt, frames=(1, t - 1), out=flat[(i * (t - 1) + 1) * frame:],
@@ -459,10 +481,11 @@ def get_latent_z_with_hidden_states(model, videos):
 def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddim_steps=50, ddim_eta=1.,
                            unconditional_guidance_scale=1.0, cfg_img=None, fs=None, text_input=False,
                            multiple_cond_cfg=False, loop=False, interp=False, timestep_spacing='uniform',
-                           guidance_rescale=0.0, solver_order=1, **kwargs):
-    """`solver_order` is not in the reference's signature (a script that never passes it gets the reference's sampler): 2
-    switches the multistep correction on, `SamplingPlan.order`."""
+                           guidance_rescale=0.0, solver_order=1, match=None, **kwargs):
+    """`solver_order` and `match` are not in the reference's signature (a script that never passes them gets the reference's
+    sampler and frames): 2 switches the multistep correction on, `SamplingPlan.order`; an `output.ColourMatch` matches the
+    decoded clips in colour to the keyframes (`synthesize`'s match)."""
     plan = SamplingPlan(steps=ddim_steps, eta=ddim_eta, scale=unconditional_guidance_scale, image_scale=cfg_img,
                         spacing=timestep_spacing, rescale=guidance_rescale, extra=kwargs, order=solver_order)
     return synthesize(model, videos, noise_shape, plan=plan, prompts=prompts if text_input else None, fs=fs,
-                      three_way=multiple_cond_cfg, hold_endpoints=bool(loop or interp), variants=n_samples)
+                      three_way=multiple_cond_cfg, hold_endpoints=bool(loop or interp), variants=n_samples, match=match)

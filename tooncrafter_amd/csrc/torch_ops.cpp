@@ -3,7 +3,7 @@
 // The reference binds ATen / xformers operators from Python (utils/utils.py:27-42 instantiates lvdm classes whose
 // forward methods call torch ops); this registers the MI355X kernels as first-class torch operators instead:
 //   torch.ops.tooncrafter.gemm / quant_mxfp8 / gemm_mx / attention / attention_temporal(_rel) / groupnorm(_pf) / layernorm(_pf) / ddim_step(_eps) / ddim_step_ms(_eps) / ddim_blend /
-//   frames_from_u8 / frames_from_yuv / frames_to_u8 / frames_to_yuv / clip_patches / randn_clips /
+//   frames_from_u8 / frames_from_yuv / frames_to_u8 / frames_to_yuv / colour_stats / colour_match / clip_patches / randn_clips /
 //   ff_geglu_fused / temporal_attn_fused / temporal_qkv_attn / attention_q8
 // with (i) a CUDA(HIP)-key implementation that validates the tensors, allocates the result from the caching allocator,
 // picks up the CURRENT stream and calls the same extern "C" entry point the ctypes binding calls, and (ii) a Meta-key
@@ -707,6 +707,80 @@ Tensor frames_to_yuv_meta(const Tensor& x, int64_t oh, int64_t ow, int64_t forma
   return at::empty(frames_to_yuv_shape(x, oh, ow, format, f0, nf, siting, m), x.options().dtype(at::kByte));
 }
 
+// Colour match (additive within ABI 14).  colour_stats: the nine float64 sums of frames f0, f0 + fstep, ... (nf of them) of every
+// clip of x (b, 3, t, h, w) fp32 -> (b, nf, 9) (tc_colour_stats).  colour_match: x matched frame by frame to the course between the
+// two reference images of its clip, from src (b, t, 9) and ref (b, 2, 9) -> (the matched clip, the (b, t, 12) fp32 coefficients)
+// (tc_colour_match).  Matching in place is the C ABI's (HipOps.colour_match with out=): an op returns its result.
+void colour_clip_check(const Tensor& x, const char* what) {
+  TORCH_CHECK(x.dim() == 5 && x.size(1) == 3 && x.numel() > 0, what, ": x must be (b, 3, t, h, w)");
+  for (int d : {0, 2, 3, 4}) TORCH_CHECK(x.size(d) <= INT32_MAX, what, ": dimension ", d, " of x");
+}
+
+std::vector<int64_t> colour_stats_shape(const Tensor& x, int64_t f0, int64_t nf, int64_t fstep) {
+  colour_clip_check(x, "colour_stats");
+  const int64_t t = x.size(2);
+  TORCH_CHECK(nf >= 1 && f0 >= 0 && f0 < t && (nf == 1 || (fstep >= 1 && fstep <= INT32_MAX && f0 + (nf - 1) * fstep <= t - 1)),
+              "colour_stats: frames (", f0, ", ", nf, ", ", fstep, ") outside a clip of ", t);
+  return {x.size(0), nf, TC_COLOUR_STATS};
+}
+
+Tensor colour_stats_cuda(const Tensor& x, int64_t f0, int64_t nf, int64_t fstep) {
+  TORCH_CHECK(x.is_cuda(), "colour_stats: expected a CUDA tensor (the product path is GPU-only)");
+  TORCH_CHECK(x.scalar_type() == at::kFloat && x.is_contiguous(), "colour_stats: contiguous fp32 (b, 3, t, h, w)");
+  Tensor stats = at::empty(colour_stats_shape(x, f0, nf, fstep), x.options().dtype(at::kDouble));
+  TcColourStatsParams p = {};
+  p.x = x.data_ptr<float>();
+  p.b = (int32_t)x.size(0); p.t = (int32_t)x.size(2); p.h = (int32_t)x.size(3); p.w = (int32_t)x.size(4);
+  p.f0 = (int32_t)f0; p.nf = (int32_t)nf; p.fstep = nf == 1 ? 1 : (int32_t)fstep;
+  p.stats = stats.data_ptr<double>();
+  p.workspace_bytes = tc_colour_stats_workspace(&p);
+  Tensor ws = workspace(p.workspace_bytes, x);
+  p.workspace = ws.data_ptr();
+  check_rc(tc_colour_stats(&p, cur_stream()), "tc_colour_stats");
+  return stats;
+}
+
+Tensor colour_stats_meta(const Tensor& x, int64_t f0, int64_t nf, int64_t fstep) {
+  return at::empty(colour_stats_shape(x, f0, nf, fstep), x.options().dtype(at::kDouble));
+}
+
+void colour_match_check(const Tensor& x, const Tensor& src, const Tensor& ref, int64_t ref_pixels, int64_t method, double strength) {
+  colour_clip_check(x, "colour_match");
+  const int64_t b = x.size(0), t = x.size(2);
+  TORCH_CHECK(src.dim() == 3 && src.size(0) == b && src.size(1) == t && src.size(2) == TC_COLOUR_STATS,
+              "colour_match: src must be (b, t, 9)");
+  TORCH_CHECK(ref.dim() == 3 && ref.size(0) == b && ref.size(1) == 2 && ref.size(2) == TC_COLOUR_STATS,
+              "colour_match: ref must be (b, 2, 9)");
+  TORCH_CHECK(method == TC_COLOUR_MEAN_STD || method == TC_COLOUR_MKL, "colour_match: method ", method);
+  TORCH_CHECK(strength >= 0.0 && strength <= 1.0, "colour_match: strength ", strength, " outside [0, 1]");
+  TORCH_CHECK(ref_pixels > 0, "colour_match: ref_pixels ", ref_pixels);
+}
+
+std::tuple<Tensor, Tensor> colour_match_cuda(const Tensor& x, const Tensor& src, const Tensor& ref, int64_t ref_pixels, int64_t method,
+                                             double strength) {
+  TORCH_CHECK(x.is_cuda() && src.is_cuda() && ref.is_cuda(), "colour_match: expected CUDA tensors (the product path is GPU-only)");
+  TORCH_CHECK(x.scalar_type() == at::kFloat && x.is_contiguous(), "colour_match: x: contiguous fp32 (b, 3, t, h, w)");
+  TORCH_CHECK(src.scalar_type() == at::kDouble && src.is_contiguous() && ref.scalar_type() == at::kDouble && ref.is_contiguous(),
+              "colour_match: src / ref: contiguous float64");
+  colour_match_check(x, src, ref, ref_pixels, method, strength);
+  Tensor out = at::empty_like(x);
+  Tensor coefs = at::empty({x.size(0), x.size(2), 12}, x.options());
+  TcColourMatchParams p = {};
+  p.x = x.data_ptr<float>(); p.out = out.data_ptr<float>();
+  p.b = (int32_t)x.size(0); p.t = (int32_t)x.size(2); p.h = (int32_t)x.size(3); p.w = (int32_t)x.size(4);
+  p.src = src.data_ptr<double>(); p.ref = ref.data_ptr<double>();
+  p.ref_pixels = ref_pixels; p.method = (int32_t)method; p.strength = (float)strength;
+  p.coefs = coefs.data_ptr<float>();
+  check_rc(tc_colour_match(&p, cur_stream()), "tc_colour_match");
+  return {out, coefs};
+}
+
+std::tuple<Tensor, Tensor> colour_match_meta(const Tensor& x, const Tensor& src, const Tensor& ref, int64_t ref_pixels, int64_t method,
+                                             double strength) {
+  colour_match_check(x, src, ref, ref_pixels, method, strength);
+  return {at::empty_like(x), at::empty({x.size(0), x.size(2), 12}, x.options())};
+}
+
 // clip_patches: (B, 3, H, W) fp32 -> the bf16 A operand [B * (size / patch)^2, ld] of the CLIP image tower's patch-embedding GEMM
 // (reference condition.py:322-330: kornia resize, (x + 1) / 2, CLIP mean / std; then open_clip's conv1 unfold)
 Tensor clip_patches_cuda(const Tensor& x, int64_t size, int64_t patch, int64_t ld, at::ArrayRef<double> mean, at::ArrayRef<double> std,
@@ -811,6 +885,8 @@ TORCH_LIBRARY(tooncrafter, m) {
         "Tensor? v_coefs) -> Tensor");
   m.def("frames_to_yuv(Tensor x, int oh, int ow, int format, int f0, int nf, int siting, int[] m, Tensor? h_bounds, Tensor? h_coefs, "
         "Tensor? v_bounds, Tensor? v_coefs) -> Tensor");
+  m.def("colour_stats(Tensor x, int f0, int nf, int fstep) -> Tensor");
+  m.def("colour_match(Tensor x, Tensor src, Tensor ref, int ref_pixels, int method, float strength) -> (Tensor, Tensor)");
   m.def("clip_patches(Tensor x, int size, int patch, int ld, float[] mean, float[] std, bool antialias) -> Tensor");
   m.def("randn_clips(int[] seeds, int[] shape, int stream, float scale, bool raw) -> Tensor");
   m.def("abi_version() -> int");
@@ -837,6 +913,8 @@ TORCH_LIBRARY_IMPL(tooncrafter, CUDA, m) {
   m.impl("frames_from_yuv", frames_from_yuv_cuda);
   m.impl("frames_to_u8", frames_to_u8_cuda);
   m.impl("frames_to_yuv", frames_to_yuv_cuda);
+  m.impl("colour_stats", colour_stats_cuda);
+  m.impl("colour_match", colour_match_cuda);
   m.impl("clip_patches", clip_patches_cuda);
   m.impl("randn_clips", randn_clips_cuda);
   m.impl("ff_geglu_fused", ff_geglu_fused_cuda);
@@ -860,6 +938,8 @@ TORCH_LIBRARY_IMPL(tooncrafter, Meta, m) {
   m.impl("frames_from_yuv", frames_from_yuv_meta);
   m.impl("frames_to_u8", frames_to_u8_meta);
   m.impl("frames_to_yuv", frames_to_yuv_meta);
+  m.impl("colour_stats", colour_stats_meta);
+  m.impl("colour_match", colour_match_meta);
   m.impl("clip_patches", clip_patches_meta);
   m.impl("randn_clips", randn_clips_meta);
   m.impl("ff_geglu_fused", ff_geglu_fused_meta);

@@ -1225,6 +1225,71 @@ class HipOps:
         _lib.check(self.lib.tc_ddim_blend(C.byref(p), _stream()), "tc_ddim_blend")
         return out
 
+    # ------------------------------------------------------------------ colour match (tc_colour_stats, tc_colour_match)
+    @staticmethod
+    def _colour_clip(x, what):
+        """The (b, t, h, w) of a (b, 3, t, h, w) fp32 contiguous device clip, or raise."""
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise _lib.TooncrafterHipError(f"{what}: expected a CUDA tensor, got {getattr(x, 'device', type(x))}: the product "
+                                           "path is GPU-only")
+        if x.dtype != torch.float32 or x.dim() != 5 or x.shape[1] != 3 or x.numel() == 0 or not x.is_contiguous():
+            raise ValueError(f"{what}: expected contiguous fp32 (b, 3, t, h, w), got {tuple(x.shape)} {x.dtype}")
+        return x.shape[0], x.shape[2], x.shape[3], x.shape[4]
+
+    @staticmethod
+    def _colour_frames(frames, t, what):
+        """The checked (f0, nf, fstep) of a statistics request on clips of t frames; None: every frame."""
+        f0, nf, fstep = (0, t, 1) if frames is None else (int(v) for v in frames)
+        if nf < 1 or not 0 <= f0 < t or (nf > 1 and (fstep < 1 or f0 + (nf - 1) * fstep > t - 1)):
+            raise ValueError(f"{what}: frames (f0, nf, fstep) = {(f0, nf, fstep)} outside a clip of {t}")
+        return f0, nf, fstep
+
+    @staticmethod
+    def _colour_match_args(x, src, ref, ref_pixels, method, strength, what="colour_match"):
+        """The checked request of a match on the clip x with dimensions (b, t, h, w): (method code, strength, ref_pixels)."""
+        b, t = x.shape[0], x.shape[2]
+        for name, s, rows in (("src", src, t), ("ref", ref, 2)):
+            if not isinstance(s, torch.Tensor) or not s.is_cuda:
+                raise _lib.TooncrafterHipError(f"{what}: {name}: expected a CUDA tensor: the product path is GPU-only")
+            if s.dtype != torch.float64 or tuple(s.shape) != (b, rows, _lib.TC_COLOUR_STATS) or not s.is_contiguous():
+                raise ValueError(f"{what}: {name}: expected contiguous float64 {(b, rows, _lib.TC_COLOUR_STATS)}, got "
+                                 f"{tuple(s.shape)} {s.dtype}")
+        code = _lib.TC_COLOUR_METHODS.get(method, method)
+        if isinstance(code, bool) or code not in _lib.TC_COLOUR_METHODS.values():
+            raise ValueError(f"{what}: method {method!r}: one of {tuple(_lib.TC_COLOUR_METHODS)}")
+        strength, ref_pixels = float(strength), int(ref_pixels)
+        if not 0.0 <= strength <= 1.0 or ref_pixels <= 0:                      # NaN fails the comparison too
+            raise ValueError(f"{what}: strength {strength} outside [0, 1] or ref_pixels {ref_pixels} <= 0")
+        return code, strength, ref_pixels
+
+    def colour_stats(self, x, frames=None):
+        """Nine float64 sums (r, g, b, rr, rg, rb, gg, gb, bb of the clamped values) per frame f0, f0 + fstep, ... (nf of them;
+        frames = (f0, nf, fstep), None: all) of every clip of x (b, 3, t, h, w) fp32: (b, nf, 9), in a summation order fixed by
+        h * w alone (tc_colour_stats)."""
+        b, t, h, w = self._colour_clip(x, "colour_stats: x")
+        f0, nf, fstep = self._colour_frames(frames, t, "colour_stats")
+        stats = torch.empty((b, nf, _lib.TC_COLOUR_STATS), dtype=torch.float64, device=x.device)
+        p = _lib.TcColourStatsParams(x=x.data_ptr(), b=b, t=t, h=h, w=w, f0=f0, nf=nf, fstep=fstep, stats=stats.data_ptr())
+        self._launch("tc_colour_stats", p, x.device)
+        return stats
+
+    def colour_match(self, x, src, ref, ref_pixels, method, strength, out=None):
+        """x (b, 3, t, h, w) fp32 matched frame by frame to the course between two reference images per clip: `src` (b, t, 9) the
+        statistics of x, `ref` (b, 2, 9) those of the reference images over `ref_pixels` pixels each, method "mkl" | "mean_std"
+        (or its code), strength in [0, 1].  Returns (matched clip, coefs (b, t, 12) fp32: A' row-major, then o').  `out` may be
+        `x` itself (in place); default: a new tensor (tc_colour_match)."""
+        b, t, h, w = self._colour_clip(x, "colour_match: x")
+        code, strength, ref_pixels = self._colour_match_args(x, src, ref, ref_pixels, method, strength)
+        if out is None:
+            out = torch.empty_like(x)
+        elif self._colour_clip(out, "colour_match: out") != (b, t, h, w) or out.device != x.device:
+            raise ValueError(f"colour_match: out {tuple(out.shape)} against x {tuple(x.shape)}")
+        coefs = torch.empty((b, t, 12), dtype=torch.float32, device=x.device)
+        p = _lib.TcColourMatchParams(x=x.data_ptr(), out=out.data_ptr(), b=b, t=t, h=h, w=w, src=src.data_ptr(), ref=ref.data_ptr(),
+                                     ref_pixels=ref_pixels, method=code, strength=strength, coefs=coefs.data_ptr())
+        _lib.check(self.lib.tc_colour_match(C.byref(p), _stream()), "tc_colour_match")
+        return out, coefs
+
 
 _backend = None
 

@@ -185,6 +185,17 @@ class TorchLibOps(HipOps):
         return self.t.frames_to_yuv(x.contiguous(), oh, ow, code, f0, nf, siting, m, *self._axis_tables(filter, w, ow, x.device),
                                     *self._axis_tables(filter, h, oh, x.device))
 
+    def colour_stats(self, x, frames=None):
+        _, t, _, _ = self._colour_clip(x, "colour_stats: x")
+        return self.t.colour_stats(x, *self._colour_frames(frames, t, "colour_stats"))
+
+    def colour_match(self, x, src, ref, ref_pixels, method, strength, out=None):
+        if out is not None:                                  # an explicit result buffer (in place): the ctypes method
+            return super().colour_match(x, src, ref, ref_pixels, method, strength, out=out)
+        self._colour_clip(x, "colour_match: x")
+        code, strength, ref_pixels = self._colour_match_args(x, src, ref, ref_pixels, method, strength)
+        return self.t.colour_match(x, src, ref, ref_pixels, code, strength)
+
     def clip_patches(self, x, *, size, patch, ld, mean, std, antialias=True):
         return self.t.clip_patches(x, int(size), int(patch), int(ld), [float(v) for v in mean], [float(v) for v in std], bool(antialias))
 
