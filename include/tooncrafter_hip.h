@@ -828,8 +828,8 @@ int tc_frames_to_yuv(const TcFramesYuvOutParams* p, void* stream);
  * any host give the same bits.  y is NOT clamped: the back end clamps.  Exact consequences: strength 0 returns clamp(x);
  * MEAN_STD of a frame against its own statistics returns clamp(x).
  *
- * Not offered: targets at inner frames, a colour space other than the model's RGB values, histogram matching, a gain limit
- * (a frame that is flat where its keyframes are not gets a large gain by the rule above; strength is the only control). */
+ * Not offered: targets at inner frames, a colour space other than the model's RGB values, a gain limit (a frame that is flat
+ * where its keyframes are not gets a large gain by the rule above; strength is the only control). */
 #define TC_COLOUR_STATS 9
 typedef struct TcColourStatsParams {
   const float* x;            /* (b, 3, t, h, w) fp32 */
@@ -863,6 +863,89 @@ typedef struct TcColourMatchParams {
  * ref_pixels <= 0, out overlapping x other than out == x; TC_EALIGN: src or ref not 8-byte aligned; TC_ESHAPE: more than
  * 2^31 - 1 blocks in all.  Nothing is launched or written on a refusal. */
 int tc_colour_match(const TcColourMatchParams* p, void* stream);
+
+/* ---- Histogram colour transfer (additive within ABI 14: two structs, three symbols).  What a decoder does to toon frames is
+ * a bent tone curve per channel (blacks lift, highlights compress), which no 3 x 3 matrix repairs: this is the per-channel
+ * monotone transfer that carries a frame's histogram onto its keyframes'.  THE RULE, stated once (restated with numpy integers
+ * and float64 for the tests: tests/colour_hist_ref.py):
+ *
+ * Bins.  TC_COLOUR_BINS = 1024: four per 8-bit code, one per 10-bit code.  c = clamp(x, -1, 1) = fminf(fmaxf(x, -1), 1), the
+ * clamp of tc_colour_stats (a NaN becomes -1);  bin(c) = min(1023, (int) floorf((c + 1.0f) * 512.0f)), the fp32 add rounded,
+ * the multiply exact.  So -1 and everything below fall into bin 0, +-0 into bin 512, 1, everything above it and the largest
+ * float below 1 into bin 1023, 1/512 - 1 into bin 1 and its fp32 predecessor into bin 0.
+ *
+ * Histogram of a frame: 3 x 1024 int32 counts, channel r, then g, then b.  Counts are exact integers: no order of summation
+ * is part of the result, and the result does not depend on what hist or the workspace held before the call.
+ *
+ * Transfer of frame f of t, per channel.  s[i]: the frame's counts, n = h * w;  a[i], b[i]: the counts of the clip's first
+ * and last reference image, m = ref_pixels each.
+ *   midpoint rank   P_i = 2 S_i - s_i with S_i = sum_{j <= i} s_j: an integer in [0, 2n].  Only bins with s_i > 0 get an
+ *                   entry (there P_i > 0); every other entry of the table is +0.0f.
+ *   quantile        for r in {a, b}:  A_j = sum_{i < j} r_i (A_0 = 0, A_1024 = m);  j the smallest index in [1, 1024] with
+ *                   A_j 2n >= P_i m, compared in integers (both sides < 2^53 by the size limit below); then A_{j-1} 2n < P_i m
+ *                   and r_{j-1} > 0, and in bin units
+ *                     q_r = (double)(j - 1) + (double)(P_i m - A_{j-1} 2n) / (double)(r_{j-1} 2n):
+ *                   both integers exact in double, one division, one addition.
+ *   course          w = (double) f / (double)(t - 1) (0 when t = 1),  T = q_a + w (q_b - q_a);  frame t - 1 of a clip with
+ *                   t > 1 takes T = q_b itself.  This interpolates quantile functions (the one-dimensional transport
+ *                   geodesic), the counterpart of the linear course of (m, C) in tc_colour_match.
+ *   entry           D[f][k][i] = (float)((T - ((double) i + 0.5)) / 512.0): the displacement of bin i in value units, rounded
+ *                   to fp32 once.  Every double operation is rounded on its own; nothing is contracted.
+ *
+ * Apply, in fp32, nothing contracted, per pixel and channel:  v = c + D[bin(c)],  y = beta + s (v - beta)  with s the
+ * strength and beta = c, or beta = clamp(base) when a base clip is given.  y is NOT clamped: it can leave [-1, 1] by less than
+ * a bin, and the back end clamps.  Each bin is translated rigidly: detail inside a bin survives, there is no banding.
+ *
+ * Exact consequences (checked on the numpy statement and on the device):
+ *   strength 0      returns clamp(x), or clamp(base), exactly;
+ *   self-match      a frame whose two references have its own histogram (also at a multiple of its pixel count) gets an
+ *                   all-zero table and comes back as clamp(x), at every frame index and every strength;
+ *   whole-bin shift a frame whose values all lie on the grid (2k + 1)/2048 - 1 and whose reference is the frame shifted by a
+ *                   whole number of bins, nothing clipped on either side, gets exactly that shift in every occupied bin
+ *                   and comes back equal to the reference bit for bit (64 bins: D = 0.125);
+ *   monotone        T is non-decreasing over the occupied bins.
+ *
+ * Size limit: h * w <= 2^26 and ref_pixels <= 2^26, otherwise TC_ESHAPE: what keeps P_i m and A_j 2n exact in int64 and double.
+ *
+ * Not offered: targets at inner frames, a colour space other than the model's RGB values, a gain limit; and a flat frame
+ * cannot be spread by any histogram match: all its pixels share a bin and move together. */
+#define TC_COLOUR_BINS 1024
+typedef struct TcColourHistParams {
+  const float* x;            /* (b, 3, t, h, w) fp32 */
+  int32_t b, t, h, w;
+  int32_t f0, nf, fstep;     /* frames f0, f0 + fstep, ... (nf of them) of every clip, as in TcColourStatsParams */
+  int32_t* hist;             /* [b * nf][3][TC_COLOUR_BINS], 4-byte aligned */
+  void* workspace; int64_t workspace_bytes;
+} TcColourHistParams;
+/* Histograms of the named frames: two launches (per-part histograms built with LDS integer atomics, a private one per wave;
+ * then their sum).  No memset and no global atomic.  16-byte loads where every plane base allows them, 4-byte loads
+ * otherwise; the counts are the same.  workspace: b * nf * 3 * P * 1024 int32 with P = min(16, ceil(h * w / 1024)) (0 for a
+ * request that is refused for anything but its workspace).
+ * TC_EINVAL: NULL p / x / hist, a size <= 0, nf <= 0, f0 outside [0, t), fstep < 1 with nf > 1, a frame past t - 1;
+ * TC_EALIGN: hist or workspace not 4-byte aligned; TC_EWORKSPACE: workspace NULL or too small; TC_ESHAPE: h * w > 2^26 or
+ * more than 2^31 - 1 blocks in all.  Nothing is launched or written on a refusal. */
+int64_t tc_colour_hist_workspace(const TcColourHistParams* p);
+int tc_colour_hist(const TcColourHistParams* p, void* stream);
+
+typedef struct TcColourTransferParams {
+  const float* x;               /* (b, 3, t, h, w) */
+  const float* base;            /* NULL, or a clip of the shape of x: what strength blends against */
+  float* out;                   /* may be EXACTLY x; any other overlap with x, and any overlap with base, is TC_EINVAL */
+  int32_t b, t, h, w;
+  const int32_t* src;           /* [b * t][3][1024]: the histograms of all frames of x (f0 = 0, nf = t, fstep = 1) */
+  const int32_t* ref;           /* [b * 2][3][1024]: histograms of the two reference images of every clip */
+  int64_t ref_pixels;           /* pixels per reference image (need not be h * w) */
+  float strength;
+  float* table;                 /* [b * t][3][1024] fp32, written by the call (required) */
+} TcColourTransferParams;
+/* The transfer: two launches (the tables, one block per frame and channel in integers and double; then the apply pass).  No
+ * allocation, no synchronisation, no host read of device memory: safe to capture in a hipGraph.  The call trusts its
+ * histograms as tc_colour_match trusts src: src must hold the counts of x and sum to h * w per channel, ref must sum to
+ * ref_pixels; with other counts the tables mean nothing (no access leaves the buffers).
+ * TC_EINVAL: NULL p / x / out / src / ref / table, a size <= 0, a strength outside [0, 1] or not finite, ref_pixels <= 0,
+ * out overlapping x other than out == x, out overlapping base; TC_EALIGN: src, ref or table not 4-byte aligned; TC_ESHAPE:
+ * h * w or ref_pixels > 2^26, more than 2^31 - 1 blocks in all.  Nothing is launched or written on a refusal. */
+int tc_colour_transfer(const TcColourTransferParams* p, void* stream);
 
 /* introspection */
 int tc_abi_version(void);

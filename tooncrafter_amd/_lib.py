@@ -215,6 +215,31 @@ class TcColourMatchParams(C.Structure):
     ]
 
 
+class TcColourHistParams(C.Structure):
+    """3 x 1024 int32 counts per named frame of fp32 clips (tc_colour_hist; additive within ABI 14)."""
+    _fields_ = [
+        ("x", C.c_void_p),
+        ("b", C.c_int32), ("t", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+        ("f0", C.c_int32), ("nf", C.c_int32), ("fstep", C.c_int32),
+        ("hist", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+    ]
+
+
+class TcColourTransferParams(C.Structure):
+    """Frames carried per channel onto the histograms of two reference images per clip (tc_colour_transfer; additive within
+    ABI 14)."""
+    _fields_ = [
+        ("x", C.c_void_p), ("base", C.c_void_p), ("out", C.c_void_p),
+        ("b", C.c_int32), ("t", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+        ("src", C.c_void_p), ("ref", C.c_void_p),
+        ("ref_pixels", C.c_int64),
+        ("strength", C.c_float),
+        ("table", C.c_void_p),
+    ]
+
+
+TC_COLOUR_BINS = 1024                                    # include/tooncrafter_hip.h: bins per channel of tc_colour_hist
 TC_COLOUR_STATS = 9                                      # include/tooncrafter_hip.h: doubles per frame of tc_colour_stats
 TC_COLOUR_METHODS = {"mean_std": 0, "mkl": 1}            # TC_COLOUR_MEAN_STD / TC_COLOUR_MKL
 TC_YUV_FORMATS = {"i420": 1, "nv12": 2, "p010": 3}       # include/tooncrafter_hip.h: the TC_PIXFMT_* tc_frames_from_yuv reads
@@ -307,6 +332,9 @@ SYMBOLS = {
     "tc_colour_stats_workspace": (C.c_int64, [C.POINTER(TcColourStatsParams)]),
     "tc_colour_stats": (C.c_int, [C.POINTER(TcColourStatsParams), C.c_void_p]),
     "tc_colour_match": (C.c_int, [C.POINTER(TcColourMatchParams), C.c_void_p]),
+    "tc_colour_hist_workspace": (C.c_int64, [C.POINTER(TcColourHistParams)]),
+    "tc_colour_hist": (C.c_int, [C.POINTER(TcColourHistParams), C.c_void_p]),
+    "tc_colour_transfer": (C.c_int, [C.POINTER(TcColourTransferParams), C.c_void_p]),
     "tc_gemm_ws_eligible": (C.c_int, [C.POINTER(TcGemmParams)]),
     "tc_gemm_gn_rows": (C.c_int, [C.POINTER(TcGemmParams)]),
     "tc_groupnorm_part": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,

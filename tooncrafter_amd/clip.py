@@ -347,7 +347,8 @@ def decode_spliced(model, latents, refs, marks=None):
 
 def _matched(video, cond, match):
     """The decoded clip as it is (match None: nothing is called), or matched in colour to the keyframes of its conditions
-    (`output.match_colour`: tc_colour_stats twice, tc_colour_match)."""
+    (`output.match_colour`: tc_colour_stats twice and tc_colour_match for the linear methods, tc_colour_hist twice and
+    tc_colour_transfer for "hm", the three stages of both for "hm_mkl_hm")."""
     if match is None:
         return video
     from .output import match_colour
@@ -361,8 +362,9 @@ def synthesize(model, videos, latent_shape, *, plan: SamplingPlan, prompts=None,
     endpoints-only: that is what the model was trained on.  With `plan.seeds`, variant k of clip i is the clip seeded
     `variant_seed(plan.seeds[i], k)`: the same pixels as a `variants=1` run with that seed.
     match: an `output.ColourMatch` -- every decoded clip is matched in colour to frames 0 and t-1 of `videos` (frame 0 alone
-    without hold_endpoints) before it is returned; None: no colour op is called.  The targets are the two endpoints only:
-    `keyframes=` pins latents, it does not add targets."""
+    without hold_endpoints) before it is returned, by a linear map ("mkl", "mean_std") or by histogram ("hm", "hm_mkl_hm");
+    None: no colour op is called.  The targets are the two endpoints only: `keyframes=` pins latents, it does not add
+    targets."""
     cond = Conditions.build(model, videos, prompts=prompts, fs=fs, guided=plan.scale != 1.0,
                             three_way=three_way, image_branch=plan.image_scale != 1.0, hold_endpoints=hold_endpoints)
     pinned = pin_frames(model, keyframes, latent_shape[2]) if keyframes else None
@@ -380,7 +382,8 @@ def synthesize_u8(model, first_u8, last_u8, latent_shape, *, size, plan: Samplin
     pixel back end) -- (b, t, oh, ow, 3) frames, or for "i420" / "nv12" the (b, t, oh * ow * 3 / 2) planes that
     `mp4.write_mp4_i420` or an encoder takes.  out_colour: an `output.Colour` for those planes (`clip_to_uint8`'s colour).
     match: an `output.ColourMatch` -- the decoded clip is matched in colour to the two keyframes at model size
-    (`output.match_colour`) before it goes to the writer; None: no colour op is called."""
+    (`output.match_colour`; methods "mkl", "mean_std", "hm", "hm_mkl_hm") before it goes to the writer; None: no colour op is
+    called."""
     from .output import clip_to_uint8
     cond = Conditions.from_uint8(model, first_u8, last_u8, size=size, t=latent_shape[2], prompts=prompts, fs=fs,
                                  guided=plan.scale != 1.0, three_way=three_way, image_branch=plan.image_scale != 1.0,
@@ -428,7 +431,8 @@ def synthesize_timeline_u8(model, keyframes, latent_shape, *, size, plan: Sampli
     "source": the colour the `Planes` keyframes came in (`Colour.of`), so the video leaves in the description it arrived with.
     match: an `output.ColourMatch` -- every batch of segments is matched in colour to its own keyframes (`output.match_colour`)
     before it is written: the last frame of segment i and frame 0 of segment i + 1 then have the same target, the inner
-    keyframe's statistics, so the video does not step in colour there.  None: no colour op is called."""
+    keyframe's statistics ("mkl", "mean_std") or its per-channel quantile function ("hm", "hm_mkl_hm"), so the video does not
+    step in colour there.  None: no colour op is called."""
     from dataclasses import replace
     planar = isinstance(keyframes, Planes)
     if not planar and not (isinstance(keyframes, torch.Tensor) and keyframes.dtype == torch.uint8 and keyframes.dim() == 4 and keyframes.shape[3] == 3):

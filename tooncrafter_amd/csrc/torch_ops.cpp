@@ -3,7 +3,7 @@
 // The reference binds ATen / xformers operators from Python (utils/utils.py:27-42 instantiates lvdm classes whose
 // forward methods call torch ops); this registers the MI355X kernels as first-class torch operators instead:
 //   torch.ops.tooncrafter.gemm / quant_mxfp8 / gemm_mx / attention / attention_temporal(_rel) / groupnorm(_pf) / layernorm(_pf) / ddim_step(_eps) / ddim_step_ms(_eps) / ddim_blend /
-//   frames_from_u8 / frames_from_yuv / frames_to_u8 / frames_to_yuv / colour_stats / colour_match / clip_patches / randn_clips /
+//   frames_from_u8 / frames_from_yuv / frames_to_u8 / frames_to_yuv / colour_stats / colour_match / colour_hist / colour_transfer / clip_patches / randn_clips /
 //   ff_geglu_fused / temporal_attn_fused / temporal_qkv_attn / attention_q8
 // with (i) a CUDA(HIP)-key implementation that validates the tensors, allocates the result from the caching allocator,
 // picks up the CURRENT stream and calls the same extern "C" entry point the ctypes binding calls, and (ii) a Meta-key
@@ -781,6 +781,80 @@ std::tuple<Tensor, Tensor> colour_match_meta(const Tensor& x, const Tensor& src,
   return {at::empty_like(x), at::empty({x.size(0), x.size(2), 12}, x.options())};
 }
 
+// Histogram transfer (additive within ABI 14).  colour_hist: the 3 x 1024 int32 counts of frames f0, f0 + fstep, ... (nf of them) of
+// every clip of x -> (b, nf, 3, 1024) (tc_colour_hist).  colour_transfer: x carried channel by channel onto the course between the
+// histograms of the two reference images of its clip, from src (b, t, 3, 1024) and ref (b, 2, 3, 1024), blended by strength against
+// clamp(x) or clamp(base) -> (the transferred clip, the (b, t, 3, 1024) fp32 tables) (tc_colour_transfer).
+std::vector<int64_t> colour_hist_shape(const Tensor& x, int64_t f0, int64_t nf, int64_t fstep) {
+  colour_clip_check(x, "colour_hist");
+  const int64_t t = x.size(2);
+  TORCH_CHECK(nf >= 1 && f0 >= 0 && f0 < t && (nf == 1 || (fstep >= 1 && fstep <= INT32_MAX && f0 + (nf - 1) * fstep <= t - 1)),
+              "colour_hist: frames (", f0, ", ", nf, ", ", fstep, ") outside a clip of ", t);
+  TORCH_CHECK(x.size(3) * x.size(4) <= (int64_t(1) << 26), "colour_hist: h * w ", x.size(3) * x.size(4), " above 2^26");
+  return {x.size(0), nf, 3, TC_COLOUR_BINS};
+}
+
+Tensor colour_hist_cuda(const Tensor& x, int64_t f0, int64_t nf, int64_t fstep) {
+  TORCH_CHECK(x.is_cuda(), "colour_hist: expected a CUDA tensor (the product path is GPU-only)");
+  TORCH_CHECK(x.scalar_type() == at::kFloat && x.is_contiguous(), "colour_hist: contiguous fp32 (b, 3, t, h, w)");
+  Tensor hist = at::empty(colour_hist_shape(x, f0, nf, fstep), x.options().dtype(at::kInt));
+  TcColourHistParams p = {};
+  p.x = x.data_ptr<float>();
+  p.b = (int32_t)x.size(0); p.t = (int32_t)x.size(2); p.h = (int32_t)x.size(3); p.w = (int32_t)x.size(4);
+  p.f0 = (int32_t)f0; p.nf = (int32_t)nf; p.fstep = nf == 1 ? 1 : (int32_t)fstep;
+  p.hist = hist.data_ptr<int32_t>();
+  p.workspace_bytes = tc_colour_hist_workspace(&p);
+  Tensor ws = workspace(p.workspace_bytes, x);
+  p.workspace = ws.data_ptr();
+  check_rc(tc_colour_hist(&p, cur_stream()), "tc_colour_hist");
+  return hist;
+}
+
+Tensor colour_hist_meta(const Tensor& x, int64_t f0, int64_t nf, int64_t fstep) {
+  return at::empty(colour_hist_shape(x, f0, nf, fstep), x.options().dtype(at::kInt));
+}
+
+void colour_transfer_check(const Tensor& x, const optional<Tensor>& base, const Tensor& src, const Tensor& ref, int64_t ref_pixels,
+                           double strength) {
+  colour_clip_check(x, "colour_transfer");
+  const int64_t b = x.size(0), t = x.size(2);
+  TORCH_CHECK(x.scalar_type() == at::kFloat, "colour_transfer: x: fp32 (b, 3, t, h, w)");
+  TORCH_CHECK(!base.has_value() || (base->sizes() == x.sizes() && base->scalar_type() == at::kFloat),
+              "colour_transfer: base must be fp32 of the shape of x");
+  TORCH_CHECK(src.dim() == 4 && src.size(0) == b && src.size(1) == t && src.size(2) == 3 && src.size(3) == TC_COLOUR_BINS &&
+                  src.scalar_type() == at::kInt, "colour_transfer: src must be int32 (b, t, 3, 1024)");
+  TORCH_CHECK(ref.dim() == 4 && ref.size(0) == b && ref.size(1) == 2 && ref.size(2) == 3 && ref.size(3) == TC_COLOUR_BINS &&
+                  ref.scalar_type() == at::kInt, "colour_transfer: ref must be int32 (b, 2, 3, 1024)");
+  TORCH_CHECK(strength >= 0.0 && strength <= 1.0, "colour_transfer: strength ", strength, " outside [0, 1]");
+  TORCH_CHECK(ref_pixels > 0 && ref_pixels <= (int64_t(1) << 26), "colour_transfer: ref_pixels ", ref_pixels, " outside [1, 2^26]");
+  TORCH_CHECK(x.size(3) * x.size(4) <= (int64_t(1) << 26), "colour_transfer: h * w ", x.size(3) * x.size(4), " above 2^26");
+}
+
+std::tuple<Tensor, Tensor> colour_transfer_cuda(const Tensor& x, const optional<Tensor>& base, const Tensor& src, const Tensor& ref,
+                                                int64_t ref_pixels, double strength) {
+  TORCH_CHECK(x.is_cuda() && src.is_cuda() && ref.is_cuda() && (!base.has_value() || base->is_cuda()),
+              "colour_transfer: expected CUDA tensors (the product path is GPU-only)");
+  colour_transfer_check(x, base, src, ref, ref_pixels, strength);
+  TORCH_CHECK(x.is_contiguous() && src.is_contiguous() && ref.is_contiguous() && (!base.has_value() || base->is_contiguous()),
+              "colour_transfer: contiguous tensors");
+  Tensor out = at::empty_like(x);
+  Tensor table = at::empty({x.size(0), x.size(2), 3, TC_COLOUR_BINS}, x.options());
+  TcColourTransferParams p = {};
+  p.x = x.data_ptr<float>(); p.base = base.has_value() ? base->data_ptr<float>() : nullptr; p.out = out.data_ptr<float>();
+  p.b = (int32_t)x.size(0); p.t = (int32_t)x.size(2); p.h = (int32_t)x.size(3); p.w = (int32_t)x.size(4);
+  p.src = src.data_ptr<int32_t>(); p.ref = ref.data_ptr<int32_t>();
+  p.ref_pixels = ref_pixels; p.strength = (float)strength;
+  p.table = table.data_ptr<float>();
+  check_rc(tc_colour_transfer(&p, cur_stream()), "tc_colour_transfer");
+  return {out, table};
+}
+
+std::tuple<Tensor, Tensor> colour_transfer_meta(const Tensor& x, const optional<Tensor>& base, const Tensor& src, const Tensor& ref,
+                                                int64_t ref_pixels, double strength) {
+  colour_transfer_check(x, base, src, ref, ref_pixels, strength);
+  return {at::empty_like(x), at::empty({x.size(0), x.size(2), 3, TC_COLOUR_BINS}, x.options())};
+}
+
 // clip_patches: (B, 3, H, W) fp32 -> the bf16 A operand [B * (size / patch)^2, ld] of the CLIP image tower's patch-embedding GEMM
 // (reference condition.py:322-330: kornia resize, (x + 1) / 2, CLIP mean / std; then open_clip's conv1 unfold)
 Tensor clip_patches_cuda(const Tensor& x, int64_t size, int64_t patch, int64_t ld, at::ArrayRef<double> mean, at::ArrayRef<double> std,
@@ -887,6 +961,8 @@ TORCH_LIBRARY(tooncrafter, m) {
         "Tensor? v_bounds, Tensor? v_coefs) -> Tensor");
   m.def("colour_stats(Tensor x, int f0, int nf, int fstep) -> Tensor");
   m.def("colour_match(Tensor x, Tensor src, Tensor ref, int ref_pixels, int method, float strength) -> (Tensor, Tensor)");
+  m.def("colour_hist(Tensor x, int f0, int nf, int fstep) -> Tensor");
+  m.def("colour_transfer(Tensor x, Tensor? base, Tensor src, Tensor ref, int ref_pixels, float strength) -> (Tensor, Tensor)");
   m.def("clip_patches(Tensor x, int size, int patch, int ld, float[] mean, float[] std, bool antialias) -> Tensor");
   m.def("randn_clips(int[] seeds, int[] shape, int stream, float scale, bool raw) -> Tensor");
   m.def("abi_version() -> int");
@@ -915,6 +991,8 @@ TORCH_LIBRARY_IMPL(tooncrafter, CUDA, m) {
   m.impl("frames_to_yuv", frames_to_yuv_cuda);
   m.impl("colour_stats", colour_stats_cuda);
   m.impl("colour_match", colour_match_cuda);
+  m.impl("colour_hist", colour_hist_cuda);
+  m.impl("colour_transfer", colour_transfer_cuda);
   m.impl("clip_patches", clip_patches_cuda);
   m.impl("randn_clips", randn_clips_cuda);
   m.impl("ff_geglu_fused", ff_geglu_fused_cuda);
@@ -940,6 +1018,8 @@ TORCH_LIBRARY_IMPL(tooncrafter, Meta, m) {
   m.impl("frames_to_yuv", frames_to_yuv_meta);
   m.impl("colour_stats", colour_stats_meta);
   m.impl("colour_match", colour_match_meta);
+  m.impl("colour_hist", colour_hist_meta);
+  m.impl("colour_transfer", colour_transfer_meta);
   m.impl("clip_patches", clip_patches_meta);
   m.impl("randn_clips", randn_clips_meta);
   m.impl("ff_geglu_fused", ff_geglu_fused_meta);

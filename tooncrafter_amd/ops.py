@@ -1290,6 +1290,56 @@ class HipOps:
         _lib.check(self.lib.tc_colour_match(C.byref(p), _stream()), "tc_colour_match")
         return out, coefs
 
+    # ------------------------------------------------------------------ histogram transfer (tc_colour_hist, tc_colour_transfer)
+    @staticmethod
+    def _colour_transfer_args(x, src, ref, ref_pixels, strength, base, what="colour_transfer"):
+        """The checked request of a histogram transfer on the clip x: (strength, ref_pixels)."""
+        b, t = x.shape[0], x.shape[2]
+        for name, s, rows in (("src", src, t), ("ref", ref, 2)):
+            if not isinstance(s, torch.Tensor) or not s.is_cuda:
+                raise _lib.TooncrafterHipError(f"{what}: {name}: expected a CUDA tensor: the product path is GPU-only")
+            if s.dtype != torch.int32 or tuple(s.shape) != (b, rows, 3, _lib.TC_COLOUR_BINS) or not s.is_contiguous():
+                raise ValueError(f"{what}: {name}: expected contiguous int32 {(b, rows, 3, _lib.TC_COLOUR_BINS)}, got "
+                                 f"{tuple(s.shape)} {s.dtype}")
+        if base is not None and (HipOps._colour_clip(base, f"{what}: base") != HipOps._colour_clip(x, f"{what}: x")
+                                 or base.device != x.device):
+            raise ValueError(f"{what}: base {tuple(base.shape)} against x {tuple(x.shape)}")
+        strength, ref_pixels = float(strength), int(ref_pixels)
+        if not 0.0 <= strength <= 1.0 or not 0 < ref_pixels <= 1 << 26 or x.shape[3] * x.shape[4] > 1 << 26:
+            raise ValueError(f"{what}: strength {strength} outside [0, 1], or ref_pixels {ref_pixels} or h * w "
+                             f"{x.shape[3] * x.shape[4]} outside [1, 2^26]")
+        return strength, ref_pixels
+
+    def colour_hist(self, x, frames=None):
+        """3 x 1024 int32 counts (r, g, b; of the clamped values, bin = min(1023, floor((c + 1) * 512))) per frame f0, f0 + fstep,
+        ... (nf of them; frames = (f0, nf, fstep), None: all) of every clip of x (b, 3, t, h, w) fp32: (b, nf, 3, 1024)
+        (tc_colour_hist)."""
+        b, t, h, w = self._colour_clip(x, "colour_hist: x")
+        f0, nf, fstep = self._colour_frames(frames, t, "colour_hist")
+        hist = torch.empty((b, nf, 3, _lib.TC_COLOUR_BINS), dtype=torch.int32, device=x.device)
+        p = _lib.TcColourHistParams(x=x.data_ptr(), b=b, t=t, h=h, w=w, f0=f0, nf=nf, fstep=fstep, hist=hist.data_ptr())
+        self._launch("tc_colour_hist", p, x.device)
+        return hist
+
+    def colour_transfer(self, x, src, ref, ref_pixels, strength, base=None, out=None):
+        """x (b, 3, t, h, w) fp32 carried channel by channel onto the course between the histograms of two reference images per
+        clip: `src` (b, t, 3, 1024) the histograms of x, `ref` (b, 2, 3, 1024) those of the reference images over `ref_pixels`
+        pixels each, strength in [0, 1] blending against clamp(x), or against clamp(base) when a `base` clip of x's shape is
+        given.  Returns (transferred clip, table (b, t, 3, 1024) fp32: the displacement of every bin).  `out` may be `x` itself
+        (in place); default: a new tensor (tc_colour_transfer)."""
+        b, t, h, w = self._colour_clip(x, "colour_transfer: x")
+        strength, ref_pixels = self._colour_transfer_args(x, src, ref, ref_pixels, strength, base)
+        if out is None:
+            out = torch.empty_like(x)
+        elif self._colour_clip(out, "colour_transfer: out") != (b, t, h, w) or out.device != x.device:
+            raise ValueError(f"colour_transfer: out {tuple(out.shape)} against x {tuple(x.shape)}")
+        table = torch.empty((b, t, 3, _lib.TC_COLOUR_BINS), dtype=torch.float32, device=x.device)
+        p = _lib.TcColourTransferParams(x=x.data_ptr(), base=None if base is None else base.data_ptr(), out=out.data_ptr(), b=b, t=t,
+                                        h=h, w=w, src=src.data_ptr(), ref=ref.data_ptr(), ref_pixels=ref_pixels, strength=strength,
+                                        table=table.data_ptr())
+        _lib.check(self.lib.tc_colour_transfer(C.byref(p), _stream()), "tc_colour_transfer")
+        return out, table
+
 
 _backend = None
 

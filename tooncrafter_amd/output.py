@@ -52,39 +52,65 @@ class Colour:
         return Colour(planes.standard, planes.range, planes.siting, 10 if planes.fmt == "p010" else 8)
 
 
+COLOUR_MATCH_METHODS = ("mkl", "mean_std", "hm", "hm_mkl_hm")
+
+
 @dataclass(frozen=True)
 class ColourMatch:
     """How decoded frames are matched in colour to the keyframes they interpolate (the `match=` keyword of the synthesis calls;
-    the rule: include/tooncrafter_hip.h, tc_colour_match): `method` "mkl" (the Monge-Kantorovich linear map: means and the
-    full 3 x 3 covariance) | "mean_std" (per-channel mean and standard deviation), `strength` in [0, 1] (0: the frames as they
-    are, 1: the full map).  Anything else raises ValueError here."""
+    the rules: include/tooncrafter_hip.h, tc_colour_match and tc_colour_transfer): `method` "mkl" (the Monge-Kantorovich linear
+    map: means and the full 3 x 3 covariance) | "mean_std" (per-channel mean and standard deviation) | "hm" (per-channel
+    histogram matching over 1024 bins: a monotone tone curve, which no linear map is) | "hm_mkl_hm" (the compound histogram ->
+    MKL -> histogram), `strength` in [0, 1] (0: the frames as they are, 1: the full map).  Anything else raises ValueError
+    here."""
     method: str = "mkl"
     strength: float = 1.0
 
     def __post_init__(self):
-        if not isinstance(self.method, str) or self.method not in ("mkl", "mean_std"):
-            raise ValueError(f"ColourMatch: method {self.method!r}: one of ('mkl', 'mean_std')")
+        if not isinstance(self.method, str) or self.method not in COLOUR_MATCH_METHODS:
+            raise ValueError(f"ColourMatch: method {self.method!r}: one of {COLOUR_MATCH_METHODS}")
         if isinstance(self.strength, bool) or not isinstance(self.strength, (int, float)) or not 0.0 <= self.strength <= 1.0:
             raise ValueError(f"ColourMatch: strength {self.strength!r}: a number in [0, 1]")
 
 
 def match_colour(video: torch.Tensor, ends: torch.Tensor, match: ColourMatch) -> torch.Tensor:
-    """`video` (b, 3, t, h, w) fp32 matched to `ends` (b, 3, 2, H, W) fp32, the two keyframes of every clip at any size: frame 0
-    takes the first keyframe's mean and covariance (of the values clamped to [-1, 1]), frame t - 1 the last one's, the frames
-    between a linear course from one to the other.  Three calls on the device, no synchronisation: the statistics of the
-    keyframes, those of the clip, the match (tc_colour_stats twice, tc_colour_match).  Returns the matched clip (not clamped:
-    the writers clamp).  Targets at inner pinned frames, colour spaces other than the model's RGB values, histogram matching
-    and a gain limit are not offered: a frame that is flat where its keyframes are not gets a large gain, and `strength` is
-    the only control."""
+    """`video` (b, 3, t, h, w) fp32 matched to `ends` (b, 3, 2, H, W) fp32, the two keyframes of every clip at any size, on the
+    device and without a synchronisation.  Returns the matched clip (not clamped: the writers clamp).
+    "mkl" / "mean_std": frame 0 takes the first keyframe's mean and covariance (of the values clamped to [-1, 1]), frame t - 1
+    the last one's, the frames between a linear course from one to the other.  Three calls: the statistics of the keyframes,
+    those of the clip, the match (tc_colour_stats twice, tc_colour_match).
+    "hm": frame 0 takes the first keyframe's per-channel quantile function, frame t - 1 the last one's, the frames between the
+    interpolated quantile functions.  Three calls: the histograms of the clip, those of the keyframes, the transfer
+    (tc_colour_hist twice, tc_colour_transfer).
+    "hm_mkl_hm": that transfer at strength 1, then "mkl" at strength 1 on its result, then the transfer again on that, with
+    `strength` blending the finished compound against the original frames (strength 0: clamp(video) exactly).  Nine calls;
+    the keyframes' histograms and statistics are computed once and the intermediate clips are overwritten in place.
+    In a timeline the last frame of one segment and frame 0 of the next are both matched to the inner keyframe's own
+    statistics or quantile function.
+    Targets at inner pinned frames, colour spaces other than the model's RGB values and a gain limit are not offered: under
+    the linear maps a frame that is flat where its keyframes are not gets a large gain, and `strength` is the only control;
+    and no histogram match can spread a flat frame: all its pixels share a bin and move together."""
     if not isinstance(match, ColourMatch):
         raise ValueError(f"match_colour: match: expected a ColourMatch, got {type(match).__name__}")
     if ends is None or ends.dim() != 5 or ends.shape[:3] != (video.shape[0], 3, 2):
         raise ValueError(f"match_colour: ends must be ({video.shape[0]}, 3, 2, H, W), got "
                          f"{None if ends is None else tuple(ends.shape)}")
     video, ends = video.to(torch.float32).contiguous(), ends.to(torch.float32).contiguous()
-    ref = ops.colour_stats(ends, frames=(0, 2, 1))
-    src = ops.colour_stats(video, frames=(0, video.shape[2], 1))
-    return ops.colour_match(video, src, ref, ends.shape[3] * ends.shape[4], match.method, match.strength)[0]
+    t, ref_pixels = video.shape[2], ends.shape[3] * ends.shape[4]
+    if match.method in ("mkl", "mean_std"):
+        ref = ops.colour_stats(ends, frames=(0, 2, 1))
+        src = ops.colour_stats(video, frames=(0, t, 1))
+        return ops.colour_match(video, src, ref, ref_pixels, match.method, match.strength)[0]
+    src = ops.colour_hist(video, frames=(0, t, 1))
+    ref = ops.colour_hist(ends, frames=(0, 2, 1))
+    if match.method == "hm":
+        return ops.colour_transfer(video, src, ref, ref_pixels, match.strength)[0]
+    work = ops.colour_transfer(video, src, ref, ref_pixels, 1.0)[0]               # a clip of our own: `video` is the caller's
+    ref_stats = ops.colour_stats(ends, frames=(0, 2, 1))
+    stats = ops.colour_stats(work, frames=(0, t, 1))
+    work = ops.colour_match(work, stats, ref_stats, ref_pixels, "mkl", 1.0, out=work)[0]
+    src = ops.colour_hist(work, frames=(0, t, 1))
+    return ops.colour_transfer(work, src, ref, ref_pixels, match.strength, base=video, out=work)[0]
 
 
 def clip_to_uint8(samples: torch.Tensor, loop: bool = False, size=None, filter: str = "bicubic", fmt: str = "rgb24",

@@ -196,6 +196,17 @@ class TorchLibOps(HipOps):
         code, strength, ref_pixels = self._colour_match_args(x, src, ref, ref_pixels, method, strength)
         return self.t.colour_match(x, src, ref, ref_pixels, code, strength)
 
+    def colour_hist(self, x, frames=None):
+        _, t, _, _ = self._colour_clip(x, "colour_hist: x")
+        return self.t.colour_hist(x, *self._colour_frames(frames, t, "colour_hist"))
+
+    def colour_transfer(self, x, src, ref, ref_pixels, strength, base=None, out=None):
+        if out is not None:                                  # an explicit result buffer (in place): the ctypes method
+            return super().colour_transfer(x, src, ref, ref_pixels, strength, base=base, out=out)
+        self._colour_clip(x, "colour_transfer: x")
+        strength, ref_pixels = self._colour_transfer_args(x, src, ref, ref_pixels, strength, base)
+        return self.t.colour_transfer(x, base, src, ref, ref_pixels, strength)
+
     def clip_patches(self, x, *, size, patch, ld, mean, std, antialias=True):
         return self.t.clip_patches(x, int(size), int(patch), int(ld), [float(v) for v in mean], [float(v) for v in std], bool(antialias))
 
