@@ -788,7 +788,7 @@ typedef struct TcFramesYuvOutParams {
 int64_t tc_frames_to_yuv_workspace(const TcFramesYuvOutParams* p);
 int tc_frames_to_yuv(const TcFramesYuvOutParams* p, void* stream);
 
-/* ---- Colour match: decoded frames to their keyframes, on the device (additive within ABI 14: two structs, three symbols).
+/* ---- Colour match: decoded frames to their keyframes, on the device (additive within ABI 14: three structs, four symbols).
  * The decoder's frames drift in colour and contrast away from the keyframes they interpolate; this is the linear colour
  * transfer that workflows around the model run on the host (mean / std transfer, or the Monge-Kantorovich linear map), as
  * one reduction, one 3 x 3 solve per frame and one affine pass, without a synchronisation.  THE RULE, stated once (its
@@ -805,10 +805,18 @@ int tc_frames_to_yuv(const TcFramesYuvOutParams* p, void* stream);
  * therefore do not depend on b, on the batch slot, on the alignment of x or on which other frames are requested.
  * From the sums: m = S1 / n, C = S2 / n - m m^T (symmetric 3 x 3).
  *
- * Target of frame f of a t-frame clip.  Every clip has two reference images with statistics (m0, C0), (m1, C1) over
- * ref_pixels pixels each:  w = f / (t - 1) (0 when t = 1),  m_t = (1 - w) m0 + w m1,  C_t = (1 - w) C0 + w C1.  Frame 0 is
- * matched to the first keyframe and frame t - 1 to the last, with a linear course between (a convex combination of
- * covariances is a covariance).
+ * Knots.  A clip of t frames has nk reference images, 1 <= nk <= TC_TEMPORAL_MAX_FRAMES, at strictly increasing frame indices
+ * k_0 < ... < k_{nk-1}, all in [0, t) and the same for every clip of the batch, each with statistics (tc_colour_match_knots)
+ * or a histogram (tc_colour_transfer_knots) over ref_pixels pixels.  The indices are HOST values inside the params struct
+ * (int32_t nk; int32_t knot[TC_TEMPORAL_MAX_FRAMES]); the launcher copies them into the kernel arguments: no device read, no
+ * synchronisation, safe to capture.  tc_colour_match and tc_colour_transfer are the knots {0, t - 1} ({0} when t = 1, with
+ * the first reference image) and no gain limit: the same launcher, the same bits as ever.
+ *
+ * Course of frame f (csrc/colour_course.h states it once for both kernels).  f <= k_0: the target is knot 0 itself;
+ * f >= k_{nk-1}: the last knot itself; otherwise j is the last knot with k_j <= f and
+ *   w = (double)(f - k_j) / (double)(k_{j+1} - k_j);
+ * a frame on a knot takes that knot itself.  For the linear methods m_t = (1 - w) m_j + w m_{j+1} and C_t likewise (a
+ * convex combination of covariances is a covariance); for the histogram transfer T = q_j + w (q_{j+1} - q_j), below.
  *
  * Regularisation: eps = 2^-16 in value^2 units (about half an 8-bit code value squared), added to every diagonal that is
  * inverted or rooted, on the source and on the target side.
@@ -819,6 +827,11 @@ int tc_frames_to_yuv(const TcFramesYuvOutParams* p, void* stream);
  *                       roots from an eigendecomposition of the 3 x 3 matrix: cyclic Jacobi, pairs (0,1), (0,2), (1,2), a
  *                       fixed eight sweeps; eigenvalues of S are clamped below at eps / 2, those of the middle matrix at 0,
  *                       and the middle matrix is symmetrised, (M + M^T) / 2, before it is decomposed;
+ *   gain limit          max_gain g (tc_colour_match_knots): 0 = none; otherwise finite and >= 1, applied to A in double before o
+ *                       and before the strength, so the means are still matched.  MEAN_STD: every diagonal entry is clamped
+ *                       to [1 / g, g], 1 / g formed once.  MKL: A is symmetrised, (A + A^T) / 2, decomposed by the same cyclic
+ *                       Jacobi (same pairs, eight sweeps), its eigenvalues are clamped to [1 / g, g] and A = V diag V^T is
+ *                       rebuilt -- whenever g > 0, whether or not an eigenvalue was outside: one path, a continuous map.
  *   o = m_t - A m_s;   with strength s in [0, 1]:  A' = I + s (A - I),  o' = s o.
  * Each of the twelve numbers is rounded to fp32 once and written to coefs[frame][12]: A' row-major, then o'.
  *
@@ -826,10 +839,11 @@ int tc_frames_to_yuv(const TcFramesYuvOutParams* p, void* stream);
  *   y_k = ((o'_k + A'_k0 r) + A'_k1 g) + A'_k2 b,
  * every product and every sum rounded on its own (nothing contracted into an FMA), so that separate float32 operations on
  * any host give the same bits.  y is NOT clamped: the back end clamps.  Exact consequences: strength 0 returns clamp(x);
- * MEAN_STD of a frame against its own statistics returns clamp(x).
+ * MEAN_STD of a frame against its own statistics returns clamp(x); MEAN_STD with g = 1 gives A' = I exactly and
+ * o' = fp32(s (m_t - m_s)), the mean shift alone.  Without a limit a frame that is flat where its references are not gets a gain
+ * of about sqrt(var_ref / eps), tens to hundreds: that is what max_gain is for.
  *
- * Not offered: targets at inner frames, a colour space other than the model's RGB values, a gain limit (a frame that is flat
- * where its keyframes are not gets a large gain by the rule above; strength is the only control). */
+ * Not offered: a colour space other than the model's RGB values. */
 #define TC_COLOUR_STATS 9
 typedef struct TcColourStatsParams {
   const float* x;            /* (b, 3, t, h, w) fp32 */
@@ -864,7 +878,25 @@ typedef struct TcColourMatchParams {
  * 2^31 - 1 blocks in all.  Nothing is launched or written on a refusal. */
 int tc_colour_match(const TcColourMatchParams* p, void* stream);
 
-/* ---- Histogram colour transfer (additive within ABI 14: two structs, three symbols).  What a decoder does to toon frames is
+typedef struct TcColourMatchKnotsParams {
+  const float* x; float* out;   /* as in TcColourMatchParams, field for field, down to coefs */
+  int32_t b, t, h, w;
+  const double* src;            /* [b * t][9] */
+  const double* ref;            /* [b * nk][9]: statistics of the nk reference images of every clip, in knot order */
+  int64_t ref_pixels;
+  int32_t method; float strength;
+  float* coefs;                 /* [b * t][12] fp32, written by the call (required) */
+  int32_t nk;                   /* 1 .. TC_TEMPORAL_MAX_FRAMES */
+  int32_t knot[TC_TEMPORAL_MAX_FRAMES];   /* the first nk: strictly increasing frame indices in [0, t); host values */
+  float max_gain;               /* 0: no limit; otherwise finite and >= 1 */
+} TcColourMatchKnotsParams;
+/* tc_colour_match towards nk reference images at the knots, with an optional gain limit (the rule above): the same two
+ * launches; only the coefficient kernel knows the course.  Refuses what tc_colour_match refuses, with the same codes, and
+ * TC_EINVAL: nk outside [1, TC_TEMPORAL_MAX_FRAMES], knots not strictly increasing or outside [0, t), max_gain negative, in
+ * (0, 1) or not finite.  Nothing is launched or written on a refusal. */
+int tc_colour_match_knots(const TcColourMatchKnotsParams* p, void* stream);
+
+/* ---- Histogram colour transfer (additive within ABI 14: three structs, four symbols).  What a decoder does to toon frames is
  * a bent tone curve per channel (blacks lift, highlights compress), which no 3 x 3 matrix repairs: this is the per-channel
  * monotone transfer that carries a frame's histogram onto its keyframes'.  THE RULE, stated once (restated with numpy integers
  * and float64 for the tests: tests/colour_hist_ref.py):
@@ -877,8 +909,9 @@ int tc_colour_match(const TcColourMatchParams* p, void* stream);
  * Histogram of a frame: 3 x 1024 int32 counts, channel r, then g, then b.  Counts are exact integers: no order of summation
  * is part of the result, and the result does not depend on what hist or the workspace held before the call.
  *
- * Transfer of frame f of t, per channel.  s[i]: the frame's counts, n = h * w;  a[i], b[i]: the counts of the clip's first
- * and last reference image, m = ref_pixels each.
+ * Transfer of frame f of t, per channel.  s[i]: the frame's counts, n = h * w;  a[i], b[i]: the counts of the reference
+ * images at knots j and j + 1 of the frame's course (the knots and the course: tc_colour_match above; tc_colour_transfer is
+ * the knots {0, t - 1}, the clip's first and last reference image), m = ref_pixels each.
  *   midpoint rank   P_i = 2 S_i - s_i with S_i = sum_{j <= i} s_j: an integer in [0, 2n].  Only bins with s_i > 0 get an
  *                   entry (there P_i > 0); every other entry of the table is +0.0f.
  *   quantile        for r in {a, b}:  A_j = sum_{i < j} r_i (A_0 = 0, A_1024 = m);  j the smallest index in [1, 1024] with
@@ -886,8 +919,9 @@ int tc_colour_match(const TcColourMatchParams* p, void* stream);
  *                   and r_{j-1} > 0, and in bin units
  *                     q_r = (double)(j - 1) + (double)(P_i m - A_{j-1} 2n) / (double)(r_{j-1} 2n):
  *                   both integers exact in double, one division, one addition.
- *   course          w = (double) f / (double)(t - 1) (0 when t = 1),  T = q_a + w (q_b - q_a);  frame t - 1 of a clip with
- *                   t > 1 takes T = q_b itself.  This interpolates quantile functions (the one-dimensional transport
+ *   course          T = q_a + w (q_b - q_a) with the w of the course;  a frame on a knot, before the first or after the last
+ *                   takes that knot's q itself (with knots {0, t - 1}: w = (double) f / (double)(t - 1), frame t - 1 takes
+ *                   q_b itself, and t = 1 takes q_a).  This interpolates quantile functions (the one-dimensional transport
  *                   geodesic), the counterpart of the linear course of (m, C) in tc_colour_match.
  *   entry           D[f][k][i] = (float)((T - ((double) i + 0.5)) / 512.0): the displacement of bin i in value units, rounded
  *                   to fp32 once.  Every double operation is rounded on its own; nothing is contracted.
@@ -907,8 +941,8 @@ int tc_colour_match(const TcColourMatchParams* p, void* stream);
  *
  * Size limit: h * w <= 2^26 and ref_pixels <= 2^26, otherwise TC_ESHAPE: what keeps P_i m and A_j 2n exact in int64 and double.
  *
- * Not offered: targets at inner frames, a colour space other than the model's RGB values, a gain limit; and a flat frame
- * cannot be spread by any histogram match: all its pixels share a bin and move together. */
+ * Not offered: a colour space other than the model's RGB values; and a flat frame cannot be spread by any histogram match:
+ * all its pixels share a bin and move together (a tone curve has no matrix, so there is no gain limit here). */
 #define TC_COLOUR_BINS 1024
 typedef struct TcColourHistParams {
   const float* x;            /* (b, 3, t, h, w) fp32 */
@@ -946,6 +980,24 @@ typedef struct TcColourTransferParams {
  * out overlapping x other than out == x, out overlapping base; TC_EALIGN: src, ref or table not 4-byte aligned; TC_ESHAPE:
  * h * w or ref_pixels > 2^26, more than 2^31 - 1 blocks in all.  Nothing is launched or written on a refusal. */
 int tc_colour_transfer(const TcColourTransferParams* p, void* stream);
+
+typedef struct TcColourTransferKnotsParams {
+  const float* x;               /* as in TcColourTransferParams, field for field, down to table */
+  const float* base;
+  float* out;
+  int32_t b, t, h, w;
+  const int32_t* src;           /* [b * t][3][1024] */
+  const int32_t* ref;           /* [b * nk][3][1024]: histograms of the nk reference images of every clip, in knot order */
+  int64_t ref_pixels;
+  float strength;
+  float* table;                 /* [b * t][3][1024] fp32, written by the call (required) */
+  int32_t nk;                   /* 1 .. TC_TEMPORAL_MAX_FRAMES */
+  int32_t knot[TC_TEMPORAL_MAX_FRAMES];   /* the first nk: strictly increasing frame indices in [0, t); host values */
+} TcColourTransferKnotsParams;
+/* tc_colour_transfer towards nk reference images at the knots: the same two launches; only the table kernel knows the
+ * course.  Refuses what tc_colour_transfer refuses, with the same codes, and TC_EINVAL: nk outside
+ * [1, TC_TEMPORAL_MAX_FRAMES], knots not strictly increasing or outside [0, t).  Nothing is launched or written on a refusal. */
+int tc_colour_transfer_knots(const TcColourTransferKnotsParams* p, void* stream);
 
 /* introspection */
 int tc_abi_version(void);

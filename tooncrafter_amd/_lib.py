@@ -239,7 +239,20 @@ class TcColourTransferParams(C.Structure):
     ]
 
 
-TC_COLOUR_BINS = 1024                                    # include/tooncrafter_hip.h: bins per channel of tc_colour_hist
+class TcColourMatchKnotsParams(C.Structure):
+    """TcColourMatchParams towards nk reference images at host knot indices, with a gain limit (tc_colour_match_knots; additive
+    within ABI 14)."""
+    _fields_ = TcColourMatchParams._fields_ + [("nk", C.c_int32), ("knot", C.c_int32 * TC_TEMPORAL_MAX_FRAMES),
+                                               ("max_gain", C.c_float)]
+
+
+class TcColourTransferKnotsParams(C.Structure):
+    """TcColourTransferParams towards nk reference images at host knot indices (tc_colour_transfer_knots; additive within
+    ABI 14)."""
+    _fields_ = TcColourTransferParams._fields_ + [("nk", C.c_int32), ("knot", C.c_int32 * TC_TEMPORAL_MAX_FRAMES)]
+
+
+TC_COLOUR_BINS = 1024                                   # include/tooncrafter_hip.h: bins per channel of tc_colour_hist
 TC_COLOUR_STATS = 9                                      # include/tooncrafter_hip.h: doubles per frame of tc_colour_stats
 TC_COLOUR_METHODS = {"mean_std": 0, "mkl": 1}            # TC_COLOUR_MEAN_STD / TC_COLOUR_MKL
 TC_YUV_FORMATS = {"i420": 1, "nv12": 2, "p010": 3}       # include/tooncrafter_hip.h: the TC_PIXFMT_* tc_frames_from_yuv reads
@@ -335,6 +348,8 @@ SYMBOLS = {
     "tc_colour_hist_workspace": (C.c_int64, [C.POINTER(TcColourHistParams)]),
     "tc_colour_hist": (C.c_int, [C.POINTER(TcColourHistParams), C.c_void_p]),
     "tc_colour_transfer": (C.c_int, [C.POINTER(TcColourTransferParams), C.c_void_p]),
+    "tc_colour_match_knots": (C.c_int, [C.POINTER(TcColourMatchKnotsParams), C.c_void_p]),
+    "tc_colour_transfer_knots": (C.c_int, [C.POINTER(TcColourTransferKnotsParams), C.c_void_p]),
     "tc_gemm_ws_eligible": (C.c_int, [C.POINTER(TcGemmParams)]),
     "tc_gemm_gn_rows": (C.c_int, [C.POINTER(TcGemmParams)]),
     "tc_groupnorm_part": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,

@@ -345,13 +345,16 @@ def decode_spliced(model, latents, refs, marks=None):
     return video
 
 
-def _matched(video, cond, match):
+def _matched(video, cond, match, pinned_px=None):
     """The decoded clip as it is (match None: nothing is called), or matched in colour to the keyframes of its conditions
     (`output.match_colour`: tc_colour_stats twice and tc_colour_match for the linear methods, tc_colour_hist twice and
-    tc_colour_transfer for "hm", the three stages of both for "hm_mkl_hm")."""
+    tc_colour_transfer for "hm", the three stages of both for "hm_mkl_hm").  pinned_px: the {frame index: pixels} a call pins;
+    with `match.targets == "pinned"` they are further targets (`match_colour`'s inner, the knots calls)."""
     if match is None:
         return video
     from .output import match_colour
+    if pinned_px and getattr(match, "targets", "ends") == "pinned":
+        return match_colour(video, cond.ends_px, match, inner={int(i): px for i, px in pinned_px.items()})
     return match_colour(video, cond.ends_px, match)
 
 
@@ -363,12 +366,15 @@ def synthesize(model, videos, latent_shape, *, plan: SamplingPlan, prompts=None,
     `variant_seed(plan.seeds[i], k)`: the same pixels as a `variants=1` run with that seed.
     match: an `output.ColourMatch` -- every decoded clip is matched in colour to frames 0 and t-1 of `videos` (frame 0 alone
     without hold_endpoints) before it is returned, by a linear map ("mkl", "mean_std") or by histogram ("hm", "hm_mkl_hm");
-    None: no colour op is called.  The targets are the two endpoints only: `keyframes=` pins latents, it does not add
-    targets."""
+    None: no colour op is called.  `ColourMatch(targets="ends")`, the default: the targets are the two endpoints only, and
+    `keyframes=` pins latents without adding targets.  `ColourMatch(targets="pinned")`: every pinned frame is a target too --
+    frame i is matched to `keyframes[i]` itself, the one image whose colours are known there, and the frames between two
+    targets to the course from one to the next (`match_colour`'s inner).  `ColourMatch(max_gain=g)` limits the linear gains."""
     cond = Conditions.build(model, videos, prompts=prompts, fs=fs, guided=plan.scale != 1.0,
                             three_way=three_way, image_branch=plan.image_scale != 1.0, hold_endpoints=hold_endpoints)
     pinned = pin_frames(model, keyframes, latent_shape[2]) if keyframes else None
-    clips = [_matched(decode_spliced(model, sample(model, cond, plan, latent_shape, pinned=pinned, variant=k), cond.refs), cond, match)
+    clips = [_matched(decode_spliced(model, sample(model, cond, plan, latent_shape, pinned=pinned, variant=k), cond.refs), cond, match,
+                      keyframes)
              for k in range(variants)]
     return torch.stack(clips, dim=1)
 
@@ -382,8 +388,8 @@ def synthesize_u8(model, first_u8, last_u8, latent_shape, *, size, plan: Samplin
     pixel back end) -- (b, t, oh, ow, 3) frames, or for "i420" / "nv12" the (b, t, oh * ow * 3 / 2) planes that
     `mp4.write_mp4_i420` or an encoder takes.  out_colour: an `output.Colour` for those planes (`clip_to_uint8`'s colour).
     match: an `output.ColourMatch` -- the decoded clip is matched in colour to the two keyframes at model size
-    (`output.match_colour`; methods "mkl", "mean_std", "hm", "hm_mkl_hm") before it goes to the writer; None: no colour op is
-    called."""
+    (`output.match_colour`; methods "mkl", "mean_std", "hm", "hm_mkl_hm"; `max_gain` as there) before it goes to the writer;
+    None: no colour op is called.  This call pins nothing: `targets="pinned"` means "ends" here."""
     from .output import clip_to_uint8
     cond = Conditions.from_uint8(model, first_u8, last_u8, size=size, t=latent_shape[2], prompts=prompts, fs=fs,
                                  guided=plan.scale != 1.0, three_way=three_way, image_branch=plan.image_scale != 1.0,
@@ -432,7 +438,8 @@ def synthesize_timeline_u8(model, keyframes, latent_shape, *, size, plan: Sampli
     match: an `output.ColourMatch` -- every batch of segments is matched in colour to its own keyframes (`output.match_colour`)
     before it is written: the last frame of segment i and frame 0 of segment i + 1 then have the same target, the inner
     keyframe's statistics ("mkl", "mean_std") or its per-channel quantile function ("hm", "hm_mkl_hm"), so the video does not
-    step in colour there.  None: no colour op is called."""
+    step in colour there.  `max_gain` as in `match_colour`; a timeline pins nothing, so `targets="pinned"` means "ends" here.
+    None: no colour op is called."""
     from dataclasses import replace
     planar = isinstance(keyframes, Planes)
     if not planar and not (isinstance(keyframes, torch.Tensor) and keyframes.dtype == torch.uint8 and keyframes.dim() == 4 and keyframes.shape[3] == 3):

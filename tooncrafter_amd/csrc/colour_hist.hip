@@ -1,5 +1,5 @@
-// Histogram colour transfer of decoded frames to their keyframes (tc_colour_hist, tc_colour_transfer; the rule:
-// include/tooncrafter_hip.h).  Counts are integers, so nothing here depends on an order of summation:
+// Histogram colour transfer of decoded frames to their keyframes (tc_colour_hist, tc_colour_transfer, tc_colour_transfer_knots;
+// the rule: include/tooncrafter_hip.h).  Counts are integers, so nothing here depends on an order of summation:
 //   colour_hist_kernel         one block per (frame slot, channel, part): a 1024-bin LDS histogram per wave (integer LDS
 //                              atomics), the four added through LDS                                        -> workspace
 //   colour_hist_finish_kernel  the parts of a (slot, channel) added                                       -> hist
@@ -13,6 +13,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "colour_course.h"
 
 namespace {
 
@@ -111,19 +112,23 @@ __device__ __forceinline__ double ref_quantile(const int32_t* cum, int64_t pm, i
 }
 
 // One block per (frame, channel), thread i = bin i.  Inclusive scans of s, a, b: an up-shuffle scan per wave, then the totals of
-// the waves before it.
+// the waves before it.  The frame's course through the knots (csrc/colour_course.h) picks the one or the two of the clip's
+// reference histograms (rows clip * ref_rows .. of `ref`, ref_rows >= knots.nk) that make its target.
 __global__ __launch_bounds__(TC_COLOUR_BINS) void colour_table_kernel(const int32_t* __restrict__ src, const int32_t* __restrict__ ref,
-                                                                      int t, int64_t n, int64_t m, float* __restrict__ table) {
+                                                                      int t, int64_t n, int64_t m, int ref_rows, TcColourKnots knots,
+                                                                      float* __restrict__ table) {
 #pragma clang fp contract(off)
   __shared__ int32_t total[TC_COLOUR_BINS / 64][3];
   __shared__ int32_t cum[2][TC_COLOUR_BINS + 1];
   const int fk = blockIdx.x, fr = fk / 3, k = fk - fr * 3;
   const int clip = fr / t, f = fr - clip * t;
+  const TcColourCourse at = tc_colour_course(knots, f);                   // the same for the whole block
+  const int ja = at.j, jb = at.single ? at.j : at.j + 1;
   const int i = threadIdx.x, lane = i & 63, wave = i >> 6;
   const int32_t s = src[(int64_t)fk * TC_COLOUR_BINS + i];
   int32_t v0 = s;
-  int32_t v1 = ref[(((int64_t)clip * 2) * 3 + k) * TC_COLOUR_BINS + i];
-  int32_t v2 = ref[(((int64_t)clip * 2 + 1) * 3 + k) * TC_COLOUR_BINS + i];
+  int32_t v1 = ref[(((int64_t)clip * ref_rows + ja) * 3 + k) * TC_COLOUR_BINS + i];
+  int32_t v2 = ref[(((int64_t)clip * ref_rows + jb) * 3 + k) * TC_COLOUR_BINS + i];
 #pragma unroll
   for (int off = 1; off < 64; off <<= 1) {
     const int32_t u0 = __shfl_up(v0, off, 64), u1 = __shfl_up(v1, off, 64), u2 = __shfl_up(v2, off, 64);
@@ -139,11 +144,10 @@ __global__ __launch_bounds__(TC_COLOUR_BINS) void colour_table_kernel(const int3
   float d = 0.0f;
   if (s > 0) {
     const int64_t pm = (2 * (int64_t)v0 - (int64_t)s) * m, n2 = 2 * n;
-    const double qa = ref_quantile(cum[0], pm, n2), qb = ref_quantile(cum[1], pm, n2);
-    double T = qb;
-    if (t == 1 || f < t - 1) {
-      const double w = t > 1 ? (double)f / (double)(t - 1) : 0.0;
-      const double step = w * (qb - qa);
+    double T = ref_quantile(cum[0], pm, n2);                              // a frame that takes one knot: that knot's q itself
+    if (!at.single) {
+      const double qa = T, qb = ref_quantile(cum[1], pm, n2);
+      const double step = at.w * (qb - qa);
       T = qa + step;
     }
     const double centre = (double)i + 0.5;
@@ -224,7 +228,7 @@ int hist_request(const TcColourHistParams* pp, int* parts, int64_t* slots) {
 }
 
 template <bool VEC>
-void launch_lut(const TcColourTransferParams& p, int64_t hw, int64_t frames, int chunks, hipStream_t s) {
+void launch_lut(const TcColourTransferKnotsParams& p, int64_t hw, int64_t frames, int chunks, hipStream_t s) {
   const dim3 grid((unsigned)(frames * chunks));
   if (p.base) hipLaunchKernelGGL((colour_lut_kernel<VEC, true>), grid, dim3(CH_THREADS), 0, s, p.x, p.base, p.out, p.table, p.strength, p.t, hw, chunks);
   else hipLaunchKernelGGL((colour_lut_kernel<VEC, false>), grid, dim3(CH_THREADS), 0, s, p.x, p.base, p.out, p.table, p.strength, p.t, hw, chunks);
@@ -263,11 +267,14 @@ extern "C" int tc_colour_hist(const TcColourHistParams* pp, void* stream) {
   return TC_OK;
 }
 
-extern "C" int tc_colour_transfer(const TcColourTransferParams* pp, void* stream) {
-  if (!pp) return TC_EINVAL;
-  const TcColourTransferParams& p = *pp;
+namespace {
+
+// The transfer of p: its checks and its two launches.  ref_rows: reference images per clip in p.ref (p.nk for the knots call; 2
+// for tc_colour_transfer, also when t = 1 and only the first is a knot).
+int colour_transfer_launch(const TcColourTransferKnotsParams& p, int ref_rows, void* stream) {
   if (!p.x || !p.out || !p.src || !p.ref || !p.table || p.b <= 0 || p.t <= 0 || p.h <= 0 || p.w <= 0) return TC_EINVAL;
   if (!std::isfinite(p.strength) || p.strength < 0.f || p.strength > 1.f || p.ref_pixels <= 0) return TC_EINVAL;
+  if (const int rc = tc_colour_knots_check(p.nk, p.knot, p.t)) return rc;
   const int64_t hw = (int64_t)p.h * p.w, frames = (int64_t)p.b * p.t;
   const uintptr_t bytes = (uintptr_t)frames * 3 * (uintptr_t)hw * sizeof(float);
   const uintptr_t a = reinterpret_cast<uintptr_t>(p.x), o = reinterpret_cast<uintptr_t>(p.out);
@@ -279,12 +286,38 @@ extern "C" int tc_colour_transfer(const TcColourTransferParams* pp, void* stream
   chunks = chunks > CH_MAX_CHUNKS ? CH_MAX_CHUNKS : chunks;
   if (frames * chunks > INT32_MAX || frames * 3 > INT32_MAX) return TC_ESHAPE;
   const bool vec = (hw & 3) == 0 && tc_aligned16(p.x) && tc_aligned16(p.out) && (!p.base || tc_aligned16(p.base));
+  TcColourKnots knots = {};
+  knots.nk = p.nk;
+  for (int i = 0; i < p.nk; ++i) knots.knot[i] = p.knot[i];
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(colour_table_kernel, dim3((unsigned)(frames * 3)), dim3(TC_COLOUR_BINS), 0, s, p.src, p.ref, p.t, hw, p.ref_pixels,
-                     p.table);
+                     ref_rows, knots, p.table);
   TC_LAUNCH_CHECK();
   if (vec) launch_lut<true>(p, hw, frames, (int)chunks, s);
   else launch_lut<false>(p, hw, frames, (int)chunks, s);
   TC_LAUNCH_CHECK();
   return TC_OK;
+}
+
+}  // namespace
+
+// the knots {0, t - 1} ({0} when t = 1) of the clip's two reference images
+extern "C" int tc_colour_transfer(const TcColourTransferParams* pp, void* stream) {
+  if (!pp) return TC_EINVAL;
+  TcColourTransferKnotsParams k = {};
+  k.x = pp->x; k.base = pp->base; k.out = pp->out;
+  k.b = pp->b; k.t = pp->t; k.h = pp->h; k.w = pp->w;
+  k.src = pp->src; k.ref = pp->ref;
+  k.ref_pixels = pp->ref_pixels;
+  k.strength = pp->strength;
+  k.table = pp->table;
+  k.nk = pp->t > 1 ? 2 : 1;
+  k.knot[0] = 0;
+  k.knot[1] = pp->t - 1;
+  return colour_transfer_launch(k, 2, stream);
+}
+
+extern "C" int tc_colour_transfer_knots(const TcColourTransferKnotsParams* pp, void* stream) {
+  if (!pp) return TC_EINVAL;
+  return colour_transfer_launch(*pp, pp->nk, stream);
 }

@@ -1,14 +1,17 @@
-// Colour match of decoded frames to their keyframes (tc_colour_stats, tc_colour_match; the rule: include/tooncrafter_hip.h).
+// Colour match of decoded frames to their keyframes (tc_colour_stats, tc_colour_match, tc_colour_match_knots; the rule:
+// include/tooncrafter_hip.h).
 // Three streaming passes over the three channel planes of a frame, t * h * w floats apart, and one thread of double
 // arithmetic per frame between them:
 //   colour_stats_kernel   nine double sums per (frame, part), parts fixed by h * w alone      -> workspace
 //   colour_finish_kernel  the parts of a frame added in index order                           -> stats
-//   colour_coefs_kernel   (m, C) of frame and target, the 3 x 3 map, twelve fp32 numbers      -> coefs
+//   colour_coefs_kernel   (m, C) of frame and target (its course through the knots: csrc/colour_course.h), the 3 x 3 map and
+//                         its optional gain limit, twelve fp32 numbers                         -> coefs
 //   colour_apply_kernel   y = o' + A' clamp(x), every operation rounded on its own            -> out
 // No atomics, no allocation, no synchronisation.
 #include <cmath>
 
 #include "common.h"
+#include "colour_course.h"
 
 namespace {
 
@@ -169,20 +172,37 @@ __device__ __forceinline__ void mkl_map(const double* cs, const double* ct, doub
   mat3_mul(tmp, ihalf, A);
 }
 
-// The twelve numbers of frame f of a t-frame clip: `src` its nine sums over n_src pixels, ref0 / ref1 those of the clip's two
-// reference images over n_ref pixels each.
-__device__ __forceinline__ void frame_coefs(const double* __restrict__ src, const double* __restrict__ ref0,
-                                            const double* __restrict__ ref1, int f, int t, double n_src, double n_ref, int method,
-                                            float strength, float* __restrict__ out) {
-  double ms[3], cs[6], m0[3], c0[6], m1[3], c1[6], mt[3], ct[6], A[9];
+// A held inside the gain limit g (lo = 1 / g): the eigenvalues of its symmetric part clamped to [lo, g], by the same Jacobi
+__device__ __forceinline__ void mkl_limit(double* A, double lo, double g) {
+  double a[6] = {A[0], 0.5 * (A[1] + A[3]), 0.5 * (A[2] + A[6]), A[4], 0.5 * (A[5] + A[7]), A[8]};
+  double v[9];
+  jacobi_eig(a, v);
+  from_eig(v, fmin(fmax(a[0], lo), g), fmin(fmax(a[3], lo), g), fmin(fmax(a[5], lo), g), A);
+}
+
+// The twelve numbers of frame f of a clip: `src` its nine sums over n_src pixels, `ref` those of the clip's reference images
+// (n_ref pixels each) in knot order; the frame's course through the knots picks the one or the two that make its target.
+__device__ __forceinline__ void frame_coefs(const double* __restrict__ src, const double* __restrict__ ref, const TcColourKnots& knots,
+                                            int f, double n_src, double n_ref, int method, float strength, float max_gain,
+                                            float* __restrict__ out) {
+  double ms[3], cs[6], m0[3], c0[6], mt[3], ct[6], A[9];
   moments(src, n_src, ms, cs);
-  moments(ref0, n_ref, m0, c0);
-  moments(ref1, n_ref, m1, c1);
-  const double w = t > 1 ? (double)f / (double)(t - 1) : 0.0, u = 1.0 - w;
+  const TcColourCourse at = tc_colour_course(knots, f);
+  moments(ref + (int64_t)at.j * TC_COLOUR_STATS, n_ref, m0, c0);
+  if (at.single) {
 #pragma unroll
-  for (int k = 0; k < 3; ++k) mt[k] = u * m0[k] + w * m1[k];
+    for (int k = 0; k < 3; ++k) mt[k] = m0[k];
 #pragma unroll
-  for (int k = 0; k < 6; ++k) ct[k] = u * c0[k] + w * c1[k];
+    for (int k = 0; k < 6; ++k) ct[k] = c0[k];
+  } else {
+    double m1[3], c1[6];
+    moments(ref + (int64_t)(at.j + 1) * TC_COLOUR_STATS, n_ref, m1, c1);
+    const double w = at.w, u = 1.0 - w;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) mt[k] = u * m0[k] + w * m1[k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) ct[k] = u * c0[k] + w * c1[k];
+  }
   if (method == TC_COLOUR_MKL) {
     mkl_map(cs, ct, A);
   } else {
@@ -190,6 +210,16 @@ __device__ __forceinline__ void frame_coefs(const double* __restrict__ src, cons
     A[0] = sqrt((ct[0] + CM_EPS) / (cs[0] + CM_EPS));
     A[4] = sqrt((ct[3] + CM_EPS) / (cs[3] + CM_EPS));
     A[8] = sqrt((ct[5] + CM_EPS) / (cs[5] + CM_EPS));
+  }
+  if (max_gain > 0.f) {
+    const double g = (double)max_gain, lo = 1.0 / g;
+    if (method == TC_COLOUR_MKL) {
+      mkl_limit(A, lo, g);
+    } else {
+      A[0] = fmin(fmax(A[0], lo), g);
+      A[4] = fmin(fmax(A[4], lo), g);
+      A[8] = fmin(fmax(A[8], lo), g);
+    }
   }
   const double s = (double)strength;
 #pragma unroll
@@ -204,16 +234,16 @@ __device__ __forceinline__ void frame_coefs(const double* __restrict__ src, cons
   }
 }
 
-// one thread per frame of the batch
+// one thread per frame of the batch; a clip's reference images are rows clip * ref_rows .. of `ref` (ref_rows >= knots.nk)
 __global__ __launch_bounds__(64) void colour_coefs_kernel(const double* __restrict__ src, const double* __restrict__ ref, int frames,
                                                           int t, double n_src, double n_ref, int method, float strength,
+                                                          float max_gain, int ref_rows, TcColourKnots knots,
                                                           float* __restrict__ coefs) {
   const int fr = blockIdx.x * 64 + threadIdx.x;
   if (fr >= frames) return;
   const int clip = fr / t;
-  const double* r0 = ref + (int64_t)clip * 2 * TC_COLOUR_STATS;
-  frame_coefs(src + (int64_t)fr * TC_COLOUR_STATS, r0, r0 + TC_COLOUR_STATS, fr - clip * t, t, n_src, n_ref, method, strength,
-              coefs + (int64_t)fr * 12);
+  frame_coefs(src + (int64_t)fr * TC_COLOUR_STATS, ref + (int64_t)clip * ref_rows * TC_COLOUR_STATS, knots, fr - clip * t, n_src,
+              n_ref, method, strength, max_gain, coefs + (int64_t)fr * 12);
 }
 
 // y = ((o + a0 r) + a1 g) + a2 b on clamped inputs; each operation is an expression of its own and nothing is contracted (the
@@ -325,12 +355,16 @@ extern "C" int tc_colour_stats(const TcColourStatsParams* pp, void* stream) {
   return TC_OK;
 }
 
-extern "C" int tc_colour_match(const TcColourMatchParams* pp, void* stream) {
-  if (!pp) return TC_EINVAL;
-  const TcColourMatchParams& p = *pp;
+namespace {
+
+// The match of p: its checks and its two launches.  ref_rows: reference images per clip in p.ref (p.nk for the knots call; 2
+// for tc_colour_match, also when t = 1 and only the first is a knot).
+int colour_match_launch(const TcColourMatchKnotsParams& p, int ref_rows, void* stream) {
   if (!p.x || !p.out || !p.src || !p.ref || !p.coefs || p.b <= 0 || p.t <= 0 || p.h <= 0 || p.w <= 0) return TC_EINVAL;
   if (p.method != TC_COLOUR_MEAN_STD && p.method != TC_COLOUR_MKL) return TC_EINVAL;
   if (!std::isfinite(p.strength) || p.strength < 0.f || p.strength > 1.f || p.ref_pixels <= 0) return TC_EINVAL;
+  if (const int rc = tc_colour_knots_check(p.nk, p.knot, p.t)) return rc;
+  if (!std::isfinite(p.max_gain) || p.max_gain < 0.f || (p.max_gain > 0.f && p.max_gain < 1.f)) return TC_EINVAL;
   const int64_t hw = (int64_t)p.h * p.w, frames = (int64_t)p.b * p.t;
   const uintptr_t bytes = (uintptr_t)frames * 3 * (uintptr_t)hw * sizeof(float);
   const uintptr_t a = reinterpret_cast<uintptr_t>(p.x), o = reinterpret_cast<uintptr_t>(p.out);
@@ -340,13 +374,40 @@ extern "C" int tc_colour_match(const TcColourMatchParams* pp, void* stream) {
   chunks = chunks > CM_MAX_PARTS ? CM_MAX_PARTS : chunks;
   if (frames * chunks > INT32_MAX) return TC_ESHAPE;
   const bool vec = (hw & 3) == 0 && tc_aligned16(p.x) && tc_aligned16(p.out);
+  TcColourKnots knots = {};
+  knots.nk = p.nk;
+  for (int i = 0; i < p.nk; ++i) knots.knot[i] = p.knot[i];
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(colour_coefs_kernel, dim3((unsigned)((frames + 63) / 64)), dim3(64), 0, s, p.src, p.ref, (int)frames, p.t,
-                     (double)hw, (double)p.ref_pixels, p.method, p.strength, p.coefs);
+                     (double)hw, (double)p.ref_pixels, p.method, p.strength, p.max_gain, ref_rows, knots, p.coefs);
   TC_LAUNCH_CHECK();
   const dim3 grid((unsigned)(frames * chunks));
   if (vec) hipLaunchKernelGGL(colour_apply_kernel<true>, grid, dim3(CM_THREADS), 0, s, p.x, p.out, p.coefs, p.t, hw, (int)chunks);
   else hipLaunchKernelGGL(colour_apply_kernel<false>, grid, dim3(CM_THREADS), 0, s, p.x, p.out, p.coefs, p.t, hw, (int)chunks);
   TC_LAUNCH_CHECK();
   return TC_OK;
+}
+
+}  // namespace
+
+// the knots {0, t - 1} ({0} when t = 1) of the clip's two reference images, no gain limit
+extern "C" int tc_colour_match(const TcColourMatchParams* pp, void* stream) {
+  if (!pp) return TC_EINVAL;
+  TcColourMatchKnotsParams k = {};
+  k.x = pp->x; k.out = pp->out;
+  k.b = pp->b; k.t = pp->t; k.h = pp->h; k.w = pp->w;
+  k.src = pp->src; k.ref = pp->ref;
+  k.ref_pixels = pp->ref_pixels;
+  k.method = pp->method; k.strength = pp->strength;
+  k.coefs = pp->coefs;
+  k.nk = pp->t > 1 ? 2 : 1;
+  k.knot[0] = 0;
+  k.knot[1] = pp->t - 1;
+  k.max_gain = 0.f;
+  return colour_match_launch(k, 2, stream);
+}
+
+extern "C" int tc_colour_match_knots(const TcColourMatchKnotsParams* pp, void* stream) {
+  if (!pp) return TC_EINVAL;
+  return colour_match_launch(*pp, pp->nk, stream);
 }

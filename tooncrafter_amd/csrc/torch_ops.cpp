@@ -3,7 +3,7 @@
 // The reference binds ATen / xformers operators from Python (utils/utils.py:27-42 instantiates lvdm classes whose
 // forward methods call torch ops); this registers the MI355X kernels as first-class torch operators instead:
 //   torch.ops.tooncrafter.gemm / quant_mxfp8 / gemm_mx / attention / attention_temporal(_rel) / groupnorm(_pf) / layernorm(_pf) / ddim_step(_eps) / ddim_step_ms(_eps) / ddim_blend /
-//   frames_from_u8 / frames_from_yuv / frames_to_u8 / frames_to_yuv / colour_stats / colour_match / colour_hist / colour_transfer / clip_patches / randn_clips /
+//   frames_from_u8 / frames_from_yuv / frames_to_u8 / frames_to_yuv / colour_stats / colour_match / colour_hist / colour_transfer / colour_match_knots / colour_transfer_knots / clip_patches / randn_clips /
 //   ff_geglu_fused / temporal_attn_fused / temporal_qkv_attn / attention_q8
 // with (i) a CUDA(HIP)-key implementation that validates the tensors, allocates the result from the caching allocator,
 // picks up the CURRENT stream and calls the same extern "C" entry point the ctypes binding calls, and (ii) a Meta-key
@@ -16,6 +16,7 @@
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
 
+#include <cmath>
 #include <tuple>
 #include <vector>
 
@@ -781,6 +782,60 @@ std::tuple<Tensor, Tensor> colour_match_meta(const Tensor& x, const Tensor& src,
   return {at::empty_like(x), at::empty({x.size(0), x.size(2), 12}, x.options())};
 }
 
+// colour_match_knots: colour_match towards the reference images at `knots` (strictly increasing frame indices, host integers that
+// travel in the params struct), ref (b, nk, 9), with the gain limit max_gain (0: none) (tc_colour_match_knots).
+void colour_knots_check(const Tensor& x, const Tensor& ref, at::IntArrayRef knots, const char* what) {
+  const int64_t t = x.size(2), nk = (int64_t)knots.size();
+  TORCH_CHECK(nk >= 1 && nk <= TC_TEMPORAL_MAX_FRAMES, what, ": ", nk, " knots outside [1, ", TC_TEMPORAL_MAX_FRAMES, "]");
+  for (int64_t i = 0; i < nk; ++i)
+    TORCH_CHECK(knots[i] >= 0 && knots[i] < t && (i == 0 || knots[i] > knots[i - 1]), what,
+                ": knots must be strictly increasing frame indices in [0, ", t, ")");
+  TORCH_CHECK(ref.dim() >= 2 && ref.size(1) == nk, what, ": ref must hold one reference image per knot");
+}
+
+void colour_match_knots_check(const Tensor& x, const Tensor& src, const Tensor& ref, int64_t ref_pixels, int64_t method, double strength,
+                              at::IntArrayRef knots, double max_gain) {
+  colour_clip_check(x, "colour_match_knots");
+  const int64_t b = x.size(0), t = x.size(2);
+  TORCH_CHECK(src.dim() == 3 && src.size(0) == b && src.size(1) == t && src.size(2) == TC_COLOUR_STATS,
+              "colour_match_knots: src must be (b, t, 9)");
+  TORCH_CHECK(ref.dim() == 3 && ref.size(0) == b && ref.size(2) == TC_COLOUR_STATS, "colour_match_knots: ref must be (b, nk, 9)");
+  colour_knots_check(x, ref, knots, "colour_match_knots");
+  TORCH_CHECK(method == TC_COLOUR_MEAN_STD || method == TC_COLOUR_MKL, "colour_match_knots: method ", method);
+  TORCH_CHECK(strength >= 0.0 && strength <= 1.0, "colour_match_knots: strength ", strength, " outside [0, 1]");
+  TORCH_CHECK(ref_pixels > 0, "colour_match_knots: ref_pixels ", ref_pixels);
+  TORCH_CHECK(max_gain == 0.0 || (max_gain >= 1.0 && std::isfinite(max_gain)), "colour_match_knots: max_gain ", max_gain,
+              ": 0 (no limit) or a finite number >= 1");
+}
+
+std::tuple<Tensor, Tensor> colour_match_knots_cuda(const Tensor& x, const Tensor& src, const Tensor& ref, int64_t ref_pixels,
+                                                   int64_t method, double strength, at::IntArrayRef knots, double max_gain) {
+  TORCH_CHECK(x.is_cuda() && src.is_cuda() && ref.is_cuda(), "colour_match_knots: expected CUDA tensors (the product path is GPU-only)");
+  TORCH_CHECK(x.scalar_type() == at::kFloat && x.is_contiguous(), "colour_match_knots: x: contiguous fp32 (b, 3, t, h, w)");
+  TORCH_CHECK(src.scalar_type() == at::kDouble && src.is_contiguous() && ref.scalar_type() == at::kDouble && ref.is_contiguous(),
+              "colour_match_knots: src / ref: contiguous float64");
+  colour_match_knots_check(x, src, ref, ref_pixels, method, strength, knots, max_gain);
+  Tensor out = at::empty_like(x);
+  Tensor coefs = at::empty({x.size(0), x.size(2), 12}, x.options());
+  TcColourMatchKnotsParams p = {};
+  p.x = x.data_ptr<float>(); p.out = out.data_ptr<float>();
+  p.b = (int32_t)x.size(0); p.t = (int32_t)x.size(2); p.h = (int32_t)x.size(3); p.w = (int32_t)x.size(4);
+  p.src = src.data_ptr<double>(); p.ref = ref.data_ptr<double>();
+  p.ref_pixels = ref_pixels; p.method = (int32_t)method; p.strength = (float)strength;
+  p.coefs = coefs.data_ptr<float>();
+  p.nk = (int32_t)knots.size();
+  for (size_t i = 0; i < knots.size(); ++i) p.knot[i] = (int32_t)knots[i];
+  p.max_gain = (float)max_gain;
+  check_rc(tc_colour_match_knots(&p, cur_stream()), "tc_colour_match_knots");
+  return {out, coefs};
+}
+
+std::tuple<Tensor, Tensor> colour_match_knots_meta(const Tensor& x, const Tensor& src, const Tensor& ref, int64_t ref_pixels,
+                                                   int64_t method, double strength, at::IntArrayRef knots, double max_gain) {
+  colour_match_knots_check(x, src, ref, ref_pixels, method, strength, knots, max_gain);
+  return {at::empty_like(x), at::empty({x.size(0), x.size(2), 12}, x.options())};
+}
+
 // Histogram transfer (additive within ABI 14).  colour_hist: the 3 x 1024 int32 counts of frames f0, f0 + fstep, ... (nf of them) of
 // every clip of x -> (b, nf, 3, 1024) (tc_colour_hist).  colour_transfer: x carried channel by channel onto the course between the
 // histograms of the two reference images of its clip, from src (b, t, 3, 1024) and ref (b, 2, 3, 1024), blended by strength against
@@ -852,6 +907,51 @@ std::tuple<Tensor, Tensor> colour_transfer_cuda(const Tensor& x, const optional<
 std::tuple<Tensor, Tensor> colour_transfer_meta(const Tensor& x, const optional<Tensor>& base, const Tensor& src, const Tensor& ref,
                                                 int64_t ref_pixels, double strength) {
   colour_transfer_check(x, base, src, ref, ref_pixels, strength);
+  return {at::empty_like(x), at::empty({x.size(0), x.size(2), 3, TC_COLOUR_BINS}, x.options())};
+}
+
+// colour_transfer_knots: colour_transfer towards the reference images at `knots`, ref (b, nk, 3, 1024) (tc_colour_transfer_knots)
+void colour_transfer_knots_check(const Tensor& x, const optional<Tensor>& base, const Tensor& src, const Tensor& ref, int64_t ref_pixels,
+                                 double strength, at::IntArrayRef knots) {
+  colour_clip_check(x, "colour_transfer_knots");
+  const int64_t b = x.size(0), t = x.size(2);
+  TORCH_CHECK(x.scalar_type() == at::kFloat, "colour_transfer_knots: x: fp32 (b, 3, t, h, w)");
+  TORCH_CHECK(!base.has_value() || (base->sizes() == x.sizes() && base->scalar_type() == at::kFloat),
+              "colour_transfer_knots: base must be fp32 of the shape of x");
+  TORCH_CHECK(src.dim() == 4 && src.size(0) == b && src.size(1) == t && src.size(2) == 3 && src.size(3) == TC_COLOUR_BINS &&
+                  src.scalar_type() == at::kInt, "colour_transfer_knots: src must be int32 (b, t, 3, 1024)");
+  TORCH_CHECK(ref.dim() == 4 && ref.size(0) == b && ref.size(2) == 3 && ref.size(3) == TC_COLOUR_BINS && ref.scalar_type() == at::kInt,
+              "colour_transfer_knots: ref must be int32 (b, nk, 3, 1024)");
+  colour_knots_check(x, ref, knots, "colour_transfer_knots");
+  TORCH_CHECK(strength >= 0.0 && strength <= 1.0, "colour_transfer_knots: strength ", strength, " outside [0, 1]");
+  TORCH_CHECK(ref_pixels > 0 && ref_pixels <= (int64_t(1) << 26), "colour_transfer_knots: ref_pixels ", ref_pixels, " outside [1, 2^26]");
+  TORCH_CHECK(x.size(3) * x.size(4) <= (int64_t(1) << 26), "colour_transfer_knots: h * w ", x.size(3) * x.size(4), " above 2^26");
+}
+
+std::tuple<Tensor, Tensor> colour_transfer_knots_cuda(const Tensor& x, const optional<Tensor>& base, const Tensor& src, const Tensor& ref,
+                                                      int64_t ref_pixels, double strength, at::IntArrayRef knots) {
+  TORCH_CHECK(x.is_cuda() && src.is_cuda() && ref.is_cuda() && (!base.has_value() || base->is_cuda()),
+              "colour_transfer_knots: expected CUDA tensors (the product path is GPU-only)");
+  colour_transfer_knots_check(x, base, src, ref, ref_pixels, strength, knots);
+  TORCH_CHECK(x.is_contiguous() && src.is_contiguous() && ref.is_contiguous() && (!base.has_value() || base->is_contiguous()),
+              "colour_transfer_knots: contiguous tensors");
+  Tensor out = at::empty_like(x);
+  Tensor table = at::empty({x.size(0), x.size(2), 3, TC_COLOUR_BINS}, x.options());
+  TcColourTransferKnotsParams p = {};
+  p.x = x.data_ptr<float>(); p.base = base.has_value() ? base->data_ptr<float>() : nullptr; p.out = out.data_ptr<float>();
+  p.b = (int32_t)x.size(0); p.t = (int32_t)x.size(2); p.h = (int32_t)x.size(3); p.w = (int32_t)x.size(4);
+  p.src = src.data_ptr<int32_t>(); p.ref = ref.data_ptr<int32_t>();
+  p.ref_pixels = ref_pixels; p.strength = (float)strength;
+  p.table = table.data_ptr<float>();
+  p.nk = (int32_t)knots.size();
+  for (size_t i = 0; i < knots.size(); ++i) p.knot[i] = (int32_t)knots[i];
+  check_rc(tc_colour_transfer_knots(&p, cur_stream()), "tc_colour_transfer_knots");
+  return {out, table};
+}
+
+std::tuple<Tensor, Tensor> colour_transfer_knots_meta(const Tensor& x, const optional<Tensor>& base, const Tensor& src, const Tensor& ref,
+                                                      int64_t ref_pixels, double strength, at::IntArrayRef knots) {
+  colour_transfer_knots_check(x, base, src, ref, ref_pixels, strength, knots);
   return {at::empty_like(x), at::empty({x.size(0), x.size(2), 3, TC_COLOUR_BINS}, x.options())};
 }
 
@@ -963,6 +1063,8 @@ TORCH_LIBRARY(tooncrafter, m) {
   m.def("colour_match(Tensor x, Tensor src, Tensor ref, int ref_pixels, int method, float strength) -> (Tensor, Tensor)");
   m.def("colour_hist(Tensor x, int f0, int nf, int fstep) -> Tensor");
   m.def("colour_transfer(Tensor x, Tensor? base, Tensor src, Tensor ref, int ref_pixels, float strength) -> (Tensor, Tensor)");
+  m.def("colour_match_knots(Tensor x, Tensor src, Tensor ref, int ref_pixels, int method, float strength, int[] knots, float max_gain) -> (Tensor, Tensor)");
+  m.def("colour_transfer_knots(Tensor x, Tensor? base, Tensor src, Tensor ref, int ref_pixels, float strength, int[] knots) -> (Tensor, Tensor)");
   m.def("clip_patches(Tensor x, int size, int patch, int ld, float[] mean, float[] std, bool antialias) -> Tensor");
   m.def("randn_clips(int[] seeds, int[] shape, int stream, float scale, bool raw) -> Tensor");
   m.def("abi_version() -> int");
@@ -993,6 +1095,8 @@ TORCH_LIBRARY_IMPL(tooncrafter, CUDA, m) {
   m.impl("colour_match", colour_match_cuda);
   m.impl("colour_hist", colour_hist_cuda);
   m.impl("colour_transfer", colour_transfer_cuda);
+  m.impl("colour_match_knots", colour_match_knots_cuda);
+  m.impl("colour_transfer_knots", colour_transfer_knots_cuda);
   m.impl("clip_patches", clip_patches_cuda);
   m.impl("randn_clips", randn_clips_cuda);
   m.impl("ff_geglu_fused", ff_geglu_fused_cuda);
@@ -1020,6 +1124,8 @@ TORCH_LIBRARY_IMPL(tooncrafter, Meta, m) {
   m.impl("colour_match", colour_match_meta);
   m.impl("colour_hist", colour_hist_meta);
   m.impl("colour_transfer", colour_transfer_meta);
+  m.impl("colour_match_knots", colour_match_knots_meta);
+  m.impl("colour_transfer_knots", colour_transfer_knots_meta);
   m.impl("clip_patches", clip_patches_meta);
   m.impl("randn_clips", randn_clips_meta);
   m.impl("ff_geglu_fused", ff_geglu_fused_meta);

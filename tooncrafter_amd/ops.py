@@ -1245,10 +1245,27 @@ class HipOps:
         return f0, nf, fstep
 
     @staticmethod
-    def _colour_match_args(x, src, ref, ref_pixels, method, strength, what="colour_match"):
-        """The checked request of a match on the clip x with dimensions (b, t, h, w): (method code, strength, ref_pixels)."""
+    def _colour_knots(knots, max_gain, t, what):
+        """The checked (knot indices, gain limit) of a knots call on clips of t frames.  knots None: the two ends ((0,) when
+        t = 1); max_gain None: 0.0, no limit."""
+        knots = ((0, t - 1) if t > 1 else (0,)) if knots is None else tuple(knots)
+        if any(isinstance(k, bool) or not isinstance(k, int) for k in knots):
+            raise ValueError(f"{what}: knots {knots!r}: frame indices")
+        if not 1 <= len(knots) <= _lib.TC_TEMPORAL_MAX_FRAMES or knots[0] < 0 or knots[-1] >= t \
+                or any(a >= b for a, b in zip(knots, knots[1:])):
+            raise ValueError(f"{what}: knots {knots!r}: 1 .. {_lib.TC_TEMPORAL_MAX_FRAMES} strictly increasing frame indices in "
+                             f"[0, {t})")
+        gain = 0.0 if max_gain is None else float(max_gain)
+        if isinstance(max_gain, bool) or not (gain == 0.0 or 1.0 <= gain < float("inf")):        # NaN fails the comparison too
+            raise ValueError(f"{what}: max_gain {max_gain!r}: None or 0 (no limit), or a finite number >= 1")
+        return knots, gain
+
+    @staticmethod
+    def _colour_match_args(x, src, ref, ref_pixels, method, strength, what="colour_match", refs=2):
+        """The checked request of a match on the clip x with dimensions (b, t, h, w) against `refs` reference images per clip:
+        (method code, strength, ref_pixels)."""
         b, t = x.shape[0], x.shape[2]
-        for name, s, rows in (("src", src, t), ("ref", ref, 2)):
+        for name, s, rows in (("src", src, t), ("ref", ref, refs)):
             if not isinstance(s, torch.Tensor) or not s.is_cuda:
                 raise _lib.TooncrafterHipError(f"{what}: {name}: expected a CUDA tensor: the product path is GPU-only")
             if s.dtype != torch.float64 or tuple(s.shape) != (b, rows, _lib.TC_COLOUR_STATS) or not s.is_contiguous():
@@ -1273,29 +1290,43 @@ class HipOps:
         self._launch("tc_colour_stats", p, x.device)
         return stats
 
-    def colour_match(self, x, src, ref, ref_pixels, method, strength, out=None):
+    def colour_match(self, x, src, ref, ref_pixels, method, strength, out=None, knots=None, max_gain=None):
         """x (b, 3, t, h, w) fp32 matched frame by frame to the course between two reference images per clip: `src` (b, t, 9) the
         statistics of x, `ref` (b, 2, 9) those of the reference images over `ref_pixels` pixels each, method "mkl" | "mean_std"
         (or its code), strength in [0, 1].  Returns (matched clip, coefs (b, t, 12) fp32: A' row-major, then o').  `out` may be
-        `x` itself (in place); default: a new tensor (tc_colour_match)."""
+        `x` itself (in place); default: a new tensor (tc_colour_match).
+        knots: strictly increasing frame indices, one per reference image -- `ref` is then (b, len(knots), 9) and the course
+        runs through them; max_gain: a number >= 1 that limits the gain of the map (0: none).  With either given the call is
+        tc_colour_match_knots (an omitted `knots` means the two ends); with both None it is tc_colour_match."""
         b, t, h, w = self._colour_clip(x, "colour_match: x")
-        code, strength, ref_pixels = self._colour_match_args(x, src, ref, ref_pixels, method, strength)
+        if knots is None and max_gain is None:
+            code, strength, ref_pixels = self._colour_match_args(x, src, ref, ref_pixels, method, strength)
+        else:
+            knots, gain = self._colour_knots(knots, max_gain, t, "colour_match")
+            code, strength, ref_pixels = self._colour_match_args(x, src, ref, ref_pixels, method, strength, refs=len(knots))
         if out is None:
             out = torch.empty_like(x)
         elif self._colour_clip(out, "colour_match: out") != (b, t, h, w) or out.device != x.device:
             raise ValueError(f"colour_match: out {tuple(out.shape)} against x {tuple(x.shape)}")
         coefs = torch.empty((b, t, 12), dtype=torch.float32, device=x.device)
-        p = _lib.TcColourMatchParams(x=x.data_ptr(), out=out.data_ptr(), b=b, t=t, h=h, w=w, src=src.data_ptr(), ref=ref.data_ptr(),
-                                     ref_pixels=ref_pixels, method=code, strength=strength, coefs=coefs.data_ptr())
-        _lib.check(self.lib.tc_colour_match(C.byref(p), _stream()), "tc_colour_match")
+        fields = dict(x=x.data_ptr(), out=out.data_ptr(), b=b, t=t, h=h, w=w, src=src.data_ptr(), ref=ref.data_ptr(),
+                      ref_pixels=ref_pixels, method=code, strength=strength, coefs=coefs.data_ptr())
+        if knots is None:
+            p = _lib.TcColourMatchParams(**fields)
+            _lib.check(self.lib.tc_colour_match(C.byref(p), _stream()), "tc_colour_match")
+        else:
+            p = _lib.TcColourMatchKnotsParams(**fields, nk=len(knots), max_gain=gain)
+            p.knot[:len(knots)] = knots
+            _lib.check(self.lib.tc_colour_match_knots(C.byref(p), _stream()), "tc_colour_match_knots")
         return out, coefs
 
     # ------------------------------------------------------------------ histogram transfer (tc_colour_hist, tc_colour_transfer)
     @staticmethod
-    def _colour_transfer_args(x, src, ref, ref_pixels, strength, base, what="colour_transfer"):
-        """The checked request of a histogram transfer on the clip x: (strength, ref_pixels)."""
+    def _colour_transfer_args(x, src, ref, ref_pixels, strength, base, what="colour_transfer", refs=2):
+        """The checked request of a histogram transfer on the clip x against `refs` reference images per clip: (strength,
+        ref_pixels)."""
         b, t = x.shape[0], x.shape[2]
-        for name, s, rows in (("src", src, t), ("ref", ref, 2)):
+        for name, s, rows in (("src", src, t), ("ref", ref, refs)):
             if not isinstance(s, torch.Tensor) or not s.is_cuda:
                 raise _lib.TooncrafterHipError(f"{what}: {name}: expected a CUDA tensor: the product path is GPU-only")
             if s.dtype != torch.int32 or tuple(s.shape) != (b, rows, 3, _lib.TC_COLOUR_BINS) or not s.is_contiguous():
@@ -1321,23 +1352,33 @@ class HipOps:
         self._launch("tc_colour_hist", p, x.device)
         return hist
 
-    def colour_transfer(self, x, src, ref, ref_pixels, strength, base=None, out=None):
+    def colour_transfer(self, x, src, ref, ref_pixels, strength, base=None, out=None, knots=None):
         """x (b, 3, t, h, w) fp32 carried channel by channel onto the course between the histograms of two reference images per
         clip: `src` (b, t, 3, 1024) the histograms of x, `ref` (b, 2, 3, 1024) those of the reference images over `ref_pixels`
         pixels each, strength in [0, 1] blending against clamp(x), or against clamp(base) when a `base` clip of x's shape is
         given.  Returns (transferred clip, table (b, t, 3, 1024) fp32: the displacement of every bin).  `out` may be `x` itself
-        (in place); default: a new tensor (tc_colour_transfer)."""
+        (in place); default: a new tensor (tc_colour_transfer).
+        knots: strictly increasing frame indices, one per reference image -- `ref` is then (b, len(knots), 3, 1024) and the
+        course runs through them (tc_colour_transfer_knots); None: tc_colour_transfer."""
         b, t, h, w = self._colour_clip(x, "colour_transfer: x")
-        strength, ref_pixels = self._colour_transfer_args(x, src, ref, ref_pixels, strength, base)
+        if knots is not None:
+            knots, _ = self._colour_knots(knots, None, t, "colour_transfer")
+        strength, ref_pixels = self._colour_transfer_args(x, src, ref, ref_pixels, strength, base,
+                                                          refs=2 if knots is None else len(knots))
         if out is None:
             out = torch.empty_like(x)
         elif self._colour_clip(out, "colour_transfer: out") != (b, t, h, w) or out.device != x.device:
             raise ValueError(f"colour_transfer: out {tuple(out.shape)} against x {tuple(x.shape)}")
         table = torch.empty((b, t, 3, _lib.TC_COLOUR_BINS), dtype=torch.float32, device=x.device)
-        p = _lib.TcColourTransferParams(x=x.data_ptr(), base=None if base is None else base.data_ptr(), out=out.data_ptr(), b=b, t=t,
-                                        h=h, w=w, src=src.data_ptr(), ref=ref.data_ptr(), ref_pixels=ref_pixels, strength=strength,
-                                        table=table.data_ptr())
-        _lib.check(self.lib.tc_colour_transfer(C.byref(p), _stream()), "tc_colour_transfer")
+        fields = dict(x=x.data_ptr(), base=None if base is None else base.data_ptr(), out=out.data_ptr(), b=b, t=t, h=h, w=w,
+                      src=src.data_ptr(), ref=ref.data_ptr(), ref_pixels=ref_pixels, strength=strength, table=table.data_ptr())
+        if knots is None:
+            p = _lib.TcColourTransferParams(**fields)
+            _lib.check(self.lib.tc_colour_transfer(C.byref(p), _stream()), "tc_colour_transfer")
+        else:
+            p = _lib.TcColourTransferKnotsParams(**fields, nk=len(knots))
+            p.knot[:len(knots)] = knots
+            _lib.check(self.lib.tc_colour_transfer_knots(C.byref(p), _stream()), "tc_colour_transfer_knots")
         return out, table
 
 

@@ -55,25 +55,59 @@ class Colour:
 COLOUR_MATCH_METHODS = ("mkl", "mean_std", "hm", "hm_mkl_hm")
 
 
+COLOUR_MATCH_TARGETS = ("ends", "pinned")
+
+
 @dataclass(frozen=True)
 class ColourMatch:
     """How decoded frames are matched in colour to the keyframes they interpolate (the `match=` keyword of the synthesis calls;
     the rules: include/tooncrafter_hip.h, tc_colour_match and tc_colour_transfer): `method` "mkl" (the Monge-Kantorovich linear
     map: means and the full 3 x 3 covariance) | "mean_std" (per-channel mean and standard deviation) | "hm" (per-channel
     histogram matching over 1024 bins: a monotone tone curve, which no linear map is) | "hm_mkl_hm" (the compound histogram ->
-    MKL -> histogram), `strength` in [0, 1] (0: the frames as they are, 1: the full map).  Anything else raises ValueError
-    here."""
+    MKL -> histogram), `strength` in [0, 1] (0: the frames as they are, 1: the full map).
+    `max_gain`: None, or a number g >= 1 that holds the gains of the linear map inside [1 / g, g] (the diagonal of "mean_std",
+    the eigenvalues of "mkl", the MKL stage of "hm_mkl_hm"); the means are still matched.  A tone curve has no matrix to
+    limit: max_gain with "hm" raises.  `targets`: "ends" (the two endpoints) | "pinned" (also the frames a call pins with
+    `keyframes=`: each is matched to the image it was pinned to, the frames between to the course from one target to the next;
+    calls that pin nothing treat it as "ends").  Anything else raises ValueError here."""
     method: str = "mkl"
     strength: float = 1.0
+    max_gain: Optional[float] = None
+    targets: str = "ends"
 
     def __post_init__(self):
         if not isinstance(self.method, str) or self.method not in COLOUR_MATCH_METHODS:
             raise ValueError(f"ColourMatch: method {self.method!r}: one of {COLOUR_MATCH_METHODS}")
         if isinstance(self.strength, bool) or not isinstance(self.strength, (int, float)) or not 0.0 <= self.strength <= 1.0:
             raise ValueError(f"ColourMatch: strength {self.strength!r}: a number in [0, 1]")
+        if self.max_gain is not None:
+            if isinstance(self.max_gain, bool) or not isinstance(self.max_gain, (int, float)) \
+                    or not 1.0 <= self.max_gain < float("inf"):
+                raise ValueError(f"ColourMatch: max_gain {self.max_gain!r}: None, or a finite number >= 1")
+            if self.method == "hm":
+                raise ValueError("ColourMatch: max_gain with method 'hm': a tone curve has no matrix to limit")
+        if not isinstance(self.targets, str) or self.targets not in COLOUR_MATCH_TARGETS:
+            raise ValueError(f"ColourMatch: targets {self.targets!r}: one of {COLOUR_MATCH_TARGETS}")
 
 
-def match_colour(video: torch.Tensor, ends: torch.Tensor, match: ColourMatch) -> torch.Tensor:
+def _match_targets(ends: torch.Tensor, t: int, inner) -> tuple:
+    """(knots, images (b, 3, nk, H, W)) of a clip of t frames: the endpoints at 0 and t - 1 (frame 0 alone when t = 1) and the
+    `inner` images at their indices, in index order; an inner index equal to 0 or t - 1 replaces that endpoint's image."""
+    images = {0: ends[:, :, 0]}
+    if t > 1:
+        images[t - 1] = ends[:, :, 1]
+    for i, px in (inner or {}).items():
+        if isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < t:
+            raise ValueError(f"match_colour: inner: frame index {i!r} outside a clip of {t} frames")
+        if not isinstance(px, torch.Tensor) or tuple(px.shape) != (ends.shape[0], 3, *ends.shape[3:]):
+            raise ValueError(f"match_colour: inner[{i}] must be {(ends.shape[0], 3, *ends.shape[3:])}, the size of the endpoints "
+                             f"(one ref_pixels for all targets), got {tuple(getattr(px, 'shape', ()))}")
+        images[i] = px.to(device=ends.device, dtype=torch.float32)
+    knots = tuple(sorted(images))
+    return knots, torch.stack([images[k] for k in knots], dim=2).contiguous()
+
+
+def match_colour(video: torch.Tensor, ends: torch.Tensor, match: ColourMatch, inner=None) -> torch.Tensor:
     """`video` (b, 3, t, h, w) fp32 matched to `ends` (b, 3, 2, H, W) fp32, the two keyframes of every clip at any size, on the
     device and without a synchronisation.  Returns the matched clip (not clamped: the writers clamp).
     "mkl" / "mean_std": frame 0 takes the first keyframe's mean and covariance (of the values clamped to [-1, 1]), frame t - 1
@@ -87,9 +121,14 @@ def match_colour(video: torch.Tensor, ends: torch.Tensor, match: ColourMatch) ->
     the keyframes' histograms and statistics are computed once and the intermediate clips are overwritten in place.
     In a timeline the last frame of one segment and frame 0 of the next are both matched to the inner keyframe's own
     statistics or quantile function.
-    Targets at inner pinned frames, colour spaces other than the model's RGB values and a gain limit are not offered: under
-    the linear maps a frame that is flat where its keyframes are not gets a large gain, and `strength` is the only control;
-    and no histogram match can spread a flat frame: all its pixels share a bin and move together."""
+    inner: {frame index: (b, 3, H, W) pixels of the size of `ends`} -- further targets inside the clip.  They are stacked with
+    the endpoints in index order (an index 0 or t - 1 replaces that endpoint's image), go through ONE statistics or histogram
+    call, and the match follows the course through all of them (tc_colour_match_knots / tc_colour_transfer_knots: frame i takes
+    target i itself, the frames between two targets their interpolation); in "hm_mkl_hm" all three stages do.
+    `match.max_gain` holds the gains of the linear stage inside [1 / g, g] (tc_colour_match_knots).  With `inner` empty or None
+    and no max_gain the calls are exactly those above.
+    Colour spaces other than the model's RGB values are not offered; and no histogram match can spread a flat frame: all its
+    pixels share a bin and move together."""
     if not isinstance(match, ColourMatch):
         raise ValueError(f"match_colour: match: expected a ColourMatch, got {type(match).__name__}")
     if ends is None or ends.dim() != 5 or ends.shape[:3] != (video.shape[0], 3, 2):
@@ -97,20 +136,37 @@ def match_colour(video: torch.Tensor, ends: torch.Tensor, match: ColourMatch) ->
                          f"{None if ends is None else tuple(ends.shape)}")
     video, ends = video.to(torch.float32).contiguous(), ends.to(torch.float32).contiguous()
     t, ref_pixels = video.shape[2], ends.shape[3] * ends.shape[4]
+    if not inner and match.max_gain is None:
+        if match.method in ("mkl", "mean_std"):
+            ref = ops.colour_stats(ends, frames=(0, 2, 1))
+            src = ops.colour_stats(video, frames=(0, t, 1))
+            return ops.colour_match(video, src, ref, ref_pixels, match.method, match.strength)[0]
+        src = ops.colour_hist(video, frames=(0, t, 1))
+        ref = ops.colour_hist(ends, frames=(0, 2, 1))
+        if match.method == "hm":
+            return ops.colour_transfer(video, src, ref, ref_pixels, match.strength)[0]
+        work = ops.colour_transfer(video, src, ref, ref_pixels, 1.0)[0]               # a clip of our own: `video` is the caller's
+        ref_stats = ops.colour_stats(ends, frames=(0, 2, 1))
+        stats = ops.colour_stats(work, frames=(0, t, 1))
+        work = ops.colour_match(work, stats, ref_stats, ref_pixels, "mkl", 1.0, out=work)[0]
+        src = ops.colour_hist(work, frames=(0, t, 1))
+        return ops.colour_transfer(work, src, ref, ref_pixels, match.strength, base=video, out=work)[0]
+    knots, targets = _match_targets(ends, t, inner)
+    every = (0, len(knots), 1)
     if match.method in ("mkl", "mean_std"):
-        ref = ops.colour_stats(ends, frames=(0, 2, 1))
+        ref = ops.colour_stats(targets, frames=every)
         src = ops.colour_stats(video, frames=(0, t, 1))
-        return ops.colour_match(video, src, ref, ref_pixels, match.method, match.strength)[0]
+        return ops.colour_match(video, src, ref, ref_pixels, match.method, match.strength, knots=knots, max_gain=match.max_gain)[0]
     src = ops.colour_hist(video, frames=(0, t, 1))
-    ref = ops.colour_hist(ends, frames=(0, 2, 1))
+    ref = ops.colour_hist(targets, frames=every)
     if match.method == "hm":
-        return ops.colour_transfer(video, src, ref, ref_pixels, match.strength)[0]
-    work = ops.colour_transfer(video, src, ref, ref_pixels, 1.0)[0]               # a clip of our own: `video` is the caller's
-    ref_stats = ops.colour_stats(ends, frames=(0, 2, 1))
+        return ops.colour_transfer(video, src, ref, ref_pixels, match.strength, knots=knots)[0]
+    work = ops.colour_transfer(video, src, ref, ref_pixels, 1.0, knots=knots)[0]
+    ref_stats = ops.colour_stats(targets, frames=every)
     stats = ops.colour_stats(work, frames=(0, t, 1))
-    work = ops.colour_match(work, stats, ref_stats, ref_pixels, "mkl", 1.0, out=work)[0]
+    work = ops.colour_match(work, stats, ref_stats, ref_pixels, "mkl", 1.0, out=work, knots=knots, max_gain=match.max_gain)[0]
     src = ops.colour_hist(work, frames=(0, t, 1))
-    return ops.colour_transfer(work, src, ref, ref_pixels, match.strength, base=video, out=work)[0]
+    return ops.colour_transfer(work, src, ref, ref_pixels, match.strength, base=video, out=work, knots=knots)[0]
 
 
 def clip_to_uint8(samples: torch.Tensor, loop: bool = False, size=None, filter: str = "bicubic", fmt: str = "rgb24",
