@@ -3,7 +3,8 @@ kernel of csrc/colour_match.hip, the table kernel of csrc/colour_hist.hip, the c
 statement of tests/colour_knots_ref.py, every case through both bindings (HipOps, TorchLibOps), whose results must be the same
 bits:
 
-  * knots {0, t - 1} without a limit are the old entry points bit for bit: coefficients, tables, outputs;
+  * knots {0, t - 1} without a limit are the old entry points bit for bit: coefficients, tables, outputs; with t = 1 and two
+    clips (2, 1, 8 x 8) the old entry points still step two reference images per clip;
   * the tables of every knot set equal the statement bit for bit; the coefficients of every knot set, limited or not, lie within
     relative 2^-22 of the statement rounded to fp32, and the apply pass is the stated fp32 arithmetic on the device's own
     coefficients, bit for bit;
@@ -106,6 +107,61 @@ def test_the_two_ends_without_a_limit_are_the_old_entry_points_bit_for_bit(hip, 
             base = x.flip(2).contiguous()
             assert torch.equal(be.colour_transfer(x, hsrc, hsome, M, strength, base=base, knots=knots)[0],
                                be.colour_transfer(x, hsrc, htwo, M, strength, base=base)[0])
+
+
+def four_references(make, seed):
+    """(2, 3, 2, 17, 23): two reference images per clip, each with an offset and a contrast of its own"""
+    refs = make(seed, 2, 2, *ref.REF_HW).astype(np.float64)
+    for (i, j), (gain, offset) in {(0, 0): (1.0, -0.3), (0, 1): (0.45, 0.35), (1, 0): (0.7, 0.15), (1, 1): (0.3, -0.1)}.items():
+        refs[i, :, j] = gain * refs[i, :, j] + offset
+    return refs.astype(np.float32)
+
+
+def test_the_old_entry_points_step_two_reference_images_per_clip_when_t_is_1(hip, tl):
+    """t = 1: only the first of a clip's two reference images is a knot, but the old entry points still take two per clip, so
+    clip 1's target is row 2 of `ref`, not row 1.  Two clips (every other t = 1 case has one, where the stride is multiplied by
+    zero) against four clearly different images.  The expectation is the numpy statements' alone: the old ones on both images,
+    which equal the knots statement on the first; the device must meet it through the old call and through knots=(0,) on
+    ref[:, :1], with the same bits."""
+    b, t, h, w = shape = (2, 1, 8, 8)
+    x_np, refs_np = cm.frames(sum(shape), *shape), four_references(cm.frames, sum(shape) + 1)
+    tx_np, trefs_np = ch.toon_frames(sum(shape), *shape), four_references(ch.toon_frames, sum(shape) + 1)
+    stats, ref_stats = cm.frame_stats(x_np), cm.frame_stats(refs_np)
+    hist, ref_hist = ch.hist(tx_np), ch.hist(trefs_np)
+    want_tab, _ = ch.table(hist, ref_hist, h * w, M)
+    assert np.array_equal(want_tab.view(np.int32), ref.table(hist, ref_hist[:, :1], (0,), h * w, M)[0].view(np.int32))
+    strided = ref.table(hist[1:], ref_hist[:1, 1:], (0,), h * w, M)[0]              # clip 1 against row 1: a stride of one
+    assert np.abs(want_tab[1] - strided[0]).max() > 0.05
+    want_out = ch.apply(tx_np, want_tab, 0.75)
+    want_co = {}
+    for method in ("mkl", "mean_std"):
+        want = cm.coefs(stats, ref_stats, h * w, M, method, 0.75)
+        assert np.array_equal(want, ref.coefs(stats, ref_stats[:, :1], (0,), h * w, M, method, 0.75))
+        strided = ref.coefs(stats[1:], ref_stats[:1, 1:], (0,), h * w, M, method, 0.75)
+        assert np.abs(want[1] - strided[0]).max() > 0.05
+        want_co[method] = want.astype(np.float32).astype(np.float64)
+    for i in range(b):
+        assert cm.cond(cm.moments(stats[i, 0], h * w)[1]) <= 1e3
+    for be in (hip, tl):
+        x, two = dev(tx_np), be.colour_hist(dev(trefs_np))
+        src = be.colour_hist(x)
+        assert two.shape == (2, 2, 3, 1024) and np.array_equal(two.cpu().numpy(), ref_hist)
+        out, tab = be.colour_transfer(x, src, two, M, 0.75)
+        assert np.array_equal(tab.cpu().numpy().view(np.int32), want_tab.view(np.int32)), type(be).__name__
+        assert np.array_equal(out.cpu().numpy().view(np.int32), want_out.view(np.int32)), type(be).__name__
+        out1, tab1 = be.colour_transfer(x, src, two[:, :1].contiguous(), M, 0.75, knots=(0,))
+        assert torch.equal(tab1, tab) and torch.equal(out1, out), type(be).__name__
+        x, two = dev(x_np), be.colour_stats(dev(refs_np))
+        src = be.colour_stats(x)
+        assert two.shape == (2, 2, 9)
+        for method in ("mkl", "mean_std"):
+            out, co = be.colour_match(x, src, two, M, method, 0.75)
+            err = np.abs(co.cpu().numpy().astype(np.float64) - want_co[method]) / np.maximum(1.0, np.abs(want_co[method]))
+            print(f"{type(be).__name__} {method}: worst coefficient error {err.max() * 2 ** 22:.3g} x 2^-22")
+            assert (err <= 2.0 ** -22).all(), (type(be).__name__, method)
+            assert torch.equal(out.cpu(), host_apply(x, co)), (type(be).__name__, method)
+            out1, co1 = be.colour_match(x, src, two[:, :1].contiguous(), M, method, 0.75, knots=(0,))
+            assert torch.equal(co1, co) and torch.equal(out1, out), (type(be).__name__, method)
 
 
 # ------------------------------------------------------------------------------------------------ 2. tables

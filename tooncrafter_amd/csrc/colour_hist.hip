@@ -10,21 +10,18 @@
 //
 // Toon content puts most lanes of a wave into one bin, and LDS atomics on one address serialise.  So a lane merges equal
 // neighbouring bins of its pixel quad into one add, and a wave whose lanes all hold one and the same bin adds its total once.
-#include <cmath>
-
-#include "common.h"
-#include "colour_course.h"
+//
+// What a request has in common with the linear match's -- the clamp, the frame slots, the clip request and its knots -- is
+// csrc/colour_request.h; here are `base`, the 4-byte alignment of the int32 counts, the 2^26 limit and the tables.
+#include "colour_request.h"
 
 namespace {
 
-constexpr int CH_THREADS = 256;
+constexpr int CH_THREADS = COLOUR_THREADS;
 constexpr int CH_WAVES = CH_THREADS / 64;
 constexpr int CH_MAX_PARTS = 16;
 constexpr int64_t CH_PART_PIXELS = 1024;
-constexpr int CH_MAX_CHUNKS = 64;
 constexpr int64_t CH_MAX_PIXELS = (int64_t)1 << 26;   // P_i m and A_j 2 n stay below 2^53: exact in int64 and in double
-
-__device__ __forceinline__ float clamp1(float v) { return fminf(fmaxf(v, -1.0f), 1.0f); }
 
 // bin of a CLAMPED value: the add is rounded, the multiply by 512 is exact; c + 1 >= 0
 __device__ __forceinline__ int bin_of(float c) {
@@ -34,12 +31,6 @@ __device__ __forceinline__ int bin_of(float c) {
   return b < TC_COLOUR_BINS - 1 ? b : TC_COLOUR_BINS - 1;
 }
 
-// parts of a frame of hw pixels (counts do not depend on it; the workspace does)
-inline int ch_parts(int64_t hw) {
-  const int64_t p = (hw + CH_PART_PIXELS - 1) / CH_PART_PIXELS;
-  return (int)(p < 1 ? 1 : p > CH_MAX_PARTS ? CH_MAX_PARTS : p);
-}
-
 // One block per (slot, channel, part), blockIdx.x = (slot * 3 + k) * parts + p.  Thread j of part p takes the pixel quads
 // q = p * 256 + j, q + 256 P, ...; VEC (plane bases 16-byte aligned, hw % 4 == 0) reads a quad as one float4.
 template <bool VEC>
@@ -47,9 +38,9 @@ __global__ __launch_bounds__(CH_THREADS) void colour_hist_kernel(const float* __
                                                                  int fstep, int parts, int32_t* __restrict__ part) {
   __shared__ int32_t h[CH_WAVES][TC_COLOUR_BINS];
   const int sk = blockIdx.x / parts, p = blockIdx.x - sk * parts;
-  const int slot = sk / 3, k = sk - slot * 3;                             // slot = clip * nf + j
-  const int clip = slot / nf, f = f0 + (slot - clip * nf) * fstep;
-  const float* px = x + (((int64_t)clip * 3 + k) * t + f) * hw;
+  const int slot = sk / 3, k = sk - slot * 3;
+  const ColourSlot at = colour_slot(slot, f0, nf, fstep);
+  const float* px = x + (((int64_t)at.clip * 3 + k) * t + at.f) * hw;
   for (int i = threadIdx.x; i < CH_WAVES * TC_COLOUR_BINS; i += CH_THREADS) (&h[0][0])[i] = 0;
   __syncthreads();
   const int lane = threadIdx.x & 63;
@@ -209,53 +200,49 @@ __global__ __launch_bounds__(CH_THREADS) void colour_lut_kernel(const float* x, 
 
 inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
-inline bool overlap(uintptr_t a, uintptr_t b, uintptr_t bytes) { return a < b + bytes && b < a + bytes; }
-
 // TC_OK and the launch geometry of a histogram request, or its refusal (the workspace is the caller's to check)
-int hist_request(const TcColourHistParams* pp, int* parts, int64_t* slots) {
+int hist_request(const TcColourHistParams* pp, int* parts, int64_t* slots, int64_t* workspace_bytes) {
   if (!pp) return TC_EINVAL;
   const TcColourHistParams& p = *pp;
-  if (!p.x || !p.hist || p.b <= 0 || p.t <= 0 || p.h <= 0 || p.w <= 0 || p.nf <= 0) return TC_EINVAL;
-  if (p.f0 < 0 || p.f0 >= p.t || (p.nf > 1 && p.fstep < 1)) return TC_EINVAL;
-  if (p.nf > 1 && (int64_t)p.f0 + (int64_t)(p.nf - 1) * p.fstep > (int64_t)p.t - 1) return TC_EINVAL;
+  if (const int rc = colour_slots_check(p, p.hist)) return rc;
   if (!aligned4(p.hist)) return TC_EALIGN;
   const int64_t hw = (int64_t)p.h * p.w;
   if (hw > CH_MAX_PIXELS) return TC_ESHAPE;
-  *parts = ch_parts(hw);
+  *parts = colour_parts(hw, CH_PART_PIXELS, CH_MAX_PARTS);                   // counts do not depend on it; the workspace does
   *slots = (int64_t)p.b * p.nf;
   if (*slots * 3 * *parts > INT32_MAX) return TC_ESHAPE;
+  *workspace_bytes = *slots * 3 * *parts * TC_COLOUR_BINS * (int64_t)sizeof(int32_t);
   return TC_OK;
 }
 
 template <bool VEC>
-void launch_lut(const TcColourTransferKnotsParams& p, int64_t hw, int64_t frames, int chunks, hipStream_t s) {
-  const dim3 grid((unsigned)(frames * chunks));
-  if (p.base) hipLaunchKernelGGL((colour_lut_kernel<VEC, true>), grid, dim3(CH_THREADS), 0, s, p.x, p.base, p.out, p.table, p.strength, p.t, hw, chunks);
-  else hipLaunchKernelGGL((colour_lut_kernel<VEC, false>), grid, dim3(CH_THREADS), 0, s, p.x, p.base, p.out, p.table, p.strength, p.t, hw, chunks);
+void launch_lut(const TcColourTransferKnotsParams& p, const ColourClip& g, hipStream_t s) {
+  const dim3 grid((unsigned)(g.frames * g.chunks));
+  if (p.base) hipLaunchKernelGGL((colour_lut_kernel<VEC, true>), grid, dim3(CH_THREADS), 0, s, p.x, p.base, p.out, p.table, p.strength, p.t, g.hw, g.chunks);
+  else hipLaunchKernelGGL((colour_lut_kernel<VEC, false>), grid, dim3(CH_THREADS), 0, s, p.x, p.base, p.out, p.table, p.strength, p.t, g.hw, g.chunks);
 }
 
 }  // namespace
 
 extern "C" int64_t tc_colour_hist_workspace(const TcColourHistParams* p) {
   int parts = 0;
-  int64_t slots = 0;
-  if (hist_request(p, &parts, &slots) != TC_OK) return 0;
-  return slots * 3 * parts * TC_COLOUR_BINS * (int64_t)sizeof(int32_t);
+  int64_t slots = 0, bytes = 0;
+  return hist_request(p, &parts, &slots, &bytes) == TC_OK ? bytes : 0;
 }
 
 extern "C" int tc_colour_hist(const TcColourHistParams* pp, void* stream) {
   int parts = 0;
-  int64_t slots = 0;
-  if (const int rc = hist_request(pp, &parts, &slots)) return rc;
+  int64_t slots = 0, bytes = 0;
+  if (const int rc = hist_request(pp, &parts, &slots, &bytes)) return rc;
   const TcColourHistParams& p = *pp;
   if (!p.workspace) return TC_EWORKSPACE;
   if (!aligned4(p.workspace)) return TC_EALIGN;
-  if (p.workspace_bytes < slots * 3 * parts * TC_COLOUR_BINS * (int64_t)sizeof(int32_t)) return TC_EWORKSPACE;
+  if (p.workspace_bytes < bytes) return TC_EWORKSPACE;
   const int64_t hw = (int64_t)p.h * p.w;
   const bool vec = (hw & 3) == 0 && tc_aligned16(p.x);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   int32_t* part = reinterpret_cast<int32_t*>(p.workspace);
-  const int fstep = p.nf > 1 ? p.fstep : 1;
+  const int fstep = colour_fstep(p.nf, p.fstep);
   const dim3 grid((unsigned)(slots * 3 * parts));
   if (vec) hipLaunchKernelGGL(colour_hist_kernel<true>, grid, dim3(CH_THREADS), 0, s, p.x, p.t, hw, p.f0, p.nf, fstep, parts, part);
   else hipLaunchKernelGGL(colour_hist_kernel<false>, grid, dim3(CH_THREADS), 0, s, p.x, p.t, hw, p.f0, p.nf, fstep, parts, part);
@@ -272,48 +259,29 @@ namespace {
 // The transfer of p: its checks and its two launches.  ref_rows: reference images per clip in p.ref (p.nk for the knots call; 2
 // for tc_colour_transfer, also when t = 1 and only the first is a knot).
 int colour_transfer_launch(const TcColourTransferKnotsParams& p, int ref_rows, void* stream) {
-  if (!p.x || !p.out || !p.src || !p.ref || !p.table || p.b <= 0 || p.t <= 0 || p.h <= 0 || p.w <= 0) return TC_EINVAL;
-  if (!std::isfinite(p.strength) || p.strength < 0.f || p.strength > 1.f || p.ref_pixels <= 0) return TC_EINVAL;
-  if (const int rc = tc_colour_knots_check(p.nk, p.knot, p.t)) return rc;
-  const int64_t hw = (int64_t)p.h * p.w, frames = (int64_t)p.b * p.t;
-  const uintptr_t bytes = (uintptr_t)frames * 3 * (uintptr_t)hw * sizeof(float);
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p.x), o = reinterpret_cast<uintptr_t>(p.out);
-  if (a != o && overlap(a, o, bytes)) return TC_EINVAL;                    // an overlap other than out == x
-  if (p.base && overlap(reinterpret_cast<uintptr_t>(p.base), o, bytes)) return TC_EINVAL;
+  if (const int rc = colour_clip_check(p, p.table, p.base)) return rc;
   if (!aligned4(p.src) || !aligned4(p.ref) || !aligned4(p.table)) return TC_EALIGN;
-  if (hw > CH_MAX_PIXELS || p.ref_pixels > CH_MAX_PIXELS) return TC_ESHAPE;
-  int64_t chunks = ((hw + 3) / 4 + CH_THREADS - 1) / CH_THREADS;            // a quad per thread and round where it fits
-  chunks = chunks > CH_MAX_CHUNKS ? CH_MAX_CHUNKS : chunks;
-  if (frames * chunks > INT32_MAX || frames * 3 > INT32_MAX) return TC_ESHAPE;
-  const bool vec = (hw & 3) == 0 && tc_aligned16(p.x) && tc_aligned16(p.out) && (!p.base || tc_aligned16(p.base));
-  TcColourKnots knots = {};
-  knots.nk = p.nk;
-  for (int i = 0; i < p.nk; ++i) knots.knot[i] = p.knot[i];
+  ColourClip g;
+  if (const int rc = colour_clip_geometry(p, p.base, &g)) return rc;
+  if (g.hw > CH_MAX_PIXELS || p.ref_pixels > CH_MAX_PIXELS || g.frames * 3 > INT32_MAX) return TC_ESHAPE;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(colour_table_kernel, dim3((unsigned)(frames * 3)), dim3(TC_COLOUR_BINS), 0, s, p.src, p.ref, p.t, hw, p.ref_pixels,
-                     ref_rows, knots, p.table);
+  hipLaunchKernelGGL(colour_table_kernel, dim3((unsigned)(g.frames * 3)), dim3(TC_COLOUR_BINS), 0, s, p.src, p.ref, p.t, g.hw, p.ref_pixels,
+                     ref_rows, g.knots, p.table);
   TC_LAUNCH_CHECK();
-  if (vec) launch_lut<true>(p, hw, frames, (int)chunks, s);
-  else launch_lut<false>(p, hw, frames, (int)chunks, s);
+  if (g.vec) launch_lut<true>(p, g, s);
+  else launch_lut<false>(p, g, s);
   TC_LAUNCH_CHECK();
   return TC_OK;
 }
 
 }  // namespace
 
-// the knots {0, t - 1} ({0} when t = 1) of the clip's two reference images
+// the two ends of the clip's two reference images
 extern "C" int tc_colour_transfer(const TcColourTransferParams* pp, void* stream) {
   if (!pp) return TC_EINVAL;
-  TcColourTransferKnotsParams k = {};
-  k.x = pp->x; k.base = pp->base; k.out = pp->out;
-  k.b = pp->b; k.t = pp->t; k.h = pp->h; k.w = pp->w;
-  k.src = pp->src; k.ref = pp->ref;
-  k.ref_pixels = pp->ref_pixels;
-  k.strength = pp->strength;
+  TcColourTransferKnotsParams k = colour_two_ends<TcColourTransferKnotsParams>(*pp);
+  k.base = pp->base;
   k.table = pp->table;
-  k.nk = pp->t > 1 ? 2 : 1;
-  k.knot[0] = 0;
-  k.knot[1] = pp->t - 1;
   return colour_transfer_launch(k, 2, stream);
 }
 

@@ -7,26 +7,17 @@
 //   colour_coefs_kernel   (m, C) of frame and target (its course through the knots: csrc/colour_course.h), the 3 x 3 map and
 //                         its optional gain limit, twelve fp32 numbers                         -> coefs
 //   colour_apply_kernel   y = o' + A' clamp(x), every operation rounded on its own            -> out
-// No atomics, no allocation, no synchronisation.
-#include <cmath>
-
-#include "common.h"
-#include "colour_course.h"
+// No atomics, no allocation, no synchronisation.  What a request has in common with the histogram transfer's -- the clamp, the frame
+// slots, the clip request and its knots -- is csrc/colour_request.h; here are the method, the gain limit, the 8-byte alignment of
+// the float64 sums and the solve.
+#include "colour_request.h"
 
 namespace {
 
-constexpr int CM_THREADS = 256;
+constexpr int CM_THREADS = COLOUR_THREADS;
 constexpr int CM_MAX_PARTS = 64;
 constexpr int64_t CM_PART_PIXELS = 2048;
 constexpr double CM_EPS = 1.0 / 65536.0;          // 2^-16, value^2 units
-
-__device__ __forceinline__ float clamp1(float v) { return fminf(fmaxf(v, -1.0f), 1.0f); }
-
-// parts of a frame of hw pixels: a function of hw alone (the summation order is part of the result)
-inline int cm_parts(int64_t hw) {
-  const int64_t p = (hw + CM_PART_PIXELS - 1) / CM_PART_PIXELS;
-  return (int)(p < 1 ? 1 : p > CM_MAX_PARTS ? CM_MAX_PARTS : p);
-}
 
 __device__ __forceinline__ void stats_add(double* s, float rf, float gf, float bf) {
   const double r = clamp1(rf), g = clamp1(gf), b = clamp1(bf);
@@ -42,9 +33,9 @@ template <bool VEC>
 __global__ __launch_bounds__(CM_THREADS) void colour_stats_kernel(const float* __restrict__ x, int t, int64_t hw, int f0, int nf,
                                                                   int fstep, int parts, double* __restrict__ part) {
   __shared__ double red[CM_THREADS / 64][TC_COLOUR_STATS];
-  const int slot = blockIdx.x / parts, p = blockIdx.x - slot * parts;     // slot = clip * nf + j
-  const int clip = slot / nf, f = f0 + (slot - clip * nf) * fstep;
-  const float* pr = x + ((int64_t)clip * 3 * t + f) * hw;
+  const int slot = blockIdx.x / parts, p = blockIdx.x - slot * parts;
+  const ColourSlot at = colour_slot(slot, f0, nf, fstep);
+  const float* pr = x + ((int64_t)at.clip * 3 * t + at.f) * hw;
   const float* pg = pr + (int64_t)t * hw;
   const float* pb = pg + (int64_t)t * hw;
   double s[TC_COLOUR_STATS] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -309,16 +300,15 @@ __global__ __launch_bounds__(CM_THREADS) void colour_apply_kernel(const float* x
 inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 
 // TC_OK and the launch geometry of a statistics request, or its refusal (the workspace is the caller's to check)
-int stats_request(const TcColourStatsParams* pp, int* parts, int64_t* slots) {
+int stats_request(const TcColourStatsParams* pp, int* parts, int64_t* slots, int64_t* workspace_bytes) {
   if (!pp) return TC_EINVAL;
   const TcColourStatsParams& p = *pp;
-  if (!p.x || !p.stats || p.b <= 0 || p.t <= 0 || p.h <= 0 || p.w <= 0 || p.nf <= 0) return TC_EINVAL;
-  if (p.f0 < 0 || p.f0 >= p.t || (p.nf > 1 && p.fstep < 1)) return TC_EINVAL;
-  if (p.nf > 1 && (int64_t)p.f0 + (int64_t)(p.nf - 1) * p.fstep > (int64_t)p.t - 1) return TC_EINVAL;
+  if (const int rc = colour_slots_check(p, p.stats)) return rc;
   if (!aligned8(p.stats)) return TC_EALIGN;
-  *parts = cm_parts((int64_t)p.h * p.w);
+  *parts = colour_parts((int64_t)p.h * p.w, CM_PART_PIXELS, CM_MAX_PARTS);   // the summation order is part of the result
   *slots = (int64_t)p.b * p.nf;
   if (*slots * *parts > INT32_MAX) return TC_ESHAPE;
+  *workspace_bytes = *slots * *parts * TC_COLOUR_STATS * (int64_t)sizeof(double);
   return TC_OK;
 }
 
@@ -326,24 +316,23 @@ int stats_request(const TcColourStatsParams* pp, int* parts, int64_t* slots) {
 
 extern "C" int64_t tc_colour_stats_workspace(const TcColourStatsParams* p) {
   int parts = 0;
-  int64_t slots = 0;
-  if (stats_request(p, &parts, &slots) != TC_OK) return 0;
-  return slots * parts * TC_COLOUR_STATS * (int64_t)sizeof(double);
+  int64_t slots = 0, bytes = 0;
+  return stats_request(p, &parts, &slots, &bytes) == TC_OK ? bytes : 0;
 }
 
 extern "C" int tc_colour_stats(const TcColourStatsParams* pp, void* stream) {
   int parts = 0;
-  int64_t slots = 0;
-  if (const int rc = stats_request(pp, &parts, &slots)) return rc;
+  int64_t slots = 0, bytes = 0;
+  if (const int rc = stats_request(pp, &parts, &slots, &bytes)) return rc;
   const TcColourStatsParams& p = *pp;
   if (!p.workspace) return TC_EWORKSPACE;
   if (!aligned8(p.workspace)) return TC_EALIGN;
-  if (p.workspace_bytes < slots * parts * TC_COLOUR_STATS * (int64_t)sizeof(double)) return TC_EWORKSPACE;
+  if (p.workspace_bytes < bytes) return TC_EWORKSPACE;
   const int64_t hw = (int64_t)p.h * p.w;
   const bool vec = (hw & 3) == 0 && tc_aligned16(p.x);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   double* part = reinterpret_cast<double*>(p.workspace);
-  const int fstep = p.nf > 1 ? p.fstep : 1;
+  const int fstep = colour_fstep(p.nf, p.fstep);
   const dim3 grid((unsigned)(slots * parts));
   if (vec) hipLaunchKernelGGL(colour_stats_kernel<true>, grid, dim3(CM_THREADS), 0, s, p.x, p.t, hw, p.f0, p.nf, fstep, parts, part);
   else hipLaunchKernelGGL(colour_stats_kernel<false>, grid, dim3(CM_THREADS), 0, s, p.x, p.t, hw, p.f0, p.nf, fstep, parts, part);
@@ -360,49 +349,31 @@ namespace {
 // The match of p: its checks and its two launches.  ref_rows: reference images per clip in p.ref (p.nk for the knots call; 2
 // for tc_colour_match, also when t = 1 and only the first is a knot).
 int colour_match_launch(const TcColourMatchKnotsParams& p, int ref_rows, void* stream) {
-  if (!p.x || !p.out || !p.src || !p.ref || !p.coefs || p.b <= 0 || p.t <= 0 || p.h <= 0 || p.w <= 0) return TC_EINVAL;
+  if (const int rc = colour_clip_check(p, p.coefs, nullptr)) return rc;
   if (p.method != TC_COLOUR_MEAN_STD && p.method != TC_COLOUR_MKL) return TC_EINVAL;
-  if (!std::isfinite(p.strength) || p.strength < 0.f || p.strength > 1.f || p.ref_pixels <= 0) return TC_EINVAL;
-  if (const int rc = tc_colour_knots_check(p.nk, p.knot, p.t)) return rc;
   if (!std::isfinite(p.max_gain) || p.max_gain < 0.f || (p.max_gain > 0.f && p.max_gain < 1.f)) return TC_EINVAL;
-  const int64_t hw = (int64_t)p.h * p.w, frames = (int64_t)p.b * p.t;
-  const uintptr_t bytes = (uintptr_t)frames * 3 * (uintptr_t)hw * sizeof(float);
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p.x), o = reinterpret_cast<uintptr_t>(p.out);
-  if (a != o && a < o + bytes && o < a + bytes) return TC_EINVAL;          // an overlap other than out == x
   if (!aligned8(p.src) || !aligned8(p.ref)) return TC_EALIGN;
-  int64_t chunks = ((hw + 3) / 4 + CM_THREADS - 1) / CM_THREADS;            // a quad per thread and round where it fits
-  chunks = chunks > CM_MAX_PARTS ? CM_MAX_PARTS : chunks;
-  if (frames * chunks > INT32_MAX) return TC_ESHAPE;
-  const bool vec = (hw & 3) == 0 && tc_aligned16(p.x) && tc_aligned16(p.out);
-  TcColourKnots knots = {};
-  knots.nk = p.nk;
-  for (int i = 0; i < p.nk; ++i) knots.knot[i] = p.knot[i];
+  ColourClip g;
+  if (const int rc = colour_clip_geometry(p, nullptr, &g)) return rc;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(colour_coefs_kernel, dim3((unsigned)((frames + 63) / 64)), dim3(64), 0, s, p.src, p.ref, (int)frames, p.t,
-                     (double)hw, (double)p.ref_pixels, p.method, p.strength, p.max_gain, ref_rows, knots, p.coefs);
+  hipLaunchKernelGGL(colour_coefs_kernel, dim3((unsigned)((g.frames + 63) / 64)), dim3(64), 0, s, p.src, p.ref, (int)g.frames, p.t,
+                     (double)g.hw, (double)p.ref_pixels, p.method, p.strength, p.max_gain, ref_rows, g.knots, p.coefs);
   TC_LAUNCH_CHECK();
-  const dim3 grid((unsigned)(frames * chunks));
-  if (vec) hipLaunchKernelGGL(colour_apply_kernel<true>, grid, dim3(CM_THREADS), 0, s, p.x, p.out, p.coefs, p.t, hw, (int)chunks);
-  else hipLaunchKernelGGL(colour_apply_kernel<false>, grid, dim3(CM_THREADS), 0, s, p.x, p.out, p.coefs, p.t, hw, (int)chunks);
+  const dim3 grid((unsigned)(g.frames * g.chunks));
+  if (g.vec) hipLaunchKernelGGL(colour_apply_kernel<true>, grid, dim3(CM_THREADS), 0, s, p.x, p.out, p.coefs, p.t, g.hw, g.chunks);
+  else hipLaunchKernelGGL(colour_apply_kernel<false>, grid, dim3(CM_THREADS), 0, s, p.x, p.out, p.coefs, p.t, g.hw, g.chunks);
   TC_LAUNCH_CHECK();
   return TC_OK;
 }
 
 }  // namespace
 
-// the knots {0, t - 1} ({0} when t = 1) of the clip's two reference images, no gain limit
+// the two ends of the clip's two reference images, no gain limit
 extern "C" int tc_colour_match(const TcColourMatchParams* pp, void* stream) {
   if (!pp) return TC_EINVAL;
-  TcColourMatchKnotsParams k = {};
-  k.x = pp->x; k.out = pp->out;
-  k.b = pp->b; k.t = pp->t; k.h = pp->h; k.w = pp->w;
-  k.src = pp->src; k.ref = pp->ref;
-  k.ref_pixels = pp->ref_pixels;
-  k.method = pp->method; k.strength = pp->strength;
+  TcColourMatchKnotsParams k = colour_two_ends<TcColourMatchKnotsParams>(*pp);
+  k.method = pp->method;
   k.coefs = pp->coefs;
-  k.nk = pp->t > 1 ? 2 : 1;
-  k.knot[0] = 0;
-  k.knot[1] = pp->t - 1;
   k.max_gain = 0.f;
   return colour_match_launch(k, 2, stream);
 }

@@ -18,6 +18,7 @@
 
 #include <cmath>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 #include "tooncrafter_hip.h"
@@ -708,251 +709,228 @@ Tensor frames_to_yuv_meta(const Tensor& x, int64_t oh, int64_t ow, int64_t forma
   return at::empty(frames_to_yuv_shape(x, oh, ow, format, f0, nf, siting, m), x.options().dtype(at::kByte));
 }
 
-// Colour match (additive within ABI 14).  colour_stats: the nine float64 sums of frames f0, f0 + fstep, ... (nf of them) of every
-// clip of x (b, 3, t, h, w) fp32 -> (b, nf, 9) (tc_colour_stats).  colour_match: x matched frame by frame to the course between the
-// two reference images of its clip, from src (b, t, 9) and ref (b, 2, 9) -> (the matched clip, the (b, t, 12) fp32 coefficients)
-// (tc_colour_match).  Matching in place is the C ABI's (HipOps.colour_match with out=): an op returns its result.
+// Colour match and histogram transfer (additive within ABI 14): six ops, every check sentence once with the op's name in front.
+// colour_stats / colour_hist: the nine float64 sums / the 3 x 1024 int32 counts of frames f0, f0 + fstep, ... (nf of them) of every
+// clip of x (b, 3, t, h, w) fp32 -> (b, nf, 9) / (b, nf, 3, 1024).  colour_match / colour_transfer: x matched frame by frame to the
+// course between the two reference images of its clip, linearly from the sums src (b, t, 9) and ref (b, 2, 9) -> (the matched clip,
+// the (b, t, 12) fp32 coefficients), or channel by channel from the counts src (b, t, 3, 1024) and ref (b, 2, 3, 1024), blended by
+// strength against clamp(x) or clamp(base) -> (the clip, the (b, t, 3, 1024) fp32 tables).  Their *_knots forms: towards the nk
+// reference images of ref (b, nk, ...) at `knots` (strictly increasing frame indices, host integers that travel in the params
+// struct), the match with the gain limit max_gain (0: none).  Each op is the C entry point tc_<its name>; matching in place is the
+// C ABI's (HipOps.colour_match with out=): an op returns its result.
 void colour_clip_check(const Tensor& x, const char* what) {
   TORCH_CHECK(x.dim() == 5 && x.size(1) == 3 && x.numel() > 0, what, ": x must be (b, 3, t, h, w)");
   for (int d : {0, 2, 3, 4}) TORCH_CHECK(x.size(d) <= INT32_MAX, what, ": dimension ", d, " of x");
 }
 
-std::vector<int64_t> colour_stats_shape(const Tensor& x, int64_t f0, int64_t nf, int64_t fstep) {
-  colour_clip_check(x, "colour_stats");
+void colour_hw_check(const Tensor& x, const char* what) {
+  TORCH_CHECK(x.size(3) * x.size(4) <= (int64_t(1) << 26), what, ": h * w ", x.size(3) * x.size(4), " above 2^26");
+}
+
+// the checked shape of colour_stats (b, nf, 9), or with `hist` of colour_hist (b, nf, 3, 1024)
+std::vector<int64_t> colour_frames_shape(const Tensor& x, int64_t f0, int64_t nf, int64_t fstep, bool hist) {
+  const char* what = hist ? "colour_hist" : "colour_stats";
+  colour_clip_check(x, what);
   const int64_t t = x.size(2);
   TORCH_CHECK(nf >= 1 && f0 >= 0 && f0 < t && (nf == 1 || (fstep >= 1 && fstep <= INT32_MAX && f0 + (nf - 1) * fstep <= t - 1)),
-              "colour_stats: frames (", f0, ", ", nf, ", ", fstep, ") outside a clip of ", t);
-  return {x.size(0), nf, TC_COLOUR_STATS};
-}
-
-Tensor colour_stats_cuda(const Tensor& x, int64_t f0, int64_t nf, int64_t fstep) {
-  TORCH_CHECK(x.is_cuda(), "colour_stats: expected a CUDA tensor (the product path is GPU-only)");
-  TORCH_CHECK(x.scalar_type() == at::kFloat && x.is_contiguous(), "colour_stats: contiguous fp32 (b, 3, t, h, w)");
-  Tensor stats = at::empty(colour_stats_shape(x, f0, nf, fstep), x.options().dtype(at::kDouble));
-  TcColourStatsParams p = {};
-  p.x = x.data_ptr<float>();
-  p.b = (int32_t)x.size(0); p.t = (int32_t)x.size(2); p.h = (int32_t)x.size(3); p.w = (int32_t)x.size(4);
-  p.f0 = (int32_t)f0; p.nf = (int32_t)nf; p.fstep = nf == 1 ? 1 : (int32_t)fstep;
-  p.stats = stats.data_ptr<double>();
-  p.workspace_bytes = tc_colour_stats_workspace(&p);
-  Tensor ws = workspace(p.workspace_bytes, x);
-  p.workspace = ws.data_ptr();
-  check_rc(tc_colour_stats(&p, cur_stream()), "tc_colour_stats");
-  return stats;
-}
-
-Tensor colour_stats_meta(const Tensor& x, int64_t f0, int64_t nf, int64_t fstep) {
-  return at::empty(colour_stats_shape(x, f0, nf, fstep), x.options().dtype(at::kDouble));
-}
-
-void colour_match_check(const Tensor& x, const Tensor& src, const Tensor& ref, int64_t ref_pixels, int64_t method, double strength) {
-  colour_clip_check(x, "colour_match");
-  const int64_t b = x.size(0), t = x.size(2);
-  TORCH_CHECK(src.dim() == 3 && src.size(0) == b && src.size(1) == t && src.size(2) == TC_COLOUR_STATS,
-              "colour_match: src must be (b, t, 9)");
-  TORCH_CHECK(ref.dim() == 3 && ref.size(0) == b && ref.size(1) == 2 && ref.size(2) == TC_COLOUR_STATS,
-              "colour_match: ref must be (b, 2, 9)");
-  TORCH_CHECK(method == TC_COLOUR_MEAN_STD || method == TC_COLOUR_MKL, "colour_match: method ", method);
-  TORCH_CHECK(strength >= 0.0 && strength <= 1.0, "colour_match: strength ", strength, " outside [0, 1]");
-  TORCH_CHECK(ref_pixels > 0, "colour_match: ref_pixels ", ref_pixels);
-}
-
-std::tuple<Tensor, Tensor> colour_match_cuda(const Tensor& x, const Tensor& src, const Tensor& ref, int64_t ref_pixels, int64_t method,
-                                             double strength) {
-  TORCH_CHECK(x.is_cuda() && src.is_cuda() && ref.is_cuda(), "colour_match: expected CUDA tensors (the product path is GPU-only)");
-  TORCH_CHECK(x.scalar_type() == at::kFloat && x.is_contiguous(), "colour_match: x: contiguous fp32 (b, 3, t, h, w)");
-  TORCH_CHECK(src.scalar_type() == at::kDouble && src.is_contiguous() && ref.scalar_type() == at::kDouble && ref.is_contiguous(),
-              "colour_match: src / ref: contiguous float64");
-  colour_match_check(x, src, ref, ref_pixels, method, strength);
-  Tensor out = at::empty_like(x);
-  Tensor coefs = at::empty({x.size(0), x.size(2), 12}, x.options());
-  TcColourMatchParams p = {};
-  p.x = x.data_ptr<float>(); p.out = out.data_ptr<float>();
-  p.b = (int32_t)x.size(0); p.t = (int32_t)x.size(2); p.h = (int32_t)x.size(3); p.w = (int32_t)x.size(4);
-  p.src = src.data_ptr<double>(); p.ref = ref.data_ptr<double>();
-  p.ref_pixels = ref_pixels; p.method = (int32_t)method; p.strength = (float)strength;
-  p.coefs = coefs.data_ptr<float>();
-  check_rc(tc_colour_match(&p, cur_stream()), "tc_colour_match");
-  return {out, coefs};
-}
-
-std::tuple<Tensor, Tensor> colour_match_meta(const Tensor& x, const Tensor& src, const Tensor& ref, int64_t ref_pixels, int64_t method,
-                                             double strength) {
-  colour_match_check(x, src, ref, ref_pixels, method, strength);
-  return {at::empty_like(x), at::empty({x.size(0), x.size(2), 12}, x.options())};
-}
-
-// colour_match_knots: colour_match towards the reference images at `knots` (strictly increasing frame indices, host integers that
-// travel in the params struct), ref (b, nk, 9), with the gain limit max_gain (0: none) (tc_colour_match_knots).
-void colour_knots_check(const Tensor& x, const Tensor& ref, at::IntArrayRef knots, const char* what) {
-  const int64_t t = x.size(2), nk = (int64_t)knots.size();
-  TORCH_CHECK(nk >= 1 && nk <= TC_TEMPORAL_MAX_FRAMES, what, ": ", nk, " knots outside [1, ", TC_TEMPORAL_MAX_FRAMES, "]");
-  for (int64_t i = 0; i < nk; ++i)
-    TORCH_CHECK(knots[i] >= 0 && knots[i] < t && (i == 0 || knots[i] > knots[i - 1]), what,
-                ": knots must be strictly increasing frame indices in [0, ", t, ")");
-  TORCH_CHECK(ref.dim() >= 2 && ref.size(1) == nk, what, ": ref must hold one reference image per knot");
-}
-
-void colour_match_knots_check(const Tensor& x, const Tensor& src, const Tensor& ref, int64_t ref_pixels, int64_t method, double strength,
-                              at::IntArrayRef knots, double max_gain) {
-  colour_clip_check(x, "colour_match_knots");
-  const int64_t b = x.size(0), t = x.size(2);
-  TORCH_CHECK(src.dim() == 3 && src.size(0) == b && src.size(1) == t && src.size(2) == TC_COLOUR_STATS,
-              "colour_match_knots: src must be (b, t, 9)");
-  TORCH_CHECK(ref.dim() == 3 && ref.size(0) == b && ref.size(2) == TC_COLOUR_STATS, "colour_match_knots: ref must be (b, nk, 9)");
-  colour_knots_check(x, ref, knots, "colour_match_knots");
-  TORCH_CHECK(method == TC_COLOUR_MEAN_STD || method == TC_COLOUR_MKL, "colour_match_knots: method ", method);
-  TORCH_CHECK(strength >= 0.0 && strength <= 1.0, "colour_match_knots: strength ", strength, " outside [0, 1]");
-  TORCH_CHECK(ref_pixels > 0, "colour_match_knots: ref_pixels ", ref_pixels);
-  TORCH_CHECK(max_gain == 0.0 || (max_gain >= 1.0 && std::isfinite(max_gain)), "colour_match_knots: max_gain ", max_gain,
-              ": 0 (no limit) or a finite number >= 1");
-}
-
-std::tuple<Tensor, Tensor> colour_match_knots_cuda(const Tensor& x, const Tensor& src, const Tensor& ref, int64_t ref_pixels,
-                                                   int64_t method, double strength, at::IntArrayRef knots, double max_gain) {
-  TORCH_CHECK(x.is_cuda() && src.is_cuda() && ref.is_cuda(), "colour_match_knots: expected CUDA tensors (the product path is GPU-only)");
-  TORCH_CHECK(x.scalar_type() == at::kFloat && x.is_contiguous(), "colour_match_knots: x: contiguous fp32 (b, 3, t, h, w)");
-  TORCH_CHECK(src.scalar_type() == at::kDouble && src.is_contiguous() && ref.scalar_type() == at::kDouble && ref.is_contiguous(),
-              "colour_match_knots: src / ref: contiguous float64");
-  colour_match_knots_check(x, src, ref, ref_pixels, method, strength, knots, max_gain);
-  Tensor out = at::empty_like(x);
-  Tensor coefs = at::empty({x.size(0), x.size(2), 12}, x.options());
-  TcColourMatchKnotsParams p = {};
-  p.x = x.data_ptr<float>(); p.out = out.data_ptr<float>();
-  p.b = (int32_t)x.size(0); p.t = (int32_t)x.size(2); p.h = (int32_t)x.size(3); p.w = (int32_t)x.size(4);
-  p.src = src.data_ptr<double>(); p.ref = ref.data_ptr<double>();
-  p.ref_pixels = ref_pixels; p.method = (int32_t)method; p.strength = (float)strength;
-  p.coefs = coefs.data_ptr<float>();
-  p.nk = (int32_t)knots.size();
-  for (size_t i = 0; i < knots.size(); ++i) p.knot[i] = (int32_t)knots[i];
-  p.max_gain = (float)max_gain;
-  check_rc(tc_colour_match_knots(&p, cur_stream()), "tc_colour_match_knots");
-  return {out, coefs};
-}
-
-std::tuple<Tensor, Tensor> colour_match_knots_meta(const Tensor& x, const Tensor& src, const Tensor& ref, int64_t ref_pixels,
-                                                   int64_t method, double strength, at::IntArrayRef knots, double max_gain) {
-  colour_match_knots_check(x, src, ref, ref_pixels, method, strength, knots, max_gain);
-  return {at::empty_like(x), at::empty({x.size(0), x.size(2), 12}, x.options())};
-}
-
-// Histogram transfer (additive within ABI 14).  colour_hist: the 3 x 1024 int32 counts of frames f0, f0 + fstep, ... (nf of them) of
-// every clip of x -> (b, nf, 3, 1024) (tc_colour_hist).  colour_transfer: x carried channel by channel onto the course between the
-// histograms of the two reference images of its clip, from src (b, t, 3, 1024) and ref (b, 2, 3, 1024), blended by strength against
-// clamp(x) or clamp(base) -> (the transferred clip, the (b, t, 3, 1024) fp32 tables) (tc_colour_transfer).
-std::vector<int64_t> colour_hist_shape(const Tensor& x, int64_t f0, int64_t nf, int64_t fstep) {
-  colour_clip_check(x, "colour_hist");
-  const int64_t t = x.size(2);
-  TORCH_CHECK(nf >= 1 && f0 >= 0 && f0 < t && (nf == 1 || (fstep >= 1 && fstep <= INT32_MAX && f0 + (nf - 1) * fstep <= t - 1)),
-              "colour_hist: frames (", f0, ", ", nf, ", ", fstep, ") outside a clip of ", t);
-  TORCH_CHECK(x.size(3) * x.size(4) <= (int64_t(1) << 26), "colour_hist: h * w ", x.size(3) * x.size(4), " above 2^26");
+              what, ": frames (", f0, ", ", nf, ", ", fstep, ") outside a clip of ", t);
+  if (!hist) return {x.size(0), nf, TC_COLOUR_STATS};
+  colour_hw_check(x, what);
   return {x.size(0), nf, 3, TC_COLOUR_BINS};
 }
 
-Tensor colour_hist_cuda(const Tensor& x, int64_t f0, int64_t nf, int64_t fstep) {
-  TORCH_CHECK(x.is_cuda(), "colour_hist: expected a CUDA tensor (the product path is GPU-only)");
-  TORCH_CHECK(x.scalar_type() == at::kFloat && x.is_contiguous(), "colour_hist: contiguous fp32 (b, 3, t, h, w)");
-  Tensor hist = at::empty(colour_hist_shape(x, f0, nf, fstep), x.options().dtype(at::kInt));
-  TcColourHistParams p = {};
+// colour_stats / colour_hist on the CUDA key: P the params struct, `result` its field for the op's tensor
+template <typename P, typename R>
+Tensor colour_frames_cuda(const Tensor& x, int64_t f0, int64_t nf, int64_t fstep, R* P::*result, int64_t (*bytes)(const P*),
+                          int (*entry)(const P*, void*)) {
+  constexpr bool hist = std::is_same_v<P, TcColourHistParams>;
+  const char* what = hist ? "colour_hist" : "colour_stats";
+  TORCH_CHECK(x.is_cuda(), what, ": expected a CUDA tensor (the product path is GPU-only)");
+  TORCH_CHECK(x.scalar_type() == at::kFloat && x.is_contiguous(), what, ": contiguous fp32 (b, 3, t, h, w)");
+  Tensor res = at::empty(colour_frames_shape(x, f0, nf, fstep, hist), x.options().dtype(c10::CppTypeToScalarType<R>::value));
+  P p = {};
   p.x = x.data_ptr<float>();
   p.b = (int32_t)x.size(0); p.t = (int32_t)x.size(2); p.h = (int32_t)x.size(3); p.w = (int32_t)x.size(4);
   p.f0 = (int32_t)f0; p.nf = (int32_t)nf; p.fstep = nf == 1 ? 1 : (int32_t)fstep;
-  p.hist = hist.data_ptr<int32_t>();
-  p.workspace_bytes = tc_colour_hist_workspace(&p);
+  p.*result = res.data_ptr<R>();
+  p.workspace_bytes = bytes(&p);
   Tensor ws = workspace(p.workspace_bytes, x);
   p.workspace = ws.data_ptr();
-  check_rc(tc_colour_hist(&p, cur_stream()), "tc_colour_hist");
-  return hist;
+  check_rc(entry(&p, cur_stream()), hist ? "tc_colour_hist" : "tc_colour_stats");
+  return res;
+}
+
+Tensor colour_stats_cuda(const Tensor& x, int64_t f0, int64_t nf, int64_t fstep) {
+  return colour_frames_cuda(x, f0, nf, fstep, &TcColourStatsParams::stats, tc_colour_stats_workspace, tc_colour_stats);
+}
+
+Tensor colour_stats_meta(const Tensor& x, int64_t f0, int64_t nf, int64_t fstep) {
+  return at::empty(colour_frames_shape(x, f0, nf, fstep, false), x.options().dtype(at::kDouble));
+}
+
+Tensor colour_hist_cuda(const Tensor& x, int64_t f0, int64_t nf, int64_t fstep) {
+  return colour_frames_cuda(x, f0, nf, fstep, &TcColourHistParams::hist, tc_colour_hist_workspace, tc_colour_hist);
 }
 
 Tensor colour_hist_meta(const Tensor& x, int64_t f0, int64_t nf, int64_t fstep) {
-  return at::empty(colour_hist_shape(x, f0, nf, fstep), x.options().dtype(at::kInt));
+  return at::empty(colour_frames_shape(x, f0, nf, fstep, true), x.options().dtype(at::kInt));
 }
 
-void colour_transfer_check(const Tensor& x, const optional<Tensor>& base, const Tensor& src, const Tensor& ref, int64_t ref_pixels,
-                           double strength) {
-  colour_clip_check(x, "colour_transfer");
-  const int64_t b = x.size(0), t = x.size(2);
-  TORCH_CHECK(x.scalar_type() == at::kFloat, "colour_transfer: x: fp32 (b, 3, t, h, w)");
-  TORCH_CHECK(!base.has_value() || (base->sizes() == x.sizes() && base->scalar_type() == at::kFloat),
-              "colour_transfer: base must be fp32 of the shape of x");
-  TORCH_CHECK(src.dim() == 4 && src.size(0) == b && src.size(1) == t && src.size(2) == 3 && src.size(3) == TC_COLOUR_BINS &&
-                  src.scalar_type() == at::kInt, "colour_transfer: src must be int32 (b, t, 3, 1024)");
-  TORCH_CHECK(ref.dim() == 4 && ref.size(0) == b && ref.size(1) == 2 && ref.size(2) == 3 && ref.size(3) == TC_COLOUR_BINS &&
-                  ref.scalar_type() == at::kInt, "colour_transfer: ref must be int32 (b, 2, 3, 1024)");
-  TORCH_CHECK(strength >= 0.0 && strength <= 1.0, "colour_transfer: strength ", strength, " outside [0, 1]");
-  TORCH_CHECK(ref_pixels > 0 && ref_pixels <= (int64_t(1) << 26), "colour_transfer: ref_pixels ", ref_pixels, " outside [1, 2^26]");
-  TORCH_CHECK(x.size(3) * x.size(4) <= (int64_t(1) << 26), "colour_transfer: h * w ", x.size(3) * x.size(4), " above 2^26");
+// What the match and the transfer family share.  An op is the old one (knots null: two reference images per clip) or its knots form.
+using Knots = const at::IntArrayRef*;
+using Pair = std::tuple<Tensor, Tensor>;                     // (the result clip, its coefficients or tables)
+
+int64_t colour_ref_rows(Knots knots) { return knots ? (int64_t)knots->size() : 2; }
+
+void colour_knots_check(const char* what, const Tensor& x, Knots knots) {
+  if (!knots) return;
+  const int64_t t = x.size(2), nk = (int64_t)knots->size();
+  TORCH_CHECK(nk >= 1 && nk <= TC_TEMPORAL_MAX_FRAMES, what, ": ", nk, " knots outside [1, ", TC_TEMPORAL_MAX_FRAMES, "]");
+  for (int64_t i = 0; i < nk; ++i)
+    TORCH_CHECK((*knots)[i] >= 0 && (*knots)[i] < t && (i == 0 || (*knots)[i] > (*knots)[i - 1]), what,
+                ": knots must be strictly increasing frame indices in [0, ", t, ")");
 }
 
-std::tuple<Tensor, Tensor> colour_transfer_cuda(const Tensor& x, const optional<Tensor>& base, const Tensor& src, const Tensor& ref,
-                                                int64_t ref_pixels, double strength) {
-  TORCH_CHECK(x.is_cuda() && src.is_cuda() && ref.is_cuda() && (!base.has_value() || base->is_cuda()),
-              "colour_transfer: expected CUDA tensors (the product path is GPU-only)");
-  colour_transfer_check(x, base, src, ref, ref_pixels, strength);
-  TORCH_CHECK(x.is_contiguous() && src.is_contiguous() && ref.is_contiguous() && (!base.has_value() || base->is_contiguous()),
-              "colour_transfer: contiguous tensors");
-  Tensor out = at::empty_like(x);
-  Tensor table = at::empty({x.size(0), x.size(2), 3, TC_COLOUR_BINS}, x.options());
-  TcColourTransferParams p = {};
-  p.x = x.data_ptr<float>(); p.base = base.has_value() ? base->data_ptr<float>() : nullptr; p.out = out.data_ptr<float>();
+void colour_strength_check(const char* what, double strength) {
+  TORCH_CHECK(strength >= 0.0 && strength <= 1.0, what, ": strength ", strength, " outside [0, 1]");
+}
+
+void colour_device_check(const char* what, const Tensor& x, const Tensor& src, const Tensor& ref, const optional<Tensor>& base) {
+  TORCH_CHECK(x.is_cuda() && src.is_cuda() && ref.is_cuda() && (!base.has_value() || base->is_cuda()), what,
+              ": expected CUDA tensors (the product path is GPU-only)");
+}
+
+// the fields that the four params structs of the two families share, and the knots of the two that have them
+template <typename P>
+void colour_clip_fill(P& p, const Tensor& x, const Tensor& out, const Tensor& src, const Tensor& ref, int64_t ref_pixels,
+                      double strength, Knots knots) {
+  p.x = x.data_ptr<float>(); p.out = out.data_ptr<float>();
   p.b = (int32_t)x.size(0); p.t = (int32_t)x.size(2); p.h = (int32_t)x.size(3); p.w = (int32_t)x.size(4);
-  p.src = src.data_ptr<int32_t>(); p.ref = ref.data_ptr<int32_t>();
+  p.src = static_cast<decltype(p.src)>(src.data_ptr()); p.ref = static_cast<decltype(p.ref)>(ref.data_ptr());
   p.ref_pixels = ref_pixels; p.strength = (float)strength;
-  p.table = table.data_ptr<float>();
-  check_rc(tc_colour_transfer(&p, cur_stream()), "tc_colour_transfer");
-  return {out, table};
+  if constexpr (std::is_same_v<P, TcColourMatchKnotsParams> || std::is_same_v<P, TcColourTransferKnotsParams>) {
+    p.nk = (int32_t)knots->size();
+    for (size_t i = 0; i < knots->size(); ++i) p.knot[i] = (int32_t)(*knots)[i];
+  }
 }
 
-std::tuple<Tensor, Tensor> colour_transfer_meta(const Tensor& x, const optional<Tensor>& base, const Tensor& src, const Tensor& ref,
-                                                int64_t ref_pixels, double strength) {
-  colour_transfer_check(x, base, src, ref, ref_pixels, strength);
+// The match family.  Dtypes are checked on the CUDA key only.
+void colour_match_check(const char* what, const Tensor& x, const Tensor& src, const Tensor& ref, int64_t ref_pixels, int64_t method,
+                        double strength, Knots knots, double max_gain) {
+  colour_clip_check(x, what);
+  const int64_t b = x.size(0), t = x.size(2);
+  TORCH_CHECK(src.dim() == 3 && src.size(0) == b && src.size(1) == t && src.size(2) == TC_COLOUR_STATS, what, ": src must be (b, t, 9)");
+  TORCH_CHECK(ref.dim() == 3 && ref.size(0) == b && ref.size(1) == colour_ref_rows(knots) && ref.size(2) == TC_COLOUR_STATS, what,
+              ": ref must be (b, ", knots ? "nk" : "2", ", 9)");
+  colour_knots_check(what, x, knots);
+  TORCH_CHECK(method == TC_COLOUR_MEAN_STD || method == TC_COLOUR_MKL, what, ": method ", method);
+  colour_strength_check(what, strength);
+  TORCH_CHECK(ref_pixels > 0, what, ": ref_pixels ", ref_pixels);
+  TORCH_CHECK(max_gain == 0.0 || (max_gain >= 1.0 && std::isfinite(max_gain)), what, ": max_gain ", max_gain,
+              ": 0 (no limit) or a finite number >= 1");
+}
+
+Pair colour_match_results(const Tensor& x) {
+  return {at::empty_like(x), at::empty({x.size(0), x.size(2), 12}, x.options())};
+}
+
+template <typename P>
+Pair colour_match_run(const char* what, int (*entry)(const P*, void*), const Tensor& x, const Tensor& src, const Tensor& ref,
+                      int64_t ref_pixels, int64_t method, double strength, Knots knots, double max_gain) {
+  colour_device_check(what, x, src, ref, optional<Tensor>());
+  TORCH_CHECK(x.scalar_type() == at::kFloat && x.is_contiguous(), what, ": x: contiguous fp32 (b, 3, t, h, w)");
+  TORCH_CHECK(src.scalar_type() == at::kDouble && src.is_contiguous() && ref.scalar_type() == at::kDouble && ref.is_contiguous(), what,
+              ": src / ref: contiguous float64");
+  colour_match_check(what, x, src, ref, ref_pixels, method, strength, knots, max_gain);
+  auto [out, coefs] = colour_match_results(x);
+  P p = {};
+  colour_clip_fill(p, x, out, src, ref, ref_pixels, strength, knots);
+  p.method = (int32_t)method;
+  p.coefs = coefs.data_ptr<float>();
+  if constexpr (std::is_same_v<P, TcColourMatchKnotsParams>) p.max_gain = (float)max_gain;
+  check_rc(entry(&p, cur_stream()), (std::string("tc_") + what).c_str());
+  return {out, coefs};
+}
+
+Pair colour_match_cuda(const Tensor& x, const Tensor& src, const Tensor& ref, int64_t ref_pixels, int64_t method, double strength) {
+  return colour_match_run("colour_match", tc_colour_match, x, src, ref, ref_pixels, method, strength, nullptr, 0.0);
+}
+
+Pair colour_match_meta(const Tensor& x, const Tensor& src, const Tensor& ref, int64_t ref_pixels, int64_t method, double strength) {
+  colour_match_check("colour_match", x, src, ref, ref_pixels, method, strength, nullptr, 0.0);
+  return colour_match_results(x);
+}
+
+Pair colour_match_knots_cuda(const Tensor& x, const Tensor& src, const Tensor& ref, int64_t ref_pixels, int64_t method, double strength,
+                             at::IntArrayRef knots, double max_gain) {
+  return colour_match_run("colour_match_knots", tc_colour_match_knots, x, src, ref, ref_pixels, method, strength, &knots, max_gain);
+}
+
+Pair colour_match_knots_meta(const Tensor& x, const Tensor& src, const Tensor& ref, int64_t ref_pixels, int64_t method, double strength,
+                             at::IntArrayRef knots, double max_gain) {
+  colour_match_check("colour_match_knots", x, src, ref, ref_pixels, method, strength, &knots, max_gain);
+  return colour_match_results(x);
+}
+
+// The transfer family.  Dtypes are part of the check that both keys run.
+void colour_transfer_check(const char* what, const Tensor& x, const optional<Tensor>& base, const Tensor& src, const Tensor& ref,
+                           int64_t ref_pixels, double strength, Knots knots) {
+  colour_clip_check(x, what);
+  const int64_t b = x.size(0), t = x.size(2);
+  TORCH_CHECK(x.scalar_type() == at::kFloat, what, ": x: fp32 (b, 3, t, h, w)");
+  TORCH_CHECK(!base.has_value() || (base->sizes() == x.sizes() && base->scalar_type() == at::kFloat), what,
+              ": base must be fp32 of the shape of x");
+  TORCH_CHECK(src.dim() == 4 && src.size(0) == b && src.size(1) == t && src.size(2) == 3 && src.size(3) == TC_COLOUR_BINS &&
+                  src.scalar_type() == at::kInt, what, ": src must be int32 (b, t, 3, 1024)");
+  TORCH_CHECK(ref.dim() == 4 && ref.size(0) == b && ref.size(1) == colour_ref_rows(knots) && ref.size(2) == 3 &&
+                  ref.size(3) == TC_COLOUR_BINS && ref.scalar_type() == at::kInt, what, ": ref must be int32 (b, ", knots ? "nk" : "2",
+              ", 3, 1024)");
+  colour_knots_check(what, x, knots);
+  colour_strength_check(what, strength);
+  TORCH_CHECK(ref_pixels > 0 && ref_pixels <= (int64_t(1) << 26), what, ": ref_pixels ", ref_pixels, " outside [1, 2^26]");
+  colour_hw_check(x, what);
+}
+
+Pair colour_transfer_results(const Tensor& x) {
   return {at::empty_like(x), at::empty({x.size(0), x.size(2), 3, TC_COLOUR_BINS}, x.options())};
 }
 
-// colour_transfer_knots: colour_transfer towards the reference images at `knots`, ref (b, nk, 3, 1024) (tc_colour_transfer_knots)
-void colour_transfer_knots_check(const Tensor& x, const optional<Tensor>& base, const Tensor& src, const Tensor& ref, int64_t ref_pixels,
-                                 double strength, at::IntArrayRef knots) {
-  colour_clip_check(x, "colour_transfer_knots");
-  const int64_t b = x.size(0), t = x.size(2);
-  TORCH_CHECK(x.scalar_type() == at::kFloat, "colour_transfer_knots: x: fp32 (b, 3, t, h, w)");
-  TORCH_CHECK(!base.has_value() || (base->sizes() == x.sizes() && base->scalar_type() == at::kFloat),
-              "colour_transfer_knots: base must be fp32 of the shape of x");
-  TORCH_CHECK(src.dim() == 4 && src.size(0) == b && src.size(1) == t && src.size(2) == 3 && src.size(3) == TC_COLOUR_BINS &&
-                  src.scalar_type() == at::kInt, "colour_transfer_knots: src must be int32 (b, t, 3, 1024)");
-  TORCH_CHECK(ref.dim() == 4 && ref.size(0) == b && ref.size(2) == 3 && ref.size(3) == TC_COLOUR_BINS && ref.scalar_type() == at::kInt,
-              "colour_transfer_knots: ref must be int32 (b, nk, 3, 1024)");
-  colour_knots_check(x, ref, knots, "colour_transfer_knots");
-  TORCH_CHECK(strength >= 0.0 && strength <= 1.0, "colour_transfer_knots: strength ", strength, " outside [0, 1]");
-  TORCH_CHECK(ref_pixels > 0 && ref_pixels <= (int64_t(1) << 26), "colour_transfer_knots: ref_pixels ", ref_pixels, " outside [1, 2^26]");
-  TORCH_CHECK(x.size(3) * x.size(4) <= (int64_t(1) << 26), "colour_transfer_knots: h * w ", x.size(3) * x.size(4), " above 2^26");
-}
-
-std::tuple<Tensor, Tensor> colour_transfer_knots_cuda(const Tensor& x, const optional<Tensor>& base, const Tensor& src, const Tensor& ref,
-                                                      int64_t ref_pixels, double strength, at::IntArrayRef knots) {
-  TORCH_CHECK(x.is_cuda() && src.is_cuda() && ref.is_cuda() && (!base.has_value() || base->is_cuda()),
-              "colour_transfer_knots: expected CUDA tensors (the product path is GPU-only)");
-  colour_transfer_knots_check(x, base, src, ref, ref_pixels, strength, knots);
-  TORCH_CHECK(x.is_contiguous() && src.is_contiguous() && ref.is_contiguous() && (!base.has_value() || base->is_contiguous()),
-              "colour_transfer_knots: contiguous tensors");
-  Tensor out = at::empty_like(x);
-  Tensor table = at::empty({x.size(0), x.size(2), 3, TC_COLOUR_BINS}, x.options());
-  TcColourTransferKnotsParams p = {};
-  p.x = x.data_ptr<float>(); p.base = base.has_value() ? base->data_ptr<float>() : nullptr; p.out = out.data_ptr<float>();
-  p.b = (int32_t)x.size(0); p.t = (int32_t)x.size(2); p.h = (int32_t)x.size(3); p.w = (int32_t)x.size(4);
-  p.src = src.data_ptr<int32_t>(); p.ref = ref.data_ptr<int32_t>();
-  p.ref_pixels = ref_pixels; p.strength = (float)strength;
+template <typename P>
+Pair colour_transfer_run(const char* what, int (*entry)(const P*, void*), const Tensor& x, const optional<Tensor>& base,
+                         const Tensor& src, const Tensor& ref, int64_t ref_pixels, double strength, Knots knots) {
+  colour_device_check(what, x, src, ref, base);
+  colour_transfer_check(what, x, base, src, ref, ref_pixels, strength, knots);
+  TORCH_CHECK(x.is_contiguous() && src.is_contiguous() && ref.is_contiguous() && (!base.has_value() || base->is_contiguous()), what,
+              ": contiguous tensors");
+  auto [out, table] = colour_transfer_results(x);
+  P p = {};
+  colour_clip_fill(p, x, out, src, ref, ref_pixels, strength, knots);
+  p.base = base.has_value() ? base->data_ptr<float>() : nullptr;
   p.table = table.data_ptr<float>();
-  p.nk = (int32_t)knots.size();
-  for (size_t i = 0; i < knots.size(); ++i) p.knot[i] = (int32_t)knots[i];
-  check_rc(tc_colour_transfer_knots(&p, cur_stream()), "tc_colour_transfer_knots");
+  check_rc(entry(&p, cur_stream()), (std::string("tc_") + what).c_str());
   return {out, table};
 }
 
-std::tuple<Tensor, Tensor> colour_transfer_knots_meta(const Tensor& x, const optional<Tensor>& base, const Tensor& src, const Tensor& ref,
-                                                      int64_t ref_pixels, double strength, at::IntArrayRef knots) {
-  colour_transfer_knots_check(x, base, src, ref, ref_pixels, strength, knots);
-  return {at::empty_like(x), at::empty({x.size(0), x.size(2), 3, TC_COLOUR_BINS}, x.options())};
+Pair colour_transfer_cuda(const Tensor& x, const optional<Tensor>& base, const Tensor& src, const Tensor& ref, int64_t ref_pixels,
+                          double strength) {
+  return colour_transfer_run("colour_transfer", tc_colour_transfer, x, base, src, ref, ref_pixels, strength, nullptr);
+}
+
+Pair colour_transfer_meta(const Tensor& x, const optional<Tensor>& base, const Tensor& src, const Tensor& ref, int64_t ref_pixels,
+                          double strength) {
+  colour_transfer_check("colour_transfer", x, base, src, ref, ref_pixels, strength, nullptr);
+  return colour_transfer_results(x);
+}
+
+Pair colour_transfer_knots_cuda(const Tensor& x, const optional<Tensor>& base, const Tensor& src, const Tensor& ref, int64_t ref_pixels,
+                                double strength, at::IntArrayRef knots) {
+  return colour_transfer_run("colour_transfer_knots", tc_colour_transfer_knots, x, base, src, ref, ref_pixels, strength, &knots);
+}
+
+Pair colour_transfer_knots_meta(const Tensor& x, const optional<Tensor>& base, const Tensor& src, const Tensor& ref, int64_t ref_pixels,
+                                double strength, at::IntArrayRef knots) {
+  colour_transfer_check("colour_transfer_knots", x, base, src, ref, ref_pixels, strength, &knots);
+  return colour_transfer_results(x);
 }
 
 // clip_patches: (B, 3, H, W) fp32 -> the bf16 A operand [B * (size / patch)^2, ld] of the CLIP image tower's patch-embedding GEMM

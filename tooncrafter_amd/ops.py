@@ -1225,7 +1225,8 @@ class HipOps:
         _lib.check(self.lib.tc_ddim_blend(C.byref(p), _stream()), "tc_ddim_blend")
         return out
 
-    # ------------------------------------------------------------------ colour match (tc_colour_stats, tc_colour_match)
+    # ------------------------------------------------------------------ colour match and histogram transfer (tc_colour_*)
+    # The helpers state each check once for both families and both bindings (torch_ops.TorchLibOps marshals their results).
     @staticmethod
     def _colour_clip(x, what):
         """The (b, t, h, w) of a (b, 3, t, h, w) fp32 contiguous device clip, or raise."""
@@ -1261,23 +1262,75 @@ class HipOps:
         return knots, gain
 
     @staticmethod
-    def _colour_match_args(x, src, ref, ref_pixels, method, strength, what="colour_match", refs=2):
-        """The checked request of a match on the clip x with dimensions (b, t, h, w) against `refs` reference images per clip:
-        (method code, strength, ref_pixels)."""
+    def _colour_refs(what, x, src, ref, knots, dtype, tail):
+        """`src` (b, t, *tail) of the clip x and `ref` (b, rows, *tail) of its reference images -- one per knot, two when
+        `knots` is None -- as contiguous device tensors of `dtype`, or raise."""
         b, t = x.shape[0], x.shape[2]
-        for name, s, rows in (("src", src, t), ("ref", ref, refs)):
+        for which, s, rows in (("src", src, t), ("ref", ref, 2 if knots is None else len(knots))):
             if not isinstance(s, torch.Tensor) or not s.is_cuda:
-                raise _lib.TooncrafterHipError(f"{what}: {name}: expected a CUDA tensor: the product path is GPU-only")
-            if s.dtype != torch.float64 or tuple(s.shape) != (b, rows, _lib.TC_COLOUR_STATS) or not s.is_contiguous():
-                raise ValueError(f"{what}: {name}: expected contiguous float64 {(b, rows, _lib.TC_COLOUR_STATS)}, got "
-                                 f"{tuple(s.shape)} {s.dtype}")
+                raise _lib.TooncrafterHipError(f"{what}: {which}: expected a CUDA tensor: the product path is GPU-only")
+            if s.dtype != dtype or s.shape != (b, rows) + tail or not s.is_contiguous():
+                raise ValueError(f"{what}: {which}: expected contiguous {str(dtype)[6:]} {(b, rows) + tail}, got {tuple(s.shape)} "
+                                 f"{s.dtype}")
+
+    # (entry point, params struct) of a family towards the two ends, and of its knots form
+    _COLOUR_MATCH = (("tc_colour_match", _lib.TcColourMatchParams), ("tc_colour_match_knots", _lib.TcColourMatchKnotsParams))
+    _COLOUR_TRANSFER = (("tc_colour_transfer", _lib.TcColourTransferParams),
+                        ("tc_colour_transfer_knots", _lib.TcColourTransferKnotsParams))
+
+    def _colour_clip_call(self, forms, x, dims, out, knots, result, tail, fields):
+        """The call of a checked clip request on x ((b, t, h, w) = dims): the first of `forms` (one of the pairs above) towards the
+        two ends (knots None), the second through `knots`, with the further params `fields`.  `out` may be x itself; None: a new
+        tensor.  Returns (out, the fp32 (b, t) + tail tensor that the params field `result` takes: coefficients or tables)."""
+        if out is None:
+            out = torch.empty_like(x)
+        elif self._colour_clip(out, f"{forms[0][0][3:]}: out") != dims or out.device != x.device:
+            raise ValueError(f"{forms[0][0][3:]}: out {tuple(out.shape)} against x {tuple(x.shape)}")
+        b, t, h, w = dims
+        res = torch.empty((b, t) + tail, dtype=torch.float32, device=x.device)
+        fields[result] = res.data_ptr()
+        entry, struct = forms[knots is not None]
+        p = struct(x=x.data_ptr(), out=out.data_ptr(), b=b, t=t, h=h, w=w, **fields)
+        if knots is not None:
+            p.nk = len(knots)
+            p.knot[:len(knots)] = knots
+        _lib.check(getattr(self.lib, entry)(C.byref(p), _stream()), entry)
+        return out, res
+
+    @staticmethod
+    def _colour_match_request(x, src, ref, ref_pixels, method, strength, knots, max_gain):
+        """The checked request of a match on the clip x: ((b, t, h, w), knots, gain, method code, strength, ref_pixels).  The
+        entry point is chosen here, once for both bindings: knots None (neither `knots` nor `max_gain` given) is tc_colour_match
+        on the two ends; otherwise tc_colour_match_knots, an omitted `knots` spelled out as the two ends and an omitted
+        `max_gain` as 0."""
+        dims = HipOps._colour_clip(x, "colour_match: x")
+        gain = 0.0
+        if knots is not None or max_gain is not None:
+            knots, gain = HipOps._colour_knots(knots, max_gain, dims[1], "colour_match")
+        HipOps._colour_refs("colour_match", x, src, ref, knots, torch.float64, (_lib.TC_COLOUR_STATS,))
         code = _lib.TC_COLOUR_METHODS.get(method, method)
         if isinstance(code, bool) or code not in _lib.TC_COLOUR_METHODS.values():
-            raise ValueError(f"{what}: method {method!r}: one of {tuple(_lib.TC_COLOUR_METHODS)}")
+            raise ValueError(f"colour_match: method {method!r}: one of {tuple(_lib.TC_COLOUR_METHODS)}")
         strength, ref_pixels = float(strength), int(ref_pixels)
         if not 0.0 <= strength <= 1.0 or ref_pixels <= 0:                      # NaN fails the comparison too
-            raise ValueError(f"{what}: strength {strength} outside [0, 1] or ref_pixels {ref_pixels} <= 0")
-        return code, strength, ref_pixels
+            raise ValueError(f"colour_match: strength {strength} outside [0, 1] or ref_pixels {ref_pixels} <= 0")
+        return dims, knots, gain, code, strength, ref_pixels
+
+    @staticmethod
+    def _colour_transfer_request(x, src, ref, ref_pixels, strength, base, knots):
+        """The checked request of a histogram transfer on the clip x: ((b, t, h, w), knots, strength, ref_pixels).  knots None
+        is tc_colour_transfer on the two ends, otherwise tc_colour_transfer_knots."""
+        dims = HipOps._colour_clip(x, "colour_transfer: x")
+        if knots is not None:
+            knots, _ = HipOps._colour_knots(knots, None, dims[1], "colour_transfer")
+        HipOps._colour_refs("colour_transfer", x, src, ref, knots, torch.int32, (3, _lib.TC_COLOUR_BINS))
+        if base is not None and (HipOps._colour_clip(base, "colour_transfer: base") != dims or base.device != x.device):
+            raise ValueError(f"colour_transfer: base {tuple(base.shape)} against x {tuple(x.shape)}")
+        strength, ref_pixels = float(strength), int(ref_pixels)
+        if not 0.0 <= strength <= 1.0 or not 0 < ref_pixels <= 1 << 26 or dims[2] * dims[3] > 1 << 26:
+            raise ValueError(f"colour_transfer: strength {strength} outside [0, 1], or ref_pixels {ref_pixels} or h * w "
+                             f"{dims[2] * dims[3]} outside [1, 2^26]")
+        return dims, knots, strength, ref_pixels
 
     def colour_stats(self, x, frames=None):
         """Nine float64 sums (r, g, b, rr, rg, rb, gg, gb, bb of the clamped values) per frame f0, f0 + fstep, ... (nf of them;
@@ -1290,57 +1343,6 @@ class HipOps:
         self._launch("tc_colour_stats", p, x.device)
         return stats
 
-    def colour_match(self, x, src, ref, ref_pixels, method, strength, out=None, knots=None, max_gain=None):
-        """x (b, 3, t, h, w) fp32 matched frame by frame to the course between two reference images per clip: `src` (b, t, 9) the
-        statistics of x, `ref` (b, 2, 9) those of the reference images over `ref_pixels` pixels each, method "mkl" | "mean_std"
-        (or its code), strength in [0, 1].  Returns (matched clip, coefs (b, t, 12) fp32: A' row-major, then o').  `out` may be
-        `x` itself (in place); default: a new tensor (tc_colour_match).
-        knots: strictly increasing frame indices, one per reference image -- `ref` is then (b, len(knots), 9) and the course
-        runs through them; max_gain: a number >= 1 that limits the gain of the map (0: none).  With either given the call is
-        tc_colour_match_knots (an omitted `knots` means the two ends); with both None it is tc_colour_match."""
-        b, t, h, w = self._colour_clip(x, "colour_match: x")
-        if knots is None and max_gain is None:
-            code, strength, ref_pixels = self._colour_match_args(x, src, ref, ref_pixels, method, strength)
-        else:
-            knots, gain = self._colour_knots(knots, max_gain, t, "colour_match")
-            code, strength, ref_pixels = self._colour_match_args(x, src, ref, ref_pixels, method, strength, refs=len(knots))
-        if out is None:
-            out = torch.empty_like(x)
-        elif self._colour_clip(out, "colour_match: out") != (b, t, h, w) or out.device != x.device:
-            raise ValueError(f"colour_match: out {tuple(out.shape)} against x {tuple(x.shape)}")
-        coefs = torch.empty((b, t, 12), dtype=torch.float32, device=x.device)
-        fields = dict(x=x.data_ptr(), out=out.data_ptr(), b=b, t=t, h=h, w=w, src=src.data_ptr(), ref=ref.data_ptr(),
-                      ref_pixels=ref_pixels, method=code, strength=strength, coefs=coefs.data_ptr())
-        if knots is None:
-            p = _lib.TcColourMatchParams(**fields)
-            _lib.check(self.lib.tc_colour_match(C.byref(p), _stream()), "tc_colour_match")
-        else:
-            p = _lib.TcColourMatchKnotsParams(**fields, nk=len(knots), max_gain=gain)
-            p.knot[:len(knots)] = knots
-            _lib.check(self.lib.tc_colour_match_knots(C.byref(p), _stream()), "tc_colour_match_knots")
-        return out, coefs
-
-    # ------------------------------------------------------------------ histogram transfer (tc_colour_hist, tc_colour_transfer)
-    @staticmethod
-    def _colour_transfer_args(x, src, ref, ref_pixels, strength, base, what="colour_transfer", refs=2):
-        """The checked request of a histogram transfer on the clip x against `refs` reference images per clip: (strength,
-        ref_pixels)."""
-        b, t = x.shape[0], x.shape[2]
-        for name, s, rows in (("src", src, t), ("ref", ref, refs)):
-            if not isinstance(s, torch.Tensor) or not s.is_cuda:
-                raise _lib.TooncrafterHipError(f"{what}: {name}: expected a CUDA tensor: the product path is GPU-only")
-            if s.dtype != torch.int32 or tuple(s.shape) != (b, rows, 3, _lib.TC_COLOUR_BINS) or not s.is_contiguous():
-                raise ValueError(f"{what}: {name}: expected contiguous int32 {(b, rows, 3, _lib.TC_COLOUR_BINS)}, got "
-                                 f"{tuple(s.shape)} {s.dtype}")
-        if base is not None and (HipOps._colour_clip(base, f"{what}: base") != HipOps._colour_clip(x, f"{what}: x")
-                                 or base.device != x.device):
-            raise ValueError(f"{what}: base {tuple(base.shape)} against x {tuple(x.shape)}")
-        strength, ref_pixels = float(strength), int(ref_pixels)
-        if not 0.0 <= strength <= 1.0 or not 0 < ref_pixels <= 1 << 26 or x.shape[3] * x.shape[4] > 1 << 26:
-            raise ValueError(f"{what}: strength {strength} outside [0, 1], or ref_pixels {ref_pixels} or h * w "
-                             f"{x.shape[3] * x.shape[4]} outside [1, 2^26]")
-        return strength, ref_pixels
-
     def colour_hist(self, x, frames=None):
         """3 x 1024 int32 counts (r, g, b; of the clamped values, bin = min(1023, floor((c + 1) * 512))) per frame f0, f0 + fstep,
         ... (nf of them; frames = (f0, nf, fstep), None: all) of every clip of x (b, 3, t, h, w) fp32: (b, nf, 3, 1024)
@@ -1352,6 +1354,21 @@ class HipOps:
         self._launch("tc_colour_hist", p, x.device)
         return hist
 
+    def colour_match(self, x, src, ref, ref_pixels, method, strength, out=None, knots=None, max_gain=None):
+        """x (b, 3, t, h, w) fp32 matched frame by frame to the course between two reference images per clip: `src` (b, t, 9) the
+        statistics of x, `ref` (b, 2, 9) those of the reference images over `ref_pixels` pixels each, method "mkl" | "mean_std"
+        (or its code), strength in [0, 1].  Returns (matched clip, coefs (b, t, 12) fp32: A' row-major, then o').  `out` may be
+        `x` itself (in place); default: a new tensor (tc_colour_match).
+        knots: strictly increasing frame indices, one per reference image -- `ref` is then (b, len(knots), 9) and the course
+        runs through them; max_gain: a number >= 1 that limits the gain of the map (0: none).  With either given the call is
+        tc_colour_match_knots (an omitted `knots` means the two ends); with both None it is tc_colour_match."""
+        dims, knots, gain, code, strength, ref_pixels = self._colour_match_request(x, src, ref, ref_pixels, method, strength, knots,
+                                                                                   max_gain)
+        fields = dict(src=src.data_ptr(), ref=ref.data_ptr(), ref_pixels=ref_pixels, method=code, strength=strength)
+        if knots is not None:
+            fields["max_gain"] = gain
+        return self._colour_clip_call(self._COLOUR_MATCH, x, dims, out, knots, "coefs", (12,), fields)
+
     def colour_transfer(self, x, src, ref, ref_pixels, strength, base=None, out=None, knots=None):
         """x (b, 3, t, h, w) fp32 carried channel by channel onto the course between the histograms of two reference images per
         clip: `src` (b, t, 3, 1024) the histograms of x, `ref` (b, 2, 3, 1024) those of the reference images over `ref_pixels`
@@ -1360,26 +1377,10 @@ class HipOps:
         (in place); default: a new tensor (tc_colour_transfer).
         knots: strictly increasing frame indices, one per reference image -- `ref` is then (b, len(knots), 3, 1024) and the
         course runs through them (tc_colour_transfer_knots); None: tc_colour_transfer."""
-        b, t, h, w = self._colour_clip(x, "colour_transfer: x")
-        if knots is not None:
-            knots, _ = self._colour_knots(knots, None, t, "colour_transfer")
-        strength, ref_pixels = self._colour_transfer_args(x, src, ref, ref_pixels, strength, base,
-                                                          refs=2 if knots is None else len(knots))
-        if out is None:
-            out = torch.empty_like(x)
-        elif self._colour_clip(out, "colour_transfer: out") != (b, t, h, w) or out.device != x.device:
-            raise ValueError(f"colour_transfer: out {tuple(out.shape)} against x {tuple(x.shape)}")
-        table = torch.empty((b, t, 3, _lib.TC_COLOUR_BINS), dtype=torch.float32, device=x.device)
-        fields = dict(x=x.data_ptr(), base=None if base is None else base.data_ptr(), out=out.data_ptr(), b=b, t=t, h=h, w=w,
-                      src=src.data_ptr(), ref=ref.data_ptr(), ref_pixels=ref_pixels, strength=strength, table=table.data_ptr())
-        if knots is None:
-            p = _lib.TcColourTransferParams(**fields)
-            _lib.check(self.lib.tc_colour_transfer(C.byref(p), _stream()), "tc_colour_transfer")
-        else:
-            p = _lib.TcColourTransferKnotsParams(**fields, nk=len(knots))
-            p.knot[:len(knots)] = knots
-            _lib.check(self.lib.tc_colour_transfer_knots(C.byref(p), _stream()), "tc_colour_transfer_knots")
-        return out, table
+        dims, knots, strength, ref_pixels = self._colour_transfer_request(x, src, ref, ref_pixels, strength, base, knots)
+        fields = dict(base=None if base is None else base.data_ptr(), src=src.data_ptr(), ref=ref.data_ptr(), ref_pixels=ref_pixels,
+                      strength=strength)
+        return self._colour_clip_call(self._COLOUR_TRANSFER, x, dims, out, knots, "table", (3, _lib.TC_COLOUR_BINS), fields)
 
 
 _backend = None

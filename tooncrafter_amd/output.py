@@ -136,37 +136,27 @@ def match_colour(video: torch.Tensor, ends: torch.Tensor, match: ColourMatch, in
                          f"{None if ends is None else tuple(ends.shape)}")
     video, ends = video.to(torch.float32).contiguous(), ends.to(torch.float32).contiguous()
     t, ref_pixels = video.shape[2], ends.shape[3] * ends.shape[4]
+    # The targets and how the clip calls name them: the only branch.  `ends` itself and no keywords (the old entry points), or
+    # the stacked targets with their knots (the knots entry points; the limit goes to the linear calls alone).
     if not inner and match.max_gain is None:
-        if match.method in ("mkl", "mean_std"):
-            ref = ops.colour_stats(ends, frames=(0, 2, 1))
-            src = ops.colour_stats(video, frames=(0, t, 1))
-            return ops.colour_match(video, src, ref, ref_pixels, match.method, match.strength)[0]
-        src = ops.colour_hist(video, frames=(0, t, 1))
-        ref = ops.colour_hist(ends, frames=(0, 2, 1))
-        if match.method == "hm":
-            return ops.colour_transfer(video, src, ref, ref_pixels, match.strength)[0]
-        work = ops.colour_transfer(video, src, ref, ref_pixels, 1.0)[0]               # a clip of our own: `video` is the caller's
-        ref_stats = ops.colour_stats(ends, frames=(0, 2, 1))
-        stats = ops.colour_stats(work, frames=(0, t, 1))
-        work = ops.colour_match(work, stats, ref_stats, ref_pixels, "mkl", 1.0, out=work)[0]
-        src = ops.colour_hist(work, frames=(0, t, 1))
-        return ops.colour_transfer(work, src, ref, ref_pixels, match.strength, base=video, out=work)[0]
-    knots, targets = _match_targets(ends, t, inner)
-    every = (0, len(knots), 1)
+        targets, every, through, limited = ends, (0, 2, 1), {}, {}
+    else:
+        knots, targets = _match_targets(ends, t, inner)
+        every, through, limited = (0, len(knots), 1), dict(knots=knots), dict(knots=knots, max_gain=match.max_gain)
     if match.method in ("mkl", "mean_std"):
         ref = ops.colour_stats(targets, frames=every)
         src = ops.colour_stats(video, frames=(0, t, 1))
-        return ops.colour_match(video, src, ref, ref_pixels, match.method, match.strength, knots=knots, max_gain=match.max_gain)[0]
+        return ops.colour_match(video, src, ref, ref_pixels, match.method, match.strength, **limited)[0]
     src = ops.colour_hist(video, frames=(0, t, 1))
     ref = ops.colour_hist(targets, frames=every)
     if match.method == "hm":
-        return ops.colour_transfer(video, src, ref, ref_pixels, match.strength, knots=knots)[0]
-    work = ops.colour_transfer(video, src, ref, ref_pixels, 1.0, knots=knots)[0]
+        return ops.colour_transfer(video, src, ref, ref_pixels, match.strength, **through)[0]
+    work = ops.colour_transfer(video, src, ref, ref_pixels, 1.0, **through)[0]           # a clip of our own: `video` is the caller's
     ref_stats = ops.colour_stats(targets, frames=every)
     stats = ops.colour_stats(work, frames=(0, t, 1))
-    work = ops.colour_match(work, stats, ref_stats, ref_pixels, "mkl", 1.0, out=work, knots=knots, max_gain=match.max_gain)[0]
+    work = ops.colour_match(work, stats, ref_stats, ref_pixels, "mkl", 1.0, out=work, **limited)[0]
     src = ops.colour_hist(work, frames=(0, t, 1))
-    return ops.colour_transfer(work, src, ref, ref_pixels, match.strength, base=video, out=work, knots=knots)[0]
+    return ops.colour_transfer(work, src, ref, ref_pixels, match.strength, base=video, out=work, **through)[0]
 
 
 def clip_to_uint8(samples: torch.Tensor, loop: bool = False, size=None, filter: str = "bicubic", fmt: str = "rgb24",

@@ -192,12 +192,9 @@ class TorchLibOps(HipOps):
     def colour_match(self, x, src, ref, ref_pixels, method, strength, out=None, knots=None, max_gain=None):
         if out is not None:                                  # an explicit result buffer (in place): the ctypes method
             return super().colour_match(x, src, ref, ref_pixels, method, strength, out=out, knots=knots, max_gain=max_gain)
-        _, t, _, _ = self._colour_clip(x, "colour_match: x")
-        if knots is None and max_gain is None:
-            code, strength, ref_pixels = self._colour_match_args(x, src, ref, ref_pixels, method, strength)
+        _, knots, gain, code, strength, ref_pixels = self._colour_match_request(x, src, ref, ref_pixels, method, strength, knots, max_gain)
+        if knots is None:
             return self.t.colour_match(x, src, ref, ref_pixels, code, strength)
-        knots, gain = self._colour_knots(knots, max_gain, t, "colour_match")
-        code, strength, ref_pixels = self._colour_match_args(x, src, ref, ref_pixels, method, strength, refs=len(knots))
         return self.t.colour_match_knots(x, src, ref, ref_pixels, code, strength, list(knots), gain)
 
     def colour_hist(self, x, frames=None):
@@ -207,12 +204,9 @@ class TorchLibOps(HipOps):
     def colour_transfer(self, x, src, ref, ref_pixels, strength, base=None, out=None, knots=None):
         if out is not None:                                  # an explicit result buffer (in place): the ctypes method
             return super().colour_transfer(x, src, ref, ref_pixels, strength, base=base, out=out, knots=knots)
-        _, t, _, _ = self._colour_clip(x, "colour_transfer: x")
+        _, knots, strength, ref_pixels = self._colour_transfer_request(x, src, ref, ref_pixels, strength, base, knots)
         if knots is None:
-            strength, ref_pixels = self._colour_transfer_args(x, src, ref, ref_pixels, strength, base)
             return self.t.colour_transfer(x, base, src, ref, ref_pixels, strength)
-        knots, _ = self._colour_knots(knots, None, t, "colour_transfer")
-        strength, ref_pixels = self._colour_transfer_args(x, src, ref, ref_pixels, strength, base, refs=len(knots))
         return self.t.colour_transfer_knots(x, base, src, ref, ref_pixels, strength, list(knots))
 
     def clip_patches(self, x, *, size, patch, ld, mean, std, antialias=True):
