@@ -262,14 +262,20 @@ def test_meta_kernel_infers_shape_and_dtype():
     t = torch_ops.load()
     assert str(t.frames_to_u8.default._schema).startswith("tooncrafter::frames_to_u8(Tensor x, int oh, int ow, int format, int f0, int nf,")
     x = torch.empty(2, 3, 5, 20, 32, device="meta")
-    tab = torch.empty(4, 2, dtype=torch.int32, device="meta")
-    for tabs in ((None,) * 4, (tab,) * 4):
-        y = t.frames_to_u8(x, 46, 72, 0, 0, 5, *tabs)
-        assert y.shape == (2, 5, 46, 72, 3) and y.dtype == torch.uint8 and y.device.type == "meta"
-        for fmt in (1, 2):
-            y = t.frames_to_u8(x, 46, 72, fmt, 1, 3, *tabs)
-            assert y.shape == (2, 3, 46 * 72 * 3 // 2) and y.dtype == torch.uint8 and y.device.type == "meta"
+    def tabs(n_out):                                      # the tables of one resized axis: a row per output index
+        return torch.empty(n_out, 2, dtype=torch.int32, device="meta"), torch.empty(n_out, 4, dtype=torch.int32, device="meta")
+    up = tabs(72) + tabs(46)                              # (20, 32) -> (46, 72): w -> ow, then h -> oh
+    y = t.frames_to_u8(x, 46, 72, 0, 0, 5, *up)
+    assert y.shape == (2, 5, 46, 72, 3) and y.dtype == torch.uint8 and y.device.type == "meta"
+    for fmt in (1, 2):
+        y = t.frames_to_u8(x, 46, 72, fmt, 1, 3, *up)
+        assert y.shape == (2, 3, 46 * 72 * 3 // 2) and y.dtype == torch.uint8 and y.device.type == "meta"
+    y = t.frames_to_u8(x, 46, 32, 0, 0, 5, None, None, *tabs(46))                # None for the axis that keeps its size
+    assert y.shape == (2, 5, 46, 32, 3) and y.dtype == torch.uint8 and y.device.type == "meta"
     assert t.frames_to_u8(x, 20, 32, 0, 4, 1, None, None, None, None).shape == (2, 1, 20, 32, 3)
+    for tables in ((None,) * 4, tabs(4) * 2, tabs(46) + tabs(72)):                # a resize without its tables: refused as on the CUDA key
+        with pytest.raises(RuntimeError, match="tables of"):
+            t.frames_to_u8(x, 46, 72, 0, 0, 5, *tables)
     for bad in ((45, 72, 1, 0, 5), (46, 71, 2, 0, 5), (46, 72, 3, 0, 5), (46, 72, 0, 3, 3), (46, 72, 0, 0, 0), (0, 72, 0, 0, 5)):
         with pytest.raises(RuntimeError):
             t.frames_to_u8(x, *bad, None, None, None, None)

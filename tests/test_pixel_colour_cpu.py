@@ -150,12 +150,17 @@ def test_meta_kernel_infers_shape_and_dtype():
     assert str(t.frames_to_yuv.default._schema).startswith(
         "tooncrafter::frames_to_yuv(Tensor x, int oh, int ow, int format, int f0, int nf, int siting, int[] m,")
     x = torch.empty(2, 3, 5, 20, 32, device="meta")
-    tab = torch.empty(4, 2, dtype=torch.int32, device="meta")
+    def tabs(n_out):                                      # the tables of one resized axis: a row per output index
+        return torch.empty(n_out, 2, dtype=torch.int32, device="meta"), torch.empty(n_out, 4, dtype=torch.int32, device="meta")
     m = ref.out_matrix("bt709", "limited", 8)
-    for tabs in ((None,) * 4, (tab,) * 4):
-        for fmt, scale in ((1, 1), (2, 1), (3, 2)):
-            y = t.frames_to_yuv(x, 46, 72, fmt, 1, 3, 2, m, *tabs)
-            assert y.shape == (2, 3, 46 * 72 * 3 // 2 * scale) and y.dtype == torch.uint8 and y.device.type == "meta"
+    for fmt, scale in ((1, 1), (2, 1), (3, 2)):
+        y = t.frames_to_yuv(x, 46, 72, fmt, 1, 3, 2, m, *tabs(72), *tabs(46))      # (20, 32) -> (46, 72): w -> ow, then h -> oh
+        assert y.shape == (2, 3, 46 * 72 * 3 // 2 * scale) and y.dtype == torch.uint8 and y.device.type == "meta"
+        y = t.frames_to_yuv(x, 20, 72, fmt, 1, 3, 2, m, *tabs(72), None, None)      # None for the axis that keeps its size
+        assert y.shape == (2, 3, 20 * 72 * 3 // 2 * scale) and y.dtype == torch.uint8 and y.device.type == "meta"
+        for tables in ((None,) * 4, tabs(4) * 2):                                  # a resize without its tables: refused as on the CUDA key
+            with pytest.raises(RuntimeError, match="tables of"):
+                t.frames_to_yuv(x, 46, 72, fmt, 1, 3, 2, m, *tables)
     for bad in ((45, 72, 1, 0, 5, 1, m), (46, 71, 2, 0, 5, 1, m), (46, 72, 0, 0, 5, 1, m), (46, 72, 4, 0, 5, 1, m), (46, 72, 2, 3, 3, 1, m),
                 (46, 72, 2, 0, 5, 0, m), (46, 72, 2, 0, 5, 3, m), (46, 72, 2, 0, 5, 1, m[:7])):
         with pytest.raises(RuntimeError):

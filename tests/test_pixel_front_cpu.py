@@ -269,11 +269,20 @@ def test_meta_kernels_infer_shape_and_dtype():
     t = torch_ops.load()
     assert str(t.frames_from_u8.default._schema).startswith("tooncrafter::frames_from_u8(Tensor images, int[] slots, int b, int t, int h, int w,")
     assert str(t.clip_patches.default._schema).startswith("tooncrafter::clip_patches(Tensor x, int size, int patch, int ld, float[] mean,")
+    def tabs(n_out):                                      # the tables of one resized axis: a row per output index
+        return torch.empty(n_out, 2, dtype=torch.int32, device="meta"), torch.empty(n_out, 4, dtype=torch.int32, device="meta")
+    from tooncrafter_amd import _lib
+    rh, rw = ctypes.c_int32(), ctypes.c_int32()               # (37, 53) images are resized to (rh, rw) on the way to (16, 24)
+    assert _lib.load().tc_frames_from_u8_resized(37, 53, 16, 24, ctypes.byref(rh), ctypes.byref(rw)) == 0
+    assert (rh.value, rw.value) != (37, 53)
     imgs = torch.empty(2, 37, 53, 3, dtype=torch.uint8, device="meta")
-    tab = torch.empty(4, 2, dtype=torch.int32, device="meta")
-    for tabs in ((None,) * 4, (tab,) * 4):
-        y = t.frames_from_u8(imgs, [0, 3], 1, 4, 16, 24, *tabs)
+    same = torch.empty(2, 16, 24, 3, dtype=torch.uint8, device="meta")          # keeps its size: no tables
+    for src, tables in ((imgs, tabs(rw.value) + tabs(rh.value)), (same, (None,) * 4), (same, tabs(4) * 2)):
+        y = t.frames_from_u8(src, [0, 3], 1, 4, 16, 24, *tables)
         assert y.shape == (1, 3, 4, 16, 24) and y.dtype == torch.float32 and y.device.type == "meta"
+    for tables in ((None,) * 4, tabs(4) * 2):                 # a resize without its tables: refused as on the CUDA key
+        with pytest.raises(RuntimeError, match="tables of"):
+            t.frames_from_u8(imgs, [0, 3], 1, 4, 16, 24, *tables)
     for (b, h, w, size, patch, ld) in ((2, 40, 64, 28, 14, 592), (1, 320, 512, 224, 14, 592)):
         y = t.clip_patches(torch.empty(b, 3, h, w, device="meta"), size, patch, ld, [0.5, 0.5, 0.5], [0.25, 0.25, 0.25], True)
         assert y.shape == (b * (size // patch) ** 2, ld) and y.dtype == torch.bfloat16 and y.device.type == "meta"

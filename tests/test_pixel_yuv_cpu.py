@@ -245,14 +245,25 @@ def test_meta_kernel_infers_the_clip_shape():
     assert str(t.frames_from_yuv.default._schema).startswith(
         "tooncrafter::frames_from_yuv(Tensor y, Tensor c0, Tensor? c1, int format, int[] m, int siting, int[] slots, int b, int t, int h, int w,")
     m = ref.matrix("bt601", "limited", 8)
-    tab = torch.empty(4, 2, dtype=torch.int32, device="meta")
+    def tabs(n_out):                                      # the tables of one resized axis: a row per output index
+        return torch.empty(n_out, 2, dtype=torch.int32, device="meta"), torch.empty(n_out, 4, dtype=torch.int32, device="meta")
+    from tooncrafter_amd import _lib
+    rh, rw = ctypes.c_int32(), ctypes.c_int32()               # (37, 53) images are resized to (rh, rw) on the way to (16, 24)
+    assert _lib.load().tc_frames_from_u8_resized(37, 53, 16, 24, ctypes.byref(rh), ctypes.byref(rw)) == 0
+    assert (rh.value, rw.value) != (37, 53)
     y = torch.empty(2, 37, 53, dtype=torch.uint8, device="meta")
     c = torch.empty(2, 19, 27, dtype=torch.uint8, device="meta")
     cc = torch.empty(2, 19, 27, 2, dtype=torch.uint8, device="meta")
     for args in ((y, c, c, 1), (y, cc, None, 2), (y.to(torch.int16), cc.to(torch.int16), None, 3)):
-        for tabs in ((None,) * 4, (tab,) * 4):
-            out = t.frames_from_yuv(*args, m, 1, [0, 3], 1, 4, 16, 24, *tabs)
-            assert out.shape == (1, 3, 4, 16, 24) and out.dtype == torch.float32 and out.device.type == "meta"
+        out = t.frames_from_yuv(*args, m, 1, [0, 3], 1, 4, 16, 24, *tabs(rw.value), *tabs(rh.value))
+        assert out.shape == (1, 3, 4, 16, 24) and out.dtype == torch.float32 and out.device.type == "meta"
+        for tables in ((None,) * 4, tabs(4) * 2):             # a resize without its tables: refused as on the CUDA key
+            with pytest.raises(RuntimeError, match="tables of"):
+                t.frames_from_yuv(*args, m, 1, [0, 3], 1, 4, 16, 24, *tables)
+    y, cc = torch.empty(2, 16, 24, dtype=torch.uint8, device="meta"), torch.empty(2, 8, 12, 2, dtype=torch.uint8, device="meta")
+    for tables in ((None,) * 4, tabs(4) * 2):                 # images of the frame size keep it: the tables are not looked at
+        out = t.frames_from_yuv(y, cc, None, 2, m, 1, [0, 3], 1, 4, 16, 24, *tables)
+        assert out.shape == (1, 3, 4, 16, 24) and out.dtype == torch.float32 and out.device.type == "meta"
     with pytest.raises((RuntimeError, NotImplementedError)):                      # no CPU kernel is registered: no fallback
         t.frames_from_yuv(torch.zeros(1, 4, 6, dtype=torch.uint8), torch.zeros(1, 2, 3, 2, dtype=torch.uint8), None, 2, m, 1, [0], 1, 1,
                           16, 24, None, None, None, None)

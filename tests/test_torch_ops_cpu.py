@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from tooncrafter_amd import _lib
+from torch_ops_cases import FAMILIES, malformed_requests
 
 
 @pytest.fixture(scope="module")
@@ -65,6 +66,24 @@ def test_meta_kernels_infer_shapes(t):
     lat = torch.empty(1, 4, 16, 40, 64, **f32)
     xp, x0 = t.ddim_step(lat, lat, lat, lat, None, 7.5, 7.5, 0.7, 0.6, 0.8, 0.7, 0.5, 0.3, 0.98)
     assert xp.shape == lat.shape and x0.shape == lat.shape
+
+
+def test_every_cuda_operator_has_a_meta_kernel(t):
+    """The operators are named once and registered under both keys, so what has a CUDA kernel has a Meta kernel."""
+    names = sorted(r.split("/")[0] for r in torch._C._dispatch_get_registrations_for_dispatch_key("CUDA")
+                   if r.startswith("tooncrafter::"))
+    assert len(names) == 31 and len(set(names)) == 31, names
+    for name in names:
+        assert torch._C._dispatch_has_kernel_for_dispatch_key(name, "Meta"), name
+
+
+@pytest.mark.parametrize("family", FAMILIES)
+def test_meta_key_refuses_what_the_cuda_key_refuses(t, family):
+    """One malformed request per operator family (torch_ops_cases.py): the Meta key runs the CUDA key's checks, so shape
+    inference raises where the first launch would.  tests/test_gpu_torch_ops.py compares the two keys' sentences."""
+    name, args = malformed_requests("meta")[family]
+    with pytest.raises(RuntimeError):
+        getattr(t, name)(*args)
 
 
 def test_cpu_tensors_are_refused(t):

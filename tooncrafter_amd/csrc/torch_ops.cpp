@@ -5,18 +5,23 @@
 //   torch.ops.tooncrafter.gemm / quant_mxfp8 / gemm_mx / attention / attention_temporal(_rel) / groupnorm(_pf) / layernorm(_pf) / ddim_step(_eps) / ddim_step_ms(_eps) / ddim_blend /
 //   frames_from_u8 / frames_from_yuv / frames_to_u8 / frames_to_yuv / colour_stats / colour_match / colour_hist / colour_transfer / colour_match_knots / colour_transfer_knots / clip_patches / randn_clips /
 //   ff_geglu_fused / temporal_attn_fused / temporal_qkv_attn / attention_q8
-// with (i) a CUDA(HIP)-key implementation that validates the tensors, allocates the result from the caching allocator,
-// picks up the CURRENT stream and calls the same extern "C" entry point the ctypes binding calls, and (ii) a Meta-key
-// implementation (shape / dtype inference only) so the ops can be traced, exported and shape-checked without a GPU.
+// Every operator is ONE function, registered under the CUDA(HIP) key and the Meta key alike (register_ops below).  In order, it
+//   1. runs every check that needs only sizes, strides, dtypes, devices and host scalars (pure host calls of the C ABI included),
+//   2. allocates its result(s) from the options of its first tensor: the caching allocator on the device, a meta tensor on Meta,
+//   3. returns here if that tensor is meta: shape / dtype inference, so the ops trace, export and shape-check without a GPU and the
+//      Meta key refuses, in the same words, exactly what the CUDA key refuses,
+//   4. marshals the pointers, runs the checks that need a pointer or ask the library (alignment, tc_gemm_ws_eligible, tc_*_workspace),
+//      picks up the CURRENT stream and calls the same extern "C" entry point the ctypes binding calls.
 // Host C++ only: the kernels live in libtooncrafter_hip.so, which this library links.
-// Built by tooncrafter_amd/build.py (build_torch_ops) with the host compiler; selected with TC_BINDING=torch
-// (tooncrafter_amd/torch_ops.py).  The ctypes binding stays the default: DESIGN.md section 1 measures the two
-// launch paths as equivalent at these shapes.
+// Built by tooncrafter_amd/build.py (build_torch_ops) with the host compiler.  This is the default binding
+// (tooncrafter_amd/torch_ops.py; TC_BINDING=ctypes selects the other): DESIGN.md section 1 measures the two launch paths as
+// equivalent at these shapes.
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
 
 #include <cmath>
+#include <string>
 #include <tuple>
 #include <type_traits>
 #include <vector>
@@ -36,82 +41,116 @@ void check_rc(int rc, const char* what) {
 }
 
 const tc_bf16* bf(const Tensor& t) { return reinterpret_cast<const tc_bf16*>(t.data_ptr()); }
+float* f32_or_null(const optional<Tensor>& t) { return t.has_value() ? t->data_ptr<float>() : nullptr; }
 
 // stream-ordered scratch of nbytes on the device of `like`: never empty, so that its pointer is one
 Tensor workspace(int64_t nbytes, const Tensor& like) {
   return at::empty({nbytes > 16 ? nbytes : 16}, like.options().dtype(at::kByte));
 }
 
-void check_rows(const Tensor& t, const char* name, at::ScalarType dt = at::kBFloat16) {
-  TORCH_CHECK(t.is_cuda(), name, ": expected a CUDA tensor (the product path is GPU-only)");
-  TORCH_CHECK(t.dim() == 2 && t.stride(1) == 1 && t.scalar_type() == dt, name,
-              ": expected a 2-D rows tensor with unit column stride and dtype ", dt);
+// "ask for the workspace bytes, allocate, set the pointer, launch, check" for a params struct that carries its workspace
+template <typename P>
+void launch_ws(P& p, const Tensor& like, int64_t (*bytes)(const P*), int (*entry)(const P*, void*), const char* what) {
+  p.workspace_bytes = bytes(&p);
+  Tensor ws = workspace(p.workspace_bytes, like);
+  p.workspace = ws.data_ptr();
+  check_rc(entry(&p, cur_stream()), what);
 }
+
+// The device rule of every operator: a tensor is on the device of the operator's first tensor, and that device is CUDA, or meta for
+// shape inference.  (The dispatcher refuses CPU tensors alone; one CPU tensor among CUDA ones reaches the CUDA key.)
+bool on_device(const Tensor& t, const Tensor& first) { return t.device() == first.device() && (first.is_cuda() || first.is_meta()); }
+
+// The one "on the device, of dtype dt, with this layout" statement; an absent optional tensor fits.
+enum Layout { kRows, kDense };   // 2-D with unit column stride (column slices of a wider tensor do) / contiguous
+bool fits1(const Tensor& t, const Tensor& first, at::ScalarType dt, Layout lay) {
+  return on_device(t, first) && t.scalar_type() == dt && (lay == kRows ? t.dim() == 2 && t.stride(1) == 1 : t.is_contiguous());
+}
+bool fits1(const optional<Tensor>& t, const Tensor& first, at::ScalarType dt, Layout lay) {
+  return !t.has_value() || fits1(*t, first, dt, lay);
+}
+template <typename... T>
+bool fits(const Tensor& first, at::ScalarType dt, Layout lay, const T&... ts) { return (fits1(ts, first, dt, lay) && ...); }
+
+void check_fits(const Tensor& t, const Tensor& first, const char* name, at::ScalarType dt = at::kBFloat16, Layout lay = kRows) {
+  TORCH_CHECK(on_device(t, first), name, ": expected a CUDA tensor (the product path is GPU-only)");
+  TORCH_CHECK(fits(first, dt, lay, t), name,
+              lay == kRows ? ": expected a 2-D rows tensor with unit column stride and dtype " : ": expected a contiguous CUDA tensor of dtype ", dt);
+}
+
+// rows [m, c] in, rows [m, c] out: a packed result whatever the row stride of x (empty_like would keep it)
+Tensor rows_like(const Tensor& x) { return at::empty({x.size(0), x.size(1)}, x.options()); }
 
 // conv = [] (linear) or [kind (1 = 3x3, 2 = t3), cin, frames, t_len, h_in, w_in, h_out, w_out, stride, upsample, pad]
 struct GemmGeom { int64_t m, n, n_out, k; };
-GemmGeom gemm_geom(const Tensor& a, const Tensor& w, int64_t act, at::IntArrayRef conv) {
+
+// every check of a GEMM request but those of a and w themselves (their dtype differs between the bf16 and the MXFP8 op), which
+// come first: the geometry is read off their two dimensions
+GemmGeom gemm_request(const Tensor& a, const Tensor& w, const optional<Tensor>& bias, const optional<Tensor>& residual,
+                      const optional<Tensor>& row_bias, int64_t row_div, int64_t act, at::IntArrayRef conv) {
+  TORCH_CHECK(conv.empty() || conv.size() == 11, "gemm: conv must be empty or 11 integers");
   GemmGeom g;
   g.n = w.size(0);
   g.k = w.size(1);
   g.n_out = act == TC_ACT_GEGLU ? g.n / 2 : g.n;
   g.m = conv.empty() ? a.size(0) : conv[2] * conv[6] * conv[7];
+  TORCH_CHECK(fits(a, at::kFloat, kDense, bias) && (!bias.has_value() || bias->numel() == g.n), "gemm: bias must be a contiguous fp32 CUDA [N]");
+  if (row_bias.has_value()) {
+    check_fits(*row_bias, a, "gemm: row_bias", at::kFloat);
+    TORCH_CHECK(row_div > 0 && row_bias->size(1) == g.n && row_bias->size(0) * row_div >= g.m, "gemm: row_bias / row_div do not cover M");
+  }
+  if (residual.has_value()) {
+    check_fits(*residual, a, "gemm: residual");
+    TORCH_CHECK(residual->size(1) == g.n_out && residual->size(0) >= g.m, "gemm: residual shape mismatch");
+  }
+  TORCH_CHECK(!conv.empty() || a.size(1) >= g.k, "gemm: A has fewer columns than the weight's K");
+  TORCH_CHECK(conv.empty() || (a.size(0) >= conv[2] * conv[4] * conv[5] && a.size(1) >= conv[1]), "gemm: conv source too small for its geometry");
   return g;
 }
 
 // fills everything of TcGemmParams except a / w / lda / ldw (operand dtype differs between the bf16 and MXFP8 ops)
-void fill_gemm(TcGemmParams& p, const Tensor& a, const GemmGeom& g, Tensor& out, const optional<Tensor>& bias,
-               const optional<Tensor>& residual, const optional<Tensor>& row_bias, int64_t row_div, int64_t act, double alpha,
-               double out_scale, bool out_f32, at::IntArrayRef conv) {
-  TORCH_CHECK(conv.empty() || conv.size() == 11, "gemm: conv must be empty or 11 integers");
+void fill_gemm(TcGemmParams& p, const GemmGeom& g, Tensor& out, const optional<Tensor>& bias, const optional<Tensor>& residual,
+               const optional<Tensor>& row_bias, int64_t row_div, int64_t act, double alpha, double out_scale, bool out_f32,
+               at::IntArrayRef conv) {
   p.c = out.data_ptr();
   p.m = (int32_t)g.m; p.n = (int32_t)g.n; p.k = (int32_t)g.k;
   p.ldc = (int32_t)out.stride(0);
   p.alpha = (float)alpha; p.out_scale = (float)out_scale; p.act = (int32_t)act; p.out_f32 = out_f32 ? 1 : 0;
   p.batch = 1;
-  if (bias.has_value()) {
-    TORCH_CHECK(bias->is_cuda() && bias->scalar_type() == at::kFloat && bias->is_contiguous() && bias->numel() == g.n,
-                "gemm: bias must be a contiguous fp32 CUDA [N]");
-    p.bias = bias->data_ptr<float>();
-  }
+  if (bias.has_value()) p.bias = bias->data_ptr<float>();
   if (row_bias.has_value()) {
-    check_rows(*row_bias, "gemm: row_bias", at::kFloat);
-    TORCH_CHECK(row_div > 0 && row_bias->size(1) == g.n && row_bias->size(0) * row_div >= g.m, "gemm: row_bias / row_div do not cover M");
     p.row_bias = row_bias->data_ptr<float>(); p.ldrb = (int32_t)row_bias->stride(0); p.row_div = (int32_t)row_div;
   }
   if (residual.has_value()) {
-    check_rows(*residual, "gemm: residual");
-    TORCH_CHECK(residual->size(1) == g.n_out && residual->size(0) >= g.m, "gemm: residual shape mismatch");
     p.residual = bf(*residual); p.ldr = (int32_t)residual->stride(0);
   }
   if (conv.empty()) {
     p.gather = TC_GATHER_LINEAR;
-    TORCH_CHECK(a.size(1) >= g.k, "gemm: A has fewer columns than the weight's K");
   } else {
     p.gather = conv[0] == 1 ? TC_GATHER_CONV3x3 : TC_GATHER_CONVT3;
     p.cin = (int32_t)conv[1]; p.frames = (int32_t)conv[2]; p.t_len = (int32_t)conv[3];
     p.h_in = (int32_t)conv[4]; p.w_in = (int32_t)conv[5]; p.h_out = (int32_t)conv[6]; p.w_out = (int32_t)conv[7];
     p.stride = (int32_t)conv[8]; p.upsample = (int32_t)conv[9]; p.pad = (int32_t)conv[10];
-    TORCH_CHECK(a.size(0) >= (int64_t)p.frames * p.h_in * p.w_in && a.size(1) >= p.cin, "gemm: conv source too small for its geometry");
   }
 }
 
-Tensor gemm_cuda(const Tensor& a, const Tensor& w, const optional<Tensor>& bias, const optional<Tensor>& residual,
-                 const optional<Tensor>& row_bias, int64_t row_div, int64_t act, double alpha, double out_scale,
-                 bool out_f32, at::IntArrayRef conv, double a_norm_eps) {
-  check_rows(a, "gemm: a");
-  check_rows(w, "gemm: w");
-  const GemmGeom g = gemm_geom(a, w, act, conv);
+Tensor gemm(const Tensor& a, const Tensor& w, const optional<Tensor>& bias, const optional<Tensor>& residual,
+            const optional<Tensor>& row_bias, int64_t row_div, int64_t act, double alpha, double out_scale, bool out_f32,
+            at::IntArrayRef conv, double a_norm_eps) {
+  check_fits(a, a, "gemm: a");
+  check_fits(w, a, "gemm: w");
+  const GemmGeom g = gemm_request(a, w, bias, residual, row_bias, row_div, act, conv);
   Tensor out = at::empty({g.m, g.n_out}, a.options().dtype(out_f32 ? at::kFloat : at::kBFloat16));
+  if (a.is_meta()) return out;
   TcGemmParams p = {};
   p.a = bf(a); p.w = bf(w);
   p.lda = (int32_t)a.stride(0); p.ldw = (int32_t)w.stride(0);
-  fill_gemm(p, a, g, out, bias, residual, row_bias, row_div, act, alpha, out_scale, out_f32, conv);
+  fill_gemm(p, g, out, bias, residual, row_bias, row_div, act, alpha, out_scale, out_f32, conv);
   if (a_norm_eps >= 0.0) {                 // ABI 8: LayerNorm of the A rows as a prologue (affine part folded into w / bias)
     p.a_norm = 1; p.a_norm_eps = (float)a_norm_eps;
     TORCH_CHECK(tc_gemm_ws_eligible(&p) == 1, "gemm: a_norm_eps needs a problem the weight-stationary kernel takes");
   }
-  Tensor ws;
+  Tensor ws;                               // only where the route asks for one: a null workspace otherwise, as through ctypes
   const int64_t nbytes = tc_gemm_workspace(&p);
   if (nbytes > 0) {
     ws = at::empty({nbytes}, a.options().dtype(at::kByte));
@@ -122,73 +161,69 @@ Tensor gemm_cuda(const Tensor& a, const Tensor& w, const optional<Tensor>& bias,
 }
 
 // MXFP8 pair (ABI 7, BASELINE.json configs[4]): bf16 rows -> (e4m3 bytes, E8M0 scales); GEMM over such operands
-std::tuple<Tensor, Tensor> quant_mxfp8_cuda(const Tensor& x, int64_t k) {
-  check_rows(x, "quant_mxfp8: x");
+std::tuple<Tensor, Tensor> quant_mxfp8(const Tensor& x, int64_t k) {
+  check_fits(x, x, "quant_mxfp8: x");
   TORCH_CHECK(k > 0 && k % 32 == 0 && x.size(1) >= k, "quant_mxfp8: k must be a multiple of 32 and <= the columns of x");
   const int64_t rows = x.size(0), lds = (k + 127) / 128 * 4;
   Tensor q = at::empty({rows, k}, x.options().dtype(at::kByte));
   Tensor s = at::empty({rows, lds}, x.options().dtype(at::kByte));
+  if (x.is_meta()) return {q, s};
   check_rc(tc_quant_mxfp8(bf(x), rows, (int32_t)k, (int32_t)x.stride(0), q.data_ptr<uint8_t>(), (int32_t)q.stride(0),
                           s.data_ptr<uint8_t>(), (int32_t)lds, cur_stream()), "tc_quant_mxfp8");
   return {q, s};
 }
 
-std::tuple<Tensor, Tensor> quant_mxfp8_meta(const Tensor& x, int64_t k) {
-  return {at::empty({x.size(0), k}, x.options().dtype(at::kByte)),
-          at::empty({x.size(0), (k + 127) / 128 * 4}, x.options().dtype(at::kByte))};
-}
-
-Tensor gemm_mx_cuda(const Tensor& aq, const Tensor& a_scale, const Tensor& wq, const Tensor& w_scale, const optional<Tensor>& bias,
-                    const optional<Tensor>& residual, const optional<Tensor>& row_bias, int64_t row_div, int64_t act,
-                    double alpha, double out_scale, bool out_f32, at::IntArrayRef conv) {
-  check_rows(aq, "gemm_mx: a", at::kByte); check_rows(wq, "gemm_mx: w", at::kByte);
-  check_rows(a_scale, "gemm_mx: a_scale", at::kByte); check_rows(w_scale, "gemm_mx: w_scale", at::kByte);
+Tensor gemm_mx(const Tensor& aq, const Tensor& a_scale, const Tensor& wq, const Tensor& w_scale, const optional<Tensor>& bias,
+               const optional<Tensor>& residual, const optional<Tensor>& row_bias, int64_t row_div, int64_t act, double alpha,
+               double out_scale, bool out_f32, at::IntArrayRef conv) {
+  check_fits(aq, aq, "gemm_mx: a", at::kByte); check_fits(wq, aq, "gemm_mx: w", at::kByte);
+  check_fits(a_scale, aq, "gemm_mx: a_scale", at::kByte); check_fits(w_scale, aq, "gemm_mx: w_scale", at::kByte);
   TORCH_CHECK(a_scale.size(0) == aq.size(0) && w_scale.size(0) == wq.size(0), "gemm_mx: one scale row per operand row");
-  const GemmGeom g = gemm_geom(aq, wq, act, conv);
+  const GemmGeom g = gemm_request(aq, wq, bias, residual, row_bias, row_div, act, conv);
   Tensor out = at::empty({g.m, g.n_out}, aq.options().dtype(out_f32 ? at::kFloat : at::kBFloat16));
+  if (aq.is_meta()) return out;
   TcGemmMxParams px = {};
-  px.g.a = reinterpret_cast<const tc_bf16*>(aq.data_ptr()); px.g.w = reinterpret_cast<const tc_bf16*>(wq.data_ptr());
+  px.g.a = bf(aq); px.g.w = bf(wq);
   px.g.lda = (int32_t)aq.stride(0); px.g.ldw = (int32_t)wq.stride(0);
-  fill_gemm(px.g, aq, g, out, bias, residual, row_bias, row_div, act, alpha, out_scale, out_f32, conv);
+  fill_gemm(px.g, g, out, bias, residual, row_bias, row_div, act, alpha, out_scale, out_f32, conv);
   px.a_scale = a_scale.data_ptr<uint8_t>(); px.lda_s = (int32_t)a_scale.stride(0);
   px.w_scale = w_scale.data_ptr<uint8_t>(); px.ldw_s = (int32_t)w_scale.stride(0);
   check_rc(tc_gemm_mxfp8(&px, cur_stream()), "tc_gemm_mxfp8");
   return out;
 }
 
-Tensor gemm_mx_meta(const Tensor& aq, const Tensor&, const Tensor& wq, const Tensor&, const optional<Tensor>&, const optional<Tensor>&,
-                    const optional<Tensor>&, int64_t, int64_t act, double, double, bool out_f32, at::IntArrayRef conv) {
-  const GemmGeom g = gemm_geom(aq, wq, act, conv);
-  return at::empty({g.m, g.n_out}, aq.options().dtype(out_f32 ? at::kFloat : at::kBFloat16));
-}
-
-Tensor gemm_meta(const Tensor& a, const Tensor& w, const optional<Tensor>&, const optional<Tensor>&, const optional<Tensor>&,
-                 int64_t, int64_t act, double, double, bool out_f32, at::IntArrayRef conv, double) {
-  const GemmGeom g = gemm_geom(a, w, act, conv);
-  return at::empty({g.m, g.n_out}, a.options().dtype(out_f32 ? at::kFloat : at::kBFloat16));
-}
-
-Tensor attention_cuda(const Tensor& q, const Tensor& k, const Tensor& v, int64_t batch, int64_t heads, int64_t lq, int64_t lk,
-                      int64_t kv_bdiv, double scale, const optional<Tensor>& k2, const optional<Tensor>& v2, int64_t lk2,
-                      int64_t kv2_bdiv) {
-  check_rows(q, "attention: q"); check_rows(k, "attention: k"); check_rows(v, "attention: v");
-  const int64_t hd = heads * 64;
-  TORCH_CHECK(q.size(0) == batch * lq && q.size(1) == hd && k.size(1) == hd && v.size(1) == hd, "attention: head layout mismatch");
-  const int64_t kvb = (batch + kv_bdiv - 1) / kv_bdiv;
-  TORCH_CHECK(k.size(0) == kvb * lk && v.size(0) == kvb * lk, "attention: K/V rows != kv_batches * lk");
-  Tensor out = at::empty({batch * lq, hd}, q.options());
-  TcAttnParams p = {};
+// what TcAttnParams and TcAttnQ8Params share: the q / k / v / o pointers with their row and batch strides, the problem, the scale
+template <typename P>
+void attn_fill(P& p, const Tensor& q, const Tensor& k, const Tensor& v, Tensor& out, int64_t batch, int64_t heads, int64_t lq,
+               int64_t lk, double scale) {
   p.q = bf(q); p.k = bf(k); p.v = bf(v); p.o = reinterpret_cast<tc_bf16*>(out.data_ptr());
   p.batch = (int32_t)batch; p.heads = (int32_t)heads; p.lq = (int32_t)lq; p.lk = (int32_t)lk;
   p.q_ss = (int32_t)q.stride(0); p.k_ss = (int32_t)k.stride(0); p.v_ss = (int32_t)v.stride(0); p.o_ss = (int32_t)out.stride(0);
   p.q_sb = lq * q.stride(0); p.k_sb = lk * k.stride(0); p.v_sb = lk * v.stride(0); p.o_sb = lq * out.stride(0);
-  p.kv_bdiv = (int32_t)kv_bdiv; p.scale = (float)scale;
+  p.scale = (float)scale;
+}
+
+Tensor attention(const Tensor& q, const Tensor& k, const Tensor& v, int64_t batch, int64_t heads, int64_t lq, int64_t lk,
+                 int64_t kv_bdiv, double scale, const optional<Tensor>& k2, const optional<Tensor>& v2, int64_t lk2, int64_t kv2_bdiv) {
+  check_fits(q, q, "attention: q"); check_fits(k, q, "attention: k"); check_fits(v, q, "attention: v");
+  const int64_t hd = heads * 64;
+  TORCH_CHECK(q.size(0) == batch * lq && q.size(1) == hd && k.size(1) == hd && v.size(1) == hd, "attention: head layout mismatch");
+  TORCH_CHECK(kv_bdiv > 0, "attention: kv_bdiv ", kv_bdiv);
+  const int64_t kvb = (batch + kv_bdiv - 1) / kv_bdiv;
+  TORCH_CHECK(k.size(0) == kvb * lk && v.size(0) == kvb * lk, "attention: K/V rows != kv_batches * lk");
   if (k2.has_value()) {
     TORCH_CHECK(v2.has_value() && lk2 > 0 && kv2_bdiv > 0, "attention: second K/V set incomplete");
-    check_rows(*k2, "attention: k2"); check_rows(*v2, "attention: v2");
+    check_fits(*k2, q, "attention: k2"); check_fits(*v2, q, "attention: v2");
     const int64_t kvb2 = (batch + kv2_bdiv - 1) / kv2_bdiv;
     TORCH_CHECK(k2->size(0) == kvb2 * lk2 && v2->size(0) == kvb2 * lk2 && k2->size(1) == hd && v2->size(1) == hd,
                 "attention: second K/V set must be [(batch / kv2_bdiv) * lk2, heads * 64]");
+  }
+  Tensor out = at::empty({batch * lq, hd}, q.options());
+  if (q.is_meta()) return out;
+  TcAttnParams p = {};
+  attn_fill(p, q, k, v, out, batch, heads, lq, lk, scale);
+  p.kv_bdiv = (int32_t)kv_bdiv;
+  if (k2.has_value()) {
     p.k2 = bf(*k2); p.v2 = bf(*v2); p.lk2 = (int32_t)lk2; p.kv2_bdiv = (int32_t)kv2_bdiv;
     p.k2_ss = (int32_t)k2->stride(0); p.v2_ss = (int32_t)v2->stride(0);
     p.k2_sb = lk2 * k2->stride(0); p.v2_sb = lk2 * v2->stride(0);
@@ -197,66 +232,52 @@ Tensor attention_cuda(const Tensor& q, const Tensor& k, const Tensor& v, int64_t
   return out;
 }
 
-Tensor attention_meta(const Tensor& q, const Tensor&, const Tensor&, int64_t batch, int64_t heads, int64_t lq, int64_t, int64_t,
-                      double, const optional<Tensor>&, const optional<Tensor>&, int64_t, int64_t) {
-  return at::empty({batch * lq, heads * 64}, q.options());
-}
-
 // ABI 14: the 8-bit self-attention -- K / V quantised into a workspace from the caching allocator, then the attention
-Tensor attention_q8_cuda(const Tensor& q, const Tensor& k, const Tensor& v, int64_t batch, int64_t heads, int64_t lq, int64_t lk,
-                         double scale) {
-  check_rows(q, "attention_q8: q"); check_rows(k, "attention_q8: k"); check_rows(v, "attention_q8: v");
+Tensor attention_q8(const Tensor& q, const Tensor& k, const Tensor& v, int64_t batch, int64_t heads, int64_t lq, int64_t lk,
+                    double scale) {
+  check_fits(q, q, "attention_q8: q"); check_fits(k, q, "attention_q8: k"); check_fits(v, q, "attention_q8: v");
   const int64_t hd = heads * 64;
   TORCH_CHECK(q.size(0) == batch * lq && q.size(1) == hd && k.size(0) == batch * lk && k.size(1) == hd &&
               v.size(0) == batch * lk && v.size(1) == hd,
               "attention_q8: q must be [batch*lq, heads*64], k and v [batch*lk, heads*64]");
   Tensor out = at::empty({batch * lq, hd}, q.options());
+  if (q.is_meta()) return out;
   TcAttnQ8Params p = {};
-  p.q = bf(q); p.k = bf(k); p.v = bf(v); p.o = reinterpret_cast<tc_bf16*>(out.data_ptr());
-  p.batch = (int32_t)batch; p.heads = (int32_t)heads; p.lq = (int32_t)lq; p.lk = (int32_t)lk;
-  p.q_ss = (int32_t)q.stride(0); p.k_ss = (int32_t)k.stride(0); p.v_ss = (int32_t)v.stride(0); p.o_ss = (int32_t)out.stride(0);
-  p.q_sb = lq * q.stride(0); p.k_sb = lk * k.stride(0); p.v_sb = lk * v.stride(0); p.o_sb = lq * out.stride(0);
-  p.scale = (float)scale;
+  attn_fill(p, q, k, v, out, batch, heads, lq, lk, scale);
   const int64_t nbytes = tc_attn_q8_workspace(&p);
-  Tensor ws = workspace(nbytes, q);
+  Tensor ws = workspace(nbytes, q);        // two launches share it, so not launch_ws
   p.workspace = ws.data_ptr(); p.workspace_bytes = ws.numel();
   check_rc(tc_attn_q8_quant_kv(&p, cur_stream()), "tc_attn_q8_quant_kv");
   check_rc(tc_attn_d64_q8(&p, cur_stream()), "tc_attn_d64_q8");
   return out;
 }
 
-Tensor attention_q8_meta(const Tensor& q, const Tensor&, const Tensor&, int64_t batch, int64_t heads, int64_t lq, int64_t, double) {
-  return at::empty({batch * lq, heads * 64}, q.options());
-}
-
-Tensor attention_temporal_cuda(const Tensor& qkv, int64_t b, int64_t t, int64_t hw, int64_t heads, double scale) {
-  check_rows(qkv, "attention_temporal: qkv");
+Tensor attention_temporal(const Tensor& qkv, int64_t b, int64_t t, int64_t hw, int64_t heads, double scale) {
+  check_fits(qkv, qkv, "attention_temporal: qkv");
   TORCH_CHECK(qkv.is_contiguous() && qkv.size(0) == b * t * hw && qkv.size(1) == 3 * heads * 64,
               "attention_temporal: qkv must be contiguous [b*t*hw, 3*heads*64]");
   Tensor out = at::empty({b * t * hw, heads * 64}, qkv.options());
+  if (qkv.is_meta()) return out;
   check_rc(tc_attn_temporal(bf(qkv), reinterpret_cast<tc_bf16*>(out.data_ptr()), (int32_t)b, (int32_t)t, (int32_t)hw,
                             (int32_t)heads, (float)scale, cur_stream()), "tc_attn_temporal");
   return out;
 }
 
-Tensor attention_temporal_meta(const Tensor& qkv, int64_t b, int64_t t, int64_t hw, int64_t heads, double) {
-  return at::empty({b * t * hw, heads * 64}, qkv.options());
-}
-
 // tc_attn_temporal_rel: relative position and / or a causal mask on the temporal attention (reference attention.py:20-39,
 // 103-124, 343-345, 376-390).  rel_k / rel_v: [2*max_rel + 1, 64] bf16, or both absent.
-Tensor attention_temporal_rel_cuda(const Tensor& qkv, const optional<Tensor>& rel_k, const optional<Tensor>& rel_v, int64_t b,
-                                   int64_t t, int64_t hw, int64_t heads, int64_t max_rel, bool causal, double scale) {
-  check_rows(qkv, "attention_temporal_rel: qkv");
+Tensor attention_temporal_rel(const Tensor& qkv, const optional<Tensor>& rel_k, const optional<Tensor>& rel_v, int64_t b, int64_t t,
+                              int64_t hw, int64_t heads, int64_t max_rel, bool causal, double scale) {
+  check_fits(qkv, qkv, "attention_temporal_rel: qkv");
   TORCH_CHECK(qkv.is_contiguous() && qkv.size(0) == b * t * hw && qkv.size(1) == 3 * heads * 64,
               "attention_temporal_rel: qkv must be contiguous [b*t*hw, 3*heads*64]");
   for (const optional<Tensor>* tab : {&rel_k, &rel_v})
     if (tab->has_value()) {
-      check_rows(**tab, "attention_temporal_rel: table");
+      check_fits(**tab, qkv, "attention_temporal_rel: table");
       TORCH_CHECK((*tab)->is_contiguous() && (*tab)->size(0) == 2 * max_rel + 1 && (*tab)->size(1) == 64,
                   "attention_temporal_rel: a table must be contiguous [2*max_rel + 1, 64]");
     }
   Tensor out = at::empty({b * t * hw, heads * 64}, qkv.options());
+  if (qkv.is_meta()) return out;
   TcAttnTemporalRelParams p{};
   p.qkv = bf(qkv);
   p.out = reinterpret_cast<tc_bf16*>(out.data_ptr());
@@ -269,22 +290,16 @@ Tensor attention_temporal_rel_cuda(const Tensor& qkv, const optional<Tensor>& re
   return out;
 }
 
-Tensor attention_temporal_rel_meta(const Tensor& qkv, const optional<Tensor>&, const optional<Tensor>&, int64_t b, int64_t t,
-                                   int64_t hw, int64_t heads, int64_t, bool, double) {
-  return at::empty({b * t * hw, heads * 64}, qkv.options());
-}
-
-void check_affine(const Tensor& g, const Tensor& b, int64_t c, const char* what) {
-  TORCH_CHECK(g.is_cuda() && b.is_cuda() && g.scalar_type() == at::kFloat && b.scalar_type() == at::kFloat &&
-              g.is_contiguous() && b.is_contiguous() && g.numel() == c && b.numel() == c, what, ": gamma / beta must be contiguous fp32 CUDA [C]");
-}
-
-// ABI 12: the consumer's weights (read-only CUDA tensors, contiguous) as a prefetch list for the norm's extra blocks
-TcPrefetch prefetch_of(at::TensorList ts, const char* what) {
+// ABI 12: the consumer's weights (read-only tensors on the device, contiguous) as a prefetch list for the norm's extra blocks
+void prefetch_check(at::TensorList ts, const Tensor& first, const char* what) {
   TORCH_CHECK((int64_t)ts.size() <= TC_PREFETCH_MAX, what, ": at most ", TC_PREFETCH_MAX, " prefetch tensors");
+  for (const Tensor& t : ts)
+    TORCH_CHECK(on_device(t, first) && t.is_contiguous(), what, ": prefetch tensors must be contiguous CUDA tensors");
+}
+
+TcPrefetch prefetch_of(at::TensorList ts) {
   TcPrefetch pf = {};
   for (const Tensor& t : ts) {
-    TORCH_CHECK(t.is_cuda() && t.is_contiguous(), what, ": prefetch tensors must be contiguous CUDA tensors");
     pf.ptr[pf.n] = t.data_ptr();
     pf.bytes[pf.n] = (int64_t)t.numel() * (int64_t)t.element_size();
     ++pf.n;
@@ -292,14 +307,17 @@ TcPrefetch prefetch_of(at::TensorList ts, const char* what) {
   return pf;
 }
 
-Tensor groupnorm_pf_cuda(const Tensor& x, const Tensor& gamma, const Tensor& beta, int64_t samples, int64_t rows, double eps, bool silu,
-                         at::TensorList prefetch) {
-  check_rows(x, "groupnorm_pf: x");
+Tensor groupnorm_pf(const Tensor& x, const Tensor& gamma, const Tensor& beta, int64_t samples, int64_t rows, double eps, bool silu,
+                    at::TensorList prefetch) {
+  check_fits(x, x, "groupnorm_pf: x");
   const int64_t c = x.size(1);
   TORCH_CHECK(x.is_contiguous() && x.size(0) == samples * rows, "groupnorm_pf: x must be contiguous [samples*rows, C]");
-  check_affine(gamma, beta, c, "groupnorm_pf");
-  const TcPrefetch pf = prefetch_of(prefetch, "groupnorm_pf");
+  TORCH_CHECK(fits(x, at::kFloat, kDense, gamma, beta) && gamma.numel() == c && beta.numel() == c,
+              "groupnorm_pf: gamma / beta must be contiguous fp32 CUDA [C]");
+  prefetch_check(prefetch, x, "groupnorm_pf");
   Tensor y = at::empty_like(x);
+  if (x.is_meta()) return y;
+  const TcPrefetch pf = prefetch_of(prefetch);
   const int64_t nbytes = tc_groupnorm_workspace((int32_t)samples, (int32_t)rows, (int32_t)c);
   Tensor ws = workspace(nbytes, x);
   check_rc(tc_groupnorm_pf(bf(x), reinterpret_cast<tc_bf16*>(y.data_ptr()), gamma.data_ptr<float>(), beta.data_ptr<float>(),
@@ -308,51 +326,43 @@ Tensor groupnorm_pf_cuda(const Tensor& x, const Tensor& gamma, const Tensor& bet
   return y;
 }
 
-Tensor layernorm_pf_cuda(const Tensor& x, const Tensor& gamma, const Tensor& beta, double eps, at::TensorList prefetch) {
-  check_rows(x, "layernorm_pf: x");
+Tensor layernorm_pf(const Tensor& x, const Tensor& gamma, const Tensor& beta, double eps, at::TensorList prefetch) {
+  check_fits(x, x, "layernorm_pf: x");
+  const int64_t c = x.size(1);
   TORCH_CHECK(x.is_contiguous(), "layernorm_pf: x must be contiguous");
-  check_affine(gamma, beta, x.size(1), "layernorm_pf");
-  const TcPrefetch pf = prefetch_of(prefetch, "layernorm_pf");
+  TORCH_CHECK(fits(x, at::kFloat, kDense, gamma, beta) && gamma.numel() == c && beta.numel() == c,
+              "layernorm_pf: gamma / beta must be contiguous fp32 CUDA [C]");
+  prefetch_check(prefetch, x, "layernorm_pf");
   Tensor y = at::empty_like(x);
+  if (x.is_meta()) return y;
+  const TcPrefetch pf = prefetch_of(prefetch);
   check_rc(tc_layernorm_pf(bf(x), reinterpret_cast<tc_bf16*>(y.data_ptr()), gamma.data_ptr<float>(), beta.data_ptr<float>(),
-                           (int32_t)x.size(0), (int32_t)x.size(1), (float)eps, &pf, cur_stream()), "tc_layernorm_pf");
+                           (int32_t)x.size(0), (int32_t)c, (float)eps, &pf, cur_stream()), "tc_layernorm_pf");
   return y;
 }
 
 // groupnorm / layernorm are their _pf forms with an empty list: an empty TcPrefetch launches what a NULL one launches
-Tensor groupnorm_cuda(const Tensor& x, const Tensor& gamma, const Tensor& beta, int64_t samples, int64_t rows, double eps, bool silu) {
-  return groupnorm_pf_cuda(x, gamma, beta, samples, rows, eps, silu, {});
+Tensor groupnorm(const Tensor& x, const Tensor& gamma, const Tensor& beta, int64_t samples, int64_t rows, double eps, bool silu) {
+  return groupnorm_pf(x, gamma, beta, samples, rows, eps, silu, {});
 }
 
-Tensor layernorm_cuda(const Tensor& x, const Tensor& gamma, const Tensor& beta, double eps) {
-  return layernorm_pf_cuda(x, gamma, beta, eps, {});
-}
-
-// Meta for every operator whose results all have the shape and dtype of its first argument: the norms (one result) and the
-// DDIM steps (two).  Boxed, so that one function serves schemas with different argument lists.
-void like_first_meta(const c10::OperatorHandle& op, torch::jit::Stack* stack) {
-  const auto& schema = op.schema();
-  const Tensor x = torch::jit::peek(*stack, 0, schema.arguments().size()).toTensor();
-  torch::jit::drop(*stack, schema.arguments().size());
-  for (size_t i = 0; i < schema.returns().size(); ++i) torch::jit::push(*stack, at::empty_like(x));
+Tensor layernorm(const Tensor& x, const Tensor& gamma, const Tensor& beta, double eps) {
+  return layernorm_pf(x, gamma, beta, eps, {});
 }
 
 // ---- the level-0 one-launch operators (ABI 9): LayerNorm + GEGLU feed-forward + residual; LayerNorm + temporal self-attention +
 // residual (lvdm/modules/attention.py:81-144,225-246,415-442).  ln_eps < 0: x is taken as already normalised.
-void check_w(const Tensor& t, at::ScalarType dt, const char* name) {
-  TORCH_CHECK(t.is_cuda() && t.scalar_type() == dt && t.is_contiguous(), name, ": expected a contiguous CUDA tensor of dtype ", dt);
-}
-
-Tensor ff_geglu_fused_cuda(const Tensor& x, const Tensor& w1, const Tensor& b1, const Tensor& w2, const Tensor& b2, double ln_eps) {
-  check_rows(x, "ff_geglu_fused: x");
-  check_w(w1, at::kBFloat16, "ff_geglu_fused: w1"); check_w(w2, at::kBFloat16, "ff_geglu_fused: w2");
-  check_w(b1, at::kFloat, "ff_geglu_fused: b1"); check_w(b2, at::kFloat, "ff_geglu_fused: b2");
+Tensor ff_geglu_fused(const Tensor& x, const Tensor& w1, const Tensor& b1, const Tensor& w2, const Tensor& b2, double ln_eps) {
+  check_fits(x, x, "ff_geglu_fused: x");
+  check_fits(w1, x, "ff_geglu_fused: w1", at::kBFloat16, kDense); check_fits(w2, x, "ff_geglu_fused: w2", at::kBFloat16, kDense);
+  check_fits(b1, x, "ff_geglu_fused: b1", at::kFloat, kDense); check_fits(b2, x, "ff_geglu_fused: b2", at::kFloat, kDense);
   const int64_t m = x.size(0), c = x.size(1);
   TORCH_CHECK(w2.dim() == 2 && w1.dim() == 2, "ff_geglu_fused: w1 [2 hidden, c], w2 [c, hidden]");
   const int64_t hidden = w2.size(1);
   TORCH_CHECK(w1.size(0) == 2 * hidden && w1.size(1) == c && w2.size(0) == c && b1.numel() == 2 * hidden && b2.numel() == c,
               "ff_geglu_fused: x [m, c] rows, w1 [2 hidden, c], b1 [2 hidden], w2 [c, hidden], b2 [c]");
-  Tensor out = at::empty({m, c}, x.options());
+  Tensor out = rows_like(x);
+  if (x.is_meta()) return out;
   TcFfParams p{};
   p.x = bf(x); p.w1 = bf(w1); p.b1 = b1.data_ptr<float>(); p.w2 = bf(w2); p.b2 = b2.data_ptr<float>();
   p.out = reinterpret_cast<tc_bf16*>(out.data_ptr());
@@ -362,20 +372,17 @@ Tensor ff_geglu_fused_cuda(const Tensor& x, const Tensor& w1, const Tensor& b1, 
   return out;
 }
 
-Tensor ff_geglu_fused_meta(const Tensor& x, const Tensor&, const Tensor&, const Tensor&, const Tensor&, double) {
-  return at::empty({x.size(0), x.size(1)}, x.options());
-}
-
-Tensor temporal_attn_fused_cuda(const Tensor& x, const Tensor& wqkv, const Tensor& bqkv, const Tensor& wo, const Tensor& bo, int64_t b,
-                                int64_t t, int64_t hw, int64_t heads, double ln_eps, double scale) {
-  check_rows(x, "temporal_attn_fused: x");
-  check_w(wqkv, at::kBFloat16, "temporal_attn_fused: wqkv"); check_w(wo, at::kBFloat16, "temporal_attn_fused: wo");
-  check_w(bqkv, at::kFloat, "temporal_attn_fused: bqkv"); check_w(bo, at::kFloat, "temporal_attn_fused: bo");
+Tensor temporal_attn_fused(const Tensor& x, const Tensor& wqkv, const Tensor& bqkv, const Tensor& wo, const Tensor& bo, int64_t b,
+                           int64_t t, int64_t hw, int64_t heads, double ln_eps, double scale) {
+  check_fits(x, x, "temporal_attn_fused: x");
+  check_fits(wqkv, x, "temporal_attn_fused: wqkv", at::kBFloat16, kDense); check_fits(wo, x, "temporal_attn_fused: wo", at::kBFloat16, kDense);
+  check_fits(bqkv, x, "temporal_attn_fused: bqkv", at::kFloat, kDense); check_fits(bo, x, "temporal_attn_fused: bo", at::kFloat, kDense);
   const int64_t m = x.size(0), c = x.size(1);
   TORCH_CHECK(m == b * t * hw && wqkv.dim() == 2 && wqkv.size(0) == 3 * c && wqkv.size(1) == c && wo.dim() == 2 && wo.size(0) == c &&
               wo.size(1) == c && bqkv.numel() == 3 * c && bo.numel() == c && c == heads * 64,
               "temporal_attn_fused: x [b*t*hw, c] rows, wqkv [3c, c], bqkv [3c], wo [c, c], bo [c], c = heads * 64");
-  Tensor out = at::empty({m, c}, x.options());
+  Tensor out = rows_like(x);
+  if (x.is_meta()) return out;
   TcTbParams p{};
   p.x = bf(x); p.wqkv = bf(wqkv); p.bqkv = bqkv.data_ptr<float>(); p.wo = bf(wo); p.bo = bo.data_ptr<float>();
   p.out = reinterpret_cast<tc_bf16*>(out.data_ptr());
@@ -386,24 +393,20 @@ Tensor temporal_attn_fused_cuda(const Tensor& x, const Tensor& wqkv, const Tenso
   return out;
 }
 
-Tensor temporal_attn_fused_meta(const Tensor& x, const Tensor&, const Tensor&, const Tensor&, const Tensor&, int64_t, int64_t, int64_t,
-                                int64_t, double, double) {
-  return at::empty({x.size(0), x.size(1)}, x.options());
-}
-
 // ABI 13: the temporal q / k / v projection and its attention as one launch (csrc/qkv_attn.hip; 17 .. 64 frames: csrc/qkv_attn_long.hip -- any t is passed through, the library decides)
-Tensor temporal_qkv_attn_cuda(const Tensor& x, const Tensor& wqkv, const optional<Tensor>& bqkv, int64_t b, int64_t t, int64_t hw,
-                              int64_t heads, double scale) {
-  check_rows(x, "temporal_qkv_attn: x");
-  check_w(wqkv, at::kBFloat16, "temporal_qkv_attn: wqkv");
-  if (bqkv.has_value()) check_w(*bqkv, at::kFloat, "temporal_qkv_attn: bqkv");
+Tensor temporal_qkv_attn(const Tensor& x, const Tensor& wqkv, const optional<Tensor>& bqkv, int64_t b, int64_t t, int64_t hw,
+                         int64_t heads, double scale) {
+  check_fits(x, x, "temporal_qkv_attn: x");
+  check_fits(wqkv, x, "temporal_qkv_attn: wqkv", at::kBFloat16, kDense);
+  if (bqkv.has_value()) check_fits(*bqkv, x, "temporal_qkv_attn: bqkv", at::kFloat, kDense);
   const int64_t m = x.size(0), c = x.size(1);
   TORCH_CHECK(m == b * t * hw && wqkv.dim() == 2 && wqkv.size(0) == 3 * c && wqkv.size(1) == c && c == heads * 64 &&
               (!bqkv.has_value() || bqkv->numel() == 3 * c),
               "temporal_qkv_attn: x [b*t*hw, c] rows, wqkv [3c, c], bqkv [3c] or None, c = heads * 64");
-  Tensor out = at::empty({m, c}, x.options());
+  Tensor out = rows_like(x);
+  if (x.is_meta()) return out;
   TcTqaParams p{};
-  p.x = bf(x); p.wqkv = bf(wqkv); p.bqkv = bqkv.has_value() ? bqkv->data_ptr<float>() : nullptr;
+  p.x = bf(x); p.wqkv = bf(wqkv); p.bqkv = f32_or_null(bqkv);
   p.out = reinterpret_cast<tc_bf16*>(out.data_ptr());
   p.b = (int32_t)b; p.t = (int32_t)t; p.hw = (int32_t)hw; p.c = (int32_t)c; p.heads = (int32_t)heads;
   p.ldx = (int32_t)x.stride(0); p.ldo = (int32_t)c;
@@ -412,56 +415,36 @@ Tensor temporal_qkv_attn_cuda(const Tensor& x, const Tensor& wqkv, const optiona
   return out;
 }
 
-Tensor temporal_qkv_attn_meta(const Tensor& x, const Tensor&, const optional<Tensor>&, int64_t, int64_t, int64_t, int64_t, double) {
-  return at::empty({x.size(0), x.size(1)}, x.options());
-}
-
-// The checked TcDdimParams of a step; x_prev and x0 are its two results.
-TcDdimParams ddim_params(const char* what, const Tensor& x, const Tensor& e_cond, const optional<Tensor>& e_uncond,
-                         const optional<Tensor>& noise, const optional<Tensor>& e_uncond_img, const optional<Tensor>& x0_hist,
-                         Tensor& x_prev, Tensor& x0, double cfg_scale, double cfg_img, double guidance_rescale, double sqrt_ac,
-                         double sqrt_1m_ac, double sqrt_a_prev, double dir_coef, double sigma, double x0_rescale) {
-  auto ok = [](const Tensor& t) { return t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous(); };
-  TORCH_CHECK(ok(x) && ok(e_cond) && (!e_uncond.has_value() || ok(*e_uncond)) && (!noise.has_value() || ok(*noise)) &&
-              (!e_uncond_img.has_value() || ok(*e_uncond_img)) && (!x0_hist.has_value() || ok(*x0_hist)),
-              what, ": contiguous fp32 CUDA tensors");
-  TORCH_CHECK(!x0_hist.has_value() || x0_hist->sizes() == x.sizes(), what, ": x0_hist must have the shape of x");
-  x_prev = at::empty_like(x);
-  x0 = at::empty_like(x);
-  TcDdimParams p = {};
-  p.x = x.data_ptr<float>(); p.e_cond = e_cond.data_ptr<float>();
-  p.e_uncond = e_uncond.has_value() ? e_uncond->data_ptr<float>() : nullptr;
-  p.noise = noise.has_value() ? noise->data_ptr<float>() : nullptr;
-  p.e_uncond_img = e_uncond_img.has_value() ? e_uncond_img->data_ptr<float>() : nullptr;
-  p.x_prev = x_prev.data_ptr<float>(); p.pred_x0 = x0.data_ptr<float>();
-  p.b = (int32_t)x.size(0); p.n = x.numel() / x.size(0);
-  p.cfg_scale = (float)cfg_scale; p.cfg_img = (float)cfg_img; p.guidance_rescale = (float)guidance_rescale;
-  p.sqrt_ac = (float)sqrt_ac; p.sqrt_1m_ac = (float)sqrt_1m_ac; p.sqrt_a_prev = (float)sqrt_a_prev;
-  p.dir_coef = (float)dir_coef; p.sigma = (float)sigma; p.x0_rescale = (float)x0_rescale;
-  return p;
-}
-
-// The one step implementation: x0_hist is the previous step's pred_x0 or None, and without one (or with corr 0) the step is
-// first order (the multistep term is additive within ABI 14).
+// The one step implementation; x_prev and pred_x0 are its two results.  x0_hist is the previous step's pred_x0 or None, and
+// without one (or with corr 0) the step is first order (the multistep term is additive within ABI 14).
 template <bool EPS>
 std::tuple<Tensor, Tensor> ddim_step_ms_any(const Tensor& x, const Tensor& e_cond, const optional<Tensor>& e_uncond,
                                             const optional<Tensor>& noise, const optional<Tensor>& e_uncond_img,
                                             const optional<Tensor>& x0_hist, double corr, double cfg_scale, double cfg_img,
                                             double guidance_rescale, double sqrt_ac, double sqrt_1m_ac, double sqrt_a_prev,
                                             double dir_coef, double sigma, double x0_rescale) {
-  Tensor x_prev, x0;
+  TORCH_CHECK(fits(x, at::kFloat, kDense, x, e_cond, e_uncond, noise, e_uncond_img, x0_hist), "ddim_step: contiguous fp32 CUDA tensors");
+  TORCH_CHECK(!x0_hist.has_value() || x0_hist->sizes() == x.sizes(), "ddim_step: x0_hist must have the shape of x");
+  Tensor x_prev = at::empty_like(x), x0 = at::empty_like(x);
+  if (x.is_meta()) return {x_prev, x0};
   TcDdimMsParams mp = {};
-  mp.base = ddim_params("ddim_step", x, e_cond, e_uncond, noise, e_uncond_img, x0_hist, x_prev, x0, cfg_scale, cfg_img,
-                        guidance_rescale, sqrt_ac, sqrt_1m_ac, sqrt_a_prev, dir_coef, sigma, x0_rescale);
-  mp.x0_hist = x0_hist.has_value() ? x0_hist->data_ptr<float>() : nullptr;
+  TcDdimParams& p = mp.base;
+  p.x = x.data_ptr<float>(); p.e_cond = e_cond.data_ptr<float>();
+  p.e_uncond = f32_or_null(e_uncond); p.noise = f32_or_null(noise); p.e_uncond_img = f32_or_null(e_uncond_img);
+  p.x_prev = x_prev.data_ptr<float>(); p.pred_x0 = x0.data_ptr<float>();
+  p.b = (int32_t)x.size(0); p.n = x.numel() / x.size(0);
+  p.cfg_scale = (float)cfg_scale; p.cfg_img = (float)cfg_img; p.guidance_rescale = (float)guidance_rescale;
+  p.sqrt_ac = (float)sqrt_ac; p.sqrt_1m_ac = (float)sqrt_1m_ac; p.sqrt_a_prev = (float)sqrt_a_prev;
+  p.dir_coef = (float)dir_coef; p.sigma = (float)sigma; p.x0_rescale = (float)x0_rescale;
+  mp.x0_hist = f32_or_null(x0_hist);
   mp.corr = (float)corr;
-  const int64_t nbytes = tc_ddim_workspace(mp.base.b);
+  const int64_t nbytes = tc_ddim_workspace(p.b);
   Tensor ws = workspace(nbytes, x);
   if (EPS)
     check_rc(tc_ddim_step_ms_eps(&mp, ws.data_ptr(), nbytes, cur_stream()), "tc_ddim_step_ms_eps");
   else
     check_rc(tc_ddim_step_ms(&mp, ws.data_ptr(), nbytes, cur_stream()), "tc_ddim_step_ms");
-  return std::make_tuple(x_prev, x0);
+  return {x_prev, x0};
 }
 
 // ddim_step / ddim_step_eps: the schema without the two history operands
@@ -474,19 +457,16 @@ std::tuple<Tensor, Tensor> ddim_step_any(const Tensor& x, const Tensor& e_cond, 
                                sqrt_ac, sqrt_1m_ac, sqrt_a_prev, dir_coef, sigma, x0_rescale);
 }
 
-Tensor ddim_blend_cuda(const optional<Tensor>& x, const Tensor& x0, const optional<Tensor>& noise, const optional<Tensor>& mask,
-                       double sqrt_ac, double sqrt_1m_ac) {
-  auto ok = [&](const Tensor& t) {
-    return t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.sizes() == x0.sizes();
-  };
-  TORCH_CHECK(x0.dim() >= 1 && ok(x0) && (!x.has_value() || ok(*x)) && (!noise.has_value() || ok(*noise)) &&
-              (!mask.has_value() || ok(*mask)), "ddim_blend: contiguous fp32 CUDA tensors of one shape (B, ...)");
+// x is optional, so x0 is the operator's first tensor
+Tensor ddim_blend(const optional<Tensor>& x, const Tensor& x0, const optional<Tensor>& noise, const optional<Tensor>& mask,
+                  double sqrt_ac, double sqrt_1m_ac) {
+  auto shaped = [&](const optional<Tensor>& t) { return !t.has_value() || t->sizes() == x0.sizes(); };
+  TORCH_CHECK(x0.dim() >= 1 && fits(x0, at::kFloat, kDense, x0, x, noise, mask) && shaped(x) && shaped(noise) && shaped(mask),
+              "ddim_blend: contiguous fp32 CUDA tensors of one shape (B, ...)");
   Tensor out = at::empty_like(x0);
+  if (x0.is_meta()) return out;
   TcDdimBlendParams p = {};
-  p.x = x.has_value() ? x->data_ptr<float>() : nullptr;
-  p.x0 = x0.data_ptr<float>();
-  p.noise = noise.has_value() ? noise->data_ptr<float>() : nullptr;
-  p.mask = mask.has_value() ? mask->data_ptr<float>() : nullptr;
+  p.x = f32_or_null(x); p.x0 = x0.data_ptr<float>(); p.noise = f32_or_null(noise); p.mask = f32_or_null(mask);
   p.out = out.data_ptr<float>();
   p.b = (int32_t)x0.size(0); p.n = p.b ? x0.numel() / x0.size(0) : 0;
   p.sqrt_ac = (float)sqrt_ac; p.sqrt_1m_ac = (float)sqrt_1m_ac;
@@ -494,78 +474,87 @@ Tensor ddim_blend_cuda(const optional<Tensor>& x, const Tensor& x0, const option
   return out;
 }
 
-Tensor ddim_blend_meta(const optional<Tensor>&, const Tensor& x0, const optional<Tensor>&, const optional<Tensor>&, double, double) {
-  return at::empty_like(x0);
-}
+// Pixel path (additive within ABI 14).  A resample request: per axis the tables of n_in -> n_out (tc_resize_tables /
+// tc_resize_tables_filter), on the device, as the C ABI takes them.  n_in == n_out: the pass does not run, its tables are not
+// looked at.  Checked in front of the allocation (resize_request), set in the params struct behind it (resize_fill).
+struct Resize {   // the tables of the passes that run, null for one that does not
+  const Tensor *h_bounds = nullptr, *h_coefs = nullptr, *v_bounds = nullptr, *v_coefs = nullptr;
+};
 
-// Pixel path (additive within ABI 14).  One axis of a resample request: the tables of n_in -> n_out (tc_resize_tables /
-// tc_resize_tables_filter), on the device, as the C ABI takes them.  n_in == n_out: the pass does not run, its tables are not looked at.
-struct ResizeAxis { const int32_t* bounds = nullptr; const int32_t* coefs = nullptr; int32_t kmax = 0; };
-ResizeAxis resize_axis(const optional<Tensor>& bounds, const optional<Tensor>& coefs, int64_t n_in, int64_t n_out, const char* name,
-                       const char* axis) {
-  ResizeAxis a;
-  if (n_in == n_out) return a;
+bool resize_axis(const optional<Tensor>& bounds, const optional<Tensor>& coefs, const Tensor& first, int64_t n_in, int64_t n_out,
+                 const char* name, const char* axis) {
+  if (n_in == n_out) return false;
   for (const auto* t : {&bounds, &coefs})
-    TORCH_CHECK(!t->has_value() || ((*t)->is_cuda() && (*t)->scalar_type() == at::kInt && (*t)->is_contiguous() && (*t)->dim() == 2),
-                name, ": ", axis, " tables: contiguous int32 CUDA [out, k]");
+    TORCH_CHECK(fits(first, at::kInt, kDense, *t) && (!t->has_value() || (*t)->dim() == 2), name, ": ", axis,
+                " tables: contiguous int32 CUDA [out, k]");
   // the tables must be the ones of this size: their rows are indexed by the output index
   TORCH_CHECK(bounds.has_value() && coefs.has_value() && bounds->size(0) == n_out && bounds->size(1) == 2 && coefs->size(0) == n_out &&
               coefs->size(1) >= 1, name, ": ", axis, " tables of ", n_in, " -> ", n_out, " expected");
-  a.bounds = bounds->data_ptr<int32_t>(); a.coefs = coefs->data_ptr<int32_t>(); a.kmax = (int32_t)coefs->size(1);
-  return a;
+  return true;
+}
+
+Resize resize_request(const optional<Tensor>& h_bounds, const optional<Tensor>& h_coefs, const optional<Tensor>& v_bounds,
+                      const optional<Tensor>& v_coefs, const Tensor& first, int64_t w_in, int64_t w_out, int64_t h_in, int64_t h_out,
+                      const char* name) {
+  Resize r;
+  if (resize_axis(h_bounds, h_coefs, first, w_in, w_out, name, "horizontal")) { r.h_bounds = &*h_bounds; r.h_coefs = &*h_coefs; }
+  if (resize_axis(v_bounds, v_coefs, first, h_in, h_out, name, "vertical")) { r.v_bounds = &*v_bounds; r.v_coefs = &*v_coefs; }
+  return r;
+}
+
+template <typename P>
+void resize_fill(P& p, const Resize& r) {
+  if (r.h_bounds) {
+    p.h_bounds = r.h_bounds->data_ptr<int32_t>(); p.h_coefs = r.h_coefs->data_ptr<int32_t>(); p.h_kmax = (int32_t)r.h_coefs->size(1);
+  }
+  if (r.v_bounds) {
+    p.v_bounds = r.v_bounds->data_ptr<int32_t>(); p.v_coefs = r.v_coefs->data_ptr<int32_t>(); p.v_kmax = (int32_t)r.v_coefs->size(1);
+  }
 }
 
 // What the two front ends ask besides their source: n images of (sh, sw), image i into frame slots[i] = batch * t + frame of a new
 // (b, 3, t, h, w) fp32 clip tensor on the device of `src`, zero elsewhere (reference scripts/evaluation/inference.py:64-69 on the
-// device); the tables are tc_resize_tables' for sw -> rw and sh -> rh (None when nothing is resized).  Fills those fields of p, which
-// points at the caller's `slot`, and returns the clip tensor.
-template <typename Params>
-Tensor front_request(Params& p, int32_t (&slot)[TC_FRAMES_U8_MAX], const char* name, const Tensor& src, int64_t n, int64_t sh, int64_t sw,
-                     at::IntArrayRef slots, int64_t b, int64_t t, int64_t h, int64_t w, const optional<Tensor>& h_bounds,
-                     const optional<Tensor>& h_coefs, const optional<Tensor>& v_bounds, const optional<Tensor>& v_coefs) {
+// device); the tables are tc_resize_tables' for sw -> rw and sh -> rh (None when nothing is resized).  front_request checks that
+// and returns the tables; front_fill sets those fields of p, which points at the caller's `slot`.
+Resize front_request(const char* name, const Tensor& src, int64_t n, int64_t sh, int64_t sw, at::IntArrayRef slots, int64_t b, int64_t t,
+                     int64_t h, int64_t w, const optional<Tensor>& h_bounds, const optional<Tensor>& h_coefs,
+                     const optional<Tensor>& v_bounds, const optional<Tensor>& v_coefs) {
   TORCH_CHECK(n >= 1 && n <= TC_FRAMES_U8_MAX && (int64_t)slots.size() == n, name, ": 1 .. ", TC_FRAMES_U8_MAX, " images, one slot each");
   TORCH_CHECK(b > 0 && t > 0 && h > 0 && w > 0, name, ": b, t, h, w must be positive");
-  Tensor out = at::zeros({b, 3, t, h, w}, src.options().dtype(at::kFloat));
-  for (int64_t i = 0; i < n; ++i) {
-    TORCH_CHECK(slots[i] >= 0 && slots[i] < b * t, name, ": slot ", slots[i], " outside the clip tensor");
-    slot[i] = (int32_t)slots[i];
-  }
-  p.n = (int32_t)n; p.sh = (int32_t)sh; p.sw = (int32_t)sw;
-  p.slots = slot;
-  p.out = out.data_ptr<float>();
-  p.b = (int32_t)b; p.t = (int32_t)t; p.h = (int32_t)h; p.w = (int32_t)w;
+  for (int64_t s : slots) TORCH_CHECK(s >= 0 && s < b * t, name, ": slot ", s, " outside the clip tensor");
   int32_t rh = 0, rw = 0;
-  check_rc(tc_frames_from_u8_resized(p.sh, p.sw, p.h, p.w, &rh, &rw), "tc_frames_from_u8_resized");
-  const ResizeAxis ah = resize_axis(h_bounds, h_coefs, sw, rw, name, "horizontal");
-  const ResizeAxis av = resize_axis(v_bounds, v_coefs, sh, rh, name, "vertical");
-  p.h_bounds = ah.bounds; p.h_coefs = ah.coefs; p.h_kmax = ah.kmax;
-  p.v_bounds = av.bounds; p.v_coefs = av.coefs; p.v_kmax = av.kmax;
-  return out;
+  check_rc(tc_frames_from_u8_resized((int32_t)sh, (int32_t)sw, (int32_t)h, (int32_t)w, &rh, &rw), "tc_frames_from_u8_resized");
+  return resize_request(h_bounds, h_coefs, v_bounds, v_coefs, src, sw, rw, sh, rh, name);
 }
 
-Tensor frames_from_u8_cuda(const Tensor& images, at::IntArrayRef slots, int64_t b, int64_t t, int64_t h, int64_t w,
-                           const optional<Tensor>& h_bounds, const optional<Tensor>& h_coefs, const optional<Tensor>& v_bounds,
-                           const optional<Tensor>& v_coefs) {
-  TORCH_CHECK(images.is_cuda(), "frames_from_u8: expected a CUDA tensor (the product path is GPU-only)");
+template <typename Params>
+void front_fill(Params& p, int32_t (&slot)[TC_FRAMES_U8_MAX], Tensor& out, int64_t sh, int64_t sw, at::IntArrayRef slots, const Resize& rs) {
+  for (size_t i = 0; i < slots.size(); ++i) slot[i] = (int32_t)slots[i];
+  p.n = (int32_t)slots.size(); p.sh = (int32_t)sh; p.sw = (int32_t)sw;
+  p.slots = slot;
+  p.out = out.data_ptr<float>();
+  p.b = (int32_t)out.size(0); p.t = (int32_t)out.size(2); p.h = (int32_t)out.size(3); p.w = (int32_t)out.size(4);
+  resize_fill(p, rs);
+}
+
+Tensor frames_from_u8(const Tensor& images, at::IntArrayRef slots, int64_t b, int64_t t, int64_t h, int64_t w,
+                      const optional<Tensor>& h_bounds, const optional<Tensor>& h_coefs, const optional<Tensor>& v_bounds,
+                      const optional<Tensor>& v_coefs) {
+  TORCH_CHECK(on_device(images, images), "frames_from_u8: expected a CUDA tensor (the product path is GPU-only)");
   TORCH_CHECK(images.scalar_type() == at::kByte && images.dim() == 4 && images.size(3) == 3 && images.stride(3) == 1 &&
               images.stride(2) == 3, "frames_from_u8: uint8 (n, h, w, 3) images with packed pixels");
+  const int64_t sh = images.size(1), sw = images.size(2);
+  const Resize rs = front_request("frames_from_u8", images, images.size(0), sh, sw, slots, b, t, h, w, h_bounds, h_coefs, v_bounds, v_coefs);
+  Tensor out = at::zeros({b, 3, t, h, w}, images.options().dtype(at::kFloat));
+  if (images.is_meta()) return out;
   TcFramesU8Params p = {};
   int32_t slot[TC_FRAMES_U8_MAX];
-  Tensor out = front_request(p, slot, "frames_from_u8", images, images.size(0), images.size(1), images.size(2), slots, b, t, h, w,
-                             h_bounds, h_coefs, v_bounds, v_coefs);
+  front_fill(p, slot, out, sh, sw, slots, rs);
   p.src = images.data_ptr<uint8_t>();
   p.pitch = (int32_t)images.stride(1);
   p.image_stride = p.n > 1 ? images.stride(0) : (int64_t)p.sh * p.pitch;
-  p.workspace_bytes = tc_frames_from_u8_workspace(&p);
-  Tensor ws = workspace(p.workspace_bytes, images);
-  p.workspace = ws.data_ptr();
-  check_rc(tc_frames_from_u8(&p, cur_stream()), "tc_frames_from_u8");
+  launch_ws(p, images, tc_frames_from_u8_workspace, tc_frames_from_u8, "tc_frames_from_u8");
   return out;
-}
-
-Tensor frames_from_u8_meta(const Tensor& images, at::IntArrayRef, int64_t b, int64_t t, int64_t h, int64_t w, const optional<Tensor>&,
-                           const optional<Tensor>&, const optional<Tensor>&, const optional<Tensor>&) {
-  return at::empty({b, 3, t, h, w}, images.options().dtype(at::kFloat));
 }
 
 // frames_from_yuv: n planar 4:2:0 images -> a new (b, 3, t, h, w) fp32 clip tensor (tc_frames_from_yuv).  y (n, sh, sw), c0 / c1
@@ -577,11 +566,10 @@ std::pair<int64_t, int64_t> plane_rows(const Tensor& p, int64_t row_elems, const
   return {p.stride(1) * es, (n > 1 ? p.stride(0) : p.size(1) * p.stride(1)) * es};
 }
 
-Tensor frames_from_yuv_cuda(const Tensor& y, const Tensor& c0, const optional<Tensor>& c1, int64_t format, at::IntArrayRef m,
-                            int64_t siting, at::IntArrayRef slots, int64_t b, int64_t t, int64_t h, int64_t w,
-                            const optional<Tensor>& h_bounds, const optional<Tensor>& h_coefs, const optional<Tensor>& v_bounds,
-                            const optional<Tensor>& v_coefs) {
-  TORCH_CHECK(y.is_cuda() && c0.is_cuda() && (!c1.has_value() || c1->is_cuda()),
+Tensor frames_from_yuv(const Tensor& y, const Tensor& c0, const optional<Tensor>& c1, int64_t format, at::IntArrayRef m, int64_t siting,
+                       at::IntArrayRef slots, int64_t b, int64_t t, int64_t h, int64_t w, const optional<Tensor>& h_bounds,
+                       const optional<Tensor>& h_coefs, const optional<Tensor>& v_bounds, const optional<Tensor>& v_coefs) {
+  TORCH_CHECK(on_device(y, y) && on_device(c0, y) && (!c1.has_value() || on_device(*c1, y)),
               "frames_from_yuv: expected CUDA tensors (the product path is GPU-only)");
   TORCH_CHECK(format == TC_PIXFMT_I420 || format == TC_PIXFMT_NV12 || format == TC_PIXFMT_P010, "frames_from_yuv: format ", format);
   const bool planar = format == TC_PIXFMT_I420, wide = format == TC_PIXFMT_P010;
@@ -600,113 +588,75 @@ Tensor frames_from_yuv_cuda(const Tensor& y, const Tensor& c0, const optional<Te
   }
   TORCH_CHECK(m.size() == 7, "frames_from_yuv: the matrix has seven entries");
   TORCH_CHECK(siting == TC_CHROMA_NEAREST || siting == TC_CHROMA_CENTER || siting == TC_CHROMA_LEFT, "frames_from_yuv: siting ", siting);
+  const Resize rs = front_request("frames_from_yuv", y, n, sh, sw, slots, b, t, h, w, h_bounds, h_coefs, v_bounds, v_coefs);
+  const auto ry = plane_rows(y, sw, "frames_from_yuv: y"), rc = plane_rows(c0, planar ? cw : 2 * cw, "frames_from_yuv: chroma");
+  Tensor out = at::zeros({b, 3, t, h, w}, y.options().dtype(at::kFloat));
+  if (y.is_meta()) return out;
   TcFramesYuvParams p = {};
   int32_t slot[TC_FRAMES_U8_MAX];
-  Tensor out = front_request(p, slot, "frames_from_yuv", y, n, sh, sw, slots, b, t, h, w, h_bounds, h_coefs, v_bounds, v_coefs);
+  front_fill(p, slot, out, sh, sw, slots, rs);
   p.y = y.data_ptr(); p.c0 = c0.data_ptr(); p.c1 = planar ? c1->data_ptr() : nullptr;
-  const auto ry = plane_rows(y, sw, "frames_from_yuv: y"), rc = plane_rows(c0, planar ? cw : 2 * cw, "frames_from_yuv: chroma");
   p.pitch_y = (int32_t)ry.first; p.image_stride_y = ry.second;
   p.pitch_c = (int32_t)rc.first; p.image_stride_c = rc.second;
   p.format = (int32_t)format; p.siting = (int32_t)siting;
   for (int i = 0; i < 7; ++i) p.m[i] = (int32_t)m[i];
-  p.workspace_bytes = tc_frames_from_yuv_workspace(&p);
-  Tensor ws = workspace(p.workspace_bytes, y);
-  p.workspace = ws.data_ptr();
-  check_rc(tc_frames_from_yuv(&p, cur_stream()), "tc_frames_from_yuv");
+  launch_ws(p, y, tc_frames_from_yuv_workspace, tc_frames_from_yuv, "tc_frames_from_yuv");
   return out;
 }
 
-Tensor frames_from_yuv_meta(const Tensor& y, const Tensor&, const optional<Tensor>&, int64_t, at::IntArrayRef, int64_t, at::IntArrayRef,
-                            int64_t b, int64_t t, int64_t h, int64_t w, const optional<Tensor>&, const optional<Tensor>&,
-                            const optional<Tensor>&, const optional<Tensor>&) {
-  return at::empty({b, 3, t, h, w}, y.options().dtype(at::kFloat));
-}
-
-// Pixel back end (additive within ABI 14).  frames_to_u8: frames f0 .. f0 + nf - 1 of every clip of x (b, 3, t, h, w) fp32 -> a new
-// packed uint8 tensor, (b, nf, oh, ow, 3) for RGB24 or (b, nf, oh * ow * 3 / 2) for I420 / NV12 (tc_frames_to_u8); the tables are
-// tc_resize_tables_filter's for w -> ow and h -> oh, on the device (None for an axis that keeps its size).  Writing into a caller's
+// Pixel back end (additive within ABI 14): the one body of frames_to_u8 and frames_to_yuv.  Frames f0 .. f0 + nf - 1 of every clip
+// of x (b, 3, t, h, w) fp32 -> a new packed uint8 tensor; the tables are tc_resize_tables_filter's for w -> ow and h -> oh, on the
+// device (None for an axis that keeps its size).  Each operator checks its own format set and says what follows from the format:
+// `sample`, the bytes of a sample of a planar 4:2:0 format, (b, nf, oh * ow * 3 / 2 * sample) with rows of sample * ow bytes, or 0
+// for RGB24, (b, nf, oh, ow, 3); and `rest`, which sets the fields that only its params struct has.  Writing into a caller's
 // buffer with strides is the C ABI's (HipOps.frames_to_u8 with out=): an op returns its result.
-std::vector<int64_t> frames_to_u8_shape(const Tensor& x, int64_t oh, int64_t ow, int64_t format, int64_t f0, int64_t nf) {
-  TORCH_CHECK(x.dim() == 5 && x.size(1) == 3 && x.numel() > 0, "frames_to_u8: x must be (b, 3, t, h, w)");
-  TORCH_CHECK(oh > 0 && ow > 0 && oh <= INT32_MAX && ow <= INT32_MAX, "frames_to_u8: output size (", oh, ", ", ow, ")");
-  TORCH_CHECK(f0 >= 0 && nf >= 1 && f0 + nf <= x.size(2), "frames_to_u8: frames ", f0, " .. ", f0 + nf - 1, " outside a clip of ", x.size(2));
-  TORCH_CHECK(format == TC_PIXFMT_RGB24 || format == TC_PIXFMT_I420 || format == TC_PIXFMT_NV12, "frames_to_u8: format ", format);
-  if (format == TC_PIXFMT_RGB24) return {x.size(0), nf, oh, ow, 3};
-  TORCH_CHECK(oh % 2 == 0 && ow % 2 == 0, "frames_to_u8: I420 / NV12 need an even size, got (", oh, ", ", ow, ")");
-  return {x.size(0), nf, oh * ow * 3 / 2};
-}
-
-Tensor frames_to_u8_cuda(const Tensor& x, int64_t oh, int64_t ow, int64_t format, int64_t f0, int64_t nf,
-                         const optional<Tensor>& h_bounds, const optional<Tensor>& h_coefs, const optional<Tensor>& v_bounds,
-                         const optional<Tensor>& v_coefs) {
-  TORCH_CHECK(x.is_cuda(), "frames_to_u8: expected a CUDA tensor (the product path is GPU-only)");
-  TORCH_CHECK(x.scalar_type() == at::kFloat && x.is_contiguous(), "frames_to_u8: contiguous fp32 (b, 3, t, h, w)");
-  Tensor out = at::empty(frames_to_u8_shape(x, oh, ow, format, f0, nf), x.options().dtype(at::kByte));
-  TcFramesOutParams p = {};
-  p.x = x.data_ptr<float>(); p.out = out.data_ptr<uint8_t>();
+template <typename P, typename Rest>
+Tensor frames_out(const char* what, int64_t (*bytes)(const P*), int (*entry)(const P*, void*), const Tensor& x, int64_t oh, int64_t ow,
+                  int64_t format, int64_t f0, int64_t nf, int64_t sample, const optional<Tensor>& h_bounds,
+                  const optional<Tensor>& h_coefs, const optional<Tensor>& v_bounds, const optional<Tensor>& v_coefs, Rest rest) {
+  TORCH_CHECK(on_device(x, x), what, ": expected a CUDA tensor (the product path is GPU-only)");
+  TORCH_CHECK(x.dim() == 5 && x.size(1) == 3 && x.numel() > 0, what, ": x must be (b, 3, t, h, w)");
+  TORCH_CHECK(x.scalar_type() == at::kFloat && x.is_contiguous(), what, ": contiguous fp32 (b, 3, t, h, w)");
+  TORCH_CHECK(oh > 0 && ow > 0 && oh <= INT32_MAX && ow <= INT32_MAX, what, ": output size (", oh, ", ", ow, ")");
+  TORCH_CHECK(f0 >= 0 && nf >= 1 && f0 + nf <= x.size(2), what, ": frames ", f0, " .. ", f0 + nf - 1, " outside a clip of ", x.size(2));
+  TORCH_CHECK(sample == 0 || (oh % 2 == 0 && ow % 2 == 0), what, ": planar frames need an even size, got (", oh, ", ", ow, ")");
+  const Resize rs = resize_request(h_bounds, h_coefs, v_bounds, v_coefs, x, x.size(4), ow, x.size(3), oh, what);
+  Tensor out = at::empty(sample ? std::vector<int64_t>{x.size(0), nf, oh * ow * 3 / 2 * sample} : std::vector<int64_t>{x.size(0), nf, oh, ow, 3},
+                         x.options().dtype(at::kByte));
+  if (x.is_meta()) return out;
+  P p = {};
+  p.x = x.data_ptr<float>(); p.out = static_cast<decltype(p.out)>(out.data_ptr());
   p.b = (int32_t)x.size(0); p.t = (int32_t)x.size(2); p.h = (int32_t)x.size(3); p.w = (int32_t)x.size(4);
   p.f0 = (int32_t)f0; p.nf = (int32_t)nf; p.oh = (int32_t)oh; p.ow = (int32_t)ow; p.format = (int32_t)format;
-  p.pitch = (int32_t)(format == TC_PIXFMT_RGB24 ? 3 * ow : ow);
+  p.pitch = (int32_t)(sample ? sample * ow : 3 * ow);
   p.frame_stride = out.stride(1); p.clip_stride = out.stride(0);
-  const ResizeAxis ah = resize_axis(h_bounds, h_coefs, p.w, p.ow, "frames_to_u8", "horizontal");
-  const ResizeAxis av = resize_axis(v_bounds, v_coefs, p.h, p.oh, "frames_to_u8", "vertical");
-  p.h_bounds = ah.bounds; p.h_coefs = ah.coefs; p.h_kmax = ah.kmax;
-  p.v_bounds = av.bounds; p.v_coefs = av.coefs; p.v_kmax = av.kmax;
-  p.workspace_bytes = tc_frames_to_u8_workspace(&p);
-  Tensor ws = workspace(p.workspace_bytes, out);
-  p.workspace = ws.data_ptr();
-  check_rc(tc_frames_to_u8(&p, cur_stream()), "tc_frames_to_u8");
+  resize_fill(p, rs);
+  rest(p);
+  launch_ws(p, x, bytes, entry, (std::string("tc_") + what).c_str());
   return out;
 }
 
-Tensor frames_to_u8_meta(const Tensor& x, int64_t oh, int64_t ow, int64_t format, int64_t f0, int64_t nf, const optional<Tensor>&,
-                         const optional<Tensor>&, const optional<Tensor>&, const optional<Tensor>&) {
-  return at::empty(frames_to_u8_shape(x, oh, ow, format, f0, nf), x.options().dtype(at::kByte));
+// frames_to_u8: RGB24, or I420 / NV12 in the fixed colour of tc_frames_to_u8
+Tensor frames_to_u8(const Tensor& x, int64_t oh, int64_t ow, int64_t format, int64_t f0, int64_t nf, const optional<Tensor>& h_bounds,
+                    const optional<Tensor>& h_coefs, const optional<Tensor>& v_bounds, const optional<Tensor>& v_coefs) {
+  TORCH_CHECK(format == TC_PIXFMT_RGB24 || format == TC_PIXFMT_I420 || format == TC_PIXFMT_NV12, "frames_to_u8: format ", format);
+  return frames_out("frames_to_u8", tc_frames_to_u8_workspace, tc_frames_to_u8, x, oh, ow, format, f0, nf, format == TC_PIXFMT_RGB24 ? 0 : 1,
+                    h_bounds, h_coefs, v_bounds, v_coefs, [](TcFramesOutParams&) {});
 }
 
-// frames_to_yuv: frames_to_u8 for planar frames in a caller's colour (tc_frames_to_yuv): format I420 / NV12 / P010, the siting code
-// and the eleven integers of the RGB -> YCbCr matrix -> a new packed uint8 tensor (b, nf, oh * ow * 3 / 2), twice the bytes for P010.
-std::vector<int64_t> frames_to_yuv_shape(const Tensor& x, int64_t oh, int64_t ow, int64_t format, int64_t f0, int64_t nf, int64_t siting,
-                                         at::IntArrayRef m) {
-  TORCH_CHECK(x.dim() == 5 && x.size(1) == 3 && x.numel() > 0, "frames_to_yuv: x must be (b, 3, t, h, w)");
-  TORCH_CHECK(oh > 0 && ow > 0 && oh <= INT32_MAX && ow <= INT32_MAX, "frames_to_yuv: output size (", oh, ", ", ow, ")");
-  TORCH_CHECK(f0 >= 0 && nf >= 1 && f0 + nf <= x.size(2), "frames_to_yuv: frames ", f0, " .. ", f0 + nf - 1, " outside a clip of ", x.size(2));
+// frames_to_yuv: planar frames in a caller's colour (tc_frames_to_yuv): format I420 / NV12 / P010 (2-byte samples), the siting code
+// and the eleven integers of the RGB -> YCbCr matrix
+Tensor frames_to_yuv(const Tensor& x, int64_t oh, int64_t ow, int64_t format, int64_t f0, int64_t nf, int64_t siting, at::IntArrayRef m,
+                     const optional<Tensor>& h_bounds, const optional<Tensor>& h_coefs, const optional<Tensor>& v_bounds,
+                     const optional<Tensor>& v_coefs) {
   TORCH_CHECK(format == TC_PIXFMT_I420 || format == TC_PIXFMT_NV12 || format == TC_PIXFMT_P010, "frames_to_yuv: format ", format);
   TORCH_CHECK(siting == TC_CHROMA_CENTER || siting == TC_CHROMA_LEFT, "frames_to_yuv: siting ", siting);
   TORCH_CHECK(m.size() == 11, "frames_to_yuv: the matrix has eleven entries");
-  TORCH_CHECK(oh % 2 == 0 && ow % 2 == 0, "frames_to_yuv: planar frames need an even size, got (", oh, ", ", ow, ")");
-  return {x.size(0), nf, oh * ow * 3 / 2 * (format == TC_PIXFMT_P010 ? 2 : 1)};
-}
-
-Tensor frames_to_yuv_cuda(const Tensor& x, int64_t oh, int64_t ow, int64_t format, int64_t f0, int64_t nf, int64_t siting,
-                          at::IntArrayRef m, const optional<Tensor>& h_bounds, const optional<Tensor>& h_coefs,
-                          const optional<Tensor>& v_bounds, const optional<Tensor>& v_coefs) {
-  TORCH_CHECK(x.is_cuda(), "frames_to_yuv: expected a CUDA tensor (the product path is GPU-only)");
-  TORCH_CHECK(x.scalar_type() == at::kFloat && x.is_contiguous(), "frames_to_yuv: contiguous fp32 (b, 3, t, h, w)");
-  Tensor out = at::empty(frames_to_yuv_shape(x, oh, ow, format, f0, nf, siting, m), x.options().dtype(at::kByte));
-  TcFramesYuvOutParams p = {};
-  p.x = x.data_ptr<float>(); p.out = out.data_ptr();
-  p.b = (int32_t)x.size(0); p.t = (int32_t)x.size(2); p.h = (int32_t)x.size(3); p.w = (int32_t)x.size(4);
-  p.f0 = (int32_t)f0; p.nf = (int32_t)nf; p.oh = (int32_t)oh; p.ow = (int32_t)ow; p.format = (int32_t)format;
-  p.pitch = (int32_t)(format == TC_PIXFMT_P010 ? 2 * ow : ow);
-  p.frame_stride = out.stride(1); p.clip_stride = out.stride(0);
-  p.siting = (int32_t)siting;
-  for (int i = 0; i < 11; ++i) p.m[i] = (int32_t)m[i];
-  const ResizeAxis ah = resize_axis(h_bounds, h_coefs, p.w, p.ow, "frames_to_yuv", "horizontal");
-  const ResizeAxis av = resize_axis(v_bounds, v_coefs, p.h, p.oh, "frames_to_yuv", "vertical");
-  p.h_bounds = ah.bounds; p.h_coefs = ah.coefs; p.h_kmax = ah.kmax;
-  p.v_bounds = av.bounds; p.v_coefs = av.coefs; p.v_kmax = av.kmax;
-  p.workspace_bytes = tc_frames_to_yuv_workspace(&p);
-  Tensor ws = workspace(p.workspace_bytes, out);
-  p.workspace = ws.data_ptr();
-  check_rc(tc_frames_to_yuv(&p, cur_stream()), "tc_frames_to_yuv");
-  return out;
-}
-
-Tensor frames_to_yuv_meta(const Tensor& x, int64_t oh, int64_t ow, int64_t format, int64_t f0, int64_t nf, int64_t siting,
-                          at::IntArrayRef m, const optional<Tensor>&, const optional<Tensor>&, const optional<Tensor>&,
-                          const optional<Tensor>&) {
-  return at::empty(frames_to_yuv_shape(x, oh, ow, format, f0, nf, siting, m), x.options().dtype(at::kByte));
+  return frames_out("frames_to_yuv", tc_frames_to_yuv_workspace, tc_frames_to_yuv, x, oh, ow, format, f0, nf, format == TC_PIXFMT_P010 ? 2 : 1,
+                    h_bounds, h_coefs, v_bounds, v_coefs, [&](TcFramesYuvOutParams& p) {
+                      p.siting = (int32_t)siting;
+                      for (int i = 0; i < 11; ++i) p.m[i] = (int32_t)m[i];
+                    });
 }
 
 // Colour match and histogram transfer (additive within ABI 14): six ops, every check sentence once with the op's name in front.
@@ -727,53 +677,37 @@ void colour_hw_check(const Tensor& x, const char* what) {
   TORCH_CHECK(x.size(3) * x.size(4) <= (int64_t(1) << 26), what, ": h * w ", x.size(3) * x.size(4), " above 2^26");
 }
 
-// the checked shape of colour_stats (b, nf, 9), or with `hist` of colour_hist (b, nf, 3, 1024)
-std::vector<int64_t> colour_frames_shape(const Tensor& x, int64_t f0, int64_t nf, int64_t fstep, bool hist) {
+// colour_stats / colour_hist: P the params struct, `result` its field for the op's tensor
+template <typename P, typename R>
+Tensor colour_frames(const Tensor& x, int64_t f0, int64_t nf, int64_t fstep, R* P::*result, int64_t (*bytes)(const P*),
+                     int (*entry)(const P*, void*)) {
+  constexpr bool hist = std::is_same_v<P, TcColourHistParams>;
   const char* what = hist ? "colour_hist" : "colour_stats";
+  TORCH_CHECK(on_device(x, x), what, ": expected a CUDA tensor (the product path is GPU-only)");
   colour_clip_check(x, what);
+  TORCH_CHECK(x.scalar_type() == at::kFloat && x.is_contiguous(), what, ": contiguous fp32 (b, 3, t, h, w)");
   const int64_t t = x.size(2);
   TORCH_CHECK(nf >= 1 && f0 >= 0 && f0 < t && (nf == 1 || (fstep >= 1 && fstep <= INT32_MAX && f0 + (nf - 1) * fstep <= t - 1)),
               what, ": frames (", f0, ", ", nf, ", ", fstep, ") outside a clip of ", t);
-  if (!hist) return {x.size(0), nf, TC_COLOUR_STATS};
-  colour_hw_check(x, what);
-  return {x.size(0), nf, 3, TC_COLOUR_BINS};
-}
-
-// colour_stats / colour_hist on the CUDA key: P the params struct, `result` its field for the op's tensor
-template <typename P, typename R>
-Tensor colour_frames_cuda(const Tensor& x, int64_t f0, int64_t nf, int64_t fstep, R* P::*result, int64_t (*bytes)(const P*),
-                          int (*entry)(const P*, void*)) {
-  constexpr bool hist = std::is_same_v<P, TcColourHistParams>;
-  const char* what = hist ? "colour_hist" : "colour_stats";
-  TORCH_CHECK(x.is_cuda(), what, ": expected a CUDA tensor (the product path is GPU-only)");
-  TORCH_CHECK(x.scalar_type() == at::kFloat && x.is_contiguous(), what, ": contiguous fp32 (b, 3, t, h, w)");
-  Tensor res = at::empty(colour_frames_shape(x, f0, nf, fstep, hist), x.options().dtype(c10::CppTypeToScalarType<R>::value));
+  if (hist) colour_hw_check(x, what);
+  Tensor res = at::empty(hist ? std::vector<int64_t>{x.size(0), nf, 3, TC_COLOUR_BINS} : std::vector<int64_t>{x.size(0), nf, TC_COLOUR_STATS},
+                         x.options().dtype(c10::CppTypeToScalarType<R>::value));
+  if (x.is_meta()) return res;
   P p = {};
   p.x = x.data_ptr<float>();
   p.b = (int32_t)x.size(0); p.t = (int32_t)x.size(2); p.h = (int32_t)x.size(3); p.w = (int32_t)x.size(4);
   p.f0 = (int32_t)f0; p.nf = (int32_t)nf; p.fstep = nf == 1 ? 1 : (int32_t)fstep;
   p.*result = res.data_ptr<R>();
-  p.workspace_bytes = bytes(&p);
-  Tensor ws = workspace(p.workspace_bytes, x);
-  p.workspace = ws.data_ptr();
-  check_rc(entry(&p, cur_stream()), hist ? "tc_colour_hist" : "tc_colour_stats");
+  launch_ws(p, x, bytes, entry, hist ? "tc_colour_hist" : "tc_colour_stats");
   return res;
 }
 
-Tensor colour_stats_cuda(const Tensor& x, int64_t f0, int64_t nf, int64_t fstep) {
-  return colour_frames_cuda(x, f0, nf, fstep, &TcColourStatsParams::stats, tc_colour_stats_workspace, tc_colour_stats);
+Tensor colour_stats(const Tensor& x, int64_t f0, int64_t nf, int64_t fstep) {
+  return colour_frames(x, f0, nf, fstep, &TcColourStatsParams::stats, tc_colour_stats_workspace, tc_colour_stats);
 }
 
-Tensor colour_stats_meta(const Tensor& x, int64_t f0, int64_t nf, int64_t fstep) {
-  return at::empty(colour_frames_shape(x, f0, nf, fstep, false), x.options().dtype(at::kDouble));
-}
-
-Tensor colour_hist_cuda(const Tensor& x, int64_t f0, int64_t nf, int64_t fstep) {
-  return colour_frames_cuda(x, f0, nf, fstep, &TcColourHistParams::hist, tc_colour_hist_workspace, tc_colour_hist);
-}
-
-Tensor colour_hist_meta(const Tensor& x, int64_t f0, int64_t nf, int64_t fstep) {
-  return at::empty(colour_frames_shape(x, f0, nf, fstep, true), x.options().dtype(at::kInt));
+Tensor colour_hist(const Tensor& x, int64_t f0, int64_t nf, int64_t fstep) {
+  return colour_frames(x, f0, nf, fstep, &TcColourHistParams::hist, tc_colour_hist_workspace, tc_colour_hist);
 }
 
 // What the match and the transfer family share.  An op is the old one (knots null: two reference images per clip) or its knots form.
@@ -796,7 +730,7 @@ void colour_strength_check(const char* what, double strength) {
 }
 
 void colour_device_check(const char* what, const Tensor& x, const Tensor& src, const Tensor& ref, const optional<Tensor>& base) {
-  TORCH_CHECK(x.is_cuda() && src.is_cuda() && ref.is_cuda() && (!base.has_value() || base->is_cuda()), what,
+  TORCH_CHECK(on_device(x, x) && on_device(src, x) && on_device(ref, x) && (!base.has_value() || on_device(*base, x)), what,
               ": expected CUDA tensors (the product path is GPU-only)");
 }
 
@@ -814,10 +748,15 @@ void colour_clip_fill(P& p, const Tensor& x, const Tensor& out, const Tensor& sr
   }
 }
 
-// The match family.  Dtypes are checked on the CUDA key only.
-void colour_match_check(const char* what, const Tensor& x, const Tensor& src, const Tensor& ref, int64_t ref_pixels, int64_t method,
-                        double strength, Knots knots, double max_gain) {
+// The match family.
+template <typename P>
+Pair colour_match_any(const char* what, int (*entry)(const P*, void*), const Tensor& x, const Tensor& src, const Tensor& ref,
+                      int64_t ref_pixels, int64_t method, double strength, Knots knots, double max_gain) {
+  colour_device_check(what, x, src, ref, optional<Tensor>());
   colour_clip_check(x, what);
+  TORCH_CHECK(x.scalar_type() == at::kFloat && x.is_contiguous(), what, ": x: contiguous fp32 (b, 3, t, h, w)");
+  TORCH_CHECK(src.scalar_type() == at::kDouble && src.is_contiguous() && ref.scalar_type() == at::kDouble && ref.is_contiguous(), what,
+              ": src / ref: contiguous float64");
   const int64_t b = x.size(0), t = x.size(2);
   TORCH_CHECK(src.dim() == 3 && src.size(0) == b && src.size(1) == t && src.size(2) == TC_COLOUR_STATS, what, ": src must be (b, t, 9)");
   TORCH_CHECK(ref.dim() == 3 && ref.size(0) == b && ref.size(1) == colour_ref_rows(knots) && ref.size(2) == TC_COLOUR_STATS, what,
@@ -828,21 +767,8 @@ void colour_match_check(const char* what, const Tensor& x, const Tensor& src, co
   TORCH_CHECK(ref_pixels > 0, what, ": ref_pixels ", ref_pixels);
   TORCH_CHECK(max_gain == 0.0 || (max_gain >= 1.0 && std::isfinite(max_gain)), what, ": max_gain ", max_gain,
               ": 0 (no limit) or a finite number >= 1");
-}
-
-Pair colour_match_results(const Tensor& x) {
-  return {at::empty_like(x), at::empty({x.size(0), x.size(2), 12}, x.options())};
-}
-
-template <typename P>
-Pair colour_match_run(const char* what, int (*entry)(const P*, void*), const Tensor& x, const Tensor& src, const Tensor& ref,
-                      int64_t ref_pixels, int64_t method, double strength, Knots knots, double max_gain) {
-  colour_device_check(what, x, src, ref, optional<Tensor>());
-  TORCH_CHECK(x.scalar_type() == at::kFloat && x.is_contiguous(), what, ": x: contiguous fp32 (b, 3, t, h, w)");
-  TORCH_CHECK(src.scalar_type() == at::kDouble && src.is_contiguous() && ref.scalar_type() == at::kDouble && ref.is_contiguous(), what,
-              ": src / ref: contiguous float64");
-  colour_match_check(what, x, src, ref, ref_pixels, method, strength, knots, max_gain);
-  auto [out, coefs] = colour_match_results(x);
+  Tensor out = at::empty_like(x), coefs = at::empty({b, t, 12}, x.options());
+  if (x.is_meta()) return {out, coefs};
   P p = {};
   colour_clip_fill(p, x, out, src, ref, ref_pixels, strength, knots);
   p.method = (int32_t)method;
@@ -852,29 +778,20 @@ Pair colour_match_run(const char* what, int (*entry)(const P*, void*), const Ten
   return {out, coefs};
 }
 
-Pair colour_match_cuda(const Tensor& x, const Tensor& src, const Tensor& ref, int64_t ref_pixels, int64_t method, double strength) {
-  return colour_match_run("colour_match", tc_colour_match, x, src, ref, ref_pixels, method, strength, nullptr, 0.0);
+Pair colour_match(const Tensor& x, const Tensor& src, const Tensor& ref, int64_t ref_pixels, int64_t method, double strength) {
+  return colour_match_any("colour_match", tc_colour_match, x, src, ref, ref_pixels, method, strength, nullptr, 0.0);
 }
 
-Pair colour_match_meta(const Tensor& x, const Tensor& src, const Tensor& ref, int64_t ref_pixels, int64_t method, double strength) {
-  colour_match_check("colour_match", x, src, ref, ref_pixels, method, strength, nullptr, 0.0);
-  return colour_match_results(x);
+Pair colour_match_knots(const Tensor& x, const Tensor& src, const Tensor& ref, int64_t ref_pixels, int64_t method, double strength,
+                        at::IntArrayRef knots, double max_gain) {
+  return colour_match_any("colour_match_knots", tc_colour_match_knots, x, src, ref, ref_pixels, method, strength, &knots, max_gain);
 }
 
-Pair colour_match_knots_cuda(const Tensor& x, const Tensor& src, const Tensor& ref, int64_t ref_pixels, int64_t method, double strength,
-                             at::IntArrayRef knots, double max_gain) {
-  return colour_match_run("colour_match_knots", tc_colour_match_knots, x, src, ref, ref_pixels, method, strength, &knots, max_gain);
-}
-
-Pair colour_match_knots_meta(const Tensor& x, const Tensor& src, const Tensor& ref, int64_t ref_pixels, int64_t method, double strength,
-                             at::IntArrayRef knots, double max_gain) {
-  colour_match_check("colour_match_knots", x, src, ref, ref_pixels, method, strength, &knots, max_gain);
-  return colour_match_results(x);
-}
-
-// The transfer family.  Dtypes are part of the check that both keys run.
-void colour_transfer_check(const char* what, const Tensor& x, const optional<Tensor>& base, const Tensor& src, const Tensor& ref,
-                           int64_t ref_pixels, double strength, Knots knots) {
+// The transfer family.
+template <typename P>
+Pair colour_transfer_any(const char* what, int (*entry)(const P*, void*), const Tensor& x, const optional<Tensor>& base,
+                         const Tensor& src, const Tensor& ref, int64_t ref_pixels, double strength, Knots knots) {
+  colour_device_check(what, x, src, ref, base);
   colour_clip_check(x, what);
   const int64_t b = x.size(0), t = x.size(2);
   TORCH_CHECK(x.scalar_type() == at::kFloat, what, ": x: fp32 (b, 3, t, h, w)");
@@ -889,91 +806,60 @@ void colour_transfer_check(const char* what, const Tensor& x, const optional<Ten
   colour_strength_check(what, strength);
   TORCH_CHECK(ref_pixels > 0 && ref_pixels <= (int64_t(1) << 26), what, ": ref_pixels ", ref_pixels, " outside [1, 2^26]");
   colour_hw_check(x, what);
-}
-
-Pair colour_transfer_results(const Tensor& x) {
-  return {at::empty_like(x), at::empty({x.size(0), x.size(2), 3, TC_COLOUR_BINS}, x.options())};
-}
-
-template <typename P>
-Pair colour_transfer_run(const char* what, int (*entry)(const P*, void*), const Tensor& x, const optional<Tensor>& base,
-                         const Tensor& src, const Tensor& ref, int64_t ref_pixels, double strength, Knots knots) {
-  colour_device_check(what, x, src, ref, base);
-  colour_transfer_check(what, x, base, src, ref, ref_pixels, strength, knots);
   TORCH_CHECK(x.is_contiguous() && src.is_contiguous() && ref.is_contiguous() && (!base.has_value() || base->is_contiguous()), what,
               ": contiguous tensors");
-  auto [out, table] = colour_transfer_results(x);
+  Tensor out = at::empty_like(x), table = at::empty({b, t, 3, TC_COLOUR_BINS}, x.options());
+  if (x.is_meta()) return {out, table};
   P p = {};
   colour_clip_fill(p, x, out, src, ref, ref_pixels, strength, knots);
-  p.base = base.has_value() ? base->data_ptr<float>() : nullptr;
+  p.base = f32_or_null(base);
   p.table = table.data_ptr<float>();
   check_rc(entry(&p, cur_stream()), (std::string("tc_") + what).c_str());
   return {out, table};
 }
 
-Pair colour_transfer_cuda(const Tensor& x, const optional<Tensor>& base, const Tensor& src, const Tensor& ref, int64_t ref_pixels,
-                          double strength) {
-  return colour_transfer_run("colour_transfer", tc_colour_transfer, x, base, src, ref, ref_pixels, strength, nullptr);
+Pair colour_transfer(const Tensor& x, const optional<Tensor>& base, const Tensor& src, const Tensor& ref, int64_t ref_pixels,
+                     double strength) {
+  return colour_transfer_any("colour_transfer", tc_colour_transfer, x, base, src, ref, ref_pixels, strength, nullptr);
 }
 
-Pair colour_transfer_meta(const Tensor& x, const optional<Tensor>& base, const Tensor& src, const Tensor& ref, int64_t ref_pixels,
-                          double strength) {
-  colour_transfer_check("colour_transfer", x, base, src, ref, ref_pixels, strength, nullptr);
-  return colour_transfer_results(x);
-}
-
-Pair colour_transfer_knots_cuda(const Tensor& x, const optional<Tensor>& base, const Tensor& src, const Tensor& ref, int64_t ref_pixels,
-                                double strength, at::IntArrayRef knots) {
-  return colour_transfer_run("colour_transfer_knots", tc_colour_transfer_knots, x, base, src, ref, ref_pixels, strength, &knots);
-}
-
-Pair colour_transfer_knots_meta(const Tensor& x, const optional<Tensor>& base, const Tensor& src, const Tensor& ref, int64_t ref_pixels,
-                                double strength, at::IntArrayRef knots) {
-  colour_transfer_check("colour_transfer_knots", x, base, src, ref, ref_pixels, strength, &knots);
-  return colour_transfer_results(x);
+Pair colour_transfer_knots(const Tensor& x, const optional<Tensor>& base, const Tensor& src, const Tensor& ref, int64_t ref_pixels,
+                           double strength, at::IntArrayRef knots) {
+  return colour_transfer_any("colour_transfer_knots", tc_colour_transfer_knots, x, base, src, ref, ref_pixels, strength, &knots);
 }
 
 // clip_patches: (B, 3, H, W) fp32 -> the bf16 A operand [B * (size / patch)^2, ld] of the CLIP image tower's patch-embedding GEMM
 // (reference condition.py:322-330: kornia resize, (x + 1) / 2, CLIP mean / std; then open_clip's conv1 unfold)
-Tensor clip_patches_cuda(const Tensor& x, int64_t size, int64_t patch, int64_t ld, at::ArrayRef<double> mean, at::ArrayRef<double> std,
-                         bool antialias) {
-  TORCH_CHECK(x.is_cuda(), "clip_patches: expected a CUDA tensor (the product path is GPU-only)");
+Tensor clip_patches(const Tensor& x, int64_t size, int64_t patch, int64_t ld, at::ArrayRef<double> mean, at::ArrayRef<double> std,
+                    bool antialias) {
+  TORCH_CHECK(on_device(x, x), "clip_patches: expected a CUDA tensor (the product path is GPU-only)");
   TORCH_CHECK(x.scalar_type() == at::kFloat && x.is_contiguous() && x.dim() == 4 && x.size(1) == 3, "clip_patches: contiguous fp32 (B, 3, H, W)");
   TORCH_CHECK(mean.size() == 3 && std.size() == 3, "clip_patches: mean and std have three entries");
   TORCH_CHECK(size > 0 && patch > 0 && size % patch == 0 && ld >= 3 * patch * patch, "clip_patches: size ", size, ", patch ", patch, ", ld ", ld);
   const int64_t g = size / patch;
   Tensor out = at::empty({x.size(0) * g * g, ld}, x.options().dtype(at::kBFloat16));
+  if (x.is_meta()) return out;
   TcClipPatchesParams p = {};
   p.x = x.data_ptr<float>(); p.out = reinterpret_cast<tc_bf16*>(out.data_ptr());
   p.b = (int32_t)x.size(0); p.h = (int32_t)x.size(2); p.w = (int32_t)x.size(3);
   p.size = (int32_t)size; p.patch = (int32_t)patch; p.ld = (int32_t)ld; p.antialias = antialias ? 1 : 0;
   for (int i = 0; i < 3; ++i) { p.mean[i] = (float)mean[i]; p.std[i] = (float)std[i]; }
-  p.workspace_bytes = tc_clip_patches_workspace(&p);
-  Tensor ws = workspace(p.workspace_bytes, x);
-  p.workspace = ws.data_ptr();
-  check_rc(tc_clip_patches(&p, cur_stream()), "tc_clip_patches");
+  launch_ws(p, x, tc_clip_patches_workspace, tc_clip_patches, "tc_clip_patches");
   return out;
-}
-
-Tensor clip_patches_meta(const Tensor& x, int64_t size, int64_t patch, int64_t ld, at::ArrayRef<double>, at::ArrayRef<double>, bool) {
-  TORCH_CHECK(size > 0 && patch > 0 && size % patch == 0, "clip_patches: size ", size, ", patch ", patch);
-  const int64_t g = size / patch;
-  return at::empty({x.size(0) * g * g, ld}, x.options().dtype(at::kBFloat16));
 }
 
 // Per-clip Philox noise (tc_randn_clips, additive within ABI 14): (b, ...) fp32 on the current device, clip i from seeds[i] alone;
 // raw: the Philox words as int32 bit patterns.  A seed from 2^63 on arrives as its two's-complement int64.  The op takes no
-// tensor, so the dispatcher cannot read a backend off its arguments: the BackendSelect kernel below sends it to the CUDA key.
-void randn_check(at::IntArrayRef seeds, at::IntArrayRef shape, int64_t stream) {
+// tensor, so the dispatcher cannot read a backend off its arguments: the BackendSelect kernel below sends it to the CUDA key, and
+// the one body takes its device from the key it was reached by (Meta: by naming that key in a redispatch).
+Tensor randn_clips(c10::DispatchKeySet keys, at::IntArrayRef seeds, at::IntArrayRef shape, int64_t stream, double scale, bool raw) {
   TORCH_CHECK(!shape.empty() && (int64_t)seeds.size() == shape[0], "randn_clips: shape (b, ...) with one seed per clip");
   for (int64_t v : shape) TORCH_CHECK(v > 0, "randn_clips: sizes must be positive");
   TORCH_CHECK(shape[0] <= INT32_MAX, "randn_clips: b ", shape[0]);
   TORCH_CHECK(stream >= 0 && stream <= (int64_t)UINT32_MAX, "randn_clips: stream ", stream, " outside [0, 2^32)");
-}
-
-Tensor randn_clips_cuda(at::IntArrayRef seeds, at::IntArrayRef shape, int64_t stream, double scale, bool raw) {
-  randn_check(seeds, shape, stream);
-  Tensor out = at::empty(shape, at::TensorOptions().device(at::kCUDA).dtype(raw ? at::kInt : at::kFloat));
+  const bool meta = keys.has_backend(c10::BackendComponent::MetaBit);
+  Tensor out = at::empty(shape, at::TensorOptions().device(meta ? at::kMeta : at::kCUDA).dtype(raw ? at::kInt : at::kFloat));
+  if (meta) return out;
   std::vector<uint64_t> held(seeds.begin(), seeds.end());
   TcRandnParams p = {};
   p.out = reinterpret_cast<float*>(out.data_ptr());
@@ -984,15 +870,45 @@ Tensor randn_clips_cuda(at::IntArrayRef seeds, at::IntArrayRef shape, int64_t st
   return out;
 }
 
-Tensor randn_clips_meta(at::IntArrayRef seeds, at::IntArrayRef shape, int64_t stream, double, bool raw) {
-  randn_check(seeds, shape, stream);
-  return at::empty(shape, at::TensorOptions().device(at::kMeta).dtype(raw ? at::kInt : at::kFloat));
-}
-
 Tensor randn_clips_select(at::IntArrayRef seeds, at::IntArrayRef shape, int64_t stream, double scale, bool raw) {
   static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("tooncrafter::randn_clips", "")
                        .typed<Tensor(at::IntArrayRef, at::IntArrayRef, int64_t, double, bool)>();
   return op.redispatch(c10::DispatchKeySet(c10::DispatchKey::CUDA), seeds, shape, stream, scale, raw);
+}
+
+// The operators, named once: the same function under the CUDA key and under the Meta key.
+void register_ops(torch::Library& m) {
+  m.impl("gemm", gemm);
+  m.impl("quant_mxfp8", quant_mxfp8);
+  m.impl("gemm_mx", gemm_mx);
+  m.impl("attention", attention);
+  m.impl("attention_temporal", attention_temporal);
+  m.impl("attention_temporal_rel", attention_temporal_rel);
+  m.impl("attention_q8", attention_q8);
+  m.impl("groupnorm", groupnorm);
+  m.impl("layernorm", layernorm);
+  m.impl("groupnorm_pf", groupnorm_pf);
+  m.impl("layernorm_pf", layernorm_pf);
+  m.impl("ddim_step", ddim_step_any<false>);
+  m.impl("ddim_step_eps", ddim_step_any<true>);
+  m.impl("ddim_step_ms", ddim_step_ms_any<false>);
+  m.impl("ddim_step_ms_eps", ddim_step_ms_any<true>);
+  m.impl("ddim_blend", ddim_blend);
+  m.impl("frames_from_u8", frames_from_u8);
+  m.impl("frames_from_yuv", frames_from_yuv);
+  m.impl("frames_to_u8", frames_to_u8);
+  m.impl("frames_to_yuv", frames_to_yuv);
+  m.impl("colour_stats", colour_stats);
+  m.impl("colour_match", colour_match);
+  m.impl("colour_hist", colour_hist);
+  m.impl("colour_transfer", colour_transfer);
+  m.impl("colour_match_knots", colour_match_knots);
+  m.impl("colour_transfer_knots", colour_transfer_knots);
+  m.impl("clip_patches", clip_patches);
+  m.impl("randn_clips", randn_clips);
+  m.impl("ff_geglu_fused", ff_geglu_fused);
+  m.impl("temporal_attn_fused", temporal_attn_fused);
+  m.impl("temporal_qkv_attn", temporal_qkv_attn);
 }
 
 }  // namespace
@@ -1048,68 +964,9 @@ TORCH_LIBRARY(tooncrafter, m) {
   m.def("abi_version() -> int");
 }
 
-TORCH_LIBRARY_IMPL(tooncrafter, CUDA, m) {
-  m.impl("gemm", gemm_cuda);
-  m.impl("quant_mxfp8", quant_mxfp8_cuda);
-  m.impl("gemm_mx", gemm_mx_cuda);
-  m.impl("attention", attention_cuda);
-  m.impl("attention_temporal", attention_temporal_cuda);
-  m.impl("attention_temporal_rel", attention_temporal_rel_cuda);
-  m.impl("attention_q8", attention_q8_cuda);
-  m.impl("groupnorm", groupnorm_cuda);
-  m.impl("layernorm", layernorm_cuda);
-  m.impl("groupnorm_pf", groupnorm_pf_cuda);
-  m.impl("layernorm_pf", layernorm_pf_cuda);
-  m.impl("ddim_step", ddim_step_any<false>);
-  m.impl("ddim_step_eps", ddim_step_any<true>);
-  m.impl("ddim_step_ms", ddim_step_ms_any<false>);
-  m.impl("ddim_step_ms_eps", ddim_step_ms_any<true>);
-  m.impl("ddim_blend", ddim_blend_cuda);
-  m.impl("frames_from_u8", frames_from_u8_cuda);
-  m.impl("frames_from_yuv", frames_from_yuv_cuda);
-  m.impl("frames_to_u8", frames_to_u8_cuda);
-  m.impl("frames_to_yuv", frames_to_yuv_cuda);
-  m.impl("colour_stats", colour_stats_cuda);
-  m.impl("colour_match", colour_match_cuda);
-  m.impl("colour_hist", colour_hist_cuda);
-  m.impl("colour_transfer", colour_transfer_cuda);
-  m.impl("colour_match_knots", colour_match_knots_cuda);
-  m.impl("colour_transfer_knots", colour_transfer_knots_cuda);
-  m.impl("clip_patches", clip_patches_cuda);
-  m.impl("randn_clips", randn_clips_cuda);
-  m.impl("ff_geglu_fused", ff_geglu_fused_cuda);
-  m.impl("temporal_attn_fused", temporal_attn_fused_cuda);
-  m.impl("temporal_qkv_attn", temporal_qkv_attn_cuda);
-}
+TORCH_LIBRARY_IMPL(tooncrafter, CUDA, m) { register_ops(m); }
 
-TORCH_LIBRARY_IMPL(tooncrafter, Meta, m) {
-  m.impl("gemm", gemm_meta);
-  m.impl("quant_mxfp8", quant_mxfp8_meta);
-  m.impl("gemm_mx", gemm_mx_meta);
-  m.impl("attention", attention_meta);
-  m.impl("attention_temporal", attention_temporal_meta);
-  m.impl("attention_temporal_rel", attention_temporal_rel_meta);
-  m.impl("attention_q8", attention_q8_meta);
-  for (const char* name : {"groupnorm", "layernorm", "groupnorm_pf", "layernorm_pf", "ddim_step", "ddim_step_eps", "ddim_step_ms",
-                           "ddim_step_ms_eps"})
-    m.impl(name, torch::CppFunction::makeFromBoxedFunction<&like_first_meta>());
-  m.impl("ddim_blend", ddim_blend_meta);
-  m.impl("frames_from_u8", frames_from_u8_meta);
-  m.impl("frames_from_yuv", frames_from_yuv_meta);
-  m.impl("frames_to_u8", frames_to_u8_meta);
-  m.impl("frames_to_yuv", frames_to_yuv_meta);
-  m.impl("colour_stats", colour_stats_meta);
-  m.impl("colour_match", colour_match_meta);
-  m.impl("colour_hist", colour_hist_meta);
-  m.impl("colour_transfer", colour_transfer_meta);
-  m.impl("colour_match_knots", colour_match_knots_meta);
-  m.impl("colour_transfer_knots", colour_transfer_knots_meta);
-  m.impl("clip_patches", clip_patches_meta);
-  m.impl("randn_clips", randn_clips_meta);
-  m.impl("ff_geglu_fused", ff_geglu_fused_meta);
-  m.impl("temporal_attn_fused", temporal_attn_fused_meta);
-  m.impl("temporal_qkv_attn", temporal_qkv_attn_meta);
-}
+TORCH_LIBRARY_IMPL(tooncrafter, Meta, m) { register_ops(m); }
 
 TORCH_LIBRARY_IMPL(tooncrafter, BackendSelect, m) {
   m.impl("randn_clips", randn_clips_select);

@@ -36,6 +36,11 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
 
 
+def attn_scale(scale) -> float:
+    """The softmax scale of an attention call: the caller's, or 1 / sqrt(64) (every attention kernel has 64-wide heads)."""
+    return float(64 ** -0.5 if scale is None else scale)
+
+
 def _rows_view(t: torch.Tensor, dtype=BF16):
     if t.dim() != 2 or t.stride(1) != 1 or t.dtype != dtype:
         raise ValueError(f"expected a 2-D {dtype} rows tensor with unit column stride, got "
@@ -360,7 +365,7 @@ class HipOps:
         p = TcTbParams()
         p.b, p.t, p.hw, p.c, p.heads, p.ldx, p.ldo = int(b), int(t), int(hw), int(c), int(heads), int(ldx), int(ldo)
         p.ln, p.ln_eps = (0, 0.0) if ln_eps is None else (1, float(ln_eps))
-        p.scale = float(64 ** -0.5 if scale is None else scale)
+        p.scale = attn_scale(scale)
         return p
 
     def temporal_attn_fused_eligible(self, *, b, t, hw, c, heads, ldx=None) -> bool:
@@ -395,7 +400,7 @@ class HipOps:
     def _tqa_params(self, b, t, hw, c, heads, ldx, ldo, scale):
         p = TcTqaParams()
         p.b, p.t, p.hw, p.c, p.heads, p.ldx, p.ldo = int(b), int(t), int(hw), int(c), int(heads), int(ldx), int(ldo)
-        p.scale = float(64 ** -0.5 if scale is None else scale)
+        p.scale = attn_scale(scale)
         return p
 
     def temporal_qkv_attn_eligible(self, *, b, t, hw, c, heads, ldx=None) -> bool:
@@ -534,7 +539,7 @@ class HipOps:
         p.q_sb, p.k_sb, p.v_sb, p.o_sb = lq * q.stride(0), lk * k.stride(0), lk * v.stride(0), lq * out.stride(0)
         p.kv_bdiv = kv_bdiv
         p.accumulate = 1 if accumulate else 0
-        p.scale = float(scale if scale is not None else 64 ** -0.5)
+        p.scale = attn_scale(scale)
         if k2 is not None:
             k2, v2 = _rows_view(k2), _rows_view(v2)
             kvb2 = (batch + kv2_bdiv - 1) // kv2_bdiv
@@ -560,7 +565,7 @@ class HipOps:
         p.batch, p.heads, p.lq, p.lk = batch, heads, lq, lk
         p.q_ss, p.k_ss, p.v_ss, p.o_ss = q.stride(0), k.stride(0), v.stride(0), out.stride(0)
         p.q_sb, p.k_sb, p.v_sb, p.o_sb = lq * q.stride(0), lk * k.stride(0), lk * v.stride(0), lq * out.stride(0)
-        p.scale = float(scale if scale is not None else 64 ** -0.5)
+        p.scale = attn_scale(scale)
         return p
 
     def attention_q8(self, q, k, v, *, batch, heads, lq, lk, scale=None):
@@ -585,7 +590,7 @@ class HipOps:
             raise ValueError("attention_temporal: qkv must be contiguous [b*t*hw, 3*C]")
         out = torch.empty((b * t * hw, cdim), dtype=BF16, device=qkv.device)
         _lib.check(self.lib.tc_attn_temporal(qkv.data_ptr(), out.data_ptr(), b, t, hw, heads,
-                                             float(scale if scale is not None else 64 ** -0.5), _stream()),
+                                             attn_scale(scale), _stream()),
                    "tc_attn_temporal")
         return out
 
@@ -604,7 +609,7 @@ class HipOps:
         out = torch.empty((b * t * hw, cdim), dtype=BF16, device=qkv.device)
         p = _lib.TcAttnTemporalRelParams(qkv=qkv.data_ptr(), out=out.data_ptr(), rel_k=_ptr(rel_k), rel_v=_ptr(rel_v),
                                          b=b, t=t, hw=hw, heads=heads, max_rel=int(max_rel), causal=int(bool(causal)),
-                                         scale=float(scale if scale is not None else 64 ** -0.5))
+                                         scale=attn_scale(scale))
         _lib.check(self.lib.tc_attn_temporal_rel(C.byref(p), _stream()), "tc_attn_temporal_rel")
         return out
 

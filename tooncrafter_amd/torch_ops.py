@@ -1,10 +1,12 @@
 """PyTorch-ROCm custom-op binding of the hot path: `torch.ops.tooncrafter.*` (csrc/torch_ops.cpp, TORCH_LIBRARY).
 
-The same `extern "C"` entry points as the ctypes binding (ops.HipOps), registered as torch operators with CUDA(HIP)
-and Meta implementations: current-stream pickup and output allocation happen in C++, and the ops can be shape-checked
-/ traced on the `meta` device without a GPU.  `TorchLibOps` is a drop-in for `HipOps`; select it with
-`TC_BINDING=torch` (or `ops.set_backend(TorchLibOps())`).  Calls that use features the functional op schema does not
-carry (an explicit `out=` buffer, batched GEMMs, accumulate) go through the inherited ctypes methods.
+The same `extern "C"` entry points as the ctypes binding (ops.HipOps), registered as torch operators.  Each operator
+is one C++ function under the CUDA(HIP) key and the Meta key: current-stream pickup and output allocation happen in
+C++, and on the `meta` device the same function checks the request and infers the result without a GPU, so a trace
+or export refuses what a launch would refuse.  `TorchLibOps` is a drop-in for `HipOps` and the default binding
+(`ops.backend()`; `TC_BINDING=ctypes` selects the other, as does `ops.set_backend(HipOps())`).  Calls that use features
+the functional op schema does not carry (an explicit `out=` buffer, batched GEMMs, accumulate) go through the
+inherited ctypes methods.
 """
 from __future__ import annotations
 
@@ -14,7 +16,7 @@ import torch
 
 from . import _lib
 from ._lib import ACT_NONE
-from .ops import HipOps
+from .ops import HipOps, attn_scale
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libtooncrafter_torch.so")
@@ -78,32 +80,32 @@ class TorchLibOps(HipOps):
         if out is not None or accumulate:
             return super().attention(q, k, v, batch=batch, heads=heads, lq=lq, lk=lk, kv_bdiv=kv_bdiv, out=out,
                                      accumulate=accumulate, scale=scale, k2=k2, v2=v2, lk2=lk2, kv2_bdiv=kv2_bdiv)
-        return self.t.attention(q, k, v, batch, heads, lq, lk, kv_bdiv, float(64 ** -0.5 if scale is None else scale),
+        return self.t.attention(q, k, v, batch, heads, lq, lk, kv_bdiv, attn_scale(scale),
                                 k2, v2, int(lk2), int(kv2_bdiv))
 
     def attention_q8(self, q, k, v, *, batch, heads, lq, lk, scale=None):
-        out = self.t.attention_q8(q, k, v, int(batch), int(heads), int(lq), int(lk), float(64 ** -0.5 if scale is None else scale))
+        out = self.t.attention_q8(q, k, v, int(batch), int(heads), int(lq), int(lk), attn_scale(scale))
         self.fp8_calls["attn_q8"] += 1
         return out
 
     def attention_temporal(self, qkv, *, b, t, hw, heads, scale=None):
-        return self.t.attention_temporal(qkv, b, t, hw, heads, float(64 ** -0.5 if scale is None else scale))
+        return self.t.attention_temporal(qkv, b, t, hw, heads, attn_scale(scale))
 
     def attention_temporal_rel(self, qkv, rel_k, rel_v, *, b, t, hw, heads, max_rel, causal, scale=None):
         return self.t.attention_temporal_rel(qkv, rel_k, rel_v, int(b), int(t), int(hw), int(heads), int(max_rel), bool(causal),
-                                             float(64 ** -0.5 if scale is None else scale))
+                                             attn_scale(scale))
 
     def ff_geglu_fused(self, x, w1, b1, w2, b2, *, ln_eps=None):
         return self.t.ff_geglu_fused(x, w1, b1, w2, b2, -1.0 if ln_eps is None else float(ln_eps))
 
     def temporal_attn_fused(self, x, wqkv, bqkv, wo, bo, *, b, t, hw, heads, ln_eps=None, scale=None):
         return self.t.temporal_attn_fused(x, wqkv, bqkv, wo, bo, int(b), int(t), int(hw), int(heads),
-                                          -1.0 if ln_eps is None else float(ln_eps), float(64 ** -0.5 if scale is None else scale))
+                                          -1.0 if ln_eps is None else float(ln_eps), attn_scale(scale))
 
     def temporal_qkv_attn(self, x, wqkv, bqkv=None, *, b, t, hw, heads, scale=None, out=None):
         if out is not None:                                  # an explicit result buffer: the ctypes method (the op schema is functional)
             return super().temporal_qkv_attn(x, wqkv, bqkv, b=b, t=t, hw=hw, heads=heads, scale=scale, out=out)
-        return self.t.temporal_qkv_attn(x, wqkv, bqkv, int(b), int(t), int(hw), int(heads), float(64 ** -0.5 if scale is None else scale))
+        return self.t.temporal_qkv_attn(x, wqkv, bqkv, int(b), int(t), int(hw), int(heads), attn_scale(scale))
 
     def groupnorm(self, x, gamma, beta, *, samples, rows, eps, silu=False, part=None, prefetch=None, prefetch_linear=False):
         if part is not None:
