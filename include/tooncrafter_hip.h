@@ -999,6 +999,70 @@ typedef struct TcColourTransferKnotsParams {
  * [1, TC_TEMPORAL_MAX_FRAMES], knots not strictly increasing or outside [0, t).  Nothing is launched or written on a refusal. */
 int tc_colour_transfer_knots(const TcColourTransferKnotsParams* p, void* stream);
 
+/* ---- Frame deltas: how much consecutive keyframes differ, measured on the surfaces a decoder leaves (additive within ABI 14:
+ * one struct, two symbols).  What a timeline needs to know where NOT to interpolate -- a scene cut, a held drawing -- without
+ * pulling the surfaces to the host.  THE RULE, stated once (restated with numpy integers for the tests:
+ * tests/frame_delta_ref.py):
+ *
+ * Images.  n images of h x w pixels in one of four layouts.  Pointers, pitches, image strides and the chroma size
+ * ch = (h + 1) / 2, cw = (w + 1) / 2 mean what they mean in TcFramesYuvParams (I420: y, c0 = Cb, c1 = Cr; NV12 / P010: y and
+ * c0 = interleaved Cb, Cr, c1 NULL).  TC_PIXFMT_RGB24: y is the packed (n, h, w, 3) image, pitch_y >= 3 w, c0 = c1 = NULL and
+ * pitch_c / image_stride_c are not read.
+ *
+ * Components.  Planar formats: 0 = Y (S_0 = h w samples), 1 = Cb, 2 = Cr (S_1 = S_2 = ch cw samples).  RGB24: R, G, B
+ * (S_c = h w each).
+ *
+ * The 8-bit value of a sample is the byte itself; for P010 it is word >> 8 (the upper byte of the little-endian word), so a
+ * P010 surface holding v << 8, whatever its low eight bits, gives exactly the NV12 numbers of v.  (tc_frames_from_yuv reads
+ * ten bits, word >> 6; a measure of difference needs no more than eight.)
+ *
+ * hist[i][c][k], k < TC_DELTA_BINS = 64: the number of samples of component c of image i with v >> 2 == k.  Exact int32.
+ *
+ * delta[p][c], for the pair (image p, image p + lag), 0 <= p < n - lag, over the samples a of image p and b of image p + lag
+ * at the same place, is three int64:
+ *   [0] sad      sum of |a - b|;
+ *   [1] changed  the number of samples with |a - b| > tau;
+ *   [2] hist_l1  sum over k of |hist[p][c][k] - hist[p + lag][c][k]|.
+ *
+ * All results are exact integers: no order of summation is part of the result, the width of the loads is not, and nothing
+ * depends on what hist, delta or the workspace held before the call.
+ *
+ * Exact consequences (checked on the numpy statement and on the device): equal images give sad = changed = hist_l1 = 0; an
+ * image of 0 against an image of 255 gives sad = 255 S_c, changed = S_c (tau < 255), hist_l1 = 2 S_c; sum_k hist = S_c.
+ *
+ * Two launches: per-part counts (a histogram per wave in LDS, integer LDS atomics; |a - b| four bytes at a time), then the sum
+ * of the parts in int64 and hist_l1.  A part is at most 3 * 2^18 samples, so its int32 counters cannot overflow (255 * 3 * 2^18
+ * < 2^31).  No memset, no global atomic, no allocation, no synchronisation, no host read of device memory: safe to capture in
+ * a hipGraph.  16-byte loads where every plane base, pitch and image stride is 16-byte aligned, byte loads otherwise and at
+ * the end of a row; the numbers are the same.  Every sample is read at most twice: once as a, once as b.
+ * workspace: tc_frame_deltas_workspace bytes = n * P * 3 * 66 int32, P the parts of one image (0 for a request that is refused
+ * for anything but its workspace).  n <= lag is legal: histograms only, delta is not touched and may be NULL.
+ * TC_EINVAL: NULL p / y / hist, NULL delta with n > lag, c0 / c1 not as the format says, an unknown format, n <= 0, lag < 1,
+ * tau outside [0, 255], a size <= 0, a pitch below the row's bytes (3 w; w; 2 w for P010; chroma cw, 2 cw, 4 cw for I420,
+ * NV12, P010), image_stride_y < h * pitch_y, image_stride_c < ch * pitch_c; TC_EALIGN: a P010 pointer, pitch or image stride
+ * that is not 2-byte aligned, hist not 4-byte aligned, delta (n > lag) or the workspace not 8-byte aligned; TC_ESHAPE:
+ * h * w > 2^26 or more than 2^31 - 1 blocks in all; TC_EWORKSPACE: workspace NULL or too small.  Nothing is launched or
+ * written on a refusal.
+ *
+ * Not offered: a judgement.  These are counts; what makes a cut or a hold of them is the caller's rule (clip.ShotRule, whose
+ * default thresholds nobody has measured on real footage).  A dissolve or a fade is a gradual change and no cut by any count
+ * of one pair. */
+#define TC_DELTA_BINS 64
+typedef struct TcFrameDeltaParams {
+  const void* y;               /* n luma planes, or n packed RGB images */
+  const void* c0;              /* Cb (I420) or interleaved Cb, Cr (NV12, P010); NULL for RGB24 */
+  const void* c1;              /* Cr (I420), else NULL */
+  int64_t image_stride_y, image_stride_c;   /* bytes from one image to the next */
+  int32_t pitch_y, pitch_c;    /* bytes from one row to the next */
+  int32_t format;              /* TC_PIXFMT_RGB24 / I420 / NV12 / P010 */
+  int32_t n, h, w, lag, tau;
+  int32_t* hist;               /* [n][3][TC_DELTA_BINS], written by the call */
+  int64_t* delta;              /* [n - lag][3][3]: sad, changed, hist_l1; written by the call */
+  void* workspace; int64_t workspace_bytes;
+} TcFrameDeltaParams;
+int64_t tc_frame_deltas_workspace(const TcFrameDeltaParams* p);
+int tc_frame_deltas(const TcFrameDeltaParams* p, void* stream);
+
 /* introspection */
 int tc_abi_version(void);
 const char* tc_build_info(void);

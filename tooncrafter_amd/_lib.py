@@ -252,6 +252,20 @@ class TcColourTransferKnotsParams(C.Structure):
     _fields_ = TcColourTransferParams._fields_ + [("nk", C.c_int32), ("knot", C.c_int32 * TC_TEMPORAL_MAX_FRAMES)]
 
 
+class TcFrameDeltaParams(C.Structure):
+    """64-bin histograms of n RGB / I420 / NV12 / P010 images and, per pair (p, p + lag) and component, sad / changed / hist_l1
+    (tc_frame_deltas; additive within ABI 14)."""
+    _fields_ = [
+        ("y", C.c_void_p), ("c0", C.c_void_p), ("c1", C.c_void_p),
+        ("image_stride_y", C.c_int64), ("image_stride_c", C.c_int64),
+        ("pitch_y", C.c_int32), ("pitch_c", C.c_int32), ("format", C.c_int32),
+        ("n", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("lag", C.c_int32), ("tau", C.c_int32),
+        ("hist", C.c_void_p), ("delta", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+    ]
+
+
+TC_DELTA_BINS = 64                                       # include/tooncrafter_hip.h: bins per component of tc_frame_deltas
 TC_COLOUR_BINS = 1024                                   # include/tooncrafter_hip.h: bins per channel of tc_colour_hist
 TC_COLOUR_STATS = 9                                      # include/tooncrafter_hip.h: doubles per frame of tc_colour_stats
 TC_COLOUR_METHODS = {"mean_std": 0, "mkl": 1}            # TC_COLOUR_MEAN_STD / TC_COLOUR_MKL
@@ -350,6 +364,8 @@ SYMBOLS = {
     "tc_colour_transfer": (C.c_int, [C.POINTER(TcColourTransferParams), C.c_void_p]),
     "tc_colour_match_knots": (C.c_int, [C.POINTER(TcColourMatchKnotsParams), C.c_void_p]),
     "tc_colour_transfer_knots": (C.c_int, [C.POINTER(TcColourTransferKnotsParams), C.c_void_p]),
+    "tc_frame_deltas_workspace": (C.c_int64, [C.POINTER(TcFrameDeltaParams)]),
+    "tc_frame_deltas": (C.c_int, [C.POINTER(TcFrameDeltaParams), C.c_void_p]),
     "tc_gemm_ws_eligible": (C.c_int, [C.POINTER(TcGemmParams)]),
     "tc_gemm_gn_rows": (C.c_int, [C.POINTER(TcGemmParams)]),
     "tc_groupnorm_part": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,

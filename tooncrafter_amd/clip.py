@@ -423,8 +423,110 @@ def timeline_layout(keyframes: int, t: int, batch: int, out_hw, fmt: str, colour
     return segments * (t - 1) + 1, frame, [(i, min(batch, segments - i)) for i in range(0, segments, batch)]
 
 
+SHOT_LABELS = ("tween", "cut", "hold")
+
+
+@dataclass(frozen=True)
+class ShotRule:
+    """What `find_shots` makes of tc_frame_deltas' counts for one segment (keyframe i -> i + 1), S_c the samples of component c:
+      moved = sum_c changed_c / sum_c S_c     the share of samples that differ by more than `tau` code values;
+      mad   = sum_c sad_c / sum_c S_c         the mean absolute difference in code values;
+      hist  = max_c hist_l1_c / (2 S_c)       the largest share of a component's 64-bin histogram that changed place.
+    "hold" if moved <= hold_moved; otherwise "cut" if hist >= cut_hist and mad >= cut_mad; otherwise "tween".  The comparisons
+    are made in exact rational arithmetic on the thresholds as written (`Fraction(str(v))`), so a tie is a tie.
+    The defaults are starting values.  Nobody has measured them on real footage: no claim is made that they find the cuts or
+    the holds of any source.  A dissolve or a fade is a gradual change and is not a cut by this rule."""
+    tau: int = 8
+    hold_moved: float = 0.002
+    cut_hist: float = 0.35
+    cut_mad: float = 20.0
+
+    def __post_init__(self):
+        import numbers
+        if isinstance(self.tau, bool) or not isinstance(self.tau, numbers.Integral) or not 0 <= int(self.tau) <= 255:
+            raise ValueError(f"ShotRule: tau {self.tau!r}: an integer in [0, 255]")
+        for name in ("hold_moved", "cut_hist", "cut_mad"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, numbers.Real) or not 0 <= v < float("inf"):
+                raise ValueError(f"ShotRule: {name} {v!r}: a finite number >= 0")
+
+
+@dataclass(frozen=True)
+class ShotPlan:
+    """One label per segment of a timeline, "tween" | "cut" | "hold", and -- where `find_shots` made it -- the three measures
+    of `ShotRule` per segment as Python floats (None for a plan written by hand: `ShotPlan(("tween", "cut", "tween"))`)."""
+    labels: tuple
+    moved: Optional[tuple] = None
+    mad: Optional[tuple] = None
+    hist: Optional[tuple] = None
+
+    def __post_init__(self):
+        object.__setattr__(self, "labels", tuple(self.labels))
+        bad = [v for v in self.labels if v not in SHOT_LABELS]
+        if bad:
+            raise ValueError(f"ShotPlan: label {bad[0]!r}: one of {SHOT_LABELS}")
+
+    def distinct(self):
+        """The keyframe indices that begin a new drawing: 0, and i + 1 for every segment i that is not a hold."""
+        return [0] + [i + 1 for i, label in enumerate(self.labels) if label != "hold"]
+
+
+def frame_deltas(keyframes, lag=1, tau=8):
+    """`ops.frame_deltas` for the keyframes of a timeline: (K, h, w, 3) uint8 or a `Planes` of K images -> (delta (K - lag, 3, 3)
+    int64: sad, changed, hist_l1 per pair (i, i + lag) and component; hist (K, 3, 64) int32), device tensors, exact integers,
+    no synchronisation (tc_frame_deltas)."""
+    if not isinstance(keyframes, Planes) and not (isinstance(keyframes, torch.Tensor) and keyframes.dtype == torch.uint8
+                                                  and keyframes.dim() == 4 and keyframes.shape[3] == 3):
+        raise ValueError("frame_deltas: keyframes must be (K, h, w, 3) uint8 or a Planes")
+    return ops.frame_deltas(keyframes, lag=lag, tau=tau)
+
+
+def component_samples(keyframes):
+    """Samples per component of one keyframe: (h w, h w, h w) for RGB frames, (h w, ch cw, ch cw) for a `Planes`."""
+    if isinstance(keyframes, Planes):
+        h, w = keyframes.y.shape[1:3]
+        return (h * w, ((h + 1) // 2) * ((w + 1) // 2), ((h + 1) // 2) * ((w + 1) // 2))
+    h, w = keyframes.shape[1:3]
+    return (h * w,) * 3
+
+
+def label_shots(table, samples, rule=ShotRule()):
+    """The `ShotPlan` of a (K - 1, 3, 3) table of integers (sad, changed, hist_l1 per segment and component) over `samples`
+    = (S_0, S_1, S_2): `ShotRule`'s labels, every comparison cross-multiplied in Python integers and fractions.  Host only."""
+    from fractions import Fraction
+    s = [int(v) for v in samples]
+    if len(s) != 3 or min(s) <= 0:
+        raise ValueError(f"label_shots: samples {samples}: three positive counts")
+    hold, cut_hist, cut_mad = (Fraction(str(v)) for v in (rule.hold_moved, rule.cut_hist, rule.cut_mad))
+    total = sum(s)
+    labels, moved, mad, hist = [], [], [], []
+    for row in table:
+        row = [[int(v) for v in comp] for comp in row]
+        if len(row) != 3 or any(len(comp) != 3 for comp in row):
+            raise ValueError("label_shots: the table must be (segments, 3, 3)")
+        m = Fraction(sum(comp[1] for comp in row), total)
+        d = Fraction(sum(comp[0] for comp in row), total)
+        q = max(Fraction(comp[2], 2 * sc) for comp, sc in zip(row, s))
+        labels.append("hold" if m <= hold else "cut" if q >= cut_hist and d >= cut_mad else "tween")
+        moved.append(float(m))
+        mad.append(float(d))
+        hist.append(float(q))
+    return ShotPlan(tuple(labels), tuple(moved), tuple(mad), tuple(hist))
+
+
+def find_shots(keyframes, rule=ShotRule()):
+    """Where a timeline should not interpolate: one tc_frame_deltas call (lag 1, tau = rule.tau) over the K keyframes, then ONE
+    device-to-host copy of its (K - 1, 3, 3) table -- that copy waits for the device: a synchronisation, so this call cannot be
+    captured in a graph -- and `label_shots` on the host.  Returns the `ShotPlan`.  The default rule's thresholds are unmeasured
+    starting values (`ShotRule`)."""
+    if not isinstance(rule, ShotRule):
+        raise ValueError(f"find_shots: rule: expected a ShotRule, got {type(rule).__name__}")
+    delta, _ = frame_deltas(keyframes, lag=1, tau=rule.tau)
+    return label_shots(delta.cpu().tolist(), component_samples(keyframes), rule)
+
+
 def synthesize_timeline_u8(model, keyframes, latent_shape, *, size, plan: SamplingPlan, prompts=None, fs=24, three_way=False,
-                           out_size=None, out_filter="bicubic", out_fmt="rgb24", out_colour=None, match=None):
+                           out_size=None, out_filter="bicubic", out_fmt="rgb24", out_colour=None, match=None, shots=None):
     """K keyframes in, one video out, all on the device.  `keyframes`: (K, h, w, 3) uint8 or a `Planes` of K images, K >= 2.
     Segment i interpolates keyframe i -> i + 1 (endpoints held); segments run in order, latent_shape[0] per batch (the last
     batch may be smaller), each batch exactly `Conditions.from_uint8` / `from_planes` with first = kf[i : i + n] and
@@ -439,7 +541,15 @@ def synthesize_timeline_u8(model, keyframes, latent_shape, *, size, plan: Sampli
     before it is written: the last frame of segment i and frame 0 of segment i + 1 then have the same target, the inner
     keyframe's statistics ("mkl", "mean_std") or its per-channel quantile function ("hm", "hm_mkl_hm"), so the video does not
     step in colour there.  `max_gain` as in `match_colour`; a timeline pins nothing, so `targets="pinned"` means "ends" here.
-    None: no colour op is called."""
+    None: no colour op is called.
+    shots: None -- every segment is sampled, the calls are exactly those above; a `ShotPlan` (K - 1 labels), or a `ShotRule`, which
+    runs `find_shots` on the keyframes first (one synchronising copy of a small table).  A segment labelled "cut" or "hold" is
+    not sampled: its frames 1 .. t-2 are keyframe i and its frame t-1 is keyframe i + 1 (frame 0 too is keyframe 0 for segment
+    0), each the bytes that the front end (`frames_from_uint8` / `frames_from_planes` at `size`) followed by the writer gives
+    for that keyframe; no colour match is applied to them, they are the targets.  The length and layout stay
+    `timeline_layout`'s.  Sampled segments are batched as maximal runs of consecutive "tween" segments, each run cut into chunks
+    of latent_shape[0]: a batch never spans a skipped segment, and every chunk is the `synthesize_u8` call it replaces.
+    `plan.seeds` and `prompts` stay indexed by the original segment number.  The default rule's thresholds are unmeasured."""
     from dataclasses import replace
     planar = isinstance(keyframes, Planes)
     if not planar and not (isinstance(keyframes, torch.Tensor) and keyframes.dtype == torch.uint8 and keyframes.dim() == 4 and keyframes.shape[3] == 3):
@@ -466,6 +576,26 @@ def synthesize_timeline_u8(model, keyframes, latent_shape, *, size, plan: Sampli
     flat, row = video.view(-1), 3 * ow if out_fmt == "rgb24" else 2 * ow if wide else ow
     write = ops.frames_to_u8 if out_colour is None else (lambda x, **kw: ops.frames_to_yuv(x, colour=out_colour, **kw))
     build = Conditions.from_planes if planar else Conditions.from_uint8
+    if shots is not None:
+        if isinstance(shots, ShotRule):
+            shots = find_shots(keyframes, shots)
+        if not isinstance(shots, ShotPlan):
+            raise ValueError(f"synthesize_timeline_u8: shots: expected a ShotRule or a ShotPlan, got {type(shots).__name__}")
+        if len(shots.labels) != k - 1 or any(v not in SHOT_LABELS for v in shots.labels):
+            raise ValueError(f"synthesize_timeline_u8: shots: labels {shots.labels} for {k - 1} segments, each one of {SHOT_LABELS}")
+        batches, front = [], frames_from_planes if planar else frames_from_uint8
+        for i, label in enumerate(shots.labels):
+            if label != "tween":                      # not sampled: t - 1 frames of keyframe i, then keyframe i + 1, as the writer gives them
+                ends = front(keyframes[i:i + 2], size, [(0, 0), (0, 1)], 2)
+                held = ends[:, :, [0] * (t - 1) + [1]].contiguous()
+                if i == 0:
+                    write(held, size=out_size, filter=out_filter, fmt=out_fmt, frames=(0, 1), out=flat, strides=(row, frame, frame))
+                write(held, size=out_size, filter=out_filter, fmt=out_fmt, frames=(1, t - 1), out=flat[(i * (t - 1) + 1) * frame:],
+                      strides=(row, frame, (t - 1) * frame))
+            elif batches and sum(batches[-1]) == i and batches[-1][1] < latent_shape[0]:
+                batches[-1] = (batches[-1][0], batches[-1][1] + 1)
+            else:
+                batches.append((i, 1))
     for i, n in batches:
         cond = build(model, keyframes[i:i + n], keyframes[i + 1:i + n + 1], size=size, t=t,
                      prompts=None if prompts is None else list(prompts[i:i + n]), fs=fs, guided=plan.scale != 1.0,

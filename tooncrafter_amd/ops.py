@@ -1387,6 +1387,38 @@ class HipOps:
                       strength=strength)
         return self._colour_clip_call(self._COLOUR_TRANSFER, x, dims, out, knots, "table", (3, _lib.TC_COLOUR_BINS), fields)
 
+    def frame_deltas(self, frames_or_planes, lag=1, tau=8):
+        """How much images p and p + lag of n keyframes differ, counted on the surfaces as they lie (tc_frame_deltas): `(n, h, w,
+        3)` uint8 frames (rows may be padded) or a `clip.Planes` (I420, NV12, P010; the 8-bit value of a P010 sample is its upper
+        byte).  Returns (delta (max(n - lag, 0), 3, 3) int64: per pair and component (Y, Cb, Cr or R, G, B) the sum of |a - b|, the
+        number of samples with |a - b| > tau and the L1 distance of the two histograms; hist (n, 3, 64) int32: samples by
+        value >> 2).  Exact integers, device tensors, no synchronisation."""
+        lag, tau = int(lag), int(tau)
+        if lag < 1 or not 0 <= tau <= 255:
+            raise ValueError(f"frame_deltas: lag {lag} (at least 1), tau {tau} (0 .. 255)")
+        if isinstance(frames_or_planes, torch.Tensor):
+            x = frames_or_planes
+            self._check_u8_images(x, "frame_deltas: frames")
+            n, h, w, _ = x.shape
+            fields = dict(y=x.data_ptr(), format=_lib.TC_PIXFMTS["rgb24"], pitch_y=x.stride(1),
+                          image_stride_y=x.stride(0) if n > 1 else h * x.stride(1))
+            device = x.device
+        else:
+            planes = frames_or_planes
+            lay = planes_layout(planes, "frame_deltas: planes")
+            if not planes.y.is_cuda:
+                raise _lib.TooncrafterHipError("frame_deltas: planes: expected CUDA tensors: the product path is GPU-only")
+            n, h, w = lay["n"], lay["sh"], lay["sw"]
+            fields = dict(zip(("y", "c0", "c1"), (plane.data_ptr() for plane in (planes.y,) + tuple(planes.chroma))))
+            fields.update({k: lay[k] for k in ("format", "pitch_y", "pitch_c", "image_stride_y", "image_stride_c")})
+            device = planes.y.device
+        hist = torch.empty((n, 3, _lib.TC_DELTA_BINS), dtype=torch.int32, device=device)
+        delta = torch.empty((max(n - lag, 0), 3, 3), dtype=torch.int64, device=device)
+        p = _lib.TcFrameDeltaParams(n=n, h=h, w=w, lag=lag, tau=tau, hist=hist.data_ptr(),
+                                    delta=delta.data_ptr() if n > lag else None, **fields)
+        self._launch("tc_frame_deltas", p, device)
+        return delta, hist
+
 
 _backend = None
 
