@@ -6,8 +6,12 @@
 // upsample of the source) and Conv3d (3,1,1): activations are channels-last rows, so a
 // convolution tap is just a different source row for the same K-slice of channels.
 //
-// Tiling (wave64): block tile 128x128x64, 4 waves as 2x2, each wave 64x64 = 2x2
-// v_mfma_f32_32x32x16_bf16 sub-tiles (64 fp32 accumulators / lane).  A and B tiles travel
+// Tiling (wave64): block tile 128x128x64, 4 waves as 2x2, each wave 64x64 = 4x4
+// v_mfma_f32_16x16x32_bf16 sub-tiles (64 fp32 accumulators / lane).  That shape SHIPS (TC_GEMM_MFMA, default 16):
+// against the same loop on 2x2 v_mfma_f32_32x32x16_bf16 -- same wave tile, LDS image, fragment bytes, launches and
+// output bits -- the chip holds a 6-11 % higher engine clock (2.02-2.11 -> 2.23-2.27 GHz sustained on the level-1 / 2
+// linear shapes), the kernels run 1.4-5.7 % shorter and the guided forward 1.0-1.2 % (profiles/mfma_shape_kernel_ab.txt,
+// profiles/mfma_shape_forward_ab.txt).  TC_GEMM_MFMA=32 is the other arm, kept as the A/B's reference.  A and B tiles travel
 // global -> LDS directly (buffer_load_dwordx4 ... lds, 1 KiB = 8 tile rows per wave
 // instruction; no staging registers, no ds_write pass) into a double-buffered LDS image whose
 // 16-byte chunks are XOR-swizzled by (row>>1)&7 -- applied on the source side of the DMA --
@@ -24,6 +28,7 @@
 // all N-tiles of one M-tile land on the same XCD (its L2 then serves the A re-reads).
 #include "gemm_common.h"
 #include "gemm_epilogue.h"
+#include "mfma_shape.h"
 
 #include <stdio.h>
 
@@ -50,7 +55,13 @@ constexpr int BK = TC_BK;
 // (0.73-1.02x: co-resident blocks are not in lock-step), and two output tiles per block back to back so that the first
 // tile's store acknowledgements arrive under the second K loop (0.90-1.09x where the grid stays >= 512 blocks, 0.57-0.85x
 // where it does not).)
-template <int GATHER, int TM, int TN, bool PIPE>
+// MF: the MFMA shape the K loop is written on, at the same wave tile, the same LDS image and the same fragment bytes:
+//   32 = TM x TN v_mfma_f32_32x32x16_bf16 tiles, four 16-deep K-slices per K-step;
+//   16 = 2TM x 2TN v_mfma_f32_16x16x32_bf16 tiles, two 32-deep K-slices per K-step (the fragment reads of gemm16.hip on this
+//        image: lane = row lane & 15, chunk 4 ks + (lane >> 4); D: column lane & 15, rows 4 (lane >> 4) + r).
+// TC_GEMM_MFMA selects per call (mfma_shape.h tc_gemm_mfma); gemm8.hip follows the same switch, so the two files always
+// sum every accumulator in the same order.
+template <int GATHER, int TM, int TN, bool PIPE, int MF = 32>
 __global__ __launch_bounds__(256, 2) void gemm_kernel(const TcGemmParams pin, const int splits, const int order,
                                                       const int late_epi) {
   // split-K (blockIdx.y = slice of the K loop): the block emits its raw fp32 partial tile into the
@@ -136,15 +147,52 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const TcGemmParams pin, co
     for (int j = 0; j < TN; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  f32x4 acc16[2 * TM][2 * TN];                     // MF == 16 (the set of the other shape is never touched and costs nothing)
+#pragma unroll
+  for (int i = 0; i < 2 * TM; ++i)
+#pragma unroll
+    for (int j = 0; j < 2 * TN; ++j) acc16[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const int frow = lane & 31;
   const int fhalf = lane >> 5;
+  const int frow16 = lane & 15;
+  const int fq = lane >> 4;
 
   // MFMA fragments are double-buffered in registers: the ds_reads of K-slice kk+1 are issued BEFORE the
   // MFMAs of slice kk, so LDS latency hides under the matrix pipe.
   auto compute = [&](int stage) {
     const char* sa = smem + stage * STAGE_BYTES;
     const char* sb = sa + BM * BK * 2;
+    if constexpr (MF == 16) {
+      // both 32-deep K-slices are read before the first MFMA: (2TM + 2TN) ds_read_b128 per slice for 4 TM TN MFMAs, the
+      // LDS bytes per FLOP of the other shape
+      bf16x8 a16[2][2 * TM], b16[2][2 * TN];
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        const int c = ks * 4 + fq;
+#pragma unroll
+        for (int i = 0; i < 2 * TM; ++i)
+          a16[ks][i] = *reinterpret_cast<const bf16x8*>(sa + lds_off(wm * 32 * TM + i * 16 + frow16, c));
+#pragma unroll
+        for (int j = 0; j < 2 * TN; ++j)
+          b16[ks][j] = *reinterpret_cast<const bf16x8*>(sb + lds_off(wn * 32 * TN + j * 16 + frow16, c));
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+#if defined(TC_ABLATE) && (TC_ABLATE & 1)
+        asm volatile("" ::"v"(a16[ks][0]), "v"(b16[ks][0]));
+        continue;
+#endif
+#pragma unroll
+        for (int i = 0; i < 2 * TM; ++i)
+#pragma unroll
+          for (int j = 0; j < 2 * TN; ++j)
+            acc16[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a16[ks][i], b16[ks][j], acc16[i][j], 0, 0, 0);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      return;
+    }
     bf16x8 af[2][TM], bf[2][TN];
     auto frags = [&](int kk, bf16x8 (&a)[TM], bf16x8 (&b)[TN]) {
       const int c = kk * 2 + fhalf;
@@ -212,10 +260,23 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const TcGemmParams pin, co
   {
     float t = 0.f;
     for (int i = 0; i < TM; ++i) for (int j = 0; j < TN; ++j) for (int r = 0; r < 16; ++r) t += acc[i][j][r];
+    for (int i = 0; i < 2 * TM; ++i) for (int j = 0; j < 2 * TN; ++j) for (int r = 0; r < 4; ++r) t += acc16[i][j][r];
     if (t == 1.2345e30f) reinterpret_cast<float*>(p.c)[tid] = t;
     return;
   }
 #endif
+  if constexpr (MF == 16) {
+#pragma unroll
+    for (int i = 0; i < 2 * TM; ++i)
+#pragma unroll
+      for (int j = 0; j < 2 * TN; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = wm * 32 * TM + i * 16 + 4 * fq + r;
+          const int col = wn * 32 * TN + j * 16 + frow16;
+          cs[row * BN + col] = acc16[i][j][r];
+        }
+  } else {
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -226,6 +287,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const TcGemmParams pin, co
         const int col = wn * 32 * TN + j * 32 + frow;
         cs[row * BN + col] = acc[i][j][r];
       }
+  }
   __syncthreads();
 
   if (fast_epi && !early) {
@@ -317,14 +379,18 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const TcGemmParams p
 
 static void tc_gemm_tile_launch(const TcGemmParams& p, const TcGemmRoute& r, hipStream_t s) {
   const dim3 grid(r.grid[0], r.grid[1], r.grid[2]), block(r.block);
-  const auto go = [&](auto g, auto pipe) {
-    constexpr int G = decltype(g)::value, P = decltype(pipe)::value;
-    if (r.tm == 2 && r.tn == 2) hipLaunchKernelGGL((gemm_kernel<G, 2, 2, P>), grid, block, 0, s, p, r.splits, r.order, r.late_epi);
-    else if (r.tm == 2) hipLaunchKernelGGL((gemm_kernel<G, 2, 1, P>), grid, block, 0, s, p, r.splits, r.order, r.late_epi);
-    else if (r.tn == 2) hipLaunchKernelGGL((gemm_kernel<G, 1, 2, P>), grid, block, 0, s, p, r.splits, r.order, r.late_epi);
-    else hipLaunchKernelGGL((gemm_kernel<G, 1, 1, P>), grid, block, 0, s, p, r.splits, r.order, r.late_epi);
+  const auto go = [&](auto g, auto pipe, auto mf) {
+    constexpr int G = decltype(g)::value, P = decltype(pipe)::value, MF = decltype(mf)::value;
+    if (r.tm == 2 && r.tn == 2) hipLaunchKernelGGL((gemm_kernel<G, 2, 2, P, MF>), grid, block, 0, s, p, r.splits, r.order, r.late_epi);
+    else if (r.tm == 2) hipLaunchKernelGGL((gemm_kernel<G, 2, 1, P, MF>), grid, block, 0, s, p, r.splits, r.order, r.late_epi);
+    else if (r.tn == 2) hipLaunchKernelGGL((gemm_kernel<G, 1, 2, P, MF>), grid, block, 0, s, p, r.splits, r.order, r.late_epi);
+    else hipLaunchKernelGGL((gemm_kernel<G, 1, 1, P, MF>), grid, block, 0, s, p, r.splits, r.order, r.late_epi);
   };
-  tc_with_gather(p.gather, [&](auto g) { if (r.pipe) go(g, std::true_type{}); else go(g, std::false_type{}); });
+  const bool mf16 = tc_gemm_mfma() == 16;          // per call, not part of the route: the instance names stay what they are
+  tc_with_gather(p.gather, [&](auto g) {
+    const auto with_mf = [&](auto pipe) { if (mf16) go(g, pipe, std::integral_constant<int, 16>{}); else go(g, pipe, std::integral_constant<int, 32>{}); };
+    if (r.pipe) with_mf(std::true_type{}); else with_mf(std::false_type{});
+  });
 }
 
 // Where the call goes is decided in gemm_route.cpp; here: validate, route, launch.

@@ -17,8 +17,11 @@
 // matrix beside memory, never matrix beside matrix.  A fragment read is issued a whole interval before its first
 // MFMA, so LDS latency never stands in front of the matrix pipe.
 //
-// Tile 256 x 256 x 64; wave (grp, wc) owns rows grp*128..+128, columns wc*64..+64 = 4 x 2 v_mfma_f32_32x32x16_bf16
-// tiles (128 fp32 accumulators per lane).  A K-tile is four phases, one output quadrant (64 x 32) each:
+// Tile 256 x 256 x 64; wave (grp, wc) owns rows grp*128..+128, columns wc*64..+64 = 8 x 4 v_mfma_f32_16x16x32_bf16
+// tiles (128 fp32 accumulators per lane; the shape that ships -- TC_GEMM_MFMA, default 16, shared with gemm.hip, whose
+// header gives the measurement: profiles/mfma_shape_kernel_ab.txt, mfma_shape_forward_ab.txt; the text below counts the
+// MFMAs of the 32x32x16 arm, 4 x 2 tiles and 8 per phase: the 16x16x32 arm issues twice as many of half the cycles each).
+// A K-tile is four phases, one output quadrant (64 x 32) each:
 //     P0: read A0 B0 -> Q(0,0)    P1: read B1 -> Q(0,1)    P2: read A1 -> Q(1,1)    P3: (B0 kept) -> Q(1,0)
 // 24 ds_read_b128 per wave per K-tile for 32 MFMAs (0.75; the 128x128 kernel needs 1.0).
 // LDS: 2 buffers x 4 HALF-TILES of 16 KiB, organised by quadrant use, not by tile row: A-half h holds tile rows
@@ -43,6 +46,7 @@
 // GEGLU / residual / store), the global operands of pass n+1 requested before pass n is computed.
 #include "gemm_persist.h"
 #include "gemm_epilogue.h"
+#include "mfma_shape.h"
 
 #include <stdlib.h>
 
@@ -58,7 +62,10 @@ constexpr int G8_SLAB = 16 * G8_WN * 4;      // per-wave epilogue slab: 16 rows 
 // but 8 / 16 / 32 set):  1 no MFMAs | 2 no tile requests after the prologue | 4 no fragment reads after the first K-tile
 //   8 no s_setprio | 16 no group stagger (all eight waves in lock-step) | 32 fragment reads waited for BEFORE the barrier
 //   64 no epilogue
-template <int GATHER, int AB = 0>
+// MF: the MFMA shape (gemm.hip; TC_GEMM_MFMA, mfma_shape.h tc_gemm_mfma).  16 = the same phases, quadrants, requests
+// and waits on v_mfma_f32_16x16x32_bf16: a 64 x 32 quadrant is 4 x 2 tiles of 16 x 16 over two 32-deep K-slices -- 16 MFMAs
+// from the same 8 (A) + 4 (B) ds_read_b128, every accumulator summed over K in ascending 32-slices as in gemm.hip.
+template <int GATHER, int AB = 0, int MF = 32>
 __global__ __launch_bounds__(G8_THREADS, 2) void gemm8_kernel(const TcGemmParams p, const int total_tiles, const int stagger) {
   __shared__ __attribute__((aligned(1024))) char smem[2 * G8_BUF + 8 * G8_SLAB];      // 160 KiB: the whole CU
 
@@ -136,7 +143,15 @@ __global__ __launch_bounds__(G8_THREADS, 2) void gemm8_kernel(const TcGemmParams
   };
 
   f32x16 acc[4][2];
+  f32x4 acc16[8][4];                             // MF == 16: 16-row tile mh * 4 + ib, 16-column tile nh * 2 + jb
   auto zero_acc = [&]() {
+    if constexpr (MF == 16) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc16[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      return;
+    }
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -148,12 +163,15 @@ __global__ __launch_bounds__(G8_THREADS, 2) void gemm8_kernel(const TcGemmParams
   // ---- fragment geometry (v_mfma_f32_32x32x16_bf16): lane holds row lane&31 of its 32-row tile, k = 8 (lane>>5) .. +7
   // of the 16-deep slice kk -> one ds_read_b128 at logical chunk 2 kk + (lane>>5).  The rows a wave reads start at
   // multiples of 32, so the swizzle term (row>>1)&7 only depends on the lane.
-  const int frow = lane & 31;
-  const int fhalf = lane >> 5;
+  // MF == 16 (v_mfma_f32_16x16x32_bf16): row lane&15 of a 16-row tile, k = 8 (lane>>4) .. +7 of the 32-deep slice ks ->
+  // logical chunk 4 ks + (lane>>4); tiles start at multiples of 16 rows.  The slots below then mean: fa[ib >> 1][2 (ib & 1)
+  // + ks] = rows 16 ib, slice ks;  fb[2 jb + ks] = W rows 16 jb, slice ks -- the same registers, the same number of reads
+  const int frow = MF == 16 ? (lane & 15) : (lane & 31);
+  const int fhalf = MF == 16 ? (lane >> 4) : (lane >> 5);
   const int sw = (frow >> 1) & 7;
   int coff[4];
 #pragma unroll
-  for (int kk = 0; kk < 4; ++kk) coff[kk] = ((kk * 2 + fhalf) ^ sw) << 4;
+  for (int kk = 0; kk < 4; ++kk) coff[kk] = (((MF == 16 ? (kk & 1) * 4 : kk * 2) + fhalf) ^ sw) << 4;
   const int a_row_off = (grp * 64 + frow) * (TC_BK * 2);
   const int b_row_off = (wc * 32 + frow) * (TC_BK * 2);
 
@@ -170,14 +188,15 @@ __global__ __launch_bounds__(G8_THREADS, 2) void gemm8_kernel(const TcGemmParams
 #pragma unroll
     for (int ib = 0; ib < 2; ++ib)
 #pragma unroll
-      for (int kk = 0; kk < 4; ++kk) fa[ib][kk] = *reinterpret_cast<const bf16x8*>(base + ib * 4096 + coff[kk]);
+      for (int kk = 0; kk < 4; ++kk)
+        fa[ib][kk] = *reinterpret_cast<const bf16x8*>(base + ib * 4096 + (MF == 16 ? (kk >> 1) * 2048 : 0) + coff[kk]);
   };
   auto read_b = [&](auto H_, int boff, bf16x8 (&fb)[4]) {
     constexpr int h = decltype(H_)::value;
     if constexpr ((AB & 4) != 0) { if (abl_started) return; }
     const char* base = smem + boff + (2 + h) * G8_HALF + b_row_off;
 #pragma unroll
-    for (int kk = 0; kk < 4; ++kk) fb[kk] = *reinterpret_cast<const bf16x8*>(base + coff[kk]);
+    for (int kk = 0; kk < 4; ++kk) fb[kk] = *reinterpret_cast<const bf16x8*>(base + (MF == 16 ? (kk >> 1) * 2048 : 0) + coff[kk]);
   };
   auto mma = [&](auto MH_, auto NH_, bf16x8 (&fb)[4]) {
     constexpr int mh = decltype(MH_)::value, nh = decltype(NH_)::value;
@@ -187,11 +206,22 @@ __global__ __launch_bounds__(G8_THREADS, 2) void gemm8_kernel(const TcGemmParams
       return;
     }
     if constexpr ((AB & 8) == 0) __builtin_amdgcn_s_setprio(1);
+    if constexpr (MF == 16) {
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int ib = 0; ib < 4; ++ib)
+#pragma unroll
+          for (int jb = 0; jb < 2; ++jb)
+            acc16[mh * 4 + ib][nh * 2 + jb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                fa[ib >> 1][2 * (ib & 1) + ks], fb[2 * jb + ks], acc16[mh * 4 + ib][nh * 2 + jb], 0, 0, 0);
+    } else {
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk)
 #pragma unroll
       for (int ib = 0; ib < 2; ++ib)
         acc[mh * 2 + ib][nh] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[ib][kk], fb[kk], acc[mh * 2 + ib][nh], 0, 0, 0);
+    }
     if constexpr ((AB & 8) == 0) __builtin_amdgcn_s_setprio(0);
   };
   auto r_end = [&]() {                           // end of an R segment
@@ -284,7 +314,14 @@ __global__ __launch_bounds__(G8_THREADS, 2) void gemm8_kernel(const TcGemmParams
     const int row_w0 = tm * G8_BM + grp * 128;
     auto spill = [&](auto I_, auto H_) {                 // accumulators of pass (i, half) -> slab
       constexpr int i = decltype(I_)::value, half = decltype(H_)::value;
+      if constexpr (MF == 16) {                          // 16-row tile 2 i + half: column frow, rows 4 fhalf + r (gemm16.hip's slab pass)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) slab[(fhalf * 4 + r) * G8_WN + j * 16 + frow] = acc16[2 * i + half][j][r];
+      } else {
       epi_spill32_half<half, 2, G8_WN>(slab, acc[i], frow, fhalf);
+      }
     };
     if (!geglu) {
       // lane -> vector column vc = lane & 7 (8 columns), slab rows lane>>3 and 8 + (lane>>3): the lane's 8 output
@@ -429,7 +466,7 @@ __global__ __launch_bounds__(G8_THREADS, 2) void gemm8_kernel(const TcGemmParams
     }
     if constexpr ((AB & 64) != 0) {
       float tsum = 0.f;
-      for (int i = 0; i < 4; ++i) for (int j = 0; j < 2; ++j) for (int r = 0; r < 16; ++r) tsum += acc[i][j][r];
+      for (int i = 0; i < 4; ++i) for (int j = 0; j < 2; ++j) for (int r = 0; r < 16; ++r) tsum += MF == 16 ? acc16[2 * i + (r >> 3)][2 * j + ((r >> 2) & 1)][r & 3] : acc[i][j][r];
       if (tsum == 1.2345e30f) reinterpret_cast<float*>(p.c)[tid] = tsum;
     } else {
       epilogue(cur_m, cur_n);
@@ -458,5 +495,9 @@ void tc_gemm8_launch(const TcGemmParams& p, const TcGemmRoute& r, hipStream_t s)
 #undef TC_G8_AB
   }
 #endif
-  tc_with_gather(p.gather, [&](auto g) { hipLaunchKernelGGL((gemm8_kernel<decltype(g)::value>), grid, block, 0, s, p, tt, stg); });
+  const bool mf16 = tc_gemm_mfma() == 16;          // per call, not part of the route (mfma_shape.h)
+  tc_with_gather(p.gather, [&](auto g) {
+    if (mf16) hipLaunchKernelGGL((gemm8_kernel<decltype(g)::value, 0, 16>), grid, block, 0, s, p, tt, stg);
+    else hipLaunchKernelGGL((gemm8_kernel<decltype(g)::value>), grid, block, 0, s, p, tt, stg);
+  });
 }

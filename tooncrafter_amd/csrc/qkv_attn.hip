@@ -16,7 +16,7 @@
 //  * a block owns 8 consecutive pixels x 16 frames = 128 GATHERED rows (tile row = pixel * 16 + frame; a pixel's frames are
 //    HW rows apart in memory) and ONE head: a 128 x 192 output tile [q_h | k_h | v_h] over K = C, on the 4-wave skeleton
 //    of csrc/gemm.hip -- tiles global -> LDS by buffer_load ... lds (XOR swizzle on the source side), two K-steps in
-//    flight (gemm_common.h tc_kloop_pipe), waves 2 x 2, each 64 x 96 = 2 x 3 v_mfma_f32_32x32x16_bf16 sub-tiles;
+//    flight (gemm_common.h tc_kloop_pipe), waves 2 x 2, each 64 x 96 = 4 x 6 v_mfma_f32_16x16x32_bf16 sub-tiles (qkv_attn_tile.h);
 //  * epilogue: + bias, bf16 (the roundings of the projection's own output), q and k row-major, v TRANSPOSED into the stage
 //    memory; then every wave runs the attention of two pixels on 16x16x32 MFMAs (attn_frames16.h tc_attn_frames16, shared with tb_fused.hip; S^T = K Q^T:
 //    a lane owns one query, softmax in-lane + two cross-row swaps, P re-laid as the A operand by permlane swaps, O = P V),
@@ -35,6 +35,7 @@
 
 namespace {
 
+template <int MF>      // the projection's MFMA shape (qkv_attn_tile.h)
 __global__ __launch_bounds__(QA_THREADS, 2) void qkv_attn_kernel(const QaArgs p) {
   __shared__ __attribute__((aligned(1024))) char smem[QA_LDS];
 
@@ -55,7 +56,7 @@ __global__ __launch_bounds__(QA_THREADS, 2) void qkv_attn_kernel(const QaArgs p)
   // ---- projection (qkv_attn_tile.h): q | k | v^T of the tile's 128 rows in the stage memory.  The A descriptor ends
   // with the last column of frame 15 of the tile's last pixel.
   const tc_rsrc_t a_rsrc = make_rsrc(p.x + row0 * p.ldx, (((int64_t)(QA_T - 1) * p.hw + 7) * p.ldx + p.c) * 2);
-  qa_project(smem, a_rsrc, p.w, p.bias, p.c, h, [&](int lr, int chunk) {
+  qa_project<MF>(smem, a_rsrc, p.w, p.bias, p.c, h, [&](int lr, int chunk) {
     return (uint32_t)((((int64_t)(lr & 15) * p.hw + (lr >> 4)) * p.ldx) * 2 + chunk * 16);
   });
 
@@ -99,7 +100,8 @@ extern "C" int tc_temporal_qkv_attn(const TcTqaParams* p, void* stream) {
   if (p->t > QA_T) return qkv_attn_long_launch(p, reinterpret_cast<hipStream_t>(stream));
   QaArgs a;
   const unsigned grid = qa_fill(a, p, 8);
-  hipLaunchKernelGGL(qkv_attn_kernel, dim3(grid), dim3(QA_THREADS), 0, reinterpret_cast<hipStream_t>(stream), a);
+  if (tc_qkv_mfma() == 16) hipLaunchKernelGGL(qkv_attn_kernel<16>, dim3(grid), dim3(QA_THREADS), 0, reinterpret_cast<hipStream_t>(stream), a);
+  else hipLaunchKernelGGL(qkv_attn_kernel<32>, dim3(grid), dim3(QA_THREADS), 0, reinterpret_cast<hipStream_t>(stream), a);
   TC_LAUNCH_CHECK();
   return TC_OK;
 }

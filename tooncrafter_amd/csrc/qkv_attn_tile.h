@@ -4,6 +4,7 @@
 // shape rule and argument fill.
 #pragma once
 #include "fused_l0.h"      // L0Scatter: the swizzled [128][64] layout of q / k is the level-0 fused kernels'
+#include "mfma_shape.h"    // TC_QKV_MFMA
 
 // the long-clip route of tc_temporal_qkv_attn (csrc/qkv_attn_long.hip): 17 .. TC_TEMPORAL_MAX_FRAMES frames, its own pixel
 // count per tile, and what TC_QKV_ATTN = 1 admits of it
@@ -57,9 +58,15 @@ inline unsigned qa_fill(QaArgs& a, const TcTqaParams* p, int px) {
 // The projection of one block: smem <- q (QA_Q_OFF) | k (QA_K_OFF) | v^T (QA_VT_OFF) of head h for the tile's 128 rows,
 // + bias, in bf16 (the roundings of the projection's own output), visible to the whole block on return.  On the 4-wave
 // skeleton of csrc/gemm.hip: tiles global -> LDS by buffer_load ... lds, two K-steps in flight, waves 2 x 2, each
-// 64 x 96 = 2 x 3 v_mfma_f32_32x32x16_bf16 sub-tiles.  `a_rsrc` covers the tile's rows of x from its first row on;
+// 64 x 96 = 4 x 6 v_mfma_f32_16x16x32_bf16 sub-tiles (the shape that ships at 16 frames; 2 x 3 v_mfma_f32_32x32x16_bf16 behind
+// TC_QKV_MFMA=32 and in qkv_attn_long.hip).  `a_rsrc` covers the tile's rows of x from its first row on;
 // `a_off(tile row, 16-byte chunk)` is a row's 32-bit byte offset in it, or TC_OOB for a row that reads zeros.
-template <class RowMap>
+// MF = 16 (what qkv_attn.hip asks for unless TC_QKV_MFMA=32, mfma_shape.h; qkv_attn_long.hip stays on 32, unmeasured there): the wave tile as 4 x 6 v_mfma_f32_16x16x32_bf16 tiles over two 32-deep
+// K-slices per K-step -- the same 20 ds_read_b128 per K-step on the same image (row lane & 15, chunk 4 ks + (lane >> 4)),
+// and the scatter of q / k / v^T restated for the 16 x 16 D (column lane & 15, rows 4 (lane >> 4) + r).  Measured against
+// MF = 32 with bit-identical outputs: the launch 2.3-2.6 % shorter at levels 1 / 2 on a 5-7 % higher engine clock (2.6 %
+// longer at level 3: 0.7 us), the guided forward +1.1-1.2 % (profiles/mfma_shape_kernel_ab.txt, mfma_shape_forward_ab.txt).
+template <int MF = 32, class RowMap>
 __device__ __forceinline__ void qa_project(char* smem, const tc_rsrc_t a_rsrc, const bf16_t* w, const float* bias, int c, int h,
                                            RowMap a_off) {
   // the lane's coordinates are formed HERE from threadIdx, not passed in: handed over as plain ints they lose their
@@ -68,6 +75,7 @@ __device__ __forceinline__ void qa_project(char* smem, const tc_rsrc_t a_rsrc, c
   const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave_u >> 1, wn = wave_u & 1;
   const int frow = tid & 31, fhalf = (tid & 63) >> 5;
+  const int frow16 = tid & 15, fq = (tid & 63) >> 4;
 
   // ---- loader geometry: thread -> (row lrow + 32 i, 16-byte chunk) of both tiles; the swizzle is on the SOURCE chunk
   const int lrow = tid >> 3;
@@ -101,6 +109,13 @@ __device__ __forceinline__ void qa_project(char* smem, const tc_rsrc_t a_rsrc, c
     bcol[j] = bias ? bias[(jb >> 1) * c + h * 64 + (jb & 1) * 32 + frow] : 0.f;
   }
 
+  float bcol16[6];                                 // MF == 16: the same for the wave's six 16-column blocks wn * 6 + j of the twelve
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    const int jb = wn * 6 + j;                     // 0..3 = q | 4..7 = k | 8..11 = v
+    bcol16[j] = (MF == 16 && bias) ? bias[(jb >> 2) * c + h * 64 + (jb & 3) * 16 + frow16] : 0.f;
+  }
+
   f32x16 acc[2][3];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -108,10 +123,36 @@ __device__ __forceinline__ void qa_project(char* smem, const tc_rsrc_t a_rsrc, c
     for (int j = 0; j < 3; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  f32x4 acc16[4][6];                               // MF == 16 (the other shape's set is never touched and costs nothing)
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 6; ++j) acc16[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   auto compute = [&](int stage) {
     const char* sa = smem + stage * QA_STAGE;
     const char* sb = sa + QA_A_BYTES;
+    if constexpr (MF == 16) {
+      bf16x8 a16[2][4], b16[2][6];                  // both 32-deep slices are read before the first MFMA
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        const int ck = ks * 4 + fq;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a16[ks][i] = *reinterpret_cast<const bf16x8*>(sa + lds_off(wm * 64 + i * 16 + frow16, ck));
+#pragma unroll
+        for (int j = 0; j < 6; ++j) b16[ks][j] = *reinterpret_cast<const bf16x8*>(sb + lds_off(wn * 96 + j * 16 + frow16, ck));
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 6; ++j)
+            acc16[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a16[ks][i], b16[ks][j], acc16[i][j], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      return;
+    }
     bf16x8 af[2][2], bf[2][3];
     auto frags = [&](int kk, bf16x8 (&a)[2], bf16x8 (&b)[3]) {
       const int ck = kk * 2 + fhalf;
@@ -144,6 +185,37 @@ __device__ __forceinline__ void qa_project(char* smem, const tc_rsrc_t a_rsrc, c
 
   // ---- K loop: two K-steps in flight (gemm_common.h tc_kloop_pipe); its last barrier frees the stage memory for the epilogue
   tc_kloop_pipe<QA_RA + QA_RB>(0, c / TC_BK, load_tile, compute);
+
+  if constexpr (MF == 16) {
+    // ---- write-out from the 16 x 16 D layout: the lane holds column frow16 of its 16-column block, rows 4 fq + (0..3).
+    // The wave's six blocks are blocks wn * 6 + j of the twelve: 0..3 = q | 4..7 = k | 8..11 = v.  q / k: the place of
+    // (row, col) in the swizzled row-major [128][64] buffer (fused_l0.h, L0Scatter's formula);  v^T: the lane's four rows
+    // are consecutive -> one 8-byte store
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      const int jb = wn * 6 + j;                    // wave-uniform
+      const int col = (jb & 3) * 16 + frow16;
+      const float b = bcol16[j];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int row0 = wm * 64 + i * 16 + 4 * fq;
+        if (jb < 8) {
+          char* buf = smem + (jb < 4 ? QA_Q_OFF : QA_K_OFF);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int row = row0 + r;
+            *reinterpret_cast<bf16_t*>(buf + row * 128 + (((col >> 3) ^ ((row >> 1) & 7)) << 4) + (col & 7) * 2) = (bf16_t)(acc16[i][j][r] + b);
+          }
+        } else {
+          const uint32_t lo = pack2(acc16[i][j][0] + b, acc16[i][j][1] + b);
+          const uint32_t hi = pack2(acc16[i][j][2] + b, acc16[i][j][3] + b);
+          *reinterpret_cast<uint2*>(smem + QA_VT_OFF + col * QA_VT_LD + row0 * 2) = uint2{lo, hi};
+        }
+      }
+    }
+    __syncthreads();
+    return;
+  }
 
   // ---- write-out of the projection: + bias, bf16.  q / k: row-major [128][64], chunks swizzled by (row >> 1) & 7 -- the
   // scatter of a 32 x 32 accumulator block stated in fused_l0.h (L0Scatter);  v: transposed [64 dims][128 rows], four
