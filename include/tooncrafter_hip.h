@@ -1063,6 +1063,82 @@ typedef struct TcFrameDeltaParams {
 int64_t tc_frame_deltas_workspace(const TcFrameDeltaParams* p);
 int tc_frame_deltas(const TcFrameDeltaParams* p, void* stream);
 
+/* ---- Still regions: where the two keyframes of a clip agree, and the decoded clip held to the keyframes there (additive
+ * within ABI 14: two structs, two symbols; csrc/still.hip).  A segment is mostly a character over a background that is the
+ * same in both keyframes; tc_still_map says where, as a latent mask for the sampler's mask / x0 blend (tc_ddim_blend) and as
+ * a pixel weight for tc_still_composite.  THE RULE, stated once (restated in numpy for the tests: tests/still_ref.py):
+ *
+ * Input.  ends (b, 3, 2, H, W) fp32: per clip and channel the first and the last keyframe a and b, values nominally in
+ * [-1, 1] (clip.Conditions.ends_px).  H and W are multiples of TC_STILL_CELL = 8, the first stage's factor; h = H / 8,
+ * w = W / 8 cells.  tau in 0 .. 255 (8-bit code values), grow >= 0 and feather >= 1 in cells,
+ * D = grow + feather + 1 <= TC_STILL_MAX_DIST = 32.
+ *
+ * Threshold.  thr = float32(tau) / float32(127.5): one code value is 2 / 255 of [-1, 1].
+ * Moved pixel.  A pixel has moved if for any channel !(fabsf(clamp(a) - clamp(b)) <= thr), where
+ * clamp(v) = v < -1 ? -1 : v > 1 ? 1 : v and the subtraction is rounded on its own.  This clamp keeps a NaN (the colour path's
+ * fminf / fmaxf form would turn it into -1), and the comparison is written so that a NaN fails it: a NaN counts as moved.
+ * Values beyond [-1, 1] on the same side clamp to equal.
+ * Moved cell.  An 8 x 8 cell has moved if any of its pixels has.
+ * Distance.  d(cell) = min(D, the Chebyshev distance in cells to the nearest moved cell of the same clip).  Outside the
+ * image nothing has moved; a clip with no moved cell has d = D everywhere, a moved cell has d = 0.
+ * Latent mask.  mask (b, 1, 1, h, w) fp32 = 1.0 where d > grow, else 0.0: the moving area grown by `grow` cells is sampled,
+ * the rest can be pinned.
+ * Cell weight.  a(cell) = clamp(d - grow - 1, 0, feather), an integer: the ring of held cells next to the grown moving area
+ * has 0, cells at least `feather` further in have `feather`.
+ * Pixel weight.  alpha (b, H, W) fp32 is the bilinear upsampling of a(cell) with cell centres at 8 i + 3.5 and replicated
+ * edges: pixel 8 i + r takes cells (i - 1, i) with weights ((7 - 2 r) / 16, (2 r + 9) / 16) for r < 4 and cells (i, i + 1)
+ * with ((23 - 2 r) / 16, (2 r - 7) / 16) for r >= 4, a cell index outside the map replaced by the nearest inside -- odd
+ * sixteenths per axis, so N = sum of (wy * wx * a) over the four cells is an exact integer in units of 1 / 256, and
+ * alpha = float32(N) / float32(256 * feather) with one correctly rounded division.  alpha == 1.0 exactly where all four cells
+ * have full weight, == 0.0 exactly where all four have none.
+ * dist (b, h, w) uint8 = d, returned so that callers and tests can see the map.
+ *
+ * Three launches ordered by the stream (per-cell flags, kept in `dist`; the distance of one clip's cell map in LDS as a
+ * separable min filter; alpha).  No workspace, no memset, no global atomic, no allocation, no synchronisation, no host read
+ * of device memory: safe to capture in a hipGraph.  Nothing depends on what mask, alpha or dist held before the call.
+ * TC_EINVAL: NULL p / ends / mask / alpha / dist, b, H or W <= 0, tau outside [0, 255], grow < 0, feather < 1,
+ * D > TC_STILL_MAX_DIST; TC_ESHAPE: H or W not a multiple of 8, more than 16384 cells per clip, b > 65535; TC_EALIGN: ends or
+ * alpha not 16-byte aligned, mask not 4-byte aligned.  Nothing is launched or written on a refusal.
+ *
+ * Not offered: motion compensation (a panned background has moved), and a judgement -- tau, grow and feather are the
+ * caller's (clip.StillRegions, whose defaults nobody has measured on real footage). */
+#define TC_STILL_CELL 8
+#define TC_STILL_MAX_DIST 32
+typedef struct TcStillMapParams {
+  const float* ends;           /* (b, 3, 2, H, W) fp32 */
+  int32_t b, h, w;             /* clips; H and W in PIXELS */
+  int32_t tau, grow, feather;
+  float* mask;                 /* (b, 1, 1, H / 8, W / 8) fp32, written by the call */
+  float* alpha;                /* (b, H, W) fp32, written by the call */
+  uint8_t* dist;               /* (b, H / 8, W / 8) uint8, written by the call */
+} TcStillMapParams;
+int tc_still_map(const TcStillMapParams* p, void* stream);
+
+/* The decoded clip held to its keyframes where alpha says so.  video (b, 3, t, H, W) fp32, ends (b, 3, 2, H, W) fp32 = (e0, e1),
+ * alpha (b, H, W) fp32 in [0, 1] (tc_still_map's), frames f0 .. f0 + nf - 1.  For frame j the entry point computes one float
+ * on the host, s = float32(j) / float32(t - 1), and per pixel and channel, with v the video's value:
+ *   key = e0 + s * (e1 - e0)
+ *   out = v                        where alpha == 0, bit for bit (key is not part of the result: a NaN in the keyframes there
+ *                                  does not spread)
+ *   out = key                      where alpha == 1
+ *   out = v + alpha * (key - v)    elsewhere
+ * every operation rounded on its own (no FMA contraction).  Frame 0 gives key = e0 + 0 * (e1 - e0); frame t - 1 gives
+ * e0 + (e1 - e0), which is e1 up to one rounding.  `out` has the layout of `video`; frames outside the range are not written.
+ * One launch, no workspace, no synchronisation, capture safe.
+ * Aliasing: `out` may be EXACTLY `video` (in place; pixels whose alpha is 0 are then not touched at all); any other overlap
+ * of `out` with video, ends or alpha returns TC_EINVAL.  Also TC_EINVAL: a NULL pointer, b, t, H or W <= 0, a frame range
+ * outside [0, t); TC_ESHAPE: H or W not a multiple of 8, t < 2 or t > TC_TEMPORAL_MAX_FRAMES, b > 65535; TC_EALIGN: a pointer
+ * that is not 16-byte aligned.  Nothing is launched or written on a refusal. */
+typedef struct TcStillCompositeParams {
+  const float* video;          /* (b, 3, t, H, W) fp32 */
+  const float* ends;           /* (b, 3, 2, H, W) fp32 */
+  const float* alpha;          /* (b, H, W) fp32 */
+  float* out;                  /* (b, 3, t, H, W) fp32; may be exactly video */
+  int32_t b, t, h, w;          /* H and W in pixels */
+  int32_t f0, nf;              /* frames f0 .. f0 + nf - 1 */
+} TcStillCompositeParams;
+int tc_still_composite(const TcStillCompositeParams* p, void* stream);
+
 /* introspection */
 int tc_abi_version(void);
 const char* tc_build_info(void);

@@ -265,6 +265,28 @@ class TcFrameDeltaParams(C.Structure):
     ]
 
 
+class TcStillMapParams(C.Structure):
+    """Where the two keyframes of a clip agree: latent mask, pixel weight and cell distance (tc_still_map; additive within
+    ABI 14).  `h`, `w` are in pixels."""
+    _fields_ = [
+        ("ends", C.c_void_p),
+        ("b", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+        ("tau", C.c_int32), ("grow", C.c_int32), ("feather", C.c_int32),
+        ("mask", C.c_void_p), ("alpha", C.c_void_p), ("dist", C.c_void_p),
+    ]
+
+
+class TcStillCompositeParams(C.Structure):
+    """Frames held to the keyframes by a pixel weight (tc_still_composite; additive within ABI 14)."""
+    _fields_ = [
+        ("video", C.c_void_p), ("ends", C.c_void_p), ("alpha", C.c_void_p), ("out", C.c_void_p),
+        ("b", C.c_int32), ("t", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+        ("f0", C.c_int32), ("nf", C.c_int32),
+    ]
+
+
+TC_STILL_CELL = 8                                        # include/tooncrafter_hip.h: pixels per cell side of tc_still_map
+TC_STILL_MAX_DIST = 32                                   # include/tooncrafter_hip.h: the largest grow + feather + 1
 TC_DELTA_BINS = 64                                       # include/tooncrafter_hip.h: bins per component of tc_frame_deltas
 TC_COLOUR_BINS = 1024                                   # include/tooncrafter_hip.h: bins per channel of tc_colour_hist
 TC_COLOUR_STATS = 9                                      # include/tooncrafter_hip.h: doubles per frame of tc_colour_stats
@@ -366,7 +388,9 @@ SYMBOLS = {
     "tc_colour_transfer_knots": (C.c_int, [C.POINTER(TcColourTransferKnotsParams), C.c_void_p]),
     "tc_frame_deltas_workspace": (C.c_int64, [C.POINTER(TcFrameDeltaParams)]),
     "tc_frame_deltas": (C.c_int, [C.POINTER(TcFrameDeltaParams), C.c_void_p]),
-    "tc_gemm_ws_eligible": (C.c_int, [C.POINTER(TcGemmParams)]),
+    "tc_still_map": (C.c_int, [C.POINTER(TcStillMapParams), C.c_void_p]),
+    "tc_still_composite": (C.c_int, [C.POINTER(TcStillCompositeParams), C.c_void_p]),
+    "tc_gemm_ws_eligible":(C.c_int, [C.POINTER(TcGemmParams)]),
     "tc_gemm_gn_rows": (C.c_int, [C.POINTER(TcGemmParams)]),
     "tc_groupnorm_part": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                     C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),

@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libtooncrafter_hip.so")
-SOURCES = ["gemm_route.cpp", "resize_tables.cpp", "gemm.hip", "gemm_wide.hip", "gemm16.hip", "conv_halo.hip", "gemm8.hip", "ff_fused.hip", "tb_fused.hip", "qkv_attn.hip", "qkv_attn_long.hip", "gemm_ws.hip", "gemm_mx.hip", "attention.hip", "attention_temporal_long.hip", "attention_temporal_rel.hip", "attention_q8.hip", "norm.hip", "elementwise.hip", "pixel_front.hip", "pixel_back.hip", "colour_match.hip", "colour_hist.hip", "frame_delta.hip", "noise.hip"]
+SOURCES = ["gemm_route.cpp", "resize_tables.cpp", "gemm.hip", "gemm_wide.hip", "gemm16.hip", "conv_halo.hip", "gemm8.hip", "ff_fused.hip", "tb_fused.hip", "qkv_attn.hip", "qkv_attn_long.hip", "gemm_ws.hip", "gemm_mx.hip", "attention.hip", "attention_temporal_long.hip", "attention_temporal_rel.hip", "attention_q8.hip", "norm.hip", "elementwise.hip", "pixel_front.hip", "pixel_back.hip", "colour_match.hip", "colour_hist.hip", "frame_delta.hip", "still.hip", "noise.hip"]
 # every header of csrc/ (sorted) plus the public one: a new header cannot be left out of the source digest
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(ROOT, "include", "tooncrafter_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on",

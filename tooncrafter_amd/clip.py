@@ -305,6 +305,101 @@ def pin_frames(model, frames, t):
     return x0, mask
 
 
+@dataclass(frozen=True)
+class StillRegions:
+    """What the `still=` keyword of the synthesis calls holds between two keyframes (the rule: include/tooncrafter_hip.h,
+    tc_still_map): a pixel has moved if a channel of the two keyframes differs by more than `tau` 8-bit code values, an 8 x 8
+    cell (one latent position) if any of its pixels has; the moving area is grown by `grow` cells and the pixel weight rises
+    from 0 to 1 over the next `feather` cells.  `pin`: the still cells' latents are held during sampling (`still_pins`);
+    `composite`: the still pixels of the decoded clip are the keyframes' own, feathered (`output.hold_still`).
+    The defaults are starting values.  Nobody has measured them on real footage: no claim is made about what they do to real
+    ToonCrafter frames.  Nothing is motion compensated: a panned background has moved."""
+    tau: int = 8
+    grow: int = 1
+    feather: int = 2
+    pin: bool = True
+    composite: bool = True
+
+    def __post_init__(self):
+        ops.HipOps.still_rule(self.tau, self.grow, self.feather, "StillRegions")
+        for name in ("pin", "composite"):
+            if not isinstance(getattr(self, name), bool):
+                raise ValueError(f"StillRegions: {name} {getattr(self, name)!r}: True or False")
+
+
+def still_map(ends_px, rule=StillRegions()):
+    """`ops.still_map` for the keyframe pixels of a batch of clips, `Conditions.ends_px` (b, 3, 2, H, W) with H and W multiples
+    of 8 -> (mask (b, 1, 1, H / 8, W / 8) fp32: 1 on the latent positions to hold; alpha (b, H, W) fp32: the pixel weight of the
+    keyframes; dist (b, H / 8, W / 8) uint8: cells to the nearest moved cell, capped).  Device tensors, no synchronisation."""
+    if not isinstance(rule, StillRegions):
+        raise ValueError(f"still_map: rule: expected a StillRegions, got {type(rule).__name__}")
+    if not isinstance(ends_px, torch.Tensor) or ends_px.dim() != 5 or ends_px.shape[1:3] != (3, 2):
+        raise ValueError(f"still_map: ends_px must be (b, 3, 2, H, W), got {tuple(getattr(ends_px, 'shape', ()))}")
+    return ops.still_map(ends_px.to(torch.float32).contiguous(), tau=rule.tau, grow=rule.grow, feather=rule.feather)
+
+
+def still_pins(cond, mask, t):
+    """The pair for `sample(..., pinned=...)` that holds the still cells of `still_map`'s `mask` (b, 1, 1, h, w): x0 (b, 4, t, h,
+    w) with x0[:, :, j] = z0 + s_j (z1 - z0), s_j = float32(j) / float32(t - 1), z0 and z1 frames 0 and t - 1 of `cond.endpoints`
+    (the latents the conditions already hold: no further encoder call), and the mask broadcast over t, (b, 1, t, h, w)."""
+    z, t = cond.endpoints, int(t)
+    if z is None or z.dim() != 5 or z.shape[2] != t or t < 2:
+        raise ValueError(f"still_pins: conditions with endpoint latents of {t} >= 2 frames, got "
+                         f"{None if z is None else tuple(z.shape)}")
+    if not isinstance(mask, torch.Tensor) or tuple(mask.shape) != (z.shape[0], 1, 1, *z.shape[3:]):
+        raise ValueError(f"still_pins: mask must be {(z.shape[0], 1, 1, *z.shape[3:])}, got {tuple(getattr(mask, 'shape', ()))}")
+    z0, z1 = z[:, :, 0].to(torch.float32).unsqueeze(2), z[:, :, t - 1].to(torch.float32).unsqueeze(2)
+    s = (torch.arange(t, dtype=torch.float32, device=z.device) / torch.tensor(float(t - 1), dtype=torch.float32, device=z.device))
+    x0 = z0 + s.view(1, 1, t, 1, 1) * (z1 - z0)
+    return x0, mask.to(torch.float32).expand(-1, -1, t, -1, -1).contiguous()
+
+
+def join_pins(frames, regions):
+    """One (x0, mask) pair of whole pinned frames (`pin_frames`: mask (b, 1, t, 1, 1)) and still regions (`still_pins`: mask
+    (b, 1, t, h, w)): the masks combine by maximum, and where a whole frame is pinned its own x0 wins.  Either may be None."""
+    if frames is None or regions is None:
+        return regions if frames is None else frames
+    (xf, mf), (xr, mr) = frames, regions
+    whole = mf.to(device=mr.device, dtype=torch.float32)
+    return torch.where(whole > 0, xf.to(device=xr.device, dtype=torch.float32), xr), torch.maximum(whole.expand_as(mr), mr)
+
+
+def _check_still(what, still, hold_endpoints=True):
+    if still is None:
+        return
+    if not isinstance(still, StillRegions):
+        raise ValueError(f"{what}: still: expected a StillRegions, got {type(still).__name__}")
+    if not hold_endpoints:
+        raise ValueError(f"{what}: still= without hold_endpoints: both keyframe slots hold the same frame, everything would be still")
+
+
+def _still_plan(cond, still, t, pinned=None):
+    """(pinned, alpha) of a batch of clips under `still` (None: `pinned` as it is, no alpha and no call): its map from the batch's
+    own keyframes, the still cells joined to `pinned` with `still.pin`, the pixel weight with `still.composite`."""
+    if still is None or not (still.pin or still.composite):
+        return pinned, None
+    mask, alpha, _ = still_map(cond.ends_px, still)
+    if still.pin:
+        pinned = join_pins(pinned, still_pins(cond, mask, t))
+    return pinned, alpha if still.composite else None
+
+
+def _held(video, cond, alpha):
+    """The clip as it is (alpha None: nothing is called), or its still pixels held to the keyframes (`output.hold_still`, in
+    place: the clip is this module's own)."""
+    if alpha is None:
+        return video
+    from .output import hold_still
+    return hold_still(video, cond.ends_px, alpha, inplace=True)
+
+
+def _sample(model, cond, plan, latent_shape, pinned):
+    """`sample` of the calls that pin nothing themselves: the call it always was without still cells, `pinned=` with them."""
+    if pinned is None:
+        return sample(model, cond, plan, latent_shape)
+    return sample(model, cond, plan, latent_shape, pinned=pinned)
+
+
 def sample(model, cond: Conditions, plan: SamplingPlan, latent_shape, x_T=None, pinned=None, variant=0):
     """Latents (b, 4, t, h, w) of one clip batch.  `pinned`: an (x0, mask) pair (`pin_frames`) -- where mask is one the
     latent is held at x0, noised to each step's level, while the rest is sampled (the reference's `mask` / `x0`).  As there,
@@ -359,7 +454,7 @@ def _matched(video, cond, match, pinned_px=None):
 
 
 def synthesize(model, videos, latent_shape, *, plan: SamplingPlan, prompts=None, fs=24, three_way=False, hold_endpoints=True,
-               variants=1, keyframes=None, match=None):
+               variants=1, keyframes=None, match=None, still=None):
     """(b, variants, 3, t, H, W) pixels in [-1, 1].  `keyframes`: {frame index: (b, 3, H, W) pixels} held in place between
     the endpoints while the rest is sampled (`pin_frames`; encoded once for all variants).  The concat conditioning stays
     endpoints-only: that is what the model was trained on.  With `plan.seeds`, variant k of clip i is the clip seeded
@@ -369,18 +464,26 @@ def synthesize(model, videos, latent_shape, *, plan: SamplingPlan, prompts=None,
     None: no colour op is called.  `ColourMatch(targets="ends")`, the default: the targets are the two endpoints only, and
     `keyframes=` pins latents without adding targets.  `ColourMatch(targets="pinned")`: every pinned frame is a target too --
     frame i is matched to `keyframes[i]` itself, the one image whose colours are known there, and the frames between two
-    targets to the course from one to the next (`match_colour`'s inner).  `ColourMatch(max_gain=g)` limits the linear gains."""
+    targets to the course from one to the next (`match_colour`'s inner).  `ColourMatch(max_gain=g)` limits the linear gains.
+    still: a `StillRegions` -- what does not move between frames 0 and t-1 of `videos` is held (one tc_still_map call for all
+    variants; H and W multiples of 8).  With `still.pin` the still cells join the sampler's mask, their x0 the course between the
+    endpoint latents (`still_pins`); where `keyframes=` pins a whole frame that frame's own x0 and mask win (`join_pins`).  With
+    `still.composite` the still pixels of every decoded clip are the keyframes' own, feathered towards the moving area
+    (`output.hold_still`), after `match=`.  Needs hold_endpoints (ValueError otherwise).  None: no still op is called.  The
+    defaults of `StillRegions` are unmeasured starting values."""
+    _check_still("synthesize", still, hold_endpoints)
     cond = Conditions.build(model, videos, prompts=prompts, fs=fs, guided=plan.scale != 1.0,
                             three_way=three_way, image_branch=plan.image_scale != 1.0, hold_endpoints=hold_endpoints)
     pinned = pin_frames(model, keyframes, latent_shape[2]) if keyframes else None
-    clips = [_matched(decode_spliced(model, sample(model, cond, plan, latent_shape, pinned=pinned, variant=k), cond.refs), cond, match,
-                      keyframes)
+    pinned, alpha = _still_plan(cond, still, latent_shape[2], pinned)
+    clips = [_held(_matched(decode_spliced(model, sample(model, cond, plan, latent_shape, pinned=pinned, variant=k), cond.refs), cond,
+                            match, keyframes), cond, alpha)
              for k in range(variants)]
     return torch.stack(clips, dim=1)
 
 
 def synthesize_u8(model, first_u8, last_u8, latent_shape, *, size, plan: SamplingPlan, prompts=None, fs=24, three_way=False,
-                  hold_endpoints=True, out_size=None, out_filter="bicubic", out_fmt="rgb24", out_colour=None, match=None):
+                  hold_endpoints=True, out_size=None, out_filter="bicubic", out_fmt="rgb24", out_colour=None, match=None, still=None):
     """uint8 keyframes in, uint8 clip out, all on the device: (b, h, w, 3) first / last frames -> (b, t, H, W, 3) frames
     (`Conditions.from_uint8`, `sample`, `decode_spliced`, `clip_to_uint8`).  The last frame of one clip can be the first
     keyframe of the next without leaving the GPU.  `plan.seeds` as in `sample`.
@@ -389,12 +492,16 @@ def synthesize_u8(model, first_u8, last_u8, latent_shape, *, size, plan: Samplin
     `mp4.write_mp4_i420` or an encoder takes.  out_colour: an `output.Colour` for those planes (`clip_to_uint8`'s colour).
     match: an `output.ColourMatch` -- the decoded clip is matched in colour to the two keyframes at model size
     (`output.match_colour`; methods "mkl", "mean_std", "hm", "hm_mkl_hm"; `max_gain` as there) before it goes to the writer;
-    None: no colour op is called.  This call pins nothing: `targets="pinned"` means "ends" here."""
+    None: no colour op is called.  This call pins nothing: `targets="pinned"` means "ends" here.
+    still: a `StillRegions` -- what does not move between the two keyframes at model size is held, as in `synthesize`: the still
+    cells' latents during sampling, the still pixels after `match=` and before the writer.  None: no still op is called."""
     from .output import clip_to_uint8
+    _check_still("synthesize_u8", still, hold_endpoints)
     cond = Conditions.from_uint8(model, first_u8, last_u8, size=size, t=latent_shape[2], prompts=prompts, fs=fs,
                                  guided=plan.scale != 1.0, three_way=three_way, image_branch=plan.image_scale != 1.0,
                                  hold_endpoints=hold_endpoints)
-    video = _matched(decode_spliced(model, sample(model, cond, plan, latent_shape), cond.refs), cond, match)
+    pinned, alpha = _still_plan(cond, still, latent_shape[2])
+    video = _held(_matched(decode_spliced(model, _sample(model, cond, plan, latent_shape, pinned), cond.refs), cond, match), cond, alpha)
     if out_colour is None:
         return clip_to_uint8(video, size=out_size, filter=out_filter, fmt=out_fmt)
     return clip_to_uint8(video, size=out_size, filter=out_filter, fmt=out_fmt, colour=out_colour)
@@ -526,7 +633,7 @@ def find_shots(keyframes, rule=ShotRule()):
 
 
 def synthesize_timeline_u8(model, keyframes, latent_shape, *, size, plan: SamplingPlan, prompts=None, fs=24, three_way=False,
-                           out_size=None, out_filter="bicubic", out_fmt="rgb24", out_colour=None, match=None, shots=None):
+                           out_size=None, out_filter="bicubic", out_fmt="rgb24", out_colour=None, match=None, shots=None, still=None):
     """K keyframes in, one video out, all on the device.  `keyframes`: (K, h, w, 3) uint8 or a `Planes` of K images, K >= 2.
     Segment i interpolates keyframe i -> i + 1 (endpoints held); segments run in order, latent_shape[0] per batch (the last
     batch may be smaller), each batch exactly `Conditions.from_uint8` / `from_planes` with first = kf[i : i + n] and
@@ -549,8 +656,12 @@ def synthesize_timeline_u8(model, keyframes, latent_shape, *, size, plan: Sampli
     for that keyframe; no colour match is applied to them, they are the targets.  The length and layout stay
     `timeline_layout`'s.  Sampled segments are batched as maximal runs of consecutive "tween" segments, each run cut into chunks
     of latent_shape[0]: a batch never spans a skipped segment, and every chunk is the `synthesize_u8` call it replaces.
-    `plan.seeds` and `prompts` stay indexed by the original segment number.  The default rule's thresholds are unmeasured."""
+    `plan.seeds` and `prompts` stay indexed by the original segment number.  The default rule's thresholds are unmeasured.
+    still: a `StillRegions` -- every batch of sampled segments holds what does not move between its own keyframe pairs (one
+    tc_still_map call per batch, at model size; `synthesize_u8`'s still): the still cells' latents during sampling, the still
+    pixels after `match=` and before the writer.  "cut" and "hold" segments are untouched.  None: no still op is called."""
     from dataclasses import replace
+    _check_still("synthesize_timeline_u8", still)
     planar = isinstance(keyframes, Planes)
     if not planar and not (isinstance(keyframes, torch.Tensor) and keyframes.dtype == torch.uint8 and keyframes.dim() == 4 and keyframes.shape[3] == 3):
         raise ValueError("synthesize_timeline_u8: keyframes must be (K, h, w, 3) uint8 or a Planes")
@@ -601,7 +712,9 @@ def synthesize_timeline_u8(model, keyframes, latent_shape, *, size, plan: Sampli
                      prompts=None if prompts is None else list(prompts[i:i + n]), fs=fs, guided=plan.scale != 1.0,
                      three_way=three_way, image_branch=plan.image_scale != 1.0, hold_endpoints=True)
         part = plan if seeds is None else replace(plan, seeds=seeds[i:i + n])
-        clips = _matched(decode_spliced(model, sample(model, cond, part, [n, *latent_shape[1:]]), cond.refs), cond, match).to(torch.float32)
+        pinned, alpha = _still_plan(cond, still, t)
+        clips = _held(_matched(decode_spliced(model, _sample(model, cond, part, [n, *latent_shape[1:]], pinned), cond.refs), cond, match),
+                      cond, alpha).to(torch.float32)
         if i == 0:                                    # the video's first frame: segment 0 alone writes its frame 0
             write(clips[:1], size=out_size, filter=out_filter, fmt=out_fmt, frames=(0, 1), out=flat, strides=(row, frame, frame))
         write(clips, size=out_size, filter=out_filter, fmt=out_fmt, frames=(1, t - 1), out=flat[(i * (t - 1) + 1) * frame:],

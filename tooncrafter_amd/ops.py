@@ -1419,6 +1419,77 @@ class HipOps:
         self._launch("tc_frame_deltas", p, device)
         return delta, hist
 
+    # ------------------------------------------------------------------ still regions (tc_still_map, tc_still_composite)
+    @staticmethod
+    def _still_ends(ends, what):
+        """The (b, H, W) of (b, 3, 2, H, W) fp32 contiguous device keyframes with H and W multiples of the cell, or raise."""
+        if not isinstance(ends, torch.Tensor) or not ends.is_cuda:
+            raise _lib.TooncrafterHipError(f"{what}: expected a CUDA tensor, got {getattr(ends, 'device', type(ends))}: the product "
+                                           "path is GPU-only")
+        if ends.dtype != torch.float32 or ends.dim() != 5 or ends.shape[1:3] != (3, 2) or ends.numel() == 0 or not ends.is_contiguous():
+            raise ValueError(f"{what}: expected contiguous fp32 (b, 3, 2, H, W), got {tuple(ends.shape)} {ends.dtype}")
+        return ends.shape[0], ends.shape[3], ends.shape[4]
+
+    @staticmethod
+    def still_rule(tau, grow, feather, what="still_map"):
+        """The checked (tau, grow, feather) of a still map: integers, tau in [0, 255], grow >= 0, feather >= 1 and
+        grow + feather + 1 <= TC_STILL_MAX_DIST.  Host only."""
+        import numbers
+        for name, v in (("tau", tau), ("grow", grow), ("feather", feather)):
+            if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+                raise ValueError(f"{what}: {name} {v!r}: an integer")
+        tau, grow, feather = int(tau), int(grow), int(feather)
+        if not 0 <= tau <= 255 or grow < 0 or feather < 1 or grow + feather + 1 > _lib.TC_STILL_MAX_DIST:
+            raise ValueError(f"{what}: tau {tau} (0 .. 255), grow {grow} (>= 0), feather {feather} (>= 1), grow + feather + 1 at most "
+                             f"{_lib.TC_STILL_MAX_DIST}")
+        return tau, grow, feather
+
+    def still_map(self, ends, tau=8, grow=1, feather=2):
+        """Where the two keyframes of every clip agree (tc_still_map; the rule: include/tooncrafter_hip.h): `ends` (b, 3, 2, H, W)
+        fp32, H and W multiples of 8.  A pixel has moved if a channel differs by more than `tau` 8-bit code values, an 8 x 8
+        cell if one of its pixels has; d is a cell's Chebyshev distance to the nearest moved cell, capped at grow + feather + 1.
+        Returns (mask (b, 1, 1, H / 8, W / 8) fp32: 1 where d > grow; alpha (b, H, W) fp32: clamp(d - grow - 1, 0, feather) /
+        feather upsampled bilinearly; dist (b, H / 8, W / 8) uint8: d).  Device tensors, no synchronisation."""
+        tau, grow, feather = self.still_rule(tau, grow, feather)
+        b, hh, ww = self._still_ends(ends, "still_map: ends")
+        cell = _lib.TC_STILL_CELL
+        if hh % cell or ww % cell:
+            raise ValueError(f"still_map: ends of {(hh, ww)} pixels: multiples of {cell}")
+        mask = torch.empty((b, 1, 1, hh // cell, ww // cell), dtype=torch.float32, device=ends.device)
+        alpha = torch.empty((b, hh, ww), dtype=torch.float32, device=ends.device)
+        dist = torch.empty((b, hh // cell, ww // cell), dtype=torch.uint8, device=ends.device)
+        p = _lib.TcStillMapParams(ends=ends.data_ptr(), b=b, h=hh, w=ww, tau=tau, grow=grow, feather=feather, mask=mask.data_ptr(),
+                                  alpha=alpha.data_ptr(), dist=dist.data_ptr())
+        _lib.check(self.lib.tc_still_map(C.byref(p), _stream()), "tc_still_map")
+        return mask, alpha, dist
+
+    def still_composite(self, video, ends, alpha, frames=None, out=None):
+        """`video` (b, 3, t, H, W) fp32 held to its keyframes `ends` (b, 3, 2, H, W) by the pixel weight `alpha` (b, H, W) in the
+        frames (f0, nf) (None: all): with key = e0 + s (e1 - e0), s = j / (t - 1), frame j becomes v where alpha == 0 (bit for
+        bit), key where alpha == 1 and v + alpha (key - v) between (tc_still_composite).  `out` may be `video` itself (in
+        place); default: a new tensor, whose frames outside the range are copies of video's."""
+        b, t, hh, ww = self._colour_clip(video, "still_composite: video")
+        if self._still_ends(ends, "still_composite: ends") != (b, hh, ww) or ends.device != video.device:
+            raise ValueError(f"still_composite: ends {tuple(ends.shape)} against video {tuple(video.shape)}")
+        if not isinstance(alpha, torch.Tensor) or not alpha.is_cuda:
+            raise _lib.TooncrafterHipError("still_composite: alpha: expected a CUDA tensor: the product path is GPU-only")
+        if alpha.dtype != torch.float32 or alpha.shape != (b, hh, ww) or not alpha.is_contiguous() or alpha.device != video.device:
+            raise ValueError(f"still_composite: alpha: expected contiguous fp32 {(b, hh, ww)}, got {tuple(alpha.shape)} {alpha.dtype}")
+        f0, nf = (0, t) if frames is None else (int(v) for v in frames)
+        if nf < 1 or not 0 <= f0 < t or f0 + nf > t:
+            raise ValueError(f"still_composite: frames (f0, nf) = {(f0, nf)} outside a clip of {t}")
+        if t < 2 or t > _lib.TC_TEMPORAL_MAX_FRAMES or hh % _lib.TC_STILL_CELL or ww % _lib.TC_STILL_CELL:
+            raise ValueError(f"still_composite: clips of {t} frames (2 .. {_lib.TC_TEMPORAL_MAX_FRAMES}) of {(hh, ww)} pixels "
+                             f"(multiples of {_lib.TC_STILL_CELL})")
+        if out is None:
+            out = torch.empty_like(video) if (f0, nf) == (0, t) else video.clone()
+        elif self._colour_clip(out, "still_composite: out") != (b, t, hh, ww) or out.device != video.device:
+            raise ValueError(f"still_composite: out {tuple(out.shape)} against video {tuple(video.shape)}")
+        p = _lib.TcStillCompositeParams(video=video.data_ptr(), ends=ends.data_ptr(), alpha=alpha.data_ptr(), out=out.data_ptr(),
+                                        b=b, t=t, h=hh, w=ww, f0=f0, nf=nf)
+        _lib.check(self.lib.tc_still_composite(C.byref(p), _stream()), "tc_still_composite")
+        return out
+
 
 _backend = None
 

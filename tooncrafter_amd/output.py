@@ -159,6 +159,22 @@ def match_colour(video: torch.Tensor, ends: torch.Tensor, match: ColourMatch, in
     return ops.colour_transfer(work, src, ref, ref_pixels, match.strength, base=video, out=work, **through)[0]
 
 
+def hold_still(video: torch.Tensor, ends: torch.Tensor, alpha: torch.Tensor, frames=None, inplace: bool = False) -> torch.Tensor:
+    """`video` (b, 3, t, H, W) held to its keyframes `ends` (b, 3, 2, H, W) where they agree: `alpha` (b, H, W) is the pixel weight
+    of `clip.still_map` (0: the decoded pixel, bit for bit; 1: the keyframes' own pixel, key = e0 + j / (t - 1) (e1 - e0) for
+    frame j; between: v + alpha (key - v)), on the device and without a synchronisation (tc_still_composite).  frames:
+    (f0, nf), None: every frame.  inplace: write into `video` itself when it is fp32 and contiguous (otherwise, and by default,
+    into a new tensor).  Unlike `match_colour`, the keyframes must have the clip's size: the weight is per pixel."""
+    if video.dim() != 5 or ends is None or ends.dim() != 5 or tuple(ends.shape) != (video.shape[0], 3, 2, *video.shape[3:]):
+        raise ValueError(f"hold_still: ends must be ({video.shape[0]}, 3, 2, {video.shape[3]}, {video.shape[4]}) for a video of "
+                         f"{tuple(video.shape)}, got {None if ends is None else tuple(ends.shape)}")
+    if not isinstance(alpha, torch.Tensor) or tuple(alpha.shape) != (video.shape[0], *video.shape[3:]):
+        raise ValueError(f"hold_still: alpha must be {(video.shape[0], *video.shape[3:])}, got {tuple(getattr(alpha, 'shape', ()))}")
+    work = video.to(torch.float32).contiguous()
+    return ops.still_composite(work, ends.to(torch.float32).contiguous(), alpha.to(torch.float32).contiguous(), frames=frames,
+                               out=work if inplace or work is not video else None)
+
+
 def clip_to_uint8(samples: torch.Tensor, loop: bool = False, size=None, filter: str = "bicubic", fmt: str = "rgb24",
                   colour: Optional[Colour] = None) -> torch.Tensor:
     """(b, 3, t, h, w) fp32 -> (b, t, h, w, 3) uint8 on the device of `samples`
