@@ -9,6 +9,9 @@ max-abs <= 3 bf16 ulps of the output scale.  fp32-output operators: rel-L2 <= 1e
 
 The attention kernels' layout and masking (every query row, key slot, head, batch -> K/V batch mapping and mask boundary)
 are pinned exactly in test_gpu_attn_exact.py; the tolerance tests here cover the softmax numerics on smooth inputs.
+GroupNorm, LayerNorm and the row softmax (every group, sample and row boundary, every element of the sums, every ragged
+tail and what lies beside the output) are held to the final bf16 rounding in test_gpu_norm_exact.py; test_groupnorm,
+test_layernorm and test_softmax_rows here cover their numerics on smooth inputs.
 """
 import math
 
