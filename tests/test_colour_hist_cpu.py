@@ -351,7 +351,7 @@ def stub_pipeline(monkeypatch):
     def from_uint8(model, first, last, *, size, t, **options):
         return Cond(int(first[0, 0, 0, 0]), len(first))
     monkeypatch.setattr(clip.Conditions, "from_uint8", staticmethod(from_uint8))
-    monkeypatch.setattr(clip, "sample", lambda model, cond, plan, latent_shape: cond)
+    monkeypatch.setattr(clip, "sample", lambda model, cond, plan, latent_shape, pinned=None, variant=0: cond)
     monkeypatch.setattr(clip, "decode_spliced", lambda model, cond, refs: torch.full((cond.n, 3, 4, 6, 8), 1.0 + cond.first))
     spy = HistSpy()
     prev = ops.set_backend(spy)

@@ -327,7 +327,7 @@ def stub_pipeline(monkeypatch):
         assert len(first) == len(last) and int(last[0, 0, 0, 0]) == int(first[0, 0, 0, 0]) + 1
         return Cond(int(first[0, 0, 0, 0]), len(first), prompts)
 
-    def sample(model, cond, plan, latent_shape):
+    def sample(model, cond, plan, latent_shape, pinned=None, variant=0):
         sampled.append((cond.first, cond.n, None if plan.seeds is None else list(plan.seeds), cond.prompts, list(latent_shape)))
         return cond
 

@@ -327,3 +327,26 @@ def test_timeline_from_planes(tiny, keyframes, g):  # noqa: F811
         a = pipeline.synthesize_timeline_u8(model, device_planes(planes, "nv12"), shape, size=(h, w), plan=plan_with([31, 32]), fs=10)
         b = pipeline.synthesize_timeline_u8(model, rgb, shape, size=(h, w), plan=plan_with([31, 32]), fs=10)
     assert a.shape == (7, h, w, 3) and torch.equal(a, b)
+
+
+def test_timeline_with_every_option_is_its_parts(tiny, keyframes, g):  # noqa: F811
+    """shots, still, match, a planar format and a named colour at once: segments 0 and 2 are their synthesize_u8 calls with the
+    same options, the held segment 1 is the writer's bytes of its two keyframes (e2e.size is a multiple of 8, as still= needs)"""
+    from tooncrafter_amd import clip as pipeline
+    from tooncrafter_amd.output import Colour, ColourMatch, clip_to_uint8
+    model, _ = tiny
+    h, w = (int(v) for v in g["e2e.size"])
+    assert h % 8 == 0 and w % 8 == 0
+    shape, seeds = [1, 4, 4, h // 8, w // 8], [41, 42, (1 << 62) + 43]
+    options = dict(size=(h, w), fs=10, still=pipeline.StillRegions(), match=ColourMatch("mkl", 0.5), out_fmt="nv12",
+                   out_colour=Colour("bt709", "full", "left"))
+    with torch.no_grad():
+        video = pipeline.synthesize_timeline_u8(model, keyframes, shape, plan=plan_with(seeds),
+                                                shots=pipeline.ShotPlan(("tween", "hold", "tween")), **options)
+        first, third = (pipeline.synthesize_u8(model, keyframes[i:i + 1], keyframes[i + 1:i + 2], shape, plan=plan_with([seeds[i]]),
+                                               **options)[0] for i in (0, 2))
+        ends = pipeline.frames_from_uint8(keyframes[1:3], (h, w), [(0, 0), (0, 1)], 2)
+        held = clip_to_uint8(ends[:, :, [0, 0, 0, 1]], fmt="nv12", colour=options["out_colour"])[0]
+    assert video.shape == (10, h * w * 3 // 2) and video.dtype == torch.uint8 and video.is_cuda
+    assert np.array_equal(video.cpu().numpy(), splice([first, held, third]))
+    assert not torch.equal(first, third) and not torch.equal(video[1], video[2]) and torch.equal(video[4], video[5])

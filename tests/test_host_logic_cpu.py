@@ -430,3 +430,112 @@ def test_conv_halo_model_design_artifact():
     spec.loader.exec_module(mod)
     err, worst = mod.check(frames=1, H=9, W=35, C=64, N=8)
     assert err < 1e-12 and worst == 0
+
+
+# ---------------------------------------------------------------- the clip pipeline's host rules: timeline plan, writer rule
+
+def test_timeline_segments_on_hand_written_labels():
+    from tooncrafter_amd.clip import timeline_segments as seg
+    tw, cut, hold = "tween", "cut", "hold"
+    # all tween: the batches are the segments in order, cut into chunks
+    assert seg((tw,) * 5, 5, 1) == ([], [(0, 1), (1, 1), (2, 1), (3, 1), (4, 1)])
+    assert seg((tw,) * 5, 5, 2) == ([], [(0, 2), (2, 2), (4, 1)])
+    assert seg((tw,) * 5, 5, 8) == ([], [(0, 5)])
+    # a held segment at the start, in the middle, at the end
+    assert seg((hold, tw, tw, tw), 4, 2) == ([0], [(1, 2), (3, 1)])
+    assert seg((tw, tw, cut, tw), 4, 4) == ([2], [(0, 2), (3, 1)])
+    assert seg((tw, tw, tw, hold), 4, 2) == ([3], [(0, 2), (2, 1)])
+    # two runs with a hold between them, batch 2: three batches, none across the hold, although (2, 3) and (4, 5) would pair up
+    assert seg((tw, tw, tw, hold, tw, tw), 6, 2) == ([3], [(0, 2), (2, 1), (4, 2)])
+    assert seg((tw, hold, tw), 3, 2) == ([1], [(0, 1), (2, 1)])
+    # nothing to sample
+    assert seg((cut, hold, hold), 3, 2) == ([0, 1, 2], [])
+    for bad in (((tw, tw), 3, 1), ((tw, "fade", tw), 3, 1), ((tw,), 1, 0)):
+        with pytest.raises(ValueError):
+            seg(*bad)
+
+
+def test_timeline_segments_without_labels_are_timeline_layouts_batches():
+    from tooncrafter_amd import clip
+    for k in range(2, 7):
+        for batch in range(1, 4):
+            assert clip.timeline_segments(None, k - 1, batch) == ([], clip.timeline_layout(k, 4, batch, (4, 6), "rgb24")[2]), (k, batch)
+
+
+def test_write_frames_picks_the_op_by_one_rule():
+    """size x fmt x colour x out: the op and the arguments are those `clip_to_uint8` (out None: frames = (0, t), or the clip alone
+    to video_to_uint8) and the timeline (a buffer: frames, out, strides) passed; the product's own request check stands in front
+    of the recording, so rgb24 with a colour raises what ops.frames_to_yuv raises, through either entry point."""
+    from tooncrafter_amd import output
+    from tooncrafter_amd._lib import TooncrafterHipError
+    from tooncrafter_amd.ops import HipOps
+    from tooncrafter_amd.output import Colour
+
+    class Recorder(HipOps):
+        calls = []
+
+        @staticmethod
+        def checked(check, *request):
+            try:
+                check(*request)
+            except TooncrafterHipError:                   # the CPU tensor, refused last: after the request checks, which raise ValueError
+                pass
+
+        def video_to_uint8(self, video):
+            self.calls.append(("video_to_uint8", tuple(video.shape)))
+
+        def frames_to_u8(self, x, size=None, filter="bicubic", fmt="rgb24", frames=None, out=None, strides=None):
+            self.checked(self._frames_out_args, x, size, filter, fmt, frames)
+            self.calls.append(("frames_to_u8", tuple(x.shape), size, filter, fmt, frames, out if out is None else out.data_ptr(), strides))
+
+        def frames_to_yuv(self, x, size=None, filter="bicubic", fmt="nv12", colour=None, frames=None, out=None, strides=None):
+            self.checked(self._frames_yuv_out_args, x, size, filter, fmt, colour, frames)
+            self.calls.append(("frames_to_yuv", tuple(x.shape), size, filter, fmt, colour, frames, out if out is None else out.data_ptr(),
+                               strides))
+    spy, calls = Recorder(), Recorder.calls
+    x, t, c = torch.zeros(2, 3, 4, 20, 32), 4, Colour()
+    buf = torch.zeros(2 * 4 * 40 * 64 * 3, dtype=torch.uint8)
+    prev = ops.set_backend(spy)
+    try:
+        for size in (None, (40, 64)):
+            for fmt in ("rgb24", "i420", "nv12"):
+                for colour in (None, c):
+                    for out in (None, buf):
+                        oh, ow = size or (20, 32)
+                        frame = oh * ow * 3 if fmt == "rgb24" else oh * ow * 3 // 2
+                        strides = (3 * ow if fmt == "rgb24" else ow, frame, (t - 1) * frame)
+                        how = dict(size=size, filter="box", fmt=fmt, colour=colour)
+                        request = dict(frames=(0, t)) if out is None else dict(frames=(1, t - 1), out=out[frame:], strides=strides)
+                        plain = size is None and fmt == "rgb24" and colour is None and out is None
+                        calls.clear()
+                        if colour is not None and fmt == "rgb24":
+                            with pytest.raises(ValueError):
+                                output.write_frames(x, **how, **request)
+                            with pytest.raises(ValueError):
+                                output.clip_to_uint8(x, **how)
+                            assert not calls
+                            continue
+                        output.write_frames(x, filter="box") if plain else output.write_frames(x, **how, **request)
+                        tail = (None, None) if out is None else (buf.data_ptr() + frame, strides)
+                        if colour is not None:
+                            want = ("frames_to_yuv", (2, 3, 4, 20, 32), size, "box", fmt, c, request["frames"], *tail)
+                        elif plain:
+                            want = ("video_to_uint8", (2, 3, 4, 20, 32))
+                        else:
+                            want = ("frames_to_u8", (2, 3, 4, 20, 32), size, "box", fmt, request["frames"], *tail)
+                        assert calls == [want], (size, fmt, colour, out is not None)
+                        if out is None:                                           # clip_to_uint8 is this rule plus `loop`
+                            output.clip_to_uint8(x, **how)
+                            assert calls == [want, want]
+        # frames alone take the clip off the whole-clip op; `loop` is a slice there and a frame count elsewhere
+        calls.clear()
+        output.write_frames(x, frames=(0, 3))
+        output.clip_to_uint8(x, True)
+        output.clip_to_uint8(x, True, fmt="nv12", colour=c)
+        assert calls == [("frames_to_u8", (2, 3, 4, 20, 32), None, "bicubic", "rgb24", (0, 3), None, None), ("video_to_uint8", (2, 3, 3, 20, 32)),
+                         ("frames_to_yuv", (2, 3, 4, 20, 32), None, "bicubic", "nv12", c, (0, 3), None, None)]
+        for bad in ("bt709", (1, 2)):
+            with pytest.raises(ValueError):
+                output.write_frames(x, fmt="nv12", colour=bad)
+    finally:
+        ops.set_backend(prev)

@@ -385,7 +385,7 @@ class StubOps:
 def test_timeline_splice_counts_and_offsets(monkeypatch, k, t, fmt):
     """Frame (segment s, index f) of the stub's clips is the constant grey 16 * s + f: the video must hold, in order, frames
     0 .. t-1 of segment 0 and frames 1 .. t-1 of every later segment, whatever the batch size."""
-    from tooncrafter_amd import clip
+    from tooncrafter_amd import clip, output
     h, w = 4, 6
     frame = h * w * 3 if fmt == "rgb24" else h * w * 3 // 2
     total = (k - 1) * (t - 1) + 1
@@ -397,7 +397,7 @@ def test_timeline_splice_counts_and_offsets(monkeypatch, k, t, fmt):
         assert options["hold_endpoints"] is True and options["prompts"] is None
         return [int(v) for v in first[:, 0, 0, 0]]                               # the batch's segments stand in for the conditions
 
-    def sample(model, cond, plan, latent_shape):
+    def sample(model, cond, plan, latent_shape, pinned=None, variant=0):
         assert latent_shape[0] == len(cond) and list(plan.seeds) == [100 + s for s in cond]
         seen.append(list(cond))
         return cond
@@ -416,6 +416,7 @@ def test_timeline_splice_counts_and_offsets(monkeypatch, k, t, fmt):
     for batch in (1, 2, 3):
         stub = StubOps()
         monkeypatch.setattr(clip, "ops", stub)
+        monkeypatch.setattr(output, "ops", stub)                                # the writer rule lives there
         seen.clear()
         plan = clip.SamplingPlan(steps=2, seeds=[100 + s for s in range(k - 1)])
         video = clip.synthesize_timeline_u8(None, kf, [batch, 4, t, 1, 1], size=(h, w), plan=plan, out_fmt=fmt)

@@ -18,7 +18,7 @@ hidden states; only those two frames are encoded here (8x less encoder work at T
 """
 from __future__ import annotations
 
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import List, Optional, Sequence
 
 import torch
@@ -27,6 +27,7 @@ from . import ops
 from .lvdm.attention import check_frames
 from .lvdm.ddim import DDIMSampler
 from .lvdm.ddim_multiplecond import DDIMSampler as ThreeWaySampler
+from .output import Colour, clip_to_uint8, hold_still, match_colour, write_frames
 
 
 def encode_endpoints(model, videos):
@@ -103,10 +104,8 @@ class Conditions:
         `clip_to_uint8` returns, or a decoder's output), `size` the model's (H, W).  They become frames 0 and t-1 of the clip
         tensor by the script's transform (`frames_from_uint8`); the encoder runs as in `build` and the image tower takes its
         patches from tc_clip_patches (`encode_on_device_front`).  `options`: the keyword options of `build` other than `embed`."""
-        for name, u8 in (("first_u8", first_u8), ("last_u8", last_u8)):
-            if not isinstance(u8, torch.Tensor) or u8.dtype != torch.uint8 or u8.dim() != 4 or u8.shape[3] != 3:
-                raise ValueError(f"from_uint8: {name} must be (b, h, w, 3) uint8, got "
-                                 f"{tuple(u8.shape) if isinstance(u8, torch.Tensor) else type(u8)} {getattr(u8, 'dtype', '')}")
+        _check_images("from_uint8: first_u8", first_u8, "b")
+        _check_images("from_uint8: last_u8", last_u8, "b")
         return Conditions._from_keyframes("from_uint8", frames_from_uint8, model, first_u8, last_u8, size, t, options)
 
     @staticmethod
@@ -164,22 +163,42 @@ class Planes:
         return Planes(self.y[index], tuple(c[index] for c in self.chroma), self.fmt, self.standard, self.range, self.siting, self.matrix)
 
 
+def _check_images(what, images, n="n", planes=False):
+    """`images` as the pixel front end takes them, or ValueError under the caller's name `what`: (n, h, w, 3) uint8 (`n`: the
+    caller's letter for the count), or, with `planes`, a `Planes`."""
+    if planes and isinstance(images, Planes):
+        return
+    if not isinstance(images, torch.Tensor) or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
+        raise ValueError(f"{what} must be ({n}, h, w, 3) uint8{' or a Planes' if planes else ''}, got "
+                         f"{tuple(images.shape) if isinstance(images, torch.Tensor) else type(images).__name__} {getattr(images, 'dtype', '')}")
+
+
+def _packed_frames(what, buf, h, w, sample_bytes):
+    """The checked buffers of `what` (planes_from_packed / planes_from_frames): (h, w, the frames as rows), for a positive even
+    size and uint8 (..., h * w * 3 / 2 * sample_bytes) buffers with unit stride, flattened without a copy to (frames, samples) --
+    uint8 samples, or for sample_bytes = 2 the 2-byte words of P010."""
+    h, w = int(h), int(w)
+    if h <= 0 or w <= 0 or h % 2 or w % 2:
+        raise ValueError(f"{what}: the packed planar formats have an even size, got {(h, w)}")
+    n = h * w * 3 // 2 * sample_bytes
+    if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8 or buf.dim() < 1 or buf.shape[-1] != n or buf.stride(-1) != 1:
+        raise ValueError(f"{what}: expected uint8 (..., {n}) {'P010 ' if sample_bytes == 2 else ''}frames with unit stride, got "
+                         f"{tuple(buf.shape) if isinstance(buf, torch.Tensor) else type(buf)} {getattr(buf, 'dtype', '')}")
+    try:
+        rows = buf.view(-1, n)
+        return h, w, rows if sample_bytes == 1 else rows.view(torch.uint16)
+    except RuntimeError as e:
+        raise ValueError(f"{what}: the frames do not flatten{' into 2-byte words' if sample_bytes == 2 else ''} without a copy (strides {buf.stride()}, "
+                         f"offset {buf.storage_offset()})") from e
+
+
 def planes_from_packed(buf, h, w, fmt, **options):
     """Views (no copy) of the (..., h * w * 3 / 2) uint8 buffers `clip_to_uint8(fmt="i420" | "nv12")` returns as a `Planes` of
     all their frames, in order: a planar clip's last frame is `planes_from_packed(clip[:, -1], h, w, fmt)`.  The back end writes
     BT.601 limited range from 2 x 2 means, which the defaults (`options`: standard, range, siting) undo."""
-    h, w = int(h), int(w)
     if fmt not in ("i420", "nv12"):
         raise ValueError(f"planes_from_packed: fmt {fmt!r}: 'i420' or 'nv12'")
-    if h <= 0 or w <= 0 or h % 2 or w % 2:
-        raise ValueError(f"planes_from_packed: the packed planar formats have an even size, got {(h, w)}")
-    if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8 or buf.dim() < 1 or buf.shape[-1] != h * w * 3 // 2 or buf.stride(-1) != 1:
-        raise ValueError(f"planes_from_packed: expected uint8 (..., {h * w * 3 // 2}) frames with unit stride, got "
-                         f"{tuple(buf.shape) if isinstance(buf, torch.Tensor) else type(buf)} {getattr(buf, 'dtype', '')}")
-    try:
-        flat = buf.view(-1, buf.shape[-1])
-    except RuntimeError as e:
-        raise ValueError(f"planes_from_packed: the leading dimensions do not flatten without a copy (strides {buf.stride()})") from e
+    h, w, flat = _packed_frames("planes_from_packed", buf, h, w, 1)
     n, q = h * w, (h // 2) * (w // 2)
     y = flat[:, :n].unflatten(1, (h, w))
     if fmt == "i420":
@@ -194,25 +213,14 @@ def planes_from_frames(buf, h, w, fmt, colour):
     copy) of the uint8 (..., bytes per frame) buffers as a `Planes` carrying the colour's standard / range / siting, so that a
     clip's last frame is the next clip's keyframe in the same description.  colour.bits == 10: the (..., h * w * 3) bytes of
     P010 frames, viewed as fmt "p010" with 2-byte elements (`fmt` is then "nv12", as it was for the call that wrote them)."""
-    from .output import Colour
     if not isinstance(colour, Colour):
         raise ValueError(f"planes_from_frames: colour: expected a Colour, got {type(colour).__name__}")
     options = dict(standard=colour.standard, range=colour.range, siting=colour.siting)
     if colour.bits == 8:
         return planes_from_packed(buf, h, w, fmt, **options)
-    h, w = int(h), int(w)
     if fmt != "nv12":
         raise ValueError(f"planes_from_frames: fmt {fmt!r}: 10-bit frames are 'nv12' in 2-byte words (P010)")
-    if h <= 0 or w <= 0 or h % 2 or w % 2:
-        raise ValueError(f"planes_from_frames: the packed planar formats have an even size, got {(h, w)}")
-    if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8 or buf.dim() < 1 or buf.shape[-1] != h * w * 3 or buf.stride(-1) != 1:
-        raise ValueError(f"planes_from_frames: expected uint8 (..., {h * w * 3}) P010 frames with unit stride, got "
-                         f"{tuple(buf.shape) if isinstance(buf, torch.Tensor) else type(buf)} {getattr(buf, 'dtype', '')}")
-    try:
-        words = buf.view(-1, buf.shape[-1]).view(torch.uint16)
-    except RuntimeError as e:
-        raise ValueError(f"planes_from_frames: the frames do not flatten into 2-byte words without a copy (strides {buf.stride()}, "
-                         f"offset {buf.storage_offset()})") from e
+    h, w, words = _packed_frames("planes_from_frames", buf, h, w, 2)
     n = h * w
     return Planes(words[:, :n].unflatten(1, (h, w)), (words[:, n:].unflatten(1, (h // 2, w // 2, 2)),), "p010", **options)
 
@@ -245,10 +253,7 @@ def frames_from_uint8(images_u8, size, slots, t, out=None):
     the (batch, frame) pair slots[i] by the script's transform (inference.py:64-69: Resize(min(size)), CenterCrop(size),
     ToTensor, Normalize(0.5, 0.5) on PIL images), bit for bit, on the device.  b = 1 + the largest batch index; frames no slot
     names are zero.  `out`: a clip tensor to fill in place instead (the frames no slot names keep their contents)."""
-    if not isinstance(images_u8, torch.Tensor) or images_u8.dtype != torch.uint8:
-        raise ValueError(f"frames_from_uint8: expected a uint8 tensor, got {getattr(images_u8, 'dtype', type(images_u8))}")
-    if images_u8.dim() != 4 or images_u8.shape[3] != 3:
-        raise ValueError(f"frames_from_uint8: expected (n, h, w, 3) images, got {tuple(images_u8.shape)}")
+    _check_images("frames_from_uint8: images_u8", images_u8)
     size, flat, b, t = _clip_slots("frames_from_uint8", images_u8.shape[0], size, slots, t, out)
     return ops.frames_from_u8(images_u8, size, flat, b=b, t=t, out=out)
 
@@ -384,22 +389,6 @@ def _still_plan(cond, still, t, pinned=None):
     return pinned, alpha if still.composite else None
 
 
-def _held(video, cond, alpha):
-    """The clip as it is (alpha None: nothing is called), or its still pixels held to the keyframes (`output.hold_still`, in
-    place: the clip is this module's own)."""
-    if alpha is None:
-        return video
-    from .output import hold_still
-    return hold_still(video, cond.ends_px, alpha, inplace=True)
-
-
-def _sample(model, cond, plan, latent_shape, pinned):
-    """`sample` of the calls that pin nothing themselves: the call it always was without still cells, `pinned=` with them."""
-    if pinned is None:
-        return sample(model, cond, plan, latent_shape)
-    return sample(model, cond, plan, latent_shape, pinned=pinned)
-
-
 def sample(model, cond: Conditions, plan: SamplingPlan, latent_shape, x_T=None, pinned=None, variant=0):
     """Latents (b, 4, t, h, w) of one clip batch.  `pinned`: an (x0, mask) pair (`pin_frames`) -- where mask is one the
     latent is held at x0, noised to each step's level, while the rest is sampled (the reference's `mask` / `x0`).  As there,
@@ -440,17 +429,25 @@ def decode_spliced(model, latents, refs, marks=None):
     return video
 
 
-def _matched(video, cond, match, pinned_px=None):
-    """The decoded clip as it is (match None: nothing is called), or matched in colour to the keyframes of its conditions
-    (`output.match_colour`: tc_colour_stats twice and tc_colour_match for the linear methods, tc_colour_hist twice and
-    tc_colour_transfer for "hm", the three stages of both for "hm_mkl_hm").  pinned_px: the {frame index: pixels} a call pins;
-    with `match.targets == "pinned"` they are further targets (`match_colour`'s inner, the knots calls)."""
-    if match is None:
-        return video
-    from .output import match_colour
-    if pinned_px and getattr(match, "targets", "ends") == "pinned":
-        return match_colour(video, cond.ends_px, match, inner={int(i): px for i, px in pinned_px.items()})
-    return match_colour(video, cond.ends_px, match)
+def _cond_options(plan, three_way, hold_endpoints, prompts, fs):
+    """The keyword options of `Conditions.build` / `from_uint8` / `from_planes` that a synthesis call makes of its own"""
+    return dict(prompts=prompts, fs=fs, guided=plan.scale != 1.0, three_way=three_way, image_branch=plan.image_scale != 1.0,
+                hold_endpoints=hold_endpoints)
+
+
+def _finish(model, cond, plan, latent_shape, *, pinned=None, alpha=None, match=None, pinned_px=None, variant=0):
+    """The finishing chain of every synthesis call, in its one order: `sample`, `decode_spliced`, then `match` (an
+    `output.ColourMatch`: the decoded clip matched in colour to the keyframes of its conditions, `output.match_colour`; with
+    `match.targets == "pinned"` the {frame index: pixels} of `pinned_px` are further targets, its inner), then `alpha`
+    (`still_map`'s pixel weight: the still pixels held to the keyframes, `output.hold_still`, in place -- the clip is this
+    module's own).  None means no call: without `match` no colour op runs, without `alpha` no still op."""
+    video = decode_spliced(model, sample(model, cond, plan, latent_shape, pinned=pinned, variant=variant), cond.refs)
+    if match is not None:
+        inner = pinned_px and getattr(match, "targets", "ends") == "pinned"
+        video = match_colour(video, cond.ends_px, match, inner={int(i): px for i, px in pinned_px.items()} if inner else None)
+    if alpha is not None:
+        video = hold_still(video, cond.ends_px, alpha, inplace=True)
+    return video
 
 
 def synthesize(model, videos, latent_shape, *, plan: SamplingPlan, prompts=None, fs=24, three_way=False, hold_endpoints=True,
@@ -472,14 +469,11 @@ def synthesize(model, videos, latent_shape, *, plan: SamplingPlan, prompts=None,
     (`output.hold_still`), after `match=`.  Needs hold_endpoints (ValueError otherwise).  None: no still op is called.  The
     defaults of `StillRegions` are unmeasured starting values."""
     _check_still("synthesize", still, hold_endpoints)
-    cond = Conditions.build(model, videos, prompts=prompts, fs=fs, guided=plan.scale != 1.0,
-                            three_way=three_way, image_branch=plan.image_scale != 1.0, hold_endpoints=hold_endpoints)
+    cond = Conditions.build(model, videos, **_cond_options(plan, three_way, hold_endpoints, prompts, fs))
     pinned = pin_frames(model, keyframes, latent_shape[2]) if keyframes else None
     pinned, alpha = _still_plan(cond, still, latent_shape[2], pinned)
-    clips = [_held(_matched(decode_spliced(model, sample(model, cond, plan, latent_shape, pinned=pinned, variant=k), cond.refs), cond,
-                            match, keyframes), cond, alpha)
-             for k in range(variants)]
-    return torch.stack(clips, dim=1)
+    return torch.stack([_finish(model, cond, plan, latent_shape, pinned=pinned, alpha=alpha, match=match, pinned_px=keyframes, variant=k)
+                        for k in range(variants)], dim=1)
 
 
 def synthesize_u8(model, first_u8, last_u8, latent_shape, *, size, plan: SamplingPlan, prompts=None, fs=24, three_way=False,
@@ -495,15 +489,11 @@ def synthesize_u8(model, first_u8, last_u8, latent_shape, *, size, plan: Samplin
     None: no colour op is called.  This call pins nothing: `targets="pinned"` means "ends" here.
     still: a `StillRegions` -- what does not move between the two keyframes at model size is held, as in `synthesize`: the still
     cells' latents during sampling, the still pixels after `match=` and before the writer.  None: no still op is called."""
-    from .output import clip_to_uint8
     _check_still("synthesize_u8", still, hold_endpoints)
-    cond = Conditions.from_uint8(model, first_u8, last_u8, size=size, t=latent_shape[2], prompts=prompts, fs=fs,
-                                 guided=plan.scale != 1.0, three_way=three_way, image_branch=plan.image_scale != 1.0,
-                                 hold_endpoints=hold_endpoints)
+    cond = Conditions.from_uint8(model, first_u8, last_u8, size=size, t=latent_shape[2],
+                                 **_cond_options(plan, three_way, hold_endpoints, prompts, fs))
     pinned, alpha = _still_plan(cond, still, latent_shape[2])
-    video = _held(_matched(decode_spliced(model, _sample(model, cond, plan, latent_shape, pinned), cond.refs), cond, match), cond, alpha)
-    if out_colour is None:
-        return clip_to_uint8(video, size=out_size, filter=out_filter, fmt=out_fmt)
+    video = _finish(model, cond, plan, latent_shape, pinned=pinned, alpha=alpha, match=match)
     return clip_to_uint8(video, size=out_size, filter=out_filter, fmt=out_fmt, colour=out_colour)
 
 
@@ -531,6 +521,26 @@ def timeline_layout(keyframes: int, t: int, batch: int, out_hw, fmt: str, colour
 
 
 SHOT_LABELS = ("tween", "cut", "hold")
+
+
+def timeline_segments(labels, segments: int, batch: int, what: str = "timeline_segments"):
+    """Which segments of a timeline are held and how the others are sampled, host arithmetic only: `labels` one of SHOT_LABELS
+    per segment (None: every segment "tween") -> (held, batches).  held: the segments labelled anything but "tween", in order.
+    batches: (first segment, segments) as in `timeline_layout` -- the maximal runs of consecutive "tween" segments, each cut into
+    chunks of at most `batch`, so no batch spans a held segment; with None they are `timeline_layout`'s batches.  `what`: the
+    caller's name for the ValueError."""
+    labels = ("tween",) * segments if labels is None else tuple(labels)
+    if len(labels) != segments or any(v not in SHOT_LABELS for v in labels) or batch < 1:
+        raise ValueError(f"{what}: labels {labels} for {segments} segments, each one of {SHOT_LABELS}, in batches of {batch}")
+    held, batches = [], []
+    for i, label in enumerate(labels):
+        if label != "tween":
+            held.append(i)
+        elif batches and sum(batches[-1]) == i and batches[-1][1] < batch:
+            batches[-1] = (batches[-1][0], batches[-1][1] + 1)
+        else:
+            batches.append((i, 1))
+    return held, batches
 
 
 @dataclass(frozen=True)
@@ -582,9 +592,7 @@ def frame_deltas(keyframes, lag=1, tau=8):
     """`ops.frame_deltas` for the keyframes of a timeline: (K, h, w, 3) uint8 or a `Planes` of K images -> (delta (K - lag, 3, 3)
     int64: sad, changed, hist_l1 per pair (i, i + lag) and component; hist (K, 3, 64) int32), device tensors, exact integers,
     no synchronisation (tc_frame_deltas)."""
-    if not isinstance(keyframes, Planes) and not (isinstance(keyframes, torch.Tensor) and keyframes.dtype == torch.uint8
-                                                  and keyframes.dim() == 4 and keyframes.shape[3] == 3):
-        raise ValueError("frame_deltas: keyframes must be (K, h, w, 3) uint8 or a Planes")
+    _check_images("frame_deltas: keyframes", keyframes, "K", planes=True)
     return ops.frame_deltas(keyframes, lag=lag, tau=tau)
 
 
@@ -660,15 +668,12 @@ def synthesize_timeline_u8(model, keyframes, latent_shape, *, size, plan: Sampli
     still: a `StillRegions` -- every batch of sampled segments holds what does not move between its own keyframe pairs (one
     tc_still_map call per batch, at model size; `synthesize_u8`'s still): the still cells' latents during sampling, the still
     pixels after `match=` and before the writer.  "cut" and "hold" segments are untouched.  None: no still op is called."""
-    from dataclasses import replace
     _check_still("synthesize_timeline_u8", still)
+    _check_images("synthesize_timeline_u8: keyframes", keyframes, "K", planes=True)
     planar = isinstance(keyframes, Planes)
-    if not planar and not (isinstance(keyframes, torch.Tensor) and keyframes.dtype == torch.uint8 and keyframes.dim() == 4 and keyframes.shape[3] == 3):
-        raise ValueError("synthesize_timeline_u8: keyframes must be (K, h, w, 3) uint8 or a Planes")
     k, t = len(keyframes), int(latent_shape[2])
     size = tuple(int(v) for v in size)
     oh, ow = size if out_size is None else (int(v) for v in out_size)
-    from .output import Colour
     if out_colour is not None and not isinstance(out_colour, (str, Colour)):
         raise ValueError(f"synthesize_timeline_u8: out_colour: expected a Colour or 'source', got {type(out_colour).__name__}")
     if isinstance(out_colour, str):
@@ -676,49 +681,36 @@ def synthesize_timeline_u8(model, keyframes, latent_shape, *, size, plan: Sampli
             raise ValueError(f"synthesize_timeline_u8: out_colour {out_colour!r}: a Colour, or 'source' with Planes keyframes "
                              "(RGB keyframes carry no colour description)")
         out_colour = Colour.of(keyframes)
-    total, frame, batches = timeline_layout(k, t, latent_shape[0], (oh, ow), out_fmt) if out_colour is None else \
-        timeline_layout(k, t, latent_shape[0], (oh, ow), out_fmt, out_colour)
+    total, frame, _ = timeline_layout(k, t, latent_shape[0], (oh, ow), out_fmt, out_colour)
     seeds = None if plan.seeds is None else ops.clip_seeds(plan.seeds, k - 1, "synthesize_timeline_u8: plan.seeds (one per segment)")
     if prompts is not None and len(prompts) != k - 1:
         raise ValueError(f"synthesize_timeline_u8: {len(prompts)} prompts for {k - 1} segments")
-    device = keyframes.y.device if planar else keyframes.device
-    video = torch.empty((total, oh, ow, 3) if out_fmt == "rgb24" else (total, frame), dtype=torch.uint8, device=device)
+    if isinstance(shots, ShotRule):
+        shots = find_shots(keyframes, shots)
+    if shots is not None and not isinstance(shots, ShotPlan):
+        raise ValueError(f"synthesize_timeline_u8: shots: expected a ShotRule or a ShotPlan, got {type(shots).__name__}")
+    held, batches = timeline_segments(None if shots is None else shots.labels, k - 1, latent_shape[0], "synthesize_timeline_u8: shots")
+    video = torch.empty((total, oh, ow, 3) if out_fmt == "rgb24" else (total, frame), dtype=torch.uint8,
+                        device=keyframes.y.device if planar else keyframes.device)
     wide = out_colour is not None and out_colour.bits == 10                                       # P010: 2-byte samples
     flat, row = video.view(-1), 3 * ow if out_fmt == "rgb24" else 2 * ow if wide else ow
-    write = ops.frames_to_u8 if out_colour is None else (lambda x, **kw: ops.frames_to_yuv(x, colour=out_colour, **kw))
-    build = Conditions.from_planes if planar else Conditions.from_uint8
-    if shots is not None:
-        if isinstance(shots, ShotRule):
-            shots = find_shots(keyframes, shots)
-        if not isinstance(shots, ShotPlan):
-            raise ValueError(f"synthesize_timeline_u8: shots: expected a ShotRule or a ShotPlan, got {type(shots).__name__}")
-        if len(shots.labels) != k - 1 or any(v not in SHOT_LABELS for v in shots.labels):
-            raise ValueError(f"synthesize_timeline_u8: shots: labels {shots.labels} for {k - 1} segments, each one of {SHOT_LABELS}")
-        batches, front = [], frames_from_planes if planar else frames_from_uint8
-        for i, label in enumerate(shots.labels):
-            if label != "tween":                      # not sampled: t - 1 frames of keyframe i, then keyframe i + 1, as the writer gives them
-                ends = front(keyframes[i:i + 2], size, [(0, 0), (0, 1)], 2)
-                held = ends[:, :, [0] * (t - 1) + [1]].contiguous()
-                if i == 0:
-                    write(held, size=out_size, filter=out_filter, fmt=out_fmt, frames=(0, 1), out=flat, strides=(row, frame, frame))
-                write(held, size=out_size, filter=out_filter, fmt=out_fmt, frames=(1, t - 1), out=flat[(i * (t - 1) + 1) * frame:],
-                      strides=(row, frame, (t - 1) * frame))
-            elif batches and sum(batches[-1]) == i and batches[-1][1] < latent_shape[0]:
-                batches[-1] = (batches[-1][0], batches[-1][1] + 1)
-            else:
-                batches.append((i, 1))
+    how = dict(size=out_size, filter=out_filter, fmt=out_fmt, colour=out_colour)
+
+    def put(i, clips):
+        """`clips`, the segments from i on, into the video: frame 0 if segment 0 is among them, frames 1 .. t-1 at their place"""
+        if i == 0:
+            write_frames(clips[:1], frames=(0, 1), out=flat, strides=(row, frame, frame), **how)
+        write_frames(clips, frames=(1, t - 1), out=flat[(i * (t - 1) + 1) * frame:], strides=(row, frame, (t - 1) * frame), **how)
+    build, front = (Conditions.from_planes, frames_from_planes) if planar else (Conditions.from_uint8, frames_from_uint8)
+    for i in held:                                    # not sampled: t - 1 frames of keyframe i, then keyframe i + 1, as the writer gives them
+        ends = front(keyframes[i:i + 2], size, [(0, 0), (0, 1)], 2)
+        put(i, ends[:, :, [0] * (t - 1) + [1]].contiguous())
     for i, n in batches:
         cond = build(model, keyframes[i:i + n], keyframes[i + 1:i + n + 1], size=size, t=t,
-                     prompts=None if prompts is None else list(prompts[i:i + n]), fs=fs, guided=plan.scale != 1.0,
-                     three_way=three_way, image_branch=plan.image_scale != 1.0, hold_endpoints=True)
+                     **_cond_options(plan, three_way, True, None if prompts is None else list(prompts[i:i + n]), fs))
         part = plan if seeds is None else replace(plan, seeds=seeds[i:i + n])
         pinned, alpha = _still_plan(cond, still, t)
-        clips = _held(_matched(decode_spliced(model, _sample(model, cond, part, [n, *latent_shape[1:]], pinned), cond.refs), cond, match),
-                      cond, alpha).to(torch.float32)
-        if i == 0:                                    # the video's first frame: segment 0 alone writes its frame 0
-            write(clips[:1], size=out_size, filter=out_filter, fmt=out_fmt, frames=(0, 1), out=flat, strides=(row, frame, frame))
-        write(clips, size=out_size, filter=out_filter, fmt=out_fmt, frames=(1, t - 1), out=flat[(i * (t - 1) + 1) * frame:],
-              strides=(row, frame, (t - 1) * frame))
+        put(i, _finish(model, cond, part, [n, *latent_shape[1:]], pinned=pinned, alpha=alpha, match=match).to(torch.float32))
     return video
 
 

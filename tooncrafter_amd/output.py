@@ -185,18 +185,32 @@ def clip_to_uint8(samples: torch.Tensor, loop: bool = False, size=None, filter: 
     colour: a `Colour` for the planes instead of the default BT.601 limited range with centre siting (tc_frames_to_yuv); fmt
     must then be "i420" or "nv12", and bits=10 ("nv12" only) gives P010, (b, t, oh * ow * 3) bytes
     (`clip.planes_from_frames` views them)."""
+    samples, t = samples.to(torch.float32), samples.shape[2]
+    if _whole_clips(size, fmt, colour):                           # `loop` is a slice there: no frames= for write_frames' rule
+        return write_frames(samples[:, :, :-1] if loop else samples)
+    return write_frames(samples, size=size, filter=filter, fmt=fmt, colour=colour, frames=(0, t - 1 if loop else t))
+
+
+def _whole_clips(size, fmt, colour) -> bool:
+    """what tc_video_to_u8 writes: packed RGB at the clips' own size (it takes whole clips, so a request for some frames, or
+    for a buffer of the caller's, goes to tc_frames_to_u8 as well: `write_frames`)"""
+    return colour is None and size is None and fmt == "rgb24"
+
+
+def write_frames(video: torch.Tensor, *, size=None, filter: str = "bicubic", fmt: str = "rgb24", colour: Optional[Colour] = None,
+                 frames=None, out=None, strides=None) -> torch.Tensor:
+    """The writer rule, the one place that picks the back-end op for (b, 3, t, h, w) fp32 clips:
+      a `colour`                                                      -> ops.frames_to_yuv (tc_frames_to_yuv);
+      the clips alone (no size, "rgb24", no frames / out / strides)   -> ops.video_to_uint8 (tc_video_to_u8);
+      anything else                                                   -> ops.frames_to_u8 (tc_frames_to_u8).
+    The keywords are those ops' own: frames = (first, count); out / strides, a buffer written in place (the timeline's)."""
     if colour is not None:
         if not isinstance(colour, Colour):
-            raise ValueError(f"clip_to_uint8: colour: expected a Colour, got {type(colour).__name__}")
-        t = samples.shape[2]
-        return ops.frames_to_yuv(samples.to(torch.float32), size=size, filter=filter, fmt=fmt, colour=colour,
-                                 frames=(0, t - 1 if loop else t))
-    if size is None and fmt == "rgb24":
-        if loop:
-            samples = samples[:, :, :-1]
-        return ops.video_to_uint8(samples.to(torch.float32))
-    t = samples.shape[2]
-    return ops.frames_to_u8(samples.to(torch.float32), size=size, filter=filter, fmt=fmt, frames=(0, t - 1 if loop else t))
+            raise ValueError(f"write_frames: colour: expected a Colour, got {type(colour).__name__}")
+        return ops.frames_to_yuv(video, size=size, filter=filter, fmt=fmt, colour=colour, frames=frames, out=out, strides=strides)
+    if _whole_clips(size, fmt, colour) and frames is None and out is None and strides is None:
+        return ops.video_to_uint8(video)
+    return ops.frames_to_u8(video, size=size, filter=filter, fmt=fmt, frames=frames, out=out, strides=strides)
 
 
 def planar_writer(width: int, height: int, fmt: str = "i420", colour: Optional[Colour] = None) -> Callable[[str, torch.Tensor, int], str]:
@@ -211,8 +225,7 @@ def planar_writer(width: int, height: int, fmt: str = "i420", colour: Optional[C
             n = width * height
             uv = planes[:, n:].reshape(len(planes), -1, 2)
             planes = np.concatenate([planes[:, :n], uv[:, :, 0], uv[:, :, 1]], axis=1)
-        return write_mp4_i420(path, planes, width, height, fps) if colour is None else \
-            write_mp4_i420(path, planes, width, height, fps, colour=colour)
+        return write_mp4_i420(path, planes, width, height, fps, colour=colour)
     return write
 
 
@@ -245,10 +258,9 @@ def save_results_seperate(prompt, samples, filename, fakedir, fps=10, loop=False
         return []
     if fmt != "rgb24":
         oh, ow = samples.shape[3:] if size is None else size
-        writer = writer or (planar_writer(int(ow), int(oh), fmt) if colour is None else planar_writer(int(ow), int(oh), fmt, colour))
+        writer = writer or planar_writer(int(ow), int(oh), fmt, colour)
     writer = writer or default_writer
-    frames = (clip_to_uint8(samples.detach(), loop=loop, size=size, filter=filter, fmt=fmt) if colour is None else
-              clip_to_uint8(samples.detach(), loop=loop, size=size, filter=filter, fmt=fmt, colour=colour)).cpu()
+    frames = clip_to_uint8(samples.detach(), loop=loop, size=size, filter=filter, fmt=fmt, colour=colour).cpu()
     outdir = fakedir.replace('samples', 'samples_separate')
     os.makedirs(outdir, exist_ok=True)
     written = []
@@ -263,6 +275,4 @@ def gather_frames(samples: torch.Tensor, dst: int = 0, loop: bool = False, size=
     """Multi-GPU writer side: convert on every rank, gather the uint8 frames to `dst` (one RCCL gather,
     7.9 MB per 16-frame clip instead of 31.5 MB fp32; half of that, 1.5 bytes per pixel, with fmt "i420" / "nv12").
     `colour` as in clip_to_uint8.  Returns the per-rank list on `dst`, None elsewhere."""
-    if colour is None:
-        return tdist.gather_clips(clip_to_uint8(samples, loop=loop, size=size, filter=filter, fmt=fmt), dst=dst)
     return tdist.gather_clips(clip_to_uint8(samples, loop=loop, size=size, filter=filter, fmt=fmt, colour=colour), dst=dst)
